@@ -9,7 +9,7 @@ with random-init weights (no checkpoint can be downloaded here), 16-bit activati
 accumulation (--dtype f16, the default: IEEE half precision; bf16: the same kernels on bfloat16 tensors).  Utterances shard embarrassingly: every rank owns its own 16 utterances (weak
 scaling) and the only collective is the result gather.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,7 +18,14 @@ ranks (length-balanced deal, evaluate_mp.py:495-518 semantics with the imbalance
 share in width-bucketed batches, and ONE gather at the end collects the per-utterance results; a step = one pass over
 the whole set; the line carries per-rank busy times and their imbalance.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): `value` (utterances/s), `ms_per_step`
+(wall time of one timed step) and the configuration.  --dump-outputs DIR also writes the separated waveforms of the last timed
+step (what a caller of the step receives; on several ranks the gathered ones of rank 0) as DIR/separated.npy, float32; the
+inputs (synthetic mixtures, weights, per-step noise seeds) depend only on the arguments, so two builds compare output for output.
+
+--full adds everything else the line has carried (each object can be dropped again with its --no-* option):
+  one_batch_alone_ms / in_flight_bit_identical — latency of one batch alone, and the same batch again with the other
+                 batches in flight (must be bit-identical).
   roofline     — the MFMA kernel instantiation with the most GPU time, named by its real template arguments (round 3:
                  the register-weight 3x3 convolution conv3x3_rw_kernel<2,4,0,2,2>, 128 -> 64 couts with GroupNorm + SiLU):
                  algorithmic FLOPs of its launches / their summed durations, measured with HIP events on the launch
@@ -52,6 +59,17 @@ import torch  # noqa: E402
 GFLOP_PER_NFE = {64: 133.83, 128: 532.89}  # SURVEY.md §8d, per utterance at W=256 (probe-counted 2*MAC)
 PEAK_TFLOPS = {"bf16": 2500.0, "f16": 2500.0, "f32": 157.3, "split": 2500.0 / 3}  # MI355X_MICROARCH.md: dense MFMA peaks (split: 3 bf16 MFMAs per product)
 HBM_PEAK_BPS = 8.0e12                          # MI355X_MICROARCH.md: HBM3E ~8 TB/s
+DUMP_MAX_BYTES = 64_000_000                    # --dump-outputs: at most this much per run
+
+
+def dump_outputs(path, name, t):
+    """Write tensor t as path/name.npy (float32).  A tensor larger than DUMP_MAX_BYTES is written as a fixed sample of its
+    flattened values (every k-th element, k the smallest stride that fits), the same elements for the same arguments."""
+    a = t.detach().float().cpu().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        a = a.reshape(-1)[::-(-a.size // (DUMP_MAX_BYTES // 4))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 def cpu_baseline(nf, T, N, corrector_steps):
     """The CPU oracle (this repo's torch-fp32 restatement of the reference path, validated against the imported reference in the
@@ -147,6 +165,8 @@ def run_strong(args, engs, ops, on_stream, sync, fence, dist, world, rank, dev, 
             dist.gather(block, blocks, dst=0)   # ONE collective per pass (RCCL over xGMI)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "separated", torch.cat(blocks) if blocks else block)
     finite = bool(torch.isfinite(block).all())
     busy_all = [busy]
     if world > 1:
@@ -225,11 +245,16 @@ def main():
     ap.add_argument("--samples", type=int, default=32000, help="samples per utterance (4 s at 8 kHz)")
     ap.add_argument("-N", type=int, default=30)
     ap.add_argument("--corrector-steps", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: one batch alone and bit identity in "
+                         "flight, roofline, the other precision modes, nf = 128, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the separated waveforms of the last timed step as DIR/separated.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline pass")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-extra-modes", action="store_true", help="skip the other precision modes and the nf = 128 section")
-    ap.add_argument("--no-nf128", action="store_true", help="skip the nf = 128 section")
+    ap.add_argument("--no-extra-modes", action="store_true", help="with --full: skip the other precision modes and the nf = 128 section")
+    ap.add_argument("--no-nf128", action="store_true", help="with --full: skip the nf = 128 section")
     ap.add_argument("--no-rw-quarter", action="store_true", help="keep every register-weight launch on all CUs even with several batches in flight")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--utterances", type=int, default=128, help="--scaling strong: size of the fixed utterance set")
@@ -239,6 +264,8 @@ def main():
                          "convolutions fill it).  1 = one batch at a time.  Every step is still a full batch through the "
                          "whole path and all timed steps finish inside the timed region.")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # HIP maps streams onto GPU_MAX_HW_QUEUES (default 4, one taken by the null stream) hardware queues; read when the
     # runtime initialises, i.e. before the first torch.cuda call
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
@@ -393,33 +420,38 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     finite = all(bool(torch.isfinite(o).all()) for o in outs[-K:])
+    if args.dump_outputs and rank == 0:
+        last = gathered[(args.warmup + args.steps - 1) % K]
+        dump_outputs(args.dump_outputs, "separated", torch.cat(last) if world > 1 else outs[-1])
     del outs
-    # latency of ONE batch with nothing else in flight (untimed extra): in the throughput mode of the timed region, then — what
-    # one_batch_alone_ms and the per-kernel roofline below report — in the engine's default configuration (every launch on all CUs)
-    alone_spread_ms = None
-    if not dry and spread:
+    alone_spread_ms = alone_ms = same_bits = None
+    if args.full:
+        # latency of ONE batch with nothing else in flight (untimed extra): in the throughput mode of the timed region, then —
+        # what one_batch_alone_ms and the per-kernel roofline below report — in the engine's default configuration (every
+        # launch on all CUs)
+        if not dry and spread:
+            fence()
+            t1 = time.perf_counter()
+            step(0, collect=False, w=0, seed=77)
+            sync()
+            alone_spread_ms = (time.perf_counter() - t1) * 1e3
+            engs[0].set_option("rw_quarter", 0)
+            for _ in range(2):   # plan + graph capture of the default configuration
+                step(0, collect=False, w=0, seed=77)
+            sync()
         fence()
         t1 = time.perf_counter()
-        step(0, collect=False, w=0, seed=77)
+        ref_out, _ = step(0, collect=False, w=0, seed=77)
         sync()
-        alone_spread_ms = (time.perf_counter() - t1) * 1e3
-        engs[0].set_option("rw_quarter", 0)
-        for _ in range(2):   # plan + graph capture of the default configuration
-            step(0, collect=False, w=0, seed=77)
+        alone_ms = (time.perf_counter() - t1) * 1e3
+        # the same batch and seed again with K-1 other batches in flight: must be bit-identical (untimed check)
+        again = [step(j, collect=False, w=j, seed=77 + j)[0] for j in range(K)]
         sync()
-    fence()
-    t1 = time.perf_counter()
-    ref_out, _ = step(0, collect=False, w=0, seed=77)
-    sync()
-    alone_ms = (time.perf_counter() - t1) * 1e3
-    # the same batch and seed again with K-1 other batches in flight: must be bit-identical (untimed check)
-    again = [step(j, collect=False, w=j, seed=77 + j)[0] for j in range(K)]
-    sync()
-    same_bits = bool(torch.equal(again[0], ref_out))
-    del again, ref_out
+        same_bits = bool(torch.equal(again[0], ref_out))
+        del again, ref_out
 
     roof = None
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         eng.profile_begin()
         step(10_000, collect=False, w=0)  # rank 0 only: no collective in this untimed pass
         prof = eng.profile_end()
@@ -562,7 +594,7 @@ def main():
                 "all_mfma_kernels_tflops": round(sum(v[0] for v in prof.values()) / (tot_ms * 1e-3) / 1e12, 2)})
 
     extra_json = {}
-    if world == 1 and not dry and not args.no_extra_modes and args.dtype in ("bf16", "f16"):
+    if args.full and world == 1 and not dry and not args.no_extra_modes and args.dtype in ("bf16", "f16"):
         # ---- the other precision modes of the same step on the driver's clock (after the main timed region): the other
         # 16-bit storage format, exact fp32, split fp32; and their agreement with the exact fp32 engine on the same seeds
         other = "bf16" if args.dtype == "f16" else "f16"
@@ -777,15 +809,7 @@ def main():
                                    "flight per GPU" % (args.N, args.corrector_steps, B, T / 8000.0, args.nf, nfe, K),
                        "batch_per_gpu": B, "samples": T, "N": args.N, "corrector_steps": args.corrector_steps,
                        "nf": args.nf, "sharding": "utterances/%d" % world, "graph": not args.no_graph,
-                       "batches_in_flight": K, "one_batch_alone_ms": round(alone_ms, 2)},
-            "one_batch_alone_ms": round(alone_ms, 2),
-            "throughput_mode": ({"rw_quarter": True, "one_batch_alone_ms_in_this_mode": round(alone_spread_ms, 2),
-                                 "note": "timed region: register-weight launches with <= 4 tiles per block on a quarter of the CUs (engine option "
-                                         "rw_quarter, set by multi-stream callers); one_batch_alone_ms and roofline: the engine's default "
-                                         "configuration (every launch on all CUs), measured after the timed region on engine 0"}
-                                if alone_spread_ms is not None else None),
-            "utt_per_s_per_gpu_one_batch_at_a_time": round(B / (alone_ms * 1e-3), 2),
-            "in_flight_bit_identical": same_bits,
+                       "batches_in_flight": K},
             "realtime_factor": round(value * T / 8000.0, 2),
             "nfe_per_s": round(value * nfe, 1),
             "model_tflops": round(value * nfe * GFLOP_PER_NFE.get(args.nf, float("nan")) * (T / 32000.0) / 1e3, 2),
@@ -801,6 +825,17 @@ def main():
                     "note": "one process and one set of engines per GPU; GPU_MAX_HW_QUEUES=8 is per process (its own device), "
                             "so eight ranks do not share hardware queues"},
         }
+        if alone_ms is not None:
+            res["config"]["one_batch_alone_ms"] = round(alone_ms, 2)
+            res.update({
+                "one_batch_alone_ms": round(alone_ms, 2),
+                "throughput_mode": ({"rw_quarter": True, "one_batch_alone_ms_in_this_mode": round(alone_spread_ms, 2),
+                                     "note": "timed region: register-weight launches with <= 4 tiles per block on a quarter of the CUs (engine option "
+                                             "rw_quarter, set by multi-stream callers); one_batch_alone_ms and roofline: the engine's default "
+                                             "configuration (every launch on all CUs), measured after the timed region on engine 0"}
+                                    if alone_spread_ms is not None else None),
+                "utt_per_s_per_gpu_one_batch_at_a_time": round(B / (alone_ms * 1e-3), 2),
+                "in_flight_bit_identical": same_bits})
         if roof is not None:
             res["roofline"] = roof
         ups_ = extra_json.pop("_ups", None)
@@ -821,7 +856,7 @@ def main():
             res["value_bf16"] = res["value"]
         elif "bf16_mode" in res:
             res["value_bf16"] = res["bf16_mode"]["utt_per_s"]
-        if not args.no_cpu_baseline and world == 1 and not dry:
+        if args.full and not args.no_cpu_baseline and world == 1 and not dry:
             t_utt, n_cpu, t_nfe, cores = cpu_baseline(args.nf, T, args.N, args.corrector_steps)
             res["cpu_baseline"] = {"value": round(1.0 / t_utt, 5), "unit": "utterances/s", "cores": cores, "kind": "port",
                                    "sample_kind": "full_run",

@@ -207,7 +207,7 @@ def test_bench_multi_rank_sequencing_gloo(tmp_path):
     for r in range(2):
         e = dict(env, RANK=str(r), LOCAL_RANK=str(r))
         procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-                                       "--warmup", "1", "--batch", "2", "--samples", "800"], env=e, cwd=root,
+                                       "--warmup", "1", "--batch", "2", "--samples", "800", "--full"], env=e, cwd=root,
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=120) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-500:] for o in outs]
@@ -222,16 +222,18 @@ def test_bench_multi_rank_sequencing_gloo(tmp_path):
     assert res["hbm"]["engines_per_rank"] == [4, 4]
 
 
-def test_bench_self_launches_its_ranks_gloo():
+def test_bench_self_launches_its_ranks_gloo(tmp_path):
     # `python bench.py --gpus 2` with NO torch.distributed.run around it (how the round-2 driver invoked it): bench.py
-    # must start the two ranks itself, and the single JSON line must say n_gpus = 2 with both ranks seen
+    # must start the two ranks itself, and the single JSON line must say n_gpus = 2 with both ranks seen.  Without --full
+    # the line carries none of the untimed extras; --dump-outputs writes the waveforms rank 0 gathered in the last step.
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["DIFFSEP_BENCH_DRYRUN"] = "1"
-    for extra in ([], ["--scaling", "strong", "--utterances", "7"], ["--in-flight", "1"]):
+    dump = tmp_path / "out"
+    for extra in ([], ["--scaling", "strong", "--utterances", "7"], ["--in-flight", "1"], ["--dump-outputs", str(dump)]):
         out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
                               "--batch", "2", "--samples", "800"] + extra, env=env, cwd=root, capture_output=True,
                              text=True, timeout=240)
@@ -243,6 +245,9 @@ def test_bench_self_launches_its_ranks_gloo():
         assert res["scaling"] == ("strong" if "strong" in extra else "weak") and res["imbalance_max_over_mean"] >= 1.0
         if "--in-flight" in extra:
             assert res["config"]["batches_in_flight"] == 1 and res["hbm"]["engines_per_rank"] == [1, 1]
+        assert res["ms_per_step"] > 0 and not {"roofline", "one_batch_alone_ms", "in_flight_bit_identical"} & set(res)
+    sep = np.load(dump / "separated.npy")
+    assert sep.dtype == np.float32 and sep.shape == (2 * 2, 2, 800)
 
 
 def test_bench_strong_scaling_sequencing_gloo():

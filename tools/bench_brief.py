@@ -5,7 +5,7 @@ DIFFSEP_LIB_F16 / DIFFSEP_* environment variables."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pat = sys.argv[1:] or ["thin_out", "128->64 @256", "64->64 @256", "@128x128"]
-out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-extra-modes", "--no-cpu-baseline"], capture_output=True, text=True)
+out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extra-modes", "--no-cpu-baseline"], capture_output=True, text=True)
 line = [l for l in out.stdout.splitlines() if l.startswith("{")]
 if not line:
     print(out.stderr[-800:]); sys.exit(1)

@@ -23,12 +23,12 @@ for MODE in inflight alone; do
   EXTRA=""; SUF=""
   if [ $MODE = alone ]; then EXTRA="--in-flight 1"; SUF="_alone"; fi
   rm -rf /tmp/kt
-  rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt --output-format csv -- python bench.py --dtype $DT --no-cpu-baseline --no-extra-modes --no-roofline $EXTRA > $O/${TAG}_kt$SUF.log 2>&1
+  rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt --output-format csv -- python bench.py --full --dtype $DT --no-cpu-baseline --no-extra-modes --no-roofline $EXTRA > $O/${TAG}_kt$SUF.log 2>&1
   cp $(find /tmp/kt -name "*kernel_stats.csv" | head -1) $O/${TAG}_kernel_stats$SUF.csv
-  python tools/kernel_stats_md.py $O/${TAG}_kernel_stats$SUF.csv "rocprofv3 --kernel-trace --stats summary of \`python bench.py --dtype $DT --no-cpu-baseline --no-extra-modes --no-roofline $EXTRA\` ($TAG, commit $COMMIT; $MODE: 2 warm-up + 8 timed steps + the latency / bit-identity extras; the tracer serialises dispatches)" > $O/${TAG}_bench_${DT}${SUF}_kernel_stats.md
+  python tools/kernel_stats_md.py $O/${TAG}_kernel_stats$SUF.csv "rocprofv3 --kernel-trace --stats summary of \`python bench.py --full --dtype $DT --no-cpu-baseline --no-extra-modes --no-roofline $EXTRA\` ($TAG, commit $COMMIT; $MODE: 2 warm-up + 8 timed steps + the latency / bit-identity extras; the tracer serialises dispatches)" > $O/${TAG}_bench_${DT}${SUF}_kernel_stats.md
 done
 # (the bench line last: its roofline.frac_rocprof reads the summaries just written when they have been copied to profiles/)
 cp $O/${TAG}_bench_${DT}_kernel_stats.md $O/${TAG}_bench_${DT}_alone_kernel_stats.md $O/${TAG}_pmc_mfma_util.json profiles/ 2>/dev/null
 cp $O/pmc_conv3x3.json profiles/pmc_conv3x3.json 2>/dev/null
-python bench.py --dtype $DT > $O/${TAG}_bench_$DT.json 2> $O/${TAG}_bench_$DT.err
+python bench.py --full --dtype $DT > $O/${TAG}_bench_$DT.json 2> $O/${TAG}_bench_$DT.err
 tail -c 1500 $O/${TAG}_bench_$DT.json

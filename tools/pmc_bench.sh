@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=${1:-gpurun_out/pmc_bench}
 mkdir -p $OUT
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c -d $OUT/$c -o pmc --output-format csv -- python bench.py --steps 1 --warmup 0 -N 4 --in-flight 1 --no-cpu-baseline --no-roofline --no-graph --no-extra-modes > $OUT/$c.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c -d $OUT/$c -o pmc --output-format csv -- python bench.py --full --steps 1 --warmup 0 -N 4 --in-flight 1 --no-cpu-baseline --no-roofline --no-graph --no-extra-modes > $OUT/$c.log 2>&1
 done
 OUT=$OUT python - <<'PY'
 import csv, glob, json, os
@@ -31,7 +31,7 @@ for k, v in res.items():
     f, w = v["FETCH_SIZE"][0] / n, v["WRITE_SIZE"][0] / max(v["WRITE_SIZE"][1], 1)
     kern[k] = {"launches": n, "fetch_size_kb_per_launch": f, "write_size_kb_per_launch": w,
                "hbm_bytes_per_launch_guide_formula": (2 * f + w) * 1024, "hbm_bytes_per_launch_lower_bound": (f + w) * 1024}
-doc = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --steps 1 "
+doc = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --full --steps 1 "
                  "--warmup 0 -N 4 --in-flight 1 --no-graph` (tools/pmc_bench.sh; with N = 30 rocprofv3 --pmc crashes in one of its own threads)",
        "commit": os.environ.get("COMMIT", "unrecorded"),
        "correction": "MI355X_MICROARCH.md (HBM): FETCH_SIZE tallies 128-byte requests at 64 B -> doubled for wide coalesced reads; "

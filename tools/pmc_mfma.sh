@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=${1:-gpurun_out/pmc_mfma}
 mkdir -p $OUT
 CTRS="SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
-rocprofv3 --kernel-trace --pmc $CTRS -d /tmp/pmc_mfma -o pmc --output-format csv -- python bench.py --in-flight 1 --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-graph > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace --pmc $CTRS -d /tmp/pmc_mfma -o pmc --output-format csv -- python bench.py --full --in-flight 1 --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-graph > $OUT/run.log 2>&1
 python - "$OUT" <<'PY'
 import csv, glob, json, os, sys
 out = sys.argv[1]

@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/pmc_total}
 mkdir -p $OUT
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_total_$c
-  rocprofv3 --kernel-trace --pmc $c -d /tmp/pmc_total_$c -o pmc --output-format csv -- python bench.py --in-flight 1 --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-graph > $OUT/$c.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c -d /tmp/pmc_total_$c -o pmc --output-format csv -- python bench.py --full --in-flight 1 --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-graph > $OUT/$c.log 2>&1
 done
 python - "$OUT" <<'PY'
 import csv, glob, json, os, sys

@@ -10,7 +10,7 @@ OUT=${1:-gpurun_out/pmc_traffic}
 DT=${2:-f16}
 mkdir -p $OUT
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c -d /tmp/pmc_traffic/$c -o pmc --output-format csv -- python bench.py --dtype $DT --steps 1 --warmup 0 -N 4 --in-flight 1 --no-cpu-baseline --no-roofline --no-graph --no-extra-modes > $OUT/$c.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c -d /tmp/pmc_traffic/$c -o pmc --output-format csv -- python bench.py --full --dtype $DT --steps 1 --warmup 0 -N 4 --in-flight 1 --no-cpu-baseline --no-roofline --no-graph --no-extra-modes > $OUT/$c.log 2>&1
 done
 OUT=$OUT DT=$DT python - <<'PY'
 import csv, glob, json, os, re
@@ -35,7 +35,7 @@ for k, v in res.items():
     kern[k] = {"launches": n, "fetch_size_kb_per_launch": round(f, 1), "write_size_kb_per_launch": round(w, 1),
                "hbm_bytes_per_launch_guide_formula": round((2 * f + w) * 1024), "hbm_bytes_per_launch_lower_bound": round((f + w) * 1024)}
 kern = dict(sorted(kern.items(), key=lambda kv: -kv[1]["hbm_bytes_per_launch_guide_formula"] * kv[1]["launches"]))
-doc = {"source": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --dtype {dt} --steps 1 "
+doc = {"source": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python bench.py --full --dtype {dt} --steps 1 "
                  "--warmup 0 -N 4 --in-flight 1 --no-graph` (tools/pmc_traffic.sh; with N = 30 rocprofv3 --pmc crashed in one of its own threads)",
        "commit": os.environ.get("COMMIT", "unrecorded"), "dtype": dt,
        "correction": "MI355X_MICROARCH.md (HBM): FETCH_SIZE tallies 128-byte requests at 64 B -> doubled for wide coalesced reads; "

@@ -9,7 +9,7 @@ DT=${2:-f16}
 mkdir -p $OUT
 P1="SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE"
 P2="SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_INSTS_MFMA"
-CMD="python bench.py --dtype $DT --in-flight 1 --steps 1 --warmup 0 -N 4 --no-cpu-baseline --no-roofline --no-graph --no-extra-modes"
+CMD="python bench.py --full --dtype $DT --in-flight 1 --steps 1 --warmup 0 -N 4 --no-cpu-baseline --no-roofline --no-graph --no-extra-modes"
 rm -rf /tmp/pmc_r03
 rocprofv3 --kernel-trace --pmc $P1 -d /tmp/pmc_r03/p1 -o pmc --output-format csv -- $CMD > $OUT/run1.log 2>&1
 rocprofv3 --kernel-trace --pmc $P2 -d /tmp/pmc_r03/p2 -o pmc --output-format csv -- $CMD > $OUT/run2.log 2>&1
