@@ -345,6 +345,19 @@ int ds_launch_istft(const void* x, float* out, int B, int S, long T, int n_fft, 
 int ds_build_stft_table(int n_fft, float** dev_tab);
 
 struct SdeP { int kind; int ndim; float d_lambda, sigma_min, sigma_max; };
+// g(t) = sigma_min r^t sqrt(2 ln r), r = sigma_max / sigma_min   MixSDE.sde (sdes/sdes.py:275-284)
+__device__ inline float sde_g_of_t(const SdeP& s, float t) {
+  const float r = s.sigma_max / s.sigma_min;
+  return s.sigma_min * powf(r, t) * sqrtf(2.0f * logf(r));
+}
+// -lambda P x at one time index (x [S] -> f [S])   MixSDE.sde drift (sdes/sdes.py:275-284).  sde_coeff_kernel and the
+// ODE drift (ode.hip) both go through these two helpers: the same operations, the same roundings.
+__device__ inline void sde_mix_drift(const SdeP& s, const float* xv, float* f, int S) {
+  float mx = 0.f;
+  for (int i = 0; i < S; ++i) mx += xv[i];
+  mx /= (float)S;
+  for (int i = 0; i < S; ++i) f[i] = -s.d_lambda * (xv[i] - mx);
+}
 // smix: per-sample sigma_mix [B][T] of PriorMixSDE (kind 1), null for MixSDE (kind 0)
 int ds_launch_sigma_mix(const float* mix, float* out, int B, long T, int avg_len, hipStream_t st);
 // lens (nullable): per-utterance lengths [B] (device); the state beyond lens[b] is kept at zero
@@ -375,6 +388,38 @@ int ds_launch_randn(float* out, long n, uint64_t seed, uint64_t stream_id, hipSt
 int ds_launch_gram(const float* ref, const float* est, double* out, int B, int S, long T, hipStream_t st);
 int ds_launch_convert(const void* src, void* dst, long n, int sd, int dd, hipStream_t st);
 int ds_launch_fill(float* p, float v, long n, hipStream_t st);
+
+// ------------------------------------------------------------------ probability-flow ODE (ode.hip)
+#define DS_ODE_MAX_K 7        // Runge-Kutta stage derivatives held at once (RK45: 6 stages + FSAL)
+#define DS_ODE_MAX_BLOCKS 1024  // grid cap of the ODE passes = rows of the per-block partial-sum slab
+// Butcher tableau of scipy.integrate's RK45 (method 0, Dormand-Prince) / RK23 (method 1, Bogacki-Shampine): A [ns][ns]
+// row-major, B [ns], C [ns], E [ns + 1]; any output may be null.  Returns -1 for an unknown method.
+int ds_ode_tableau(int method, double* A, double* B, double* C, double* E, int* n_stages, int* error_order);
+// One pass over the state [B][S][T] (ode.hip, ode_stage_kernel):
+//   kout != null:  kout = x's probability-flow drift  f(x, t) - 0.5 g(t)^2 [sigma_mix^2] score   (the K of this stage)
+//   acc = sum_{j < nk} c[j] k[j]   (k[kidx] is the drift just computed, taken from registers)
+//   mode 1: xo = fp32(y + acc * h)                      (the next stage's network input)
+//   mode 2: yo = y + h * acc;  xo = fp32(yo)             (the step's result and the FSAL input)
+//   mode 3: part[2 blk] += ((acc h) / sc)^2, part[2 blk + 1] += (y / sc)^2, sc = atol + max(|y|, |ynew|) rtol
+//           (ynew null: sc = atol + |y| rtol); then ds_launch_ode_norm_final.
+//   t_next_out != null: t_next_out[0..B) = t_next (the next network evaluation's time; the pass reads the drift's time
+//   from tt [B], or the scalar t when tt is null).
+struct OdeArgs {
+  SdeP s;
+  const float* x; const float* score; const float* tt; float t; const float* smix;
+  float* kout; int kidx; int nk;
+  const float* k[DS_ODE_MAX_K]; double c[DS_ODE_MAX_K];
+  double h; int mode;
+  const double* y; const double* ynew; double* yo; float* xo;
+  double rtol, atol; double* part;
+  float* t_next_out; float t_next;
+  int B, S; long T;
+};
+int ds_launch_ode_stage(const OdeArgs& a, hipStream_t st, int* nblk = nullptr);
+// out[q] = sqrt(sum_blk part[2 blk + q]) / sqrt(n), q = 0, 1: the RMS norms of the last mode-3 pass (fixed order)
+int ds_launch_ode_norm_final(const double* part, int nblk, long n, double* out, hipStream_t st);
+int ds_launch_ode_cast(const float* x, double* y, long n, hipStream_t st);   // y = (double) x
+int ds_launch_ode_round(const double* y, float* x, long n, hipStream_t st);  // x = (float) y
 
 // time embedding: y[b][o] = sum_k act_in(x[b][k]) * W[o][k] + bias[o]   (fp32)
 int ds_launch_linear(const float* x, const float* W, const float* bias, float* y, int B, int K, int O, int silu_in,

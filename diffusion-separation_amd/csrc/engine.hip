@@ -522,6 +522,12 @@ struct diffsep_engine {
   std::vector<ProfRec> prof_done;  // the records of the last profile_begin .. profile_end span, with their times
   std::vector<ProfRec> prof_recs;
   std::vector<hipEvent_t> ev_pool;
+  // probability-flow ODE sampler (diffsep_ode_sample): y, y_new (fp64), K[7] (fp32), the partial-sum slab and the two
+  // norms, in one allocation made at the first ODE call (outside the arena: the PC sampler's plan does not change)
+  char* ode_buf = nullptr;
+  size_t ode_cap = 0;
+  double* ode_pin = nullptr;  // pinned readback of the norms (+ the event it waits on)
+  hipEvent_t ode_ev = nullptr;
 };
 #define DS_NCLS 12
 static hipEvent_t prof_event(diffsep_engine* e) {
@@ -1285,6 +1291,9 @@ extern "C" void diffsep_engine_destroy(diffsep_engine* e) {
   if (e->ext_pin) hipHostFree(e->ext_pin);
   if (e->ev_in) hipEventDestroy(e->ev_in);
   if (e->ev_out) hipEventDestroy(e->ev_out);
+  if (e->ode_buf) hipFree(e->ode_buf);
+  if (e->ode_pin) hipHostFree(e->ode_pin);
+  if (e->ode_ev) hipEventDestroy(e->ode_ev);
   delete e;
 }
 extern "C" int32_t diffsep_engine_reserve(diffsep_engine* e, int32_t B, int64_t T, void* stream) {
@@ -1339,7 +1348,9 @@ extern "C" int32_t diffsep_engine_debug_arena(const diffsep_engine* e, void** ba
   *base = e->arena; *bytes = (int64_t)e->cap; *fwd_base = (int64_t)e->fwd_base;
   return 0;
 }
-extern "C" int64_t diffsep_engine_device_bytes(const diffsep_engine* e) { return e ? e->weight_bytes + (int64_t)e->cap : 0; }
+extern "C" int64_t diffsep_engine_device_bytes(const diffsep_engine* e) {
+  return e ? e->weight_bytes + (int64_t)e->cap + (int64_t)e->ode_cap : 0;
+}
 extern "C" int32_t diffsep_engine_set_graph(diffsep_engine* e, int32_t enable) {
   DS_CHECK(e, "null engine");
   e->use_graph = enable;
@@ -1740,6 +1751,237 @@ extern "C" int32_t diffsep_pc_sample(diffsep_engine* e, const diffsep_sde_config
                                      const float* mix_norm, float* out, int32_t B, int64_t T, const float* noise,
                                      uint64_t seed, const float* timesteps_host, int32_t* nfe_out, void* stream) {
   return diffsep_pc_sample_ex(e, sde, smp, nullptr, mix_norm, out, B, T, noise, seed, timesteps_host, nfe_out, stream);
+}
+
+// ------------------------------------------------------------------ probability-flow ODE sampler
+// sdes.get_ode_sampler(...)() (reference sdes/__init__.py:193-278): scipy.integrate.solve_ivp(RK45 | RK23) on the
+// probability-flow ODE, the controller ported from scipy 1.15 (integrate/_ivp/rk.py RungeKutta._step_impl, common.py
+// select_initial_step / norm, base.py OdeSolver.step, ivp.py solve_ivp's loop) and run on the host; every stage is one
+// graph-replayed network evaluation (run_nfe) + one fused pass (ode.hip), every step attempt one pinned readback of its
+// error norm.
+static int ode_buffers(diffsep_engine* e, size_t n) {
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t need = 2 * al(n * 8) + DS_ODE_MAX_K * al(n * 4) + al(2 * DS_ODE_MAX_BLOCKS * 8) + 256;
+  if (need > e->ode_cap) {
+    if (e->ode_buf) {
+      DS_HIP(hipDeviceSynchronize());
+      DS_HIP(hipFree(e->ode_buf));
+    }
+    e->ode_buf = nullptr;
+    e->ode_cap = 0;
+    DS_HIP(hipMalloc((void**)&e->ode_buf, need));
+    e->ode_cap = need;
+  }
+  if (!e->ode_pin) DS_HIP(hipHostMalloc((void**)&e->ode_pin, 2 * sizeof(double), hipHostMallocDefault));
+  if (!e->ode_ev) DS_HIP(hipEventCreateWithFlags(&e->ode_ev, hipEventDisableTiming));
+  return 0;
+}
+
+extern "C" int32_t diffsep_ode_sample(diffsep_engine* e, const diffsep_sde_config* sde, const diffsep_ode_config* oc,
+                                      const float* mix_norm, const float* x_init, const float* noise, uint64_t seed,
+                                      float* out, int32_t B, int64_t T, diffsep_ode_info* info, void* stream) {
+  DS_CHECK(e && sde && oc && mix_norm && out, "ode_sample: null argument");
+  DS_CHECK(sde->kind == DIFFSEP_SDE_MIX || sde->kind == DIFFSEP_SDE_PRIORMIX, "ode_sample: unknown SDE kind");
+  DS_CHECK(sde->kind == DIFFSEP_SDE_MIX || sde->avg_len >= 1, "ode_sample: PriorMixSDE needs avg_len >= 1");
+  DS_CHECK(sde->ndim == e->cfg.num_sources, "ode_sample: sde.ndim != num_sources");
+  DS_CHECK(B >= 1 && T >= 1, "ode_sample: empty batch");
+  DS_CHECK(!(x_init && noise), "ode_sample: x_init and noise are alternatives");
+  double Ab[DS_ODE_MAX_K * DS_ODE_MAX_K], Bb[DS_ODE_MAX_K], Cb[DS_ODE_MAX_K], Eb[DS_ODE_MAX_K + 1];
+  int ns = 0, eorder = 0;
+  DS_CHECK(ds_ode_tableau(oc->method, nullptr, nullptr, nullptr, nullptr, &ns, &eorder) == 0,
+           "ode_sample: method must be DIFFSEP_ODE_RK45 or DIFFSEP_ODE_RK23 (DOP853 / Radau / BDF / LSODA are not implemented)");
+  {
+    double A0[6 * 6];
+    ds_ode_tableau(oc->method, A0, Bb, Cb, Eb, nullptr, nullptr);
+    for (int i = 0; i < ns; ++i) for (int j = 0; j < ns; ++j) Ab[i * DS_ODE_MAX_K + j] = A0[i * ns + j];
+  }
+  const double eps = oc->eps;
+  DS_CHECK(eps > 0.0 && eps < 1.0, "ode_sample: eps must be in (0, 1)");
+  DS_CHECK(oc->atol >= 0.0 && oc->rtol >= 0.0, "ode_sample: tolerances must be non-negative");
+  DS_CHECK(oc->N >= 1 || !oc->denoise, "ode_sample: the denoise step needs N >= 1");
+  DS_CHECK(oc->max_nfe >= 0, "ode_sample: max_nfe must be >= 0");
+  // common.validate_tol: rtol below 100 machine epsilons is raised to it (scipy warns)
+  const double rtol = std::max(oc->rtol, 100 * 2.220446049250313e-16), atol = oc->atol;
+  const double max_step = (oc->max_step > 0.0) ? oc->max_step : INFINITY;
+  const double t0 = 1.0, t_bound = eps, dir = -1.0, interval = std::fabs(t_bound - t0);  // sde.T = 1
+  DS_CHECK(oc->first_step <= 0.0 || oc->first_step <= interval, "ode_sample: first_step exceeds the interval (scipy: `first_step` exceeds bounds)");
+
+  StreamScope sc_(e, stream);
+  hipStream_t st = sc_.st;
+  const int S = e->cfg.num_sources;
+  if (ensure_plan(e, B, T, st)) return 1;
+  const size_t nst = (size_t)B * S * T;
+  if (ode_buffers(e, nst)) return 1;
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  char* p = e->ode_buf;
+  double* y = (double*)p; p += al(nst * 8);
+  double* ynew = (double*)p; p += al(nst * 8);
+  float* K[DS_ODE_MAX_K];
+  for (int j = 0; j < DS_ODE_MAX_K; ++j) { K[j] = (float*)p; p += al(nst * 4); }
+  double* part = (double*)p; p += al(2 * DS_ODE_MAX_BLOCKS * 8);
+  double* dnorm = (double*)p;
+  const SdeP sp{sde->kind, sde->ndim, sde->d_lambda, sde->sigma_min, sde->sigma_max};
+
+  // x_T -> st_x (and y = x_T in fp64)
+  DS_HIP(hipMemcpyAsync(e->st_mix, mix_norm, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
+  const float* smix = nullptr;
+  if (sde->kind == DIFFSEP_SDE_PRIORMIX) {
+    if (ds_launch_sigma_mix(e->st_mix, e->st_smix, B, T, sde->avg_len, st)) return 1;
+    smix = e->st_smix;
+  }
+  if (x_init) {
+    DS_HIP(hipMemcpyAsync(e->st_x, x_init, nst * 4, hipMemcpyDeviceToDevice, st));
+  } else {
+    const float* z = noise;
+    if (!z) {  // the PC sampler's prior draw of the same seed (its draw 0)
+      if (ds_launch_randn(e->st_noise, (long)nst, seed, 0, st)) return 1;
+      z = e->st_noise;
+    }
+    if (ds_launch_sde_prior(sp, e->st_mix, z, e->st_x, B, S, T, smix, st)) return 1;
+  }
+  if (ds_launch_ode_cast(e->st_x, y, (long)nst, st)) return 1;
+
+  OdeArgs base;
+  memset(&base, 0, sizeof(base));
+  base.s = sp; base.x = e->st_x; base.score = e->st_score; base.smix = smix;
+  base.rtol = rtol; base.atol = atol; base.part = part; base.B = B; base.S = S; base.T = T;
+  base.kidx = -1;
+  // the fused pass after the network evaluation at (float) t_eval: K[kout] = drift, then the combination `mode` of
+  // K[0..nk) with coefficients c, written for the next evaluation at (float) t_next (mode 3: the error scale from
+  // max(|y|, |y_new|), or from |y| alone in select_initial_step)
+  auto pass = [&](int kout, double t_eval, int mode, int nk, const double* c, double h, double t_next, int* nblk,
+                  bool scale_ynew = true) -> int {
+    OdeArgs a = base;
+    a.kout = kout >= 0 ? K[kout] : nullptr;
+    a.t = (float)t_eval;
+    a.kidx = (kout >= 0 && kout < nk) ? kout : -1;
+    a.nk = nk;
+    for (int j = 0; j < nk; ++j) { a.k[j] = K[j]; a.c[j] = c[j]; }
+    a.h = h; a.mode = mode; a.y = y;
+    if (mode == 1) a.xo = e->st_x;
+    if (mode == 2) { a.yo = ynew; a.xo = e->st_x; }
+    if (mode == 3 && scale_ynew) a.ynew = ynew;
+    if (mode == 1 || mode == 2) { a.t_next_out = e->st_t; a.t_next = (float)t_next; }
+    return hbm_launch_prof(e, st, "ode_stage (fused drift + RK stage)", 4.0 * nst * (2 + nk) + 8.0 * nst * (mode >= 2 ? 2 : 1),
+                           B, 1, (int)T, S, [&]() { return ds_launch_ode_stage(a, st, nblk); });
+  };
+  // the two norms of the last mode-3 pass -> host (stream-ordered pinned readback, waited on by its event)
+  auto read_norms = [&](int nblk, double* n0, double* n1) -> int {
+    if (ds_launch_ode_norm_final(part, nblk, (long)nst, dnorm, st)) return 1;
+    DS_HIP(hipMemcpyAsync(e->ode_pin, dnorm, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    DS_HIP(hipEventRecord(e->ode_ev, st));
+    DS_HIP(hipEventSynchronize(e->ode_ev));
+    *n0 = e->ode_pin[0];
+    if (n1) *n1 = e->ode_pin[1];
+    return 0;
+  };
+
+  int nfev = 0, n_acc = 0, n_rej = 0, status = 2;
+  double t = t0;
+  if (ds_launch_fill(e->st_t, (float)t, B, st)) return 1;
+  if (run_nfe(e, B, T, st)) return 1;
+  ++nfev;
+  double h_abs;
+  const double one = 1.0;
+  if (oc->first_step <= 0.0) {  // common.select_initial_step
+    const double pm[2] = {-1.0, 1.0};
+    int nb = 0;
+    double d0, d1, d2;
+    if (pass(0, t, 3, 1, &one, 1.0, 0.0, &nb, false)) return 1;  // K0 = f0; norm(f0 / scale), norm(y0 / scale)
+    if (read_norms(nb, &d1, &d0)) return 1;
+    double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+    h0 = std::min(h0, interval);
+    OdeArgs a = base;  // y1 = y0 + h0 * direction * f0
+    a.nk = 1; a.k[0] = K[0]; a.c[0] = 1.0; a.h = h0 * dir; a.mode = 1; a.y = y; a.xo = e->st_x;
+    a.t_next_out = e->st_t; a.t_next = (float)(t0 + h0 * dir);
+    if (ds_launch_ode_stage(a, st)) return 1;
+    if (run_nfe(e, B, T, st)) return 1;
+    ++nfev;
+    if (pass(1, t0 + h0 * dir, 3, 2, pm, 1.0, 0.0, &nb, false)) return 1;  // norm((f1 - f0) / scale)
+    if (read_norms(nb, &d2, nullptr)) return 1;
+    d2 = d2 / h0;
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0 * 1e-3)
+                                                   : std::pow(0.01 / std::max(d1, d2), 1.0 / (eorder + 1));
+    h_abs = std::min(std::min(100 * h0, h1), std::min(interval, max_step));
+  } else {
+    if (pass(0, t, 0, 0, nullptr, 0.0, 0.0, nullptr)) return 1;  // K0 = f0
+    h_abs = oc->first_step;
+  }
+
+  const double err_exp = -1.0 / (eorder + 1);
+  for (;;) {  // solve_ivp: while status is None: solver.step()
+    const double min_step = 10 * std::fabs(std::nextafter(t, dir * INFINITY) - t);
+    if (h_abs > max_step) h_abs = max_step;
+    else if (h_abs < min_step) h_abs = min_step;
+    bool accepted = false, rejected = false;
+    double t_new = t;
+    while (!accepted) {
+      if (h_abs < min_step) { status = -1; break; }
+      if (oc->max_nfe > 0 && nfev + ns > oc->max_nfe) { status = 1; break; }
+      double h = h_abs * dir;
+      t_new = t + h;
+      if (dir * (t_new - t_bound) > 0) t_new = t_bound;
+      h = t_new - t;
+      h_abs = std::fabs(h);
+      // rk_step: stage s input fp32(y + dot(K[:s].T, A[s,:s]) h) at t + C[s] h; y_new; f_new = f(t + h, y_new)
+      {
+        OdeArgs a = base;
+        a.nk = 1; a.k[0] = K[0]; a.c[0] = Ab[1 * DS_ODE_MAX_K]; a.h = h; a.mode = 1; a.y = y; a.xo = e->st_x;
+        a.t_next_out = e->st_t; a.t_next = (float)(t + Cb[1] * h);
+        if (hbm_launch_prof(e, st, "ode_stage (RK stage input)", 16.0 * nst, B, 1, (int)T, S,
+                            [&]() { return ds_launch_ode_stage(a, st); }))
+          return 1;
+      }
+      int nb = 0;
+      for (int s = 1; s <= ns; ++s) {
+        if (run_nfe(e, B, T, st)) return 1;
+        ++nfev;
+        const double ts = s < ns ? t + Cb[s] * h : t + h;
+        if (s < ns - 1) {
+          if (pass(s, ts, 1, s + 1, Ab + (s + 1) * DS_ODE_MAX_K, h, t + Cb[s + 1] * h, nullptr)) return 1;
+        } else if (s == ns - 1) {
+          if (pass(s, ts, 2, ns, Bb, h, t + h, nullptr)) return 1;
+        } else {
+          if (pass(s, ts, 3, ns + 1, Eb, h, 0.0, &nb)) return 1;
+        }
+      }
+      double err;
+      if (read_norms(nb, &err, nullptr)) return 1;
+      if (err < 1) {
+        double factor = err == 0 ? 10.0 : std::min(10.0, 0.9 * std::pow(err, err_exp));
+        if (rejected) factor = std::min(1.0, factor);
+        h_abs *= factor;
+        accepted = true;
+      } else {
+        h_abs *= std::max(0.2, 0.9 * std::pow(err, err_exp));
+        rejected = true;
+        ++n_rej;
+      }
+    }
+    if (!accepted) break;
+    std::swap(y, ynew);  // y <- y_new, f <- f_new: pointer swaps, no copies
+    std::swap(K[0], K[ns]);
+    base.y = y;
+    t = t_new;
+    ++n_acc;
+    if (dir * (t - t_bound) >= 0) { status = 0; break; }
+  }
+
+  // solution.y[:, -1] (the last accepted state) -> float32; optional denoise: x_mean of one reverse_diffusion step at
+  // eps without noise (reference denoise_update_fn; dt = 1/N, quirk Q1)
+  if (ds_launch_ode_round(y, e->st_x, (long)nst, st)) return 1;
+  if (oc->denoise) {
+    if (ds_launch_fill(e->st_t, (float)eps, B, st)) return 1;
+    if (run_nfe(e, B, T, st)) return 1;
+    if (ds_launch_sde_predictor(sp, oc->N, e->st_x, e->st_t, e->st_score, nullptr, e->st_xm, out, B, S, T, smix, 0, st))
+      return 1;
+  } else {
+    DS_HIP(hipMemcpyAsync(out, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
+  }
+  if (info) {
+    info->nfev = nfev; info->n_accepted = n_acc; info->n_rejected = n_rej; info->status = status; info->t_final = t;
+  }
+  return 0;
 }
 
 // ------------------------------------------------------------------ unit entry points

@@ -1,0 +1,325 @@
+// ode.hip — the passes of the probability-flow ODE sampler (reference sdes/__init__.py:193-278: get_ode_sampler, i.e.
+// scipy.integrate.solve_ivp(method="RK45" / "RK23") on  dx/dt = f(x,t) - 0.5 g(t)^2 score(x,t,mix), sdes/sdes.py:130-160).
+//
+// The solver state y / y_new is fp64 (scipy holds its state in float64), the stage derivatives K_j are fp32 (they are the
+// network's float32 drift, which is what scipy stores after its float64 round trip), and a stage input is
+// fp32(y + (sum_j a_j K_j) h) formed in fp64: the very numbers scipy's rk_step hands the reference's ode_func.
+// One thread = V consecutive time indices of one utterance x all sources (the drift couples the sources through
+// their mean); loads are float4 / 2 x double2 when the rows allow it (V = 4), grid-stride over a capped grid.
+// Contraction is off in this file: every sum and product rounds on its own, like numpy's, so that the stage inputs
+// can be reproduced bit for bit in float64 on the host (tests/test_ode_gpu.py).
+#include <string.h>
+
+#include <algorithm>
+
+#include "common.h"
+#include "../../include/diffsep_hip.h"
+
+#pragma clang fp contract(off)
+
+// ------------------------------------------------------------------ tableaux (scipy/integrate/_ivp/rk.py, scipy 1.15)
+int ds_ode_tableau(int method, double* A, double* B, double* C, double* E, int* n_stages, int* error_order) {
+  if (method == DIFFSEP_ODE_RK45) {  // Dormand-Prince 5(4)
+    static const double a[6][6] = {
+        {0, 0, 0, 0, 0, 0},
+        {1.0 / 5, 0, 0, 0, 0, 0},
+        {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
+        {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
+        {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
+        {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0}};
+    static const double b[6] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
+    static const double c[6] = {0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1};
+    static const double e[7] = {-71.0 / 57600, 0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
+    if (A) memcpy(A, a, sizeof(a));
+    if (B) memcpy(B, b, sizeof(b));
+    if (C) memcpy(C, c, sizeof(c));
+    if (E) memcpy(E, e, sizeof(e));
+    if (n_stages) *n_stages = 6;
+    if (error_order) *error_order = 4;
+    return 0;
+  }
+  if (method == DIFFSEP_ODE_RK23) {  // Bogacki-Shampine 3(2)
+    static const double a[3][3] = {{0, 0, 0}, {1.0 / 2, 0, 0}, {0, 3.0 / 4, 0}};
+    static const double b[3] = {2.0 / 9, 1.0 / 3, 4.0 / 9};
+    static const double c[3] = {0, 1.0 / 2, 3.0 / 4};
+    static const double e[4] = {5.0 / 72, -1.0 / 12, -1.0 / 9, 1.0 / 8};
+    if (A) memcpy(A, a, sizeof(a));
+    if (B) memcpy(B, b, sizeof(b));
+    if (C) memcpy(C, c, sizeof(c));
+    if (E) memcpy(E, e, sizeof(e));
+    if (n_stages) *n_stages = 3;
+    if (error_order) *error_order = 2;
+    return 0;
+  }
+  return -1;
+}
+
+// ------------------------------------------------------------------ vector loads / stores
+template <int V> __device__ inline void ldf(const float* p, float* v) {
+  if constexpr (V == 4) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+    v[0] = p[0];
+  }
+}
+template <int V> __device__ inline void stf(float* p, const float* v) {
+  if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else p[0] = v[0];
+}
+template <int V> __device__ inline void ldd(const double* p, double* v) {
+  if constexpr (V == 4) {
+    const double2 q0 = reinterpret_cast<const double2*>(p)[0], q1 = reinterpret_cast<const double2*>(p)[1];
+    v[0] = q0.x; v[1] = q0.y; v[2] = q1.x; v[3] = q1.y;
+  } else {
+    v[0] = p[0];
+  }
+}
+template <int V> __device__ inline void std_(double* p, const double* v) {
+  if constexpr (V == 4) {
+    reinterpret_cast<double2*>(p)[0] = make_double2(v[0], v[1]);
+    reinterpret_cast<double2*>(p)[1] = make_double2(v[2], v[3]);
+  } else {
+    p[0] = v[0];
+  }
+}
+
+// ------------------------------------------------------------------ the fused pass (see OdeArgs in common.h)
+template <int V>
+__global__ __launch_bounds__(256) void ode_stage_kernel(OdeArgs a) {
+  __shared__ double sh[2][4];
+  const int S = a.S;
+  const long T = a.T, TV = T / V;
+  const long items = (long)a.B * TV;
+  if (a.t_next_out && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < a.B; i += 256) a.t_next_out[i] = a.t_next;
+  double q0 = 0.0, q1 = 0.0;
+  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
+    const int b = (int)(it / TV);
+    const long t0 = (it - (long)b * TV) * V;
+    float kd[DS_MAX_SRC][V];
+    if (a.kout) {
+      // the drift of sde_coeff_kernel (f, g through the same helpers), then rev_f = f - g g score 0.5 in the operation
+      // order of sde_reverse_kernel (RSDE.sde with probability_flow = True, sdes/sdes.py:130-160)
+      float xv[DS_MAX_SRC][V];
+#pragma unroll
+      for (int s = 0; s < DS_MAX_SRC; ++s)
+        if (s < S) ldf<V>(a.x + ((long)b * S + s) * T + t0, xv[s]);
+      const float g0 = sde_g_of_t(a.s, a.tt ? a.tt[b] : a.t);
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        float xs[DS_MAX_SRC], f[DS_MAX_SRC];
+#pragma unroll
+        for (int s = 0; s < DS_MAX_SRC; ++s) xs[s] = s < S ? xv[s][v] : 0.f;
+        sde_mix_drift(a.s, xs, f, S);
+#pragma unroll
+        for (int s = 0; s < DS_MAX_SRC; ++s)
+          if (s < S) kd[s][v] = f[s];
+      }
+#pragma unroll
+      for (int s = 0; s < DS_MAX_SRC; ++s) {
+        if (s >= S) continue;
+        const long o = ((long)b * S + s) * T + t0;
+        float sc[V];
+        ldf<V>(a.score + o, sc);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const float g = a.smix ? g0 * a.smix[(long)b * T + t0 + v] : g0;
+          kd[s][v] = kd[s][v] - g * g * sc[v] * 0.5f;
+        }
+        stf<V>(a.kout + o, kd[s]);
+      }
+    }
+    if (a.mode == 0) continue;
+#pragma unroll
+    for (int s = 0; s < DS_MAX_SRC; ++s) {
+      if (s >= S) continue;
+      const long o = ((long)b * S + s) * T + t0;
+      double yv[V], acc[V];
+      ldd<V>(a.y + o, yv);
+#pragma unroll
+      for (int v = 0; v < V; ++v) acc[v] = 0.0;
+      for (int j = 0; j < a.nk; ++j) {
+        float kv[V];
+        if (j == a.kidx) {
+#pragma unroll
+          for (int v = 0; v < V; ++v) kv[v] = kd[s][v];
+        } else {
+          ldf<V>(a.k[j] + o, kv);
+        }
+        const double cj = a.c[j];
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[v] = acc[v] + cj * (double)kv[v];
+      }
+      if (a.mode == 1) {  // rk_step: fun(t + c h, y + dot(K[:s].T, a[:s]) * h)
+        float xo[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) xo[v] = (float)(yv[v] + acc[v] * a.h);
+        stf<V>(a.xo + o, xo);
+      } else if (a.mode == 2) {  // rk_step: y_new = y + h * dot(K[:-1].T, B)
+        double yn[V];
+        float xo[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          yn[v] = yv[v] + a.h * acc[v];
+          xo[v] = (float)yn[v];
+        }
+        std_<V>(a.yo + o, yn);
+        if (a.xo) stf<V>(a.xo + o, xo);
+      } else {  // _estimate_error_norm: norm(dot(K.T, E) * h / (atol + max(|y|, |y_new|) rtol))
+        double yn[V];
+        if (a.ynew) ldd<V>(a.ynew + o, yn);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const double m = a.ynew ? fmax(fabs(yv[v]), fabs(yn[v])) : fabs(yv[v]);
+          const double scale = a.atol + m * a.rtol;
+          const double d = (acc[v] * a.h) / scale;
+          const double dy = yv[v] / scale;
+          q0 = q0 + d * d;
+          q1 = q1 + dy * dy;
+        }
+      }
+    }
+  }
+  if (a.mode != 3) return;
+  // per-block partials, fixed order (no float atomics): wave butterfly, then the 4 waves in order
+  q0 = wave_sum_d(q0);
+  q1 = wave_sum_d(q1);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) { sh[0][w] = q0; sh[1][w] = q1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r0 = 0.0, r1 = 0.0;
+    for (int i = 0; i < 4; ++i) { r0 = r0 + sh[0][i]; r1 = r1 + sh[1][i]; }
+    a.part[2 * blockIdx.x] = r0;
+    a.part[2 * blockIdx.x + 1] = r1;
+  }
+}
+
+__global__ __launch_bounds__(256) void ode_norm_final_kernel(const double* __restrict__ part, int nblk, long n,
+                                                             double* __restrict__ out) {
+  __shared__ double sh[2][4];
+  double r[2] = {0.0, 0.0};
+  for (int i = threadIdx.x; i < nblk; i += 256) { r[0] = r[0] + part[2 * i]; r[1] = r[1] + part[2 * i + 1]; }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int q = 0; q < 2; ++q) {
+    const double v = wave_sum_d(r[q]);
+    if (lane == 0) sh[q][w] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    double s = 0.0;
+    for (int i = 0; i < 4; ++i) s = s + sh[threadIdx.x][i];
+    out[threadIdx.x] = sqrt(s) / sqrt((double)n);  // common.norm: ||x||_2 / sqrt(x.size)
+  }
+}
+
+__global__ __launch_bounds__(256) void ode_cast_kernel(const float* __restrict__ x, double* __restrict__ y, long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) y[i] = (double)x[i];
+}
+__global__ __launch_bounds__(256) void ode_round_kernel(const double* __restrict__ y, float* __restrict__ x, long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] = (float)y[i];
+}
+
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int ds_launch_ode_stage(const OdeArgs& a, hipStream_t st, int* nblk) {
+  DS_CHECK(a.S >= 1 && a.S <= DS_MAX_SRC && a.B >= 1 && a.T >= 1, "ode: bad shape");
+  DS_CHECK(a.nk >= 0 && a.nk <= DS_ODE_MAX_K && a.kidx < a.nk && (a.kidx < 0 || a.kout), "ode: bad stage combination");
+  DS_CHECK(a.mode >= 0 && a.mode <= 3, "ode: bad mode");
+  DS_CHECK(!a.kout || (a.x && a.score && (a.tt || a.t > 0.f)), "ode: the drift needs x, t and the score");
+  DS_CHECK(a.mode == 0 || a.y, "ode: the stage combination needs y");
+  DS_CHECK(a.mode != 1 || a.xo, "ode: stage mode needs x_out");
+  DS_CHECK(a.mode != 2 || a.yo, "ode: y_new mode needs y_new_out");
+  DS_CHECK(a.mode != 3 || a.part, "ode: error mode needs the partial-sum slab");
+  for (int j = 0; j < a.nk; ++j) DS_CHECK(j == a.kidx || a.k[j], "ode: null stage derivative");
+  bool vec = a.T % 4 == 0;
+  const void* ps[] = {a.x, a.score, a.kout, a.y, a.ynew, a.yo, a.xo};
+  for (const void* p : ps) vec = vec && al16(p);
+  for (int j = 0; j < a.nk; ++j) vec = vec && al16(a.k[j]);
+  const int V = vec ? 4 : 1;
+  const long items = (long)a.B * (a.T / V);
+  const int nb = (int)std::min<long>(cdiv(items, 256), DS_ODE_MAX_BLOCKS);
+  if (vec) hipLaunchKernelGGL(ode_stage_kernel<4>, dim3(nb), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(ode_stage_kernel<1>, dim3(nb), dim3(256), 0, st, a);
+  DS_LAUNCH_CHECK();
+  if (nblk) *nblk = nb;
+  return 0;
+}
+int ds_launch_ode_norm_final(const double* part, int nblk, long n, double* out, hipStream_t st) {
+  hipLaunchKernelGGL(ode_norm_final_kernel, dim3(1), dim3(256), 0, st, part, nblk, n, out);
+  DS_LAUNCH_CHECK();
+  return 0;
+}
+int ds_launch_ode_cast(const float* x, double* y, long n, hipStream_t st) {
+  const int nb = (int)std::min<long>(cdiv(n, 256), 4096);
+  hipLaunchKernelGGL(ode_cast_kernel, dim3(nb), dim3(256), 0, st, x, y, n);
+  DS_LAUNCH_CHECK();
+  return 0;
+}
+int ds_launch_ode_round(const double* y, float* x, long n, hipStream_t st) {
+  const int nb = (int)std::min<long>(cdiv(n, 256), 4096);
+  hipLaunchKernelGGL(ode_round_kernel, dim3(nb), dim3(256), 0, st, y, x, n);
+  DS_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------ C-ABI: tableau + unit entry points
+extern "C" int32_t diffsep_ode_tableau(int32_t method, double* A, double* B, double* C, double* E, int32_t* n_stages,
+                                       int32_t* error_order) {
+  int ns = 0, eo = 0;
+  DS_CHECK(ds_ode_tableau(method, A, B, C, E, &ns, &eo) == 0, "ode_tableau: method must be RK45 (0) or RK23 (1)");
+  if (n_stages) *n_stages = ns;
+  if (error_order) *error_order = eo;
+  return 0;
+}
+
+static int unit_args(OdeArgs& a, const diffsep_sde_config* sde, const float* x, const float* t, const float* score,
+                     const float* sigma_mix, const double* y, const float* const* K, const double* coef, int32_t n_k,
+                     int32_t k_out, double h, int32_t B, int32_t S, int64_t T) {
+  DS_CHECK(n_k >= 0 && n_k <= DS_ODE_MAX_K && k_out < DS_ODE_MAX_K && (n_k == 0 || (K && coef)) &&
+               (k_out < 0 || (K && K[k_out])),
+           "ode unit: bad stage list");
+  memset(&a, 0, sizeof(a));
+  if (sde) a.s = SdeP{sde->kind, sde->ndim, sde->d_lambda, sde->sigma_min, sde->sigma_max};
+  DS_CHECK(k_out < 0 || (sde && (sde->kind == 1) == (sigma_mix != nullptr)),
+           "ode unit: the drift needs the SDE (PriorMixSDE with sigma_mix, MixSDE without)");
+  a.x = x; a.score = score; a.tt = t; a.smix = sigma_mix;
+  a.kout = k_out >= 0 ? const_cast<float*>(K[k_out]) : nullptr;
+  a.kidx = k_out < n_k ? k_out : -1;
+  a.nk = n_k;
+  for (int j = 0; j < n_k; ++j) { a.k[j] = K[j]; a.c[j] = coef[j]; }
+  a.h = h; a.y = y; a.B = B; a.S = S; a.T = T;
+  return 0;
+}
+
+extern "C" int32_t diffsep_ode_stage_update(const diffsep_sde_config* sde, const float* x, const float* t,
+                                            const float* score, const float* sigma_mix, const double* y,
+                                            float* const* K, const double* coef, int32_t n_k, int32_t k_out, double h,
+                                            float* x_out, double* y_new_out, int32_t B, int32_t S, int64_t T,
+                                            void* stream) {
+  OdeArgs a;
+  if (unit_args(a, sde, x, t, score, sigma_mix, y, K, coef, n_k, k_out, h, B, S, T)) return 1;
+  DS_CHECK(k_out < 0 || t, "ode_stage_update: null t");
+  a.mode = n_k == 0 ? 0 : (y_new_out ? 2 : 1);
+  a.xo = x_out; a.yo = y_new_out;
+  return ds_launch_ode_stage(a, (hipStream_t)stream);
+}
+
+extern "C" int32_t diffsep_ode_error_norm(const diffsep_sde_config* sde, const float* x, const float* t,
+                                          const float* score, const float* sigma_mix, const double* y,
+                                          const double* y_new, float* const* K, const double* coef, int32_t n_k,
+                                          int32_t k_out, double h, double rtol, double atol, double* norms_out,
+                                          int32_t B, int32_t S, int64_t T, void* workspace, int64_t workspace_bytes,
+                                          void* stream) {
+  OdeArgs a;
+  if (unit_args(a, sde, x, t, score, sigma_mix, y, K, coef, n_k, k_out, h, B, S, T)) return 1;
+  DS_CHECK(k_out < 0 || t, "ode_error_norm: null t");
+  DS_CHECK(norms_out && workspace && workspace_bytes >= DIFFSEP_ODE_WORKSPACE_BYTES && n_k >= 1,
+           "ode_error_norm: bad argument (workspace >= DIFFSEP_ODE_WORKSPACE_BYTES)");
+  a.mode = 3;
+  a.ynew = y_new; a.rtol = rtol; a.atol = atol; a.part = (double*)workspace;
+  int nb = 0;
+  if (ds_launch_ode_stage(a, (hipStream_t)stream, &nb)) return 1;
+  return ds_launch_ode_norm_final(a.part, nb, (long)B * S * T, norms_out, (hipStream_t)stream);
+}

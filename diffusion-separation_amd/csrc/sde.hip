@@ -209,14 +209,13 @@ __global__ __launch_bounds__(256) void sde_coeff_kernel(SdeP s, const float* x, 
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   if (t >= T) return;
-  const float r = s.sigma_max / s.sigma_min;
-  const float g = s.sigma_min * powf(r, tt[b]) * sqrtf(2.0f * logf(r));
-  float xv[DS_MAX_SRC], mx = 0.f;
-  for (int i = 0; i < S; ++i) { xv[i] = x[((long)b * S + i) * T + t]; mx += xv[i]; }
-  mx /= (float)S;
+  const float g = sde_g_of_t(s, tt[b]);
+  float xv[DS_MAX_SRC], f[DS_MAX_SRC];
+  for (int i = 0; i < S; ++i) xv[i] = x[((long)b * S + i) * T + t];
+  sde_mix_drift(s, xv, f, S);
   for (int i = 0; i < S; ++i) {
     const long o = ((long)b * S + i) * T + t;
-    drift[o] = (-s.d_lambda * (xv[i] - mx)) * fs;
+    drift[o] = f[i] * fs;
     if (smix) diffusion[o] = (g * smix[(long)b * T + t]) * gs;
   }
   if (!smix && t == 0) diffusion[b] = g * gs;

@@ -39,6 +39,22 @@ class SamplerExt(C.Structure):
                 ("tail_engine", C.c_void_p), ("tail_steps", C.c_int32), ("head_steps", C.c_int32)]
 
 
+ODE_RK45, ODE_RK23 = 0, 1
+ODE_METHODS = {"RK45": ODE_RK45, "RK23": ODE_RK23}
+ODE_WORKSPACE_BYTES = 16384
+
+
+class OdeConfig(C.Structure):  # diffsep_ode_config
+    _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("eps", C.c_double), ("first_step", C.c_double),
+                ("max_step", C.c_double), ("method", C.c_int32), ("max_nfe", C.c_int32), ("denoise", C.c_int32),
+                ("N", C.c_int32)]
+
+
+class OdeInfo(C.Structure):  # diffsep_ode_info
+    _fields_ = [("nfev", C.c_int32), ("n_accepted", C.c_int32), ("n_rejected", C.c_int32), ("status", C.c_int32),
+                ("t_final", C.c_double)]
+
+
 class ProfRecord(C.Structure):  # diffsep_prof_record
     _fields_ = [("kernel", C.c_char * 128), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32),
                 ("Cout", C.c_int32), ("taps", C.c_int32), ("skip_cin", C.c_int32), ("has_res", C.c_int32),
@@ -73,6 +89,13 @@ _SIGS = {
                                C.POINTER(_I), _P]),
     "diffsep_pc_sample_ex": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(SamplerConfig), C.POINTER(SamplerExt), _P, _P, _I,
                                   _L, _P, _U64, _P, C.POINTER(_I), _P]),
+    "diffsep_ode_sample": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(OdeConfig), _P, _P, _P, _U64, _P, _I, _L,
+                                C.POINTER(OdeInfo), _P]),
+    "diffsep_ode_tableau": (_I, [_I, _P, _P, _P, _P, C.POINTER(_I), C.POINTER(_I)]),
+    "diffsep_ode_stage_update": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_double, _P, _P, _I,
+                                      _I, _L, _P]),
+    "diffsep_ode_error_norm": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_double,
+                                    C.c_double, C.c_double, _P, _I, _I, _L, _P, _L, _P]),
     "diffsep_engine_set_graph": (_I, [_P, _I]),
     "diffsep_set_option": (_I, [C.c_char_p, _L]),
     "diffsep_engine_set_option": (_I, [_P, C.c_char_p, _L]),
@@ -169,3 +192,18 @@ def model_config(nf=64, num_sources=2, ch_mult=(1, 1, 2, 2, 2, 2, 2), num_res_bl
     c.num_res_blocks, c.attn_resolution, c.n_fft, c.hop = num_res_blocks, attn_resolution, n_fft, hop
     c.spec_abs_exponent, c.spec_factor, c.dtype = spec_abs_exponent, spec_factor, dtype
     return c
+
+
+def ode_tableau(method="RK45"):
+    """(A [ns,ns], B [ns], C [ns], E [ns+1], n_stages, error_estimator_order) of diffsep_ode_tableau: the Butcher tableau
+    the device solver uses, as scipy's rk.py holds it.  Host code only (no GPU needed)."""
+    import numpy as np
+    l = lib()
+    code = ODE_METHODS[method]
+    ns, eo = C.c_int32(), C.c_int32()
+    check(l.diffsep_ode_tableau(code, None, None, None, None, C.byref(ns), C.byref(eo)), l)
+    n = ns.value
+    A, B, Cc, E = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros(n + 1)
+    check(l.diffsep_ode_tableau(code, A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
+                                Cc.ctypes.data_as(C.c_void_p), E.ctypes.data_as(C.c_void_p), None, None), l)
+    return A, B, Cc, E, n, eo.value

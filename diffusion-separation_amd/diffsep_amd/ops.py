@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import F32_SPLIT, F32, BF16, SdeConfig, SDE_MIX, check, lib
+from ._lib import F32_SPLIT, F32, BF16, ODE_WORKSPACE_BYTES, SdeConfig, SDE_MIX, check, lib
 from .engine import _ptr, _stream_ptr
 
 
@@ -400,4 +400,39 @@ def gram(ref, est):
     B, S, T = ref.shape
     out = torch.empty((B, 3, S, S), dtype=torch.float64, device=ref.device)
     check(lib().diffsep_gram(_ptr(ref.contiguous()), _ptr(est.contiguous()), _ptr(out), B, S, T, _stream_ptr()))
+    return out
+
+
+def _ode_ptrs(K):
+    return (C.c_void_p * max(1, len(K)))(*[k.data_ptr() for k in K])
+
+
+def ode_stage_update(sde, K, coef, h, y, k_out=-1, x=None, t=None, score=None, sigma_mix=None, x_out=None,
+                     y_new_out=None):
+    """diffsep_ode_stage_update: K[k_out] = probability-flow drift of (x, t, score) (k_out >= 0), then with
+    acc = sum_j coef[j] K[j]: x_out = fp32(y + acc h), or (y_new_out given) y_new_out = y + h acc and x_out = fp32 of it.
+    K: list of float32 [B,S,T] tensors (written in place at k_out); y float64 [B,S,T]."""
+    B, S, T = K[0].shape
+    c = np.ascontiguousarray(coef, dtype=np.float64)
+    assert len(c) <= len(K) and k_out < len(K) and all(k.shape == (B, S, T) and k.dtype == torch.float32 for k in K)
+    sc = _sde(sde)
+    check(lib().diffsep_ode_stage_update(C.byref(sc), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y),
+                                         _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), float(h),
+                                         _ptr(x_out), _ptr(y_new_out), B, S, T, _stream_ptr()))
+    return x_out, y_new_out
+
+
+def ode_error_norm(sde, K, coef, h, y, rtol, atol, y_new=None, k_out=-1, x=None, t=None, score=None, sigma_mix=None):
+    """diffsep_ode_error_norm: float64 [2] device tensor (||acc h / sc||_rms, ||y / sc||_rms), sc = atol + max(|y|,
+    |y_new|) rtol; with k_out >= 0 the drift K[k_out] is produced in the same pass."""
+    B, S, T = K[0].shape
+    c = np.ascontiguousarray(coef, dtype=np.float64)
+    assert len(c) <= len(K) and k_out < len(K) and all(k.shape == (B, S, T) and k.dtype == torch.float32 for k in K)
+    out = torch.empty(2, dtype=torch.float64, device=K[0].device)
+    ws = torch.empty(ODE_WORKSPACE_BYTES, dtype=torch.uint8, device=K[0].device)
+    sc = _sde(sde)
+    check(lib().diffsep_ode_error_norm(C.byref(sc), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y), _ptr(y_new),
+                                       _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), float(h),
+                                       float(rtol), float(atol), _ptr(out), B, S, T, _ptr(ws), ws.numel(),
+                                       _stream_ptr()))
     return out

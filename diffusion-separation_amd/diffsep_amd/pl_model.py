@@ -243,6 +243,15 @@ class DiffSepModel:
     __call__ = forward
 
     # ---- sampler factory (pl_model.py:687-759) ---------------------------------------------
+    def get_ode_sampler(self, y, N=None, **kwargs):
+        """sdes.get_ode_sampler on this model (reference sdes/__init__.py:193-278): eps defaults to t_eps, the denoise
+        step's N to sde.N.  No overflow rerun: a 16-bit model's samples come back as they are (see the docstring of
+        sdes.get_ode_sampler for the cost of 16-bit engines; dtype="hybrid" runs every evaluation on its split engine)."""
+        sde = self.sde.copy()
+        sde.N = self.sde.N if N is None else N
+        kwargs = {"eps": self.t_eps, **kwargs}
+        return sdes.get_ode_sampler(sde, self, y, **kwargs)
+
     def get_pc_sampler(self, predictor_name, corrector_name, y, N=None, minibatch=None, schedule=None, check_finite=True,
                        **kwargs):
         """check_finite (extension): the returned sampler looks at its samples and repeats the request on fallback_model()

@@ -1,6 +1,7 @@
 """Sampler factories with the reference signatures (sdes/__init__.py:46-190).
 
-get_pc_sampler(...) returns a closure `pc_sampler() -> (x, nfe[, intermediates])`.  When score_fn is an
+get_pc_sampler(...) returns a closure `pc_sampler() -> (x, nfe[, intermediates])`; get_ode_sampler(...) returns
+`ode_sampler(z=None) -> (x, nfe)`, the probability-flow ODE integrated by the engine's device-resident RK45 / RK23.  When score_fn is an
 engine-backed model and the request is the default path (reverse_diffusion + ald2/none, no
 intermediates) the whole loop runs as ONE engine call (hipGraph-replayed network evaluations, fused
 update kernels, on-device Philox noise seeded from torch's generator); otherwise the generic
@@ -10,12 +11,14 @@ import math
 
 import torch
 
+from .. import _lib
+
 from .correctors import Corrector, CorrectorRegistry
 from .predictors import Predictor, PredictorRegistry, ReverseDiffusionPredictor
 from .sdes import MixSDE, PriorMixSDE, SDERegistry
 
 __all__ = ["PredictorRegistry", "CorrectorRegistry", "SDERegistry", "Predictor", "Corrector", "MixSDE", "PriorMixSDE",
-           "get_pc_sampler", "get_pc_scheduled_sampler"]
+           "get_pc_sampler", "get_pc_scheduled_sampler", "get_ode_sampler"]
 
 
 def _timesteps(sde, eps, schedule, device):
@@ -128,3 +131,61 @@ def get_pc_scheduled_sampler(predictor_name, corrector_name, sde, score_fn, y, d
     return _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, denoise, eps, snr,
                          corrector_steps, probability_flow, intermediate, schedule, seed=kwargs.get("seed"),
                          lengths=kwargs.get("lengths"), seeds=kwargs.get("seeds"))
+
+
+_ODE_KWARGS = ("first_step", "max_step", "max_nfe", "seed", "noise")
+
+
+def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e-5, atol=1e-5, method="RK45", eps=3e-2,
+                    device="cuda", **kwargs):
+    """Reference: sdes/__init__.py:193-278 — the probability-flow ODE dx/dt = f(x,t) - 0.5 G(t)^2 score(x,t,y)
+    (RSDE.sde with probability_flow=True) from t = sde.T down to eps with scipy's solve_ivp(method), then (denoise) one
+    reverse_diffusion predictor step at eps without noise, its x_mean.  Here the whole solve is ONE engine call
+    (Engine.ode_sample): scipy's RK45 / RK23 controller on the host, the state [B,S,T] real and resident on the device
+    (fp64 solver state, fp32 network drift), every network evaluation a replayed hipGraph.  The batch is one ODE system
+    with one error norm and one step size, as in the reference.  Differences from the reference:
+    its ode_func reshapes the state to y.shape ([B,1,T], Q11) and casts it to complex64 (Q12), which makes it fail on
+    DiffSep; neither is reproduced.
+
+    method: "RK45" / "RK23" (other solve_ivp methods raise NotImplementedError); device: accepted and ignored.
+    **kwargs: solve_ivp's first_step / max_step, and the extensions max_nfe (no step attempt starts that would take the
+    evaluation count above it), seed (device RNG seed of the prior draw; default: drawn from torch's generator) and
+    noise ([B,S,T] draws of the prior).  Anything else raises TypeError.
+
+    Cost: every network evaluation runs on the score function's engine; on a dtype="hybrid" model all of them run on its
+    split-precision engine.  A 16-bit (f16 / bf16) model runs as it is, and that is costly: the score's rounding noise
+    (~3e-3 relative per evaluation) enters the embedded error estimate, which can shrink the step far below what the
+    fp32 drift needs at tight tolerances — bound the work with max_nfe.
+
+    The returned ode_sampler(z=None) -> (x, nfe): z [B,S,T] is used as x_T when given (the reference documents z as the
+    latent code and ignores it); nfe is solve_ivp's nfev (the denoise evaluation is not counted).  After a call,
+    ode_sampler.info holds nfev, n_accepted, n_rejected, status (0 reached eps, -1 step too small, 1 max_nfe) and t_final.
+    """
+    if method not in _lib.ODE_METHODS:
+        raise NotImplementedError(f"get_ode_sampler: method '{method}' is not implemented on the engine (RK45, RK23)")
+    bad = sorted(set(kwargs) - set(_ODE_KWARGS))
+    if bad:
+        raise TypeError(f"get_ode_sampler() got unexpected keyword argument(s) {bad} (accepted: {list(_ODE_KWARGS)})")
+    if not isinstance(sde, MixSDE):
+        raise TypeError("get_ode_sampler: sde must be a MixSDE / PriorMixSDE")
+    tail = getattr(score_fn, "tail_engine", None)
+    eng = (tail() if callable(tail) else None) or _engine_of(score_fn)
+    if eng is None:
+        raise ValueError("get_ode_sampler: score_fn has no engine (an engine-backed DiffSepModel / ScoreModelNCSNpp is "
+                         "needed; the ODE sampler has no host fallback)")
+    seed, noise_ = kwargs.get("seed"), kwargs.get("noise")
+
+    def ode_sampler(z=None, **_):
+        with torch.no_grad():
+            s_ = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+            x, info = eng.ode_sample(y, sde.engine_config(), method=method, rtol=rtol, atol=atol, eps=eps,
+                                     first_step=kwargs.get("first_step"), max_step=kwargs.get("max_step"),
+                                     max_nfe=kwargs.get("max_nfe") or 0, denoise=denoise, N=sde.N, x_init=z,
+                                     noise=noise_ if z is None else None, seed=s_)
+            ode_sampler.info = info
+            if inverse_scaler is not None:
+                x = inverse_scaler(x)
+            return x, info["nfev"]
+
+    ode_sampler.info = None
+    return ode_sampler

@@ -10,7 +10,9 @@ available (there is no network here: the HF default 'fakufaku/diffsep' cannot be
 hybrid), --batch B: files whose padded spectrogram width is equal share one engine call (zero-padded to the longest,
 each file's tail kept at zero by the engine: evaluate.py has the details), --streams K engine calls in flight on K
 engines / HIP streams, and --seed (file i of the sorted folder then gets the i-th draw of that generator as its device
-RNG seed: the written files do not depend on --batch or --streams).  Output files are 32-bit float WAV like
+RNG seed: the written files do not depend on --batch or --streams).  --sampler ode [--rtol --atol --max-nfe] runs the
+probability-flow ODE sampler (sdes.get_ode_sampler, adaptive RK45 on the device) instead of the PC sampler, one file
+per engine call (the batch is one ODE system with one step size).  Output files are 32-bit float WAV like
 torchaudio.save of a float tensor (separate.py:160-162).
 """
 import argparse
@@ -78,6 +80,20 @@ def separate_on_device(mix, model, sampler_kwargs, device, lengths=None, seeds=N
     return out
 
 
+def separate_ode(mix, model, ode_kwargs, device, seed=None):
+    """mix [1,T] / [B,1,T] through the probability-flow ODE sampler (DiffSepModel.get_ode_sampler); the same
+    normalisation and output scaling as the PC path.  Returns (device tensor [B,S,T], nfe)."""
+    mix = mix.to(device)
+    if mix.dim() == 2:
+        mix = mix[None]
+    (mix_norm, _), *_ = model.normalize_batch((mix, None))
+    kw = dict(ode_kwargs)
+    if seed is not None:
+        kw["seed"] = seed
+    sep, nfe = model.get_ode_sampler(mix_norm, **kw)()
+    return scale_output(mix, sep), nfe
+
+
 def separate(mix, model, sampler_kwargs, device):
     """mix [1,T] (one file, like the reference) or [B,1,T] (a batch of equal-length files)."""
     return separate_on_device(mix, model, sampler_kwargs, device, check_finite=True).cpu()
@@ -104,7 +120,16 @@ def main(argv=None):
     ap.add_argument("--streams", type=int, default=1, help="engine calls in flight: K engines on K HIP streams")
     ap.add_argument("--seed", type=int, default=None,
                     help="file i (sorted) gets the i-th draw of a generator with this seed as its device RNG seed")
+    ap.add_argument("--sampler", default="pc", choices=["pc", "ode"],
+                    help="pc (default): the reference's predictor-corrector sampler; ode: the probability-flow ODE "
+                         "(adaptive RK45, sdes.get_ode_sampler), one file per engine call")
+    ap.add_argument("--rtol", type=float, default=1e-5, help="--sampler ode: relative tolerance (reference default)")
+    ap.add_argument("--atol", type=float, default=1e-5, help="--sampler ode: absolute tolerance (reference default)")
+    ap.add_argument("--max-nfe", type=int, default=0,
+                    help="--sampler ode: no step attempt starts beyond this many network evaluations (0: unbounded)")
     args = ap.parse_args(argv)
+    if args.sampler == "ode" and (args.batch > 1 or args.streams > 1):
+        raise SystemExit("--sampler ode runs one file per engine call: --batch and --streams must be 1")
     K = max(1, args.streams)
     if K > 1:  # (see evaluate.py: hardware queues; must precede the first torch.cuda call)
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
@@ -126,6 +151,24 @@ def main(argv=None):
     args.output_dir.mkdir(parents=True, exist_ok=True)
     files = sorted(args.input_dir.glob("*.wav"))
     lengths = [wavio.info(p)[1] for p in files]
+    seeds = None
+    if args.seed is not None:
+        seeds = torch.randint(0, 2 ** 62, (max(len(files), 1),),
+                              generator=torch.Generator().manual_seed(args.seed)).tolist()
+    if args.sampler == "ode":
+        ode_kw = {"N": kw["N"], "denoise": args.denoise, "rtol": args.rtol, "atol": args.atol, "max_nfe": args.max_nfe}
+        for i, f in enumerate(files):
+            wav, sr = wavio.load(f)
+            if sr != model_sr:  # the reference only warns (separate.py:151-155, quirk Q9)
+                print(f"Warning: {f.stem}: this model expects {model_sr} Hz, but the file is {sr} Hz.")
+            sep, _ = separate_ode(wav[:1], model, ode_kw, args.device, seed=seeds[i] if seeds is not None else None)
+            sep = sep.cpu()
+            for k in range(sep.shape[1]):
+                d = args.output_dir / f"s{k}"
+                d.mkdir(parents=True, exist_ok=True)
+                wavio.save(d / f"{f.stem}.wav", sep[0, k:k + 1], sr, bits=32)
+        print(f"separated {len(files)} files into {args.output_dir} (probability-flow ODE)")
+        return
     eng = model.score_model.engine()
     from .evaluate import plan_batches
     batches = plan_batches(range(len(files)), lengths, eng.padded_frames, max(1, args.batch))
@@ -135,10 +178,6 @@ def main(argv=None):
             m.score_model.engine().reserve(max(len(g) for g in batches), tmax)
             if m.tail_engine() is not None:
                 m.tail_engine().reserve(max(len(g) for g in batches), tmax)
-    seeds = None
-    if args.seed is not None:
-        seeds = torch.randint(0, 2 ** 62, (max(len(files), 1),),
-                              generator=torch.Generator().manual_seed(args.seed)).tolist()
     streams = [torch.cuda.Stream() for _ in range(K)] if K > 1 else [torch.cuda.current_stream()]
     in_flight = [None] * K  # per worker: (file indices, lengths, sample rates, device result) of its running batch
 

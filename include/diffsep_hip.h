@@ -58,6 +58,10 @@ extern "C" {
 #define DIFFSEP_CORR_ALD 2      /* sdes/correctors.py:58-91 (MixSDE only) */
 #define DIFFSEP_CORR_LANGEVIN 3 /* sdes/correctors.py:35-55 (one step size for the whole batch) */
 
+#define DIFFSEP_ODE_RK45 0 /* scipy.integrate.RK45 (Dormand-Prince 5(4)), the reference's default (sdes/__init__.py:193-278) */
+#define DIFFSEP_ODE_RK23 1 /* scipy.integrate.RK23 (Bogacki-Shampine 3(2)) */
+#define DIFFSEP_ODE_WORKSPACE_BYTES 16384 /* workspace of the error-norm unit entry: per-block fp64 partial sums */
+
 typedef struct diffsep_engine diffsep_engine; /* opaque */
 
 /* Hyper-parameters of ScoreModelNCSNpp + its NCSNpp backbone.
@@ -186,6 +190,61 @@ int32_t diffsep_pc_sample_ex(diffsep_engine* e, const diffsep_sde_config* sde, c
                              const diffsep_sampler_ext* ext, const float* mix_norm, float* out, int32_t B, int64_t T,
                              const float* noise, uint64_t seed, const float* timesteps_host, int32_t* nfe_out,
                              void* stream);
+
+/* The probability-flow ODE sampler: sdes.get_ode_sampler(...)() (sdes/__init__.py:193-278), i.e.
+ * scipy.integrate.solve_ivp(method = RK45 | RK23) on dx/dt = f(x,t) - 0.5 G(t)^2 score(x,t,mix) (RSDE.sde with
+ * probability_flow, sdes/sdes.py:130-160) from t = 1 down to eps, the whole batch [B,S,T] as ONE system (one error
+ * norm, one step size), followed by the optional denoise step.  The controller is scipy's (rk.py / common.py, scipy
+ * 1.15): select_initial_step, the embedded error norm ||h K^T E / (atol + max(|y|,|y_new|) rtol)||_rms, accept if < 1,
+ * factor min(10, 0.9 err^(-1/(p+1))) (at most 1 after a rejection), reject factor max(0.2, 0.9 err^(-1/(p+1))), last
+ * step clipped onto eps, stop when the step falls below 10 ulp(t).  State in fp64, stage derivatives in fp32.
+ *   mix_norm [B,1,T], out [B,S,T] (device float32);
+ *   x_init   : NULL -> x_T = prior sample (noise [B,S,T] given, or on-device Philox draws keyed by `seed`: the draws of
+ *              the PC sampler's prior with the same seed); otherwise the caller's x_T [B,S,T] (the reference's `z`);
+ *   info     : may be NULL.  nfev is scipy's solution.nfev (the denoise evaluation is not counted).
+ * Buffers: y, y_new, 7 K and a partial-sum slab, allocated at the first call (diffsep_engine_device_bytes grows then;
+ * the workspace of the PC sampler does not change).  No mixed-length batches, no tail engine. */
+typedef struct {
+  double rtol, atol;   /* solve_ivp tolerances (reference default 1e-5 / 1e-5) */
+  double eps;          /* t_bound: integrate from 1 down to eps (3e-2) */
+  double first_step;   /* <= 0: select_initial_step (one more evaluation) */
+  double max_step;     /* <= 0 or inf: unbounded */
+  int32_t method;      /* DIFFSEP_ODE_* */
+  int32_t max_nfe;     /* 0: unbounded; otherwise no step attempt starts that would take nfev above it (status 1) */
+  int32_t denoise;     /* one reverse_diffusion predictor step at eps without noise, its x_mean (dt = 1/N: quirk Q1) */
+  int32_t N;           /* sde.N of that denoise step */
+} diffsep_ode_config;
+typedef struct {
+  int32_t nfev;        /* network evaluations of the solver (scipy's nfev) */
+  int32_t n_accepted, n_rejected;
+  int32_t status;      /* 0 reached eps, -1 step size below 10 ulp(t) (scipy's failure), 1 max_nfe reached */
+  double t_final;      /* time of the returned state (before the denoise step) */
+} diffsep_ode_info;
+int32_t diffsep_ode_sample(diffsep_engine* e, const diffsep_sde_config* sde, const diffsep_ode_config* ode,
+                           const float* mix_norm, const float* x_init, const float* noise, uint64_t seed, float* out,
+                           int32_t B, int64_t T, diffsep_ode_info* info, void* stream);
+/* Butcher tableau of RK45 / RK23 exactly as scipy's rk.py holds it (sdes/__init__.py:193-278 -> solve_ivp): A [ns][ns]
+ * row-major, B [ns], C [ns], E [ns+1]; every pointer may be NULL (host memory, no GPU needed). */
+int32_t diffsep_ode_tableau(int32_t method, double* A, double* B, double* C, double* E, int32_t* n_stages,
+                            int32_t* error_order);
+/* The two passes of the ODE sampler as unit entries (sdes/__init__.py:193-278; the sampler launches them on its own
+ * state).  State [B,S,T]: x, score, K[j] float32; y, y_new fp64.  K is a HOST array of n_k (<= 7) device pointers.
+ *   k_out >= 0: K[k_out] = f(x,t) - 0.5 G(t)^2 score (t [B] device; sigma_mix [B,T] for PriorMixSDE, else NULL),
+ *              computed in the operation order of diffsep_sde_coefficients + diffsep_sde_reverse_drift(probability_flow);
+ *   acc = sum_{j < n_k} coef[j] K[j] (fp64, in order j = 0, 1, ...);
+ * stage_update: y_new_out == NULL: x_out = fp32(y + acc h) (the next stage input; x_out may be x);
+ *               otherwise y_new_out = y + h acc and x_out (may be NULL) = fp32(y_new_out).  n_k = 0: the drift only.
+ * error_norm:   norms_out[0] = ||acc h / sc||_rms, norms_out[1] = ||y / sc||_rms (device fp64 [2]),
+ *               sc = atol + max(|y|, |y_new|) rtol (y_new NULL: atol + |y| rtol); fixed-order fp64 reduction. */
+int32_t diffsep_ode_stage_update(const diffsep_sde_config* sde, const float* x, const float* t, const float* score,
+                                 const float* sigma_mix, const double* y, float* const* K, const double* coef,
+                                 int32_t n_k, int32_t k_out, double h, float* x_out, double* y_new_out, int32_t B,
+                                 int32_t S, int64_t T, void* stream);
+int32_t diffsep_ode_error_norm(const diffsep_sde_config* sde, const float* x, const float* t, const float* score,
+                               const float* sigma_mix, const double* y, const double* y_new, float* const* K,
+                               const double* coef, int32_t n_k, int32_t k_out, double h, double rtol, double atol,
+                               double* norms_out, int32_t B, int32_t S, int64_t T, void* workspace,
+                               int64_t workspace_bytes, void* stream);
 
 /* Use hipGraph replay of the per-NFE launch sequence inside diffsep_pc_sample (default 1). */
 int32_t diffsep_engine_set_graph(diffsep_engine* e, int32_t enable);

@@ -1,0 +1,82 @@
+"""Cost of the probability-flow ODE sampler (Engine.ode_sample, sdes.get_ode_sampler) on one GPU.
+
+    python tools/ode_bench.py [--nf 64] [--B 16] [--T 32000] [--rtol 1e-5] [--atol 1e-5] [--max-nfe 600]
+                              [--dtypes f32,split,f16] [--reps 2]
+
+Synthetic weights, synthetic mixtures, MixSDE.  Per engine dtype: nfev / accepted / rejected / status of the solve, the
+wall time of one batch (median of --reps timed calls after one warm-up call), and the share of that time spent outside
+the network evaluations.  That share is estimated as 1 - (nfev + denoise) * t_nfe / wall, with t_nfe the time of one
+graph-replayed evaluation of the same (B, T) plan measured through a PC sampler run without corrector (N evaluations +
+N light update kernels).  Prints one JSON line per dtype.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "diffusion-separation_amd"))
+
+import torch  # noqa: E402
+
+from diffsep_amd import _lib, ops, synth  # noqa: E402
+from diffsep_amd.engine import Engine, pack_state_dict, param_table  # noqa: E402
+
+DTYPES = {"f32": _lib.F32, "split": _lib.F32_SPLIT, "f16": _lib.F16, "bf16": _lib.BF16}
+MIX = dict(kind=_lib.SDE_MIX, ndim=2, d_lambda=2.0, sigma_min=0.05, sigma_max=0.5)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return r, time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nf", type=int, default=64)
+    ap.add_argument("--B", type=int, default=16)
+    ap.add_argument("--T", type=int, default=32000)
+    ap.add_argument("--rtol", type=float, default=1e-5)
+    ap.add_argument("--atol", type=float, default=1e-5)
+    ap.add_argument("--max-nfe", type=int, default=600)
+    ap.add_argument("--dtypes", default="f32,split,f16")
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--pc-steps", type=int, default=30)
+    args = ap.parse_args()
+    torch.set_grad_enabled(False)
+    mix = torch.from_numpy(synth.synth_batch(args.B, T=args.T)[0]).cuda()
+    mix_norm, _, _ = ops.normalize_batch(mix)
+    sd = None
+    for name in args.dtypes.split(","):
+        cfg = _lib.model_config(nf=args.nf, num_sources=2, dtype=DTYPES[name])
+        if sd is None:
+            sd = synth.synth_state_dict([(n, s) for n, s, _ in param_table(cfg)], 7)
+        eng = Engine(cfg, pack_state_dict(cfg, sd))
+        # one evaluation of this plan, graph-replayed: PC sampler without corrector
+        eng.pc_sample(mix_norm, MIX, N=args.pc_steps, corrector="none", seed=1)
+        _, t_pc = timed(lambda: eng.pc_sample(mix_norm, MIX, N=args.pc_steps, corrector="none", seed=1))
+        t_nfe = t_pc / args.pc_steps
+        run = lambda: eng.ode_sample(mix_norm, MIX, rtol=args.rtol, atol=args.atol, max_nfe=args.max_nfe, seed=3)  # noqa
+        (out, info) = run()
+        walls = []
+        for _ in range(max(1, args.reps)):
+            (out, info), w = timed(run)
+            walls.append(w)
+        wall = sorted(walls)[len(walls) // 2]
+        outside = 1.0 - (info["nfev"] + 1) * t_nfe / wall
+        print(json.dumps(dict(dtype=name, nf=args.nf, B=args.B, T=args.T, rtol=args.rtol, atol=args.atol,
+                              max_nfe=args.max_nfe, **info, finite=bool(torch.isfinite(out).all()),
+                              wall_ms=round(wall * 1e3, 1), ms_per_nfe=round(t_nfe * 1e3, 3),
+                              share_outside_nfe=round(outside, 4), walls_ms=[round(w * 1e3, 1) for w in walls])),
+              flush=True)
+        eng.close()
+        del eng
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
