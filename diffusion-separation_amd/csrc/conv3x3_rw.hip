@@ -40,48 +40,17 @@
 // 32-cycle MFMA, the GroupNorm variant has ~9).  K order (chunk, tap, 16-channel block) as in conv_mfma.hip / conv3x3_ws.hip.
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "common.h"
-
-#ifdef RW_TIMING  // profiling build only: per-phase cycle totals of wave 0
-__device__ unsigned long long g_rw_dbg[16];
-#define RT_DECL unsigned rt_prev = (unsigned)__builtin_readcyclecounter(), rt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define RT_MARK(i) { unsigned rt_now = (unsigned)__builtin_readcyclecounter(); rt_acc[i] += rt_now - rt_prev; rt_prev = rt_now; }
-#define RT_FLUSH if (threadIdx.x == 0) { for (int q = 0; q < 8; ++q) atomicAdd(&g_rw_dbg[q], (unsigned long long)rt_acc[q]); atomicAdd(&g_rw_dbg[15], 1ull); }
-extern "C" int diffsep_rw_debug_read(unsigned long long* out, int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rw_dbg), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rw_dbg), z, sizeof(z)); }
-  return 0;
-}
-#else
-#define RT_DECL
-#define RT_MARK(i)
-#define RT_FLUSH
+#ifdef RW_TIMING  // profiling build only: per-phase cycle totals of wave 0 (diffsep_rw_debug_read)
+#define HALO_TIMING rw
 #endif
+#include "conv3x3_halo.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ inline __amdgpu_buffer_rsrc_t rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-__device__ inline u32x4_t ld16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-}
-// block barrier that orders LDS traffic only (a __syncthreads() would also drain the global prefetch)
-__device__ inline void sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-constexpr int TW = 32, HW_ = TW + 2;  // tile width, halo row
 constexpr int KC = 64;                // channels per chunk: a pixel's chunk is ONE full 128-byte line of a 64-channel tensor
 constexpr int NKB = KC / 16;          // 16-channel k-blocks per tap
 constexpr int KSC = 9 * NKB;          // k-steps of a 3x3 chunk
-constexpr int AROW = KC * 2 + 16;     // 144 B: LDS pitch of a halo pixel (16 consecutive rows = 16 distinct bank slots)
-constexpr int PPL = KC / 8;           // 16-byte pieces (lanes) per pixel
-constexpr int NT = 256;
+static_assert(KC * 2 + 16 == AROW && KC / 8 == PPL, "a pixel's chunk is one 128-byte line");
 
 struct RwK {
   const bf16_t* x; long x_bs; int ldx; int C1;     // channels [0, C1) from x, [C1, Cin) from x2
@@ -303,6 +272,8 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
     TileG g;
     const int y0 = ty * TH, x0 = tx * TW;
     g.edge = (y0 == 0 ? 1u : 0u) | (y0 + TH == p.H ? 2u : 0u) | (x0 == 0 ? 4u : 0u) | (x0 + TW == p.W ? 8u : 0u);
+    // (0x3fffff rather than M as in conv3x3_sw.hip: safe while the pixel pitch stays under 1 KB, and M moves the register
+    // allocation of the whole kernel — profiles/experiments/README.md, "Sharing the halo-tile pipeline")
     g.pix0 = valid ? y0 * p.W + x0 : 0x3fffff;
     return g;
   };
@@ -350,7 +321,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
   // v_pk_fma_f16, 2 x v_exp_f16, v_pk_add_f16, 2 x v_rcp_f16, v_pk_mul_f16 = 7 instructions (8 without FOLD) instead of 11
   // (2 fma_mix, 2 exp, 2 add, 2 rcp, 2 mul, cvt_pk); the upper halves go through SDWA forms of the transcendentals, no
   // unpack / pack.  What it costs in rounding is gated by tests/test_engine_gpu.py against the CPU oracle (-DRW_ACT_F32
-  // restores the fp32 arithmetic for the A/B).  (ii) RW_PIPE: a unit runs in THREE stages, one unit apart (affine + exp |
+  // restores the fp32 arithmetic for the A/B).  (ii) A unit runs in THREE stages, one unit apart (affine + exp |
   // 1 + e, rcp | multiply, write, re-issue): the single in-order wave no longer issues a transcendental's consumer straight
   // behind it (a k-step carries 0.6 units: inside one unit every instruction depends on the previous one).
 #if defined(DS_HALF_F16) && !defined(RW_ACT_F32)
@@ -358,11 +329,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
 #else
   constexpr bool ACT_PK = false;
 #endif
-#ifdef RW_NO_PIPE
-  constexpr int PIPE_LAG = 0;
-#else
   constexpr int PIPE_LAG = 2;
-#endif
   float gsc[ACT_PK ? 1 : 8], gsh[ACT_PK ? 1 : 8];
   unsigned psc[ACT_PK ? 4 : 1], psh[ACT_PK ? 4 : 1];
   auto act_tab = [&](int c) __attribute__((always_inline)) {  // scale / shift of this thread's 8 channels of chunk c
@@ -438,13 +405,12 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
   };
   // stage 2: z * sigmoid, the dword into the piece (unit_s2); the piece's last unit writes it and re-issues its registers
   // (unit_fin: that part alone, for the hand-placed stream whose multiply sits in an earlier lump)
-  // (RAW: the chunk's registers already hold the ACTIVATED values — the pre-activation of round 5, see half())
-  auto unit_s2x = [&](auto P1_, auto P2_, auto FIN_, auto RAW_, const TileG& g1, const TileG& g2, int sl, int u, int rel) __attribute__((always_inline)) {
+  auto unit_s2x = [&](auto P1_, auto P2_, auto FIN_, const TileG& g1, const TileG& g2, int sl, int u, int rel) __attribute__((always_inline)) {
     constexpr int P1 = decltype(P1_)::value;
-    constexpr bool FIN_ONLY = decltype(FIN_)::value, RAW = decltype(RAW_)::value;
+    constexpr bool FIN_ONLY = decltype(FIN_)::value;
     const int k = u >> 2, d = u & 3, q = u % 3;
     if constexpr (!FIN_ONLY) {
-    if constexpr (P1 < NCH && MODE != 0 && !RAW) {
+    if constexpr (P1 < NCH && MODE != 0) {
       if constexpr (ACT_PK) {
         unsigned v = uzp[q];
         if constexpr (MODE == 2) asm volatile("v_pk_mul_f16 %0, %1, %2" : "=v"(v) : "v"(uzp[q]), "v"(urp[q]));
@@ -480,13 +446,10 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
     }
   };
   auto unit_s2 = [&](auto P1_, auto P2_, const TileG& g1, const TileG& g2, int sl, int u, int rel) __attribute__((always_inline)) {
-    unit_s2x(P1_, P2_, std::false_type{}, std::false_type{}, g1, g2, sl, u, rel);
+    unit_s2x(P1_, P2_, std::false_type{}, g1, g2, sl, u, rel);
   };
   auto unit_fin = [&](auto P1_, auto P2_, const TileG& g1, const TileG& g2, int sl, int u, int rel) __attribute__((always_inline)) {
-    unit_s2x(P1_, P2_, std::true_type{}, std::false_type{}, g1, g2, sl, u, rel);
-  };
-  auto unit_raw = [&](auto P1_, auto P2_, const TileG& g1, const TileG& g2, int sl, int u, int rel) __attribute__((always_inline)) {
-    unit_s2x(P1_, P2_, std::false_type{}, std::true_type{}, g1, g2, sl, u, rel);
+    unit_s2x(P1_, P2_, std::true_type{}, g1, g2, sl, u, rel);
   };
   // a whole unit at once (the prologue)
   auto unit = [&](auto P1_, auto P2_, const TileG& g1, const TileG& g2, int sl, int u, int rel) __attribute__((always_inline)) {
@@ -608,43 +571,22 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
   constexpr int W_E = RW_W_E, W_N = RW_W_N;  // capacity of a gap for unit lumps: epilogue half / other half (A/B: -DRW_W_E=.. -DRW_W_N=..)
   float et[2][2] = {{0.f, 0.f}, {0.f, 0.f}};  // the two cout pairs in flight through the epilogue lumps
   u32x4_t osa = {0, 0, 0, 0}, osb = {0, 0, 0, 0};  // the row's two store pieces after the regrouping
-  // PRE-ACTIVATION (round 5, the 64 -> 64 layers with ONE folded skip / residual chunk, fp16 build).  A tile of those layers is a
-  // SHORT phase (the skip chunk: 16 MFMAs per wave) and a long one (the 3x3 chunk: 144); the short phase staged the next 3x3 chunk,
-  // i.e. carried its whole activation under 16 MFMAs, VALU-bound.  The registers of that chunk are re-issued as loads DURING the
-  // long phase (as the raw skip pieces leave them): now the raw units are placed in the first third of the long phase and, from there
-  // on, the landed 3x3 pieces are activated IN PLACE (pa[k][d] <- silu(GN(pa[k][d])), same lumps, the multiply's destination is the
-  // register itself): the short phase only copies, zeroes the padding and writes.  The first tile of a block has no long phase in
-  // front of it and activates as before (PD_ = false).
-  // MEASURED, NOT SHIPPED (-DRW_PREACT builds it): same box, 64 -> 64 + residual @256^2 136.9 / 139.8 us with, 136.5 / 133.6 without —
-  // the short phase was not waiting for its activation VALU (its first half also carries the previous tile's 44 epilogue lumps).
-  constexpr bool PRE_CFG = NCH == 1 && NSK == 1 && MODE == 2 && NCG == 2 && ACT_PK && PIPE_LAG == 2
-#ifndef RW_PREACT
-                           && false
-#endif
-      ;
-  auto half = [&](auto P_, auto HF_, auto EPI_, auto PD_, int slot_r, const TileG& ge, const TileG& g1, const TileG& g2) __attribute__((always_inline)) {
+  auto half = [&](auto P_, auto HF_, auto EPI_, int slot_r, const TileG& ge, const TileG& g1, const TileG& g2) __attribute__((always_inline)) {
     constexpr int P = decltype(P_)::value, HF = decltype(HF_)::value;
     constexpr bool EPI = decltype(EPI_)::value;
-    constexpr bool PREDONE = decltype(PD_)::value;      // the chunk this phase stages was activated in registers by the phase before
-    constexpr bool PRE = PRE_CFG && P == NPH - 1;       // this phase activates, in place, the chunk whose loads it issues
     constexpr int C = G::chunk_of(P);
     constexpr bool CONV = C < NCH;
     constexpr int NK = CONV ? KSC : NKB;
     constexpr int W0 = CONV ? C * KSC : NCH * KSC + (C - NCH) * NKB;
     constexpr int C1 = G::chunk_of((P + 1) % NPH), C2 = G::chunk_of((P + 2) % NPH);
     constexpr int NU = NL * 4;
-    constexpr bool ACT1 = C1 < NCH && MODE != 0 && !PREDONE;
+    constexpr bool ACT1 = C1 < NCH && MODE != 0;
     // virtual unit index v: stage 0 of unit v, stage 1 of unit v - 1, stage 2 of unit v - LAG (LAG = 0: the whole unit at v)
     constexpr int LAG = ACT1 ? PIPE_LAG : 0, NUV = NU + LAG, NLU = 2 * NUV;
     constexpr int NGH = NK * RH;  // gaps (MFMAs) of this half
     constexpr int w0 = (P == 0) ? W_E : W_N, w1 = (P == NPH - 1) ? W_E : W_N, CAP = NGH * (w0 + w1);
     // first unit lump of phase gap GP in [0, 2 NGH]
-    // (PRE: the raw units of this phase in its first third, the in-place activation lumps in the rest)
-    constexpr int GPRE = 2 * NGH / 3, NLP = PRE ? 2 * (NU + 2) : 0;
-    auto lub = [](int GP) constexpr {
-      return PRE ? NLU * (GP < GPRE ? GP : GPRE) / GPRE : NLU * (GP <= NGH ? GP * w0 : NGH * w0 + (GP - NGH) * w1) / CAP;
-    };
-    auto lpb = [](int GP) constexpr { return GP <= GPRE ? 0 : NLP * (GP - GPRE) / (2 * NGH - GPRE); };
+    auto lub = [](int GP) constexpr { return NLU * (GP <= NGH ? GP * w0 : NGH * w0 + (GP - NGH) * w1) / CAP; };
     constexpr int NLE = RH * 22;  // epilogue lumps of an EPI half
     constexpr int R0 = HF * RH, ER0 = HF ? 0 : RH;
     const char* fb = sA + slot_r * LDS_A + fbase + R0 * HW_ * AROW;
@@ -730,32 +672,9 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
         if (s2) {
           const int rel = ((u2 & 3) == 3 && (u2 >> 2) >= NI) ? rels[par][u2 >> 2] : 0;
           if constexpr (ACT1 && ACT_PK) unit_fin(std::integral_constant<int, C1>{}, std::integral_constant<int, C2>{}, g1, g2, slot_r ^ 1, u2, rel);
-          else if constexpr (PREDONE) unit_raw(std::integral_constant<int, C1>{}, std::integral_constant<int, C2>{}, g1, g2, slot_r ^ 1, u2, rel);
           else unit_s2(std::integral_constant<int, C1>{}, std::integral_constant<int, C2>{}, g1, g2, slot_r ^ 1, u2, rel);
         }
 #endif
-      }
-    };
-    // in-place activation lumps (PRE): virtual step v = {affine + exp of unit v, 1 + e and reciprocal of unit v - 1, multiply of unit
-    // v - 2 INTO ITS OWN REGISTER}; the chunk is C2 — its scale / shift table is the one in psc / psh (NCH = 1: one table)
-    auto pre_lump = [&](int L) __attribute__((always_inline)) {
-      if constexpr (PRE) {
-        const int v = L >> 1;
-        const int u0 = v < NU ? v : -1, u1 = (v >= 1 && v - 1 < NU) ? v - 1 : -1, u2 = v - 2;
-        const bool s2 = u2 >= 0 && u2 < NU;
-        if ((L & 1) == 0) {
-          if (u0 >= 0) {
-            asm volatile("v_pk_fma_f16 %0, %1, %2, %3" : "=v"(uzp[u0 % 3]) : "v"(pa[u0 >> 2][u0 & 3]), "v"(psc[u0 & 3]), "v"(psh[u0 & 3]));
-            if constexpr (!FOLD) asm volatile("v_pk_mul_f16 %0, %1, %2" : "=v"(uxp[u0 % 3]) : "v"(uzp[u0 % 3]), "s"(0xbdc5bdc5u));
-          }
-          if (u1 >= 0) asm volatile("v_pk_add_f16 %0, %1, %2" : "=v"(udp[u1 % 3]) : "v"(utp[u1 % 3]), "s"(0x3c003c00u));
-          if (s2) asm volatile("v_pk_mul_f16 %0, %1, %2" : "=v"(pa[u2 >> 2][u2 & 3]) : "v"(uzp[u2 % 3]), "v"(urp[u2 % 3]));
-          if (u0 >= 0) asm volatile("v_exp_f16 %0, %1" : "=v"(utp[u0 % 3]) : "v"(FOLD ? uzp[u0 % 3] : uxp[u0 % 3]));
-          if (u1 >= 0) asm volatile("v_rcp_f16 %0, %1" : "=v"(urp[u1 % 3]) : "v"(udp[u1 % 3]));
-        } else {
-          if (u0 >= 0) asm volatile("v_exp_f16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1" : "+v"(utp[u0 % 3]) : "v"(FOLD ? uzp[u0 % 3] : uxp[u0 % 3]));
-          if (u1 >= 0) asm volatile("v_rcp_f16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1" : "+v"(urp[u1 % 3]) : "v"(udp[u1 % 3]));
-        }
       }
     };
     // epilogue lumps of row rr, 22 per row: per half row j the pairs p = 0 .. 3 of the lane's 8 couts as a two-deep
@@ -827,11 +746,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
       const u32x4_t wk = wi < NWR ? wf[wi < NWR ? wi : 0] : wl;
       // RW_DEP: the k-step's LAST pixel fragment rides along as an unused operand of every MFMA of the k-step: the
       // compiler then waits ONCE per k-step (for the newest fragment) instead of once per MFMA
-#ifdef RW_NO_DEP
-#define RW_DEP
-#else
 #define RW_DEP , "v"(RW_FRAG_LAST(ks))
-#endif
 #pragma unroll
       for (int r = 0; r < RH; ++r) {
         // Inline asm: the register-resident weight fragment is pinned to the accumulator half of the register file ("a")
@@ -853,10 +768,6 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
         const int gh = ks * RH + r, gp = HF * NGH + gh;
 #pragma unroll
         for (int L = lub(gp); L < lub(gp + 1); ++L) unit_lump(L, ks & 1);
-        if constexpr (PRE) {
-#pragma unroll
-          for (int L = lpb(gp); L < lpb(gp + 1); ++L) pre_lump(L);
-        }
 #ifndef RW_ABL_NOEPI
         if constexpr (EPI) {
 #pragma unroll
@@ -913,31 +824,16 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
     auto run = [&](auto self, auto P_) __attribute__((always_inline)) {
       constexpr int P = decltype(P_)::value;
       sync_lds();
-#ifdef RW_SKEW
-      if (wave == 1) __builtin_amdgcn_s_sleep(RW_SKEW);
-      if (wave == 2) __builtin_amdgcn_s_sleep(2 * RW_SKEW);
-      if (wave == 3) __builtin_amdgcn_s_sleep(3 * RW_SKEW);
-#endif
       RT_MARK(1)
       const int slot_r = ph & 1;
-      if constexpr (P == 0 && PRE_CFG) {  // (the first tile's 3x3 chunk was not pre-activated)
-        if (i == 0) half(P_, std::integral_constant<int, 0>{}, std::true_type{}, std::false_type{}, slot_r, gp, gc, gn);
-        else half(P_, std::integral_constant<int, 0>{}, std::true_type{}, std::true_type{}, slot_r, gp, gc, gn);
-      } else {
-        half(P_, std::integral_constant<int, 0>{}, std::integral_constant<bool, P == 0>{}, std::false_type{}, slot_r, gp, ((P + 1) / NPH == 0 ? gc : gn), ((P + 2) / NPH == 0 ? gc : ((P + 2) / NPH == 1 ? gn : gnn)));
-      }
+      half(P_, std::integral_constant<int, 0>{}, std::integral_constant<bool, P == 0>{}, slot_r, gp, ((P + 1) / NPH == 0 ? gc : gn), ((P + 2) / NPH == 0 ? gc : ((P + 2) / NPH == 1 ? gn : gnn)));
       if constexpr (P == 0) {
         if (i == 0) {  // (the first tile has no predecessor: what that epilogue summed up was not an output)
 #pragma unroll
           for (int j = 0; j < 16; ++j) { ssum[j] = 0.f; ssq[j] = 0.f; }
         }
       }
-      if constexpr (P == 0 && PRE_CFG) {
-        if (i == 0) half(P_, std::integral_constant<int, 1>{}, std::false_type{}, std::false_type{}, slot_r, gc, gc, gn);
-        else half(P_, std::integral_constant<int, 1>{}, std::false_type{}, std::true_type{}, slot_r, gc, gc, gn);
-      } else {
-        half(P_, std::integral_constant<int, 1>{}, std::integral_constant<bool, P == NPH - 1>{}, std::false_type{}, slot_r, gc, ((P + 1) / NPH == 0 ? gc : gn), ((P + 2) / NPH == 0 ? gc : ((P + 2) / NPH == 1 ? gn : gnn)));
-      }
+      half(P_, std::integral_constant<int, 1>{}, std::integral_constant<bool, P == NPH - 1>{}, slot_r, gc, ((P + 1) / NPH == 0 ? gc : gn), ((P + 2) / NPH == 0 ? gc : ((P + 2) / NPH == 1 ? gn : gnn)));
       ++ph;
       RT_MARK(G::chunk_of(P) < NCH ? 2 : 3)
       if constexpr (P + 1 < NPH) self(self, std::integral_constant<int, P + 1>{});

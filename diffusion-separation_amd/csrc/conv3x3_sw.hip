@@ -26,48 +26,17 @@
 // skip chunks against an identity copy (exact in the fp32 accumulators).
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "common.h"
-
-#ifdef SW_TIMING  // profiling build only: per-phase cycle totals of wave 0
-__device__ unsigned long long g_sw_dbg[16];
-#define RT_DECL unsigned rt_prev = (unsigned)__builtin_readcyclecounter(), rt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define RT_MARK(i) { unsigned rt_now = (unsigned)__builtin_readcyclecounter(); rt_acc[i] += rt_now - rt_prev; rt_prev = rt_now; }
-#define RT_FLUSH if (threadIdx.x == 0) { for (int q = 0; q < 8; ++q) atomicAdd(&g_sw_dbg[q], (unsigned long long)rt_acc[q]); atomicAdd(&g_sw_dbg[15], 1ull); }
-extern "C" int diffsep_sw_debug_read(unsigned long long* out, int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sw_dbg), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sw_dbg), z, sizeof(z)); }
-  return 0;
-}
-#else
-#define RT_DECL
-#define RT_MARK(i)
-#define RT_FLUSH
+#ifdef SW_TIMING  // profiling build only: per-phase cycle totals of wave 0 (diffsep_sw_debug_read)
+#define HALO_TIMING sw
 #endif
+#include "conv3x3_halo.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ inline __amdgpu_buffer_rsrc_t rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-__device__ inline u32x4_t ld16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-}
-// block barrier that orders LDS traffic only (a __syncthreads() would also drain the global prefetch)
-__device__ inline void sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-constexpr int TW = 32, HW_ = TW + 2;  // tile width, halo row
 constexpr int KC = 64;                // channels per chunk: a pixel's chunk is ONE full 128-byte line of a 64-channel tensor
 constexpr int NKB = KC / 16;          // 16-channel k-blocks per tap
 constexpr int KSC = 9 * NKB;          // k-steps of a 3x3 chunk
-constexpr int AROW = KC * 2 + 16;     // 144 B: LDS pitch of a halo pixel (16 consecutive rows = 16 distinct bank slots)
-constexpr int PPL = KC / 8;           // 16-byte pieces (lanes) per pixel
-constexpr int NT = 256;
+static_assert(KC * 2 + 16 == AROW && KC / 8 == PPL, "a pixel's chunk is one 128-byte line");
 
 struct SwK {
   const bf16_t* x; long x_bs; int ldx; int C1;     // channels [0, C1) from x, [C1, Cin) from x2
@@ -122,13 +91,8 @@ struct SwGeom {
   static constexpr int nk_of(int P) { return chunk_of(P) < NCH ? KSC : NKB; }
   // ---- the weight stream of one tile: position s = (phase, half, k-step of the half) in program order
   // (the first and the last phase run as two half-phases of 4 rows — the epilogue of the other half rides under each — and walk
-  // their chunk's k-steps twice; the phases in between have no epilogue to carry and run all 8 rows per fragment: SW_NO_FULL
-  // builds them as halves too, for the A/B)
-#ifdef SW_NO_FULL
-  static constexpr bool mid(int P) { return false; }
-#else
+  // their chunk's k-steps twice; the phases in between have no epilogue to carry and run all 8 rows per fragment)
   static constexpr bool mid(int P) { return P > 0 && P < NPH - 1; }
-#endif
   static constexpr int len_of(int P) { return (mid(P) ? 1 : 2) * nk_of(P); }
   static constexpr int pos0(int P) { int s = 0; for (int q = 0; q < P; ++q) s += len_of(q); return s; }
   static constexpr int S = pos0(NPH);
@@ -331,7 +295,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
   // v_pk_fma_f16, 2 x v_exp_f16, v_pk_add_f16, 2 x v_rcp_f16, v_pk_mul_f16 = 7 instructions (8 without FOLD) instead of 11
   // (2 fma_mix, 2 exp, 2 add, 2 rcp, 2 mul, cvt_pk); the upper halves go through SDWA forms of the transcendentals, no
   // unpack / pack.  What it costs in rounding is gated by tests/test_engine_gpu.py against the CPU oracle (-DSW_ACT_F32
-  // restores the fp32 arithmetic for the A/B).  (ii) SW_PIPE: a unit runs in THREE stages, one unit apart (affine + exp |
+  // restores the fp32 arithmetic for the A/B).  (ii) A unit runs in THREE stages, one unit apart (affine + exp |
   // 1 + e, rcp | multiply, write, re-issue): the single in-order wave no longer issues a transcendental's consumer straight
   // behind it (a k-step carries 0.6 units: inside one unit every instruction depends on the previous one).
 #if defined(DS_HALF_F16) && !defined(SW_ACT_F32)
@@ -339,11 +303,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
 #else
   constexpr bool ACT_PK = false;
 #endif
-#ifdef SW_NO_PIPE
-  constexpr int PIPE_LAG = 0;
-#else
   constexpr int PIPE_LAG = 2;
-#endif
   float gsc[ACT_PK ? 1 : 8], gsh[ACT_PK ? 1 : 8];
   unsigned psc[ACT_PK ? 4 : 1], psh[ACT_PK ? 4 : 1];
   auto act_tab = [&](int c) __attribute__((always_inline)) {  // scale / shift of this thread's 8 channels of chunk c
@@ -446,17 +406,9 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
         so.z = ok ? so.z : 0u;
         so.w = ok ? so.w : 0u;
       }
-#ifdef SW_ABL_NOLDSW
-      asm volatile("" :: "v"(so));
-#else
       if (P1 < NCH || k < NI)  // (border pieces of a skip chunk: nothing was loaded, nothing is read)
         *reinterpret_cast<u32x4_t*>(sA + sl * LDS_A + (k < NI ? ldi0 + k * HW_ * AROW : dstb[k < NI ? 0 : k - NI])) = so;
-#endif
-#ifdef SW_ABL_NOLOAD
-      pa[k][0] += rel;
-#else
       issue_one(P2_, g2, k, rel);
-#endif
     }
   };
   auto unit_s2 = [&](auto P1_, auto P2_, const TileG& g1, const TileG& g2, int sl, int u, int rel) __attribute__((always_inline)) {
@@ -510,13 +462,11 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
     v[4] = fmaf(acc[r][8 * j + 4], osc, t1.x); v[5] = fmaf(acc[r][8 * j + 5], osc, t1.y);
     v[6] = fmaf(acc[r][8 * j + 6], osc, t1.z); v[7] = fmaf(acc[r][8 * j + 7], osc, t1.w);
     // (always taken: a branch here would cut the half-phase's instruction stream into separately scheduled pieces)
-#ifndef SW_ABL_NOSTATS
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       ssum[8 * j + e] += v[e];
       ssq[8 * j + e] = fmaf(v[e], v[e], ssq[8 * j + e]);
     }
-#endif
     u32x4_t ov = {pack_h2(v[0], v[1]), pack_h2(v[2], v[3]), pack_h2(v[4], v[5]), pack_h2(v[6], v[7])};
     swap_halves(ov);  // lane (pixel l32, half h): couts 16 j + 8 h .. + 7
     if (j == 0) {
@@ -535,12 +485,8 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
 #else
       const unsigned o1 = o, o2 = o + 16u * (unsigned)p.ldy * 2u;
 #endif
-#ifdef SW_ABL_NOSTORE
-      asm volatile("" :: "v"(a), "v"(b2), "v"(o1), "v"(o2));
-#else
       __builtin_amdgcn_raw_buffer_store_b128(a, ry, o1, 0, 0);    // pixels 0 .. 15 of the row
       __builtin_amdgcn_raw_buffer_store_b128(b2, ry, o2, 0, 0);   // pixels 16 .. 31
-#endif
     }
   };
   // (bias + temb bias) * out_scale of the unit's two cout quads: LDS broadcast reads, issued ahead of the k-step's MFMAs
@@ -675,13 +621,11 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
         } else if constexpr (ACT1) {
           if (u1 >= 0) unit_s01(std::integral_constant<int, C1>{}, -1, u1);
         }
-#ifndef SW_ABL_NOSTAGE
         if (s2) {
           const int rel = ((u2 & 3) == 3 && (u2 >> 2) >= NI) ? rels[par][u2 >> 2] : 0;
           if constexpr (ACT1 && ACT_PK) unit_fin(std::integral_constant<int, C1>{}, std::integral_constant<int, C2>{}, g1, g2, slot_r ^ 1, u2, rel);
           else unit_s2(std::integral_constant<int, C1>{}, std::integral_constant<int, C2>{}, g1, g2, slot_r ^ 1, u2, rel);
         }
-#endif
       }
     };
     // epilogue lumps of row rr, 22 per row: per half row j the pairs p = 0 .. 3 of the lane's 8 couts as a two-deep
@@ -720,13 +664,11 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
             else asm volatile(DS_CVT_PK_H_ASM " %0, %1, %2" : "=v"(osb[q]) : "v"(et[q & 1][0]), "v"(et[q & 1][1]));
           }
         } else {
-#ifndef SW_ABL_NOSTATS
           const int e0 = 8 * j + 2 * pr;
           asm volatile("v_add_f32 %0, %0, %1" : "+v"(ssum[e0]) : "v"(et[pr & 1][0]));
           asm volatile("v_add_f32 %0, %0, %1" : "+v"(ssum[e0 + 1]) : "v"(et[pr & 1][1]));
           asm volatile("v_fma_f32 %0, %1, %1, %0" : "+v"(ssq[e0]) : "v"(et[pr & 1][0]));
           asm volatile("v_fma_f32 %0, %1, %1, %0" : "+v"(ssq[e0 + 1]) : "v"(et[pr & 1][1]));
-#endif
         }
       } else if (x == 20) {
 #pragma unroll
@@ -739,12 +681,8 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
 #else
         const unsigned o1 = o, o2 = o + 16u * (unsigned)p.ldy * 2u;
 #endif
-#ifdef SW_ABL_NOSTORE
-        asm volatile("" :: "v"(osa), "v"(osb), "v"(o1), "v"(o2));
-#else
         __builtin_amdgcn_raw_buffer_store_b128(osa, ry, o1, 0, 0);   // pixels 0 .. 15 of the row
         __builtin_amdgcn_raw_buffer_store_b128(osb, ry, o2, 0, 0);   // pixels 16 .. 31
-#endif
       }
     };
 
@@ -753,11 +691,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
       if (ks + 1 < NK) fetch_rels(ks + 1, (ks + 1) & 1);
       // SW_DEP: the k-step's LAST pixel fragment rides along as an unused operand of every MFMA of the k-step: the
       // compiler then waits ONCE per k-step (for the newest fragment) instead of once per MFMA
-#ifdef SW_NO_DEP
-#define SW_DEP
-#else
 #define SW_DEP , "v"(SW_FRAG_LAST(ks))
-#endif
 #pragma unroll
       for (int r = 0; r < RR; ++r) {
         // Inline asm: the weight fragment (ring, loaded by the compiler's own buffer_load straight into the accumulator half
@@ -774,18 +708,14 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
         const int gh = ks * RR + r, gp = GP0 + gh;
 #pragma unroll
         for (int L = lub(gp); L < lub(gp + 1); ++L) unit_lump(L, ks & 1);
-#ifndef SW_ABL_NOEPI
         if constexpr (EPI) {
 #pragma unroll
           for (int LE = gh * NLE / NGH; LE < (gh + 1) * NLE / NGH; ++LE) epi_lump(LE);
         }
-#endif
       }
       // this k-step's ring slot is free: the fragment RING positions ahead (the tile's last RING positions load nothing: the
       // ring is primed again at the top of the next tile)
-#ifndef SW_ABL_NOSTREAM  // (ablation build: the ring keeps the tile's first fragments)
       if (SP0 + ks + RING < G::S) load_frag(SP0 + ks + RING);
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
   };

@@ -24,49 +24,19 @@
 // the 16-bit kernels.
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "common.h"
-
-#ifdef SWS_TIMING  // profiling build only: per-phase cycle totals of wave 0
-__device__ unsigned long long g_sws_dbg[16];
-#define RT_DECL unsigned rt_prev = (unsigned)__builtin_readcyclecounter(), rt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define RT_MARK(i) { unsigned rt_now = (unsigned)__builtin_readcyclecounter(); rt_acc[i] += rt_now - rt_prev; rt_prev = rt_now; }
-#define RT_FLUSH if (threadIdx.x == 0) { for (int q = 0; q < 8; ++q) atomicAdd(&g_sws_dbg[q], (unsigned long long)rt_acc[q]); atomicAdd(&g_sws_dbg[15], 1ull); }
-extern "C" int diffsep_sws_debug_read(unsigned long long* out, int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sws_dbg), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sws_dbg), z, sizeof(z)); }
-  return 0;
-}
-#else
-#define RT_DECL
-#define RT_MARK(i)
-#define RT_FLUSH
+#ifdef SWS_TIMING  // profiling build only: per-phase cycle totals of wave 0 (diffsep_sws_debug_read)
+#define HALO_TIMING sws
 #endif
+#include "conv3x3_halo.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ inline __amdgpu_buffer_rsrc_t rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-__device__ inline u32x4_t ld16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-}
-// block barrier that orders LDS traffic only (a __syncthreads() would also drain the global prefetch)
-__device__ inline void sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-constexpr int TW = 32, HW_ = TW + 2;  // tile width, halo row
 constexpr int KC = 32;                // channels per chunk: a pixel's chunk is ONE full 128-byte line of fp32 values
 constexpr int NKB = KC / 16;          // 16-channel k-blocks per tap
 constexpr int KSC = 9 * NKB;          // k-steps of a 3x3 chunk
-constexpr int AROW = KC * 4 + 16;     // 144 B: LDS pitch of a halo pixel: [32 bf16 hi][32 bf16 lo] + pad
 constexpr int LO_OFF = KC * 2;        // byte offset of the lo plane in a pixel's row
-constexpr int PPL = KC / 4;           // 16-byte pieces (4 fp32 values) per pixel
-constexpr int NT = 256;
+static_assert(KC * 4 + 16 == AROW && KC / 4 == PPL, "a pixel's chunk is one 128-byte line: [32 bf16 hi][32 bf16 lo] + pad");
 constexpr int RPW = 4, RH = RPW / 2;  // pixel rows per wave, rows per half-phase
 #ifndef SWS_D
 #define SWS_D 10  // ring depth in k-steps (each: a hi and a lo fragment = 8 registers)
