@@ -1,0 +1,375 @@
+// unit.hip — the unit entry points of the C-ABI: single kernels and single blocks on caller-supplied tensors, for the
+// parity tests and the Python operator surface.  No engine state survives a call.
+#include "engine_host.h"
+
+// The time embedding of NCSNpp.forward (ncsnpp.py:324-343): GaussianFourierProjection(log t) -> Linear -> SiLU -> Linear, with
+// the kernels net_forward launches.  temb [B][4 nf]; workspace >= B * 6 nf floats.
+extern "C" int32_t diffsep_time_embedding(const float* t, const float* fourier_w, const float* w1, const float* b1,
+                                          const float* w2, const float* b2, float* temb, int32_t B, int32_t nf,
+                                          void* workspace, int64_t workspace_bytes, void* stream) {
+  DS_CHECK(t && fourier_w && w1 && b1 && w2 && b2 && temb && workspace, "time_embedding: null pointer");
+  DS_CHECK(B >= 1 && nf >= 8 && nf % 8 == 0, "time_embedding: bad B / nf");
+  DS_CHECK(workspace_bytes >= (int64_t)B * 6 * nf * 4, "time_embedding: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  float* emb = (float*)workspace;
+  float* t1 = emb + (size_t)B * 2 * nf;
+  if (ds_launch_fourier(t, fourier_w, emb, B, nf, st)) return 1;
+  if (ds_launch_linear(emb, w1, b1, t1, B, 2 * nf, 4 * nf, 0, st)) return 1;
+  return ds_launch_linear(t1, w2, b2, temb, B, 4 * nf, 4 * nf, 1, st);
+}
+
+extern "C" int32_t diffsep_upfirdn2d(const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ldx,
+                                     int32_t ldy, int32_t up, int32_t dtype, void* stream) {
+  DS_CHECK(x && y, "upfirdn2d: null pointer");
+  return ds_launch_gn_apply(x, ldx, nullptr, nullptr, C, nullptr, 0, y, ldy, B, H, W, 0, up ? 1 : 2, dtype,
+                            (hipStream_t)stream);
+}
+
+extern "C" int32_t diffsep_groupnorm_act(const void* x, const float* gamma, const float* beta, void* y, void* xr,
+                                         int32_t B, int32_t H, int32_t W, int32_t C, int32_t ldx, int32_t ldy,
+                                         int32_t ldxr, int32_t groups, float eps, int32_t act, int32_t resample,
+                                         int32_t dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+  DS_CHECK(x && y && workspace, "groupnorm: null pointer");
+  const long wsb = (ds_gn_workspace_bytes(B, H, W, C) + 255) & ~255L;
+  DS_CHECK(workspace_bytes >= wsb + 2L * B * C * 4, "groupnorm: workspace too small");
+  float* scale = (float*)((char*)workspace + wsb);
+  float* shift = scale + (long)B * C;
+  hipStream_t st = (hipStream_t)stream;
+  if (ds_launch_gn_stats(x, ldx, nullptr, 0, C, B, H, W, C, groups, eps, gamma, beta, workspace, scale, shift, dtype, st))
+    return 1;
+  return ds_launch_gn_apply(x, ldx, scale, shift, C, y, ldy, xr, ldxr, B, H, W, act, resample, dtype, st);
+}
+
+// dense-or-strided NHWC view of a caller's tensor
+static Tn view(const void* p, int H, int W, int C, int ld) {
+  Tn t;
+  t.p = const_cast<void*>(p); t.H = H; t.W = W; t.C = C; t.ld = ld;
+  return t;
+}
+
+extern "C" int32_t diffsep_groupnorm_stats(const void* x, const void* x2, int32_t C1, const float* gamma,
+                                           const float* beta, float* scale, float* shift, int32_t B, int32_t H,
+                                           int32_t W, int32_t C, int32_t ldx, int32_t ldx2, int32_t groups, float eps,
+                                           int32_t dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+  DS_CHECK(x && scale && shift && workspace, "groupnorm_stats: null pointer");
+  DS_CHECK(workspace_bytes >= ds_gn_workspace_bytes(B, H, W, C), "groupnorm_stats: workspace too small");
+  return ds_launch_gn_stats(x, ldx, x2, ldx2, x2 ? C1 : C, B, H, W, C, groups, eps, gamma, beta, workspace, scale, shift,
+                            dtype, (hipStream_t)stream);
+}
+
+extern "C" int32_t diffsep_conv2d_fused(const void* x, const void* x2, int32_t C1, const float* gn_scale,
+                                        const float* gn_shift, int32_t gn_act, const void* w, const float* bias,
+                                        const float* bias_b, const void* res, void* y, int32_t B, int32_t H, int32_t W,
+                                        int32_t Cin, int32_t Cout, int32_t ksize, int32_t ldx, int32_t ldx2,
+                                        int32_t ldr, int32_t ldy, float out_scale, int32_t dtype, int64_t* stats,
+                                        int32_t w_chunk, const int64_t* gn_acc1, const int64_t* gn_acc2,
+                                        const float* gn_gamma, const float* gn_beta, int32_t gn_groups, void* stream) {
+  DS_CHECK(ksize == 1 || ksize == 3, "conv2d: ksize must be 1 or 3");
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.opts = ds_default_opts();
+  a.stats_acc = (long long*)stats;
+  if (gn_acc1) {
+    DS_CHECK(gn_groups > 0 && Cin % gn_groups == 0, "conv2d: bad GroupNorm group count");
+    a.gn_acc1 = (const long long*)gn_acc1; a.gn_acc2 = (const long long*)gn_acc2; a.gn_gamma = gn_gamma;
+    a.gn_beta = gn_beta; a.gn_groups = gn_groups; a.gn_eps = 1e-6f;
+    a.gn_inv_count = gn_inv_count((long)H * W, Cin, gn_groups);
+  }
+  a.w_chunked = w_chunk;
+  Tn xin = view(x, H, W, Cin, ldx);
+  xin.p2 = const_cast<void*>(x2); xin.ld2 = ldx2; xin.C1 = C1;
+  conv_input(a, xin);
+  a.gn_scale = gn_scale; a.gn_shift = gn_shift; a.gn_act = gn_act;
+  a.w = w; a.w_bs = 0;
+  a.bias = bias; a.bias_b = bias_b; a.bias_b_ld = Cout; a.bias_mode = 0;
+  conv_residual(a, view(res, H, W, Cout, ldr));
+  a.out_scale = out_scale;
+  conv_output(a, view(y, H, W, Cout, ldy));
+  a.B = B; a.Cout = Cout; a.taps = ksize == 3 ? 9 : 1;
+  const DtypeSplit ds = split_dtype(dtype);
+  a.dtype = ds.dtype; a.split = ds.split;
+  return ds_launch_conv(a, (hipStream_t)stream);
+}
+// (the plain convolution: no concat, no GroupNorm, no statistics, row-major weights)
+extern "C" int32_t diffsep_conv2d(const void* x, const void* w, const float* bias, const float* bias_b, const void* res,
+                                  void* y, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t ksize,
+                                  int32_t ldx, int32_t ldr, int32_t ldy, float out_scale, int32_t dtype, void* stream) {
+  return diffsep_conv2d_fused(x, /*x2, C1*/ nullptr, 0, /*gn_scale, gn_shift, gn_act*/ nullptr, nullptr, 0, w, bias, bias_b, res, y,
+                              B, H, W, Cin, Cout, ksize, ldx, /*ldx2*/ 0, ldr, ldy, out_scale, dtype, /*stats, w_chunk*/ nullptr, 0,
+                              /*gn_acc1, gn_acc2, gn_gamma, gn_beta, gn_groups*/ nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+
+// Unit entry of the streamed-weight 3x3 kernel (conv3x3_sw.hip), whatever the dispatch would have chosen for the shape: dense
+// NHWC tensors, weights already in the fragment-major order of diffsep_frag_index (include/diffsep_hip.h).
+extern "C" int32_t diffsep_conv3x3_streamed(const void* x, const void* x2, int32_t C1, const float* gn_scale,
+                                            const float* gn_shift, const void* w_frag, const float* bias,
+                                            const float* bias_b, const void* sx, const void* sx2, int32_t sC1,
+                                            int32_t sCin, const void* sw_frag, void* y, int32_t B, int32_t H, int32_t W,
+                                            int32_t Cin, int32_t Cout, float out_scale, int32_t dtype, int64_t* stats,
+                                            const void* res, const void* ident_frag, void* stream) {
+  DS_CHECK(x && w_frag && y, "conv3x3_streamed: null pointer");
+  DS_CHECK(!res || (ident_frag && !sx), "conv3x3_streamed: a residual needs the identity copy and no skip");
+  DS_CHECK(B > 0 && H > 0 && W > 0, "conv3x3_streamed: empty problem");
+  DS_CHECK(!x2 || (C1 > 0 && C1 < Cin), "conv3x3_streamed: bad concat split");
+  DS_CHECK(!sx || (sw_frag && sCin > 0 && (!sx2 || (sC1 > 0 && sC1 < sCin))), "conv3x3_streamed: bad skip operands");
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.opts = ds_default_opts();
+  a.stats_acc = (long long*)stats;
+  const int c1 = x2 ? C1 : Cin;  // dense sources: each one's leading dimension is its channel count
+  Tn xin = view(x, H, W, Cin, c1);
+  xin.p2 = const_cast<void*>(x2); xin.ld2 = Cin - c1; xin.C1 = x2 ? C1 : 0;
+  conv_input(a, xin);
+  a.gn_scale = gn_scale; a.gn_shift = gn_shift; a.gn_act = gn_scale ? 1 : 0;
+  a.w = w_frag; a.w_frag = w_frag; a.w_bs = 0;
+  a.bias = bias; a.bias_b = bias_b; a.bias_b_ld = Cout; a.bias_mode = 0;
+  if (sx) {
+    const int s1 = sx2 ? sC1 : sCin;
+    Tn sin = view(sx, H, W, sCin, s1);
+    sin.p2 = const_cast<void*>(sx2); sin.ld2 = sCin - s1; sin.C1 = sx2 ? sC1 : 0;
+    conv_skip_input(a, sin);
+    a.sw = sw_frag; a.sw_frag = sw_frag;
+  }
+  a.out_scale = out_scale;
+  conv_output(a, view(y, H, W, Cout, Cout));
+  a.B = B; a.Cout = Cout; a.taps = 9;
+  const DtypeSplit ds = split_dtype(dtype);
+  a.dtype = ds.dtype; a.split = ds.split;
+  DS_CHECK((long)H * W * (Cin > Cout ? Cin : Cout) * 4 < 2147483647L, "conv3x3_streamed: image too large for 32-bit buffer offsets");
+  conv_residual(a, view(res, H, W, Cout, Cout));
+  a.ident_frag = ident_frag;
+  if (a.split) {  // fp32 tensors, hi / lo fragment copies: conv3x3_sws.hip
+    DS_CHECK(ds_conv_sws_supported(a), "conv3x3_streamed: shape outside the split kernel's instantiations (Cout = 64 / 128 / 256, Cin = 64 .. 256 "
+                                       "by 64, W % 32 == 0, H % 8 == 0; skip / residual channels 64 .. 256 by 64 behind GroupNorm; raw input: Cin <= 128)");
+    return ds_launch_conv_sws(a, (hipStream_t)stream);
+  }
+  DS_CHECK(ds_conv_sw_supported(a), "conv3x3_streamed: shape outside the kernel's instantiations (16-bit, Cout = 128 / 256, Cin = 64 .. 256 "
+                                    "by 64, W % 32 == 0, H % 4 == 0; a skip needs GroupNorm and Cin = 128; raw input: Cin <= 128; Cout = 64: Cin = 192)");
+  return ds_launch_conv_sw(a, (hipStream_t)stream);
+}
+extern "C" int64_t diffsep_frag_index(int32_t cout, int32_t tap, int32_t cin, int32_t taps, int32_t Cout) {
+  return ds_rw_frag_index(cout, tap, cin, taps, Cout);
+}
+extern "C" int64_t diffsep_frag_index_split(int32_t cout, int32_t tap, int32_t cin, int32_t taps, int32_t Cout, int32_t plane) {
+  return ds_sws_frag_index(cout, tap, cin, taps, Cout, plane);
+}
+
+extern "C" int32_t diffsep_conv2d_chunk(int32_t ksize, int32_t dtype) { return ds_conv_chunk(ksize == 3 ? 9 : 1, dtype); }
+
+extern "C" int32_t diffsep_attention(const void* q, const void* k, const void* vt, void* o, int32_t B, int32_t L,
+                                     int32_t C, int32_t ld, int32_t dtype, void* workspace, int64_t workspace_bytes,
+                                     void* stream) {
+  DS_CHECK(q && k && vt && o && workspace, "attention: null pointer");
+  DS_CHECK(ld == C, "attention: q/k must be dense [B,L,C] (ld == C)");
+  const DtypeSplit ds = split_dtype(dtype);
+  const int Lp = rup8(L), esz = ds.dtype == DS_F32 ? 4 : 2;
+  const long one = (((long)B * L * Lp * esz) + 255) & ~255L;
+  DS_CHECK(workspace_bytes >= 2 * one, "attention: workspace too small");
+  return attention_core(view(q, 1, L, C, ld), k, vt, view(o, 1, L, C, ld), B, workspace, (char*)workspace + one, ds.dtype,
+                        (hipStream_t)stream, ds.split);
+}
+
+// ---- one ResnetBlockBigGANpp / AttnBlockpp through the ENGINE's block code (res_block / attn_block of engine.hip: folded
+// Conv_2, GroupNorm from the producer's accumulators, fused FIR resampling, MFMA attention), on caller-supplied
+// parameters: the parity tests check the composition against the reference blocks in isolation (layerspp.py:291-323,
+// 76-92).  A throw-away one-module engine is built per call (test path, not a hot path) and freed when the call returns.
+static std::unique_ptr<diffsep_engine> unit_engine(int dtype, int nf) {
+  std::unique_ptr<diffsep_engine> e(new diffsep_engine());
+  memset(&e->cfg, 0, sizeof(e->cfg));
+  e->cfg.dtype = dtype;
+  e->cfg.nf = nf;
+  e->opts = ds_default_opts();
+  return e;
+}
+template <typename F>
+static int unit_engine_run(diffsep_engine* e, hipStream_t st, F&& body) {
+  e->fwd_base = 0;
+  e->dry = true;
+  e->top = 0;
+  if (stats_begin(e, st)) return 1;
+  if (body()) { e->dry = false; return 1; }
+  e->dry = false;
+  const size_t need = e->top + e->stats_need + 8192;
+  DS_HIP(hipMalloc((void**)&e->arena, need));
+  e->cap = need;
+  DS_HIP(hipMemsetAsync(e->arena, 0, need, st));
+  e->top = 0;
+  if (stats_begin(e, st)) return 1;
+  if (body()) return 1;
+  DS_HIP(hipStreamSynchronize(st));  // the arena is freed with the engine when the caller returns
+  return 0;
+}
+
+extern "C" int32_t diffsep_resblock_forward(int32_t in_ch, int32_t out_ch, int32_t up, int32_t down, int32_t temb_dim,
+                                            int32_t dtype, const float* params_host, int64_t n_floats, const void* x,
+                                            const float* temb, void* y, int32_t B, int32_t H, int32_t W, void* stream) {
+  DS_CHECK(params_host && x && temb && y, "resblock_forward: null pointer");
+  DS_CHECK(dtype == DS_F32 || dtype == DS_BF16, "resblock_forward: bad dtype");
+  DS_CHECK(in_ch % 8 == 0 && out_ch % 8 == 0 && in_ch >= 8 && out_ch >= 8, "resblock_forward: channels must be multiples of 8");
+  DS_CHECK(temb_dim >= 4 && temb_dim % 4 == 0, "resblock_forward: temb_dim must be a multiple of 4");
+  DS_CHECK(!(up && down) && B >= 1 && H >= 1 && W >= 1 && (!down || (H % 2 == 0 && W % 2 == 0)), "resblock_forward: bad shape");
+  const std::unique_ptr<diffsep_engine> owner = unit_engine(dtype, temb_dim / 4);
+  diffsep_engine* e = owner.get();
+  ArchBuilder(e->arch).res(in_ch, out_ch, up != 0, down != 0, temb_dim);
+  if (upload_weights(e, params_host, n_floats, "block_forward: parameter blob")) return 1;
+  const Module& m = e->arch.mods[0];
+  hipStream_t st = (hipStream_t)stream;
+  const int Ho = up ? 2 * H : (down ? H / 2 : H), Wo = up ? 2 * W : (down ? W / 2 : W);
+  return unit_engine_run(e, st, [&]() -> int {
+    float* proj = e_f32(e, (size_t)B * e->arch.dense_total);
+    // Dense_0(act(temb))  layerspp.py:311-312
+    if (!e->dry && ds_launch_linear_t(temb, e->d_dense_w, e->d_dense_b, proj, B, temb_dim, e->arch.dense_total, 1, st)) return 1;
+    Tn out;
+    if (res_block(e, m, view(x, H, W, in_ch, in_ch), proj, B, out, st)) return 1;
+    if (!e->dry)
+      DS_HIP(hipMemcpyAsync(y, out.p, (size_t)B * Ho * Wo * out_ch * e->esz, hipMemcpyDeviceToDevice, st));
+    return 0;
+  });
+}
+
+extern "C" int32_t diffsep_attnblock_forward(int32_t channels, int32_t dtype, const float* params_host, int64_t n_floats,
+                                             const void* x, void* y, int32_t B, int32_t H, int32_t W, void* stream) {
+  DS_CHECK(params_host && x && y, "attnblock_forward: null pointer");
+  DS_CHECK(dtype == DS_F32 || dtype == DS_BF16, "attnblock_forward: bad dtype");
+  DS_CHECK(channels % 8 == 0 && channels >= 8 && B >= 1 && H >= 1 && W >= 1, "attnblock_forward: bad shape");
+  const std::unique_ptr<diffsep_engine> owner = unit_engine(dtype, 8);
+  diffsep_engine* e = owner.get();
+  ArchBuilder(e->arch).attn(channels);
+  if (upload_weights(e, params_host, n_floats, "block_forward: parameter blob")) return 1;
+  const Module& m = e->arch.mods[0];
+  hipStream_t st = (hipStream_t)stream;
+  return unit_engine_run(e, st, [&]() -> int {
+    Tn out;
+    if (attn_block(e, m, view(x, H, W, channels, channels), B, out, st)) return 1;
+    if (!e->dry)
+      DS_HIP(hipMemcpyAsync(y, out.p, (size_t)B * H * W * channels * e->esz, hipMemcpyDeviceToDevice, st));
+    return 0;
+  });
+}
+
+static float* g_tab = nullptr;
+static int g_tab_n = 0;
+static int unit_tab(int n_fft, float** tab) {
+  if (g_tab_n != n_fft) {
+    if (g_tab) hipFree(g_tab);
+    g_tab = nullptr;
+    g_tab_n = 0;
+    if (ds_build_stft_table(n_fft, &g_tab)) return 1;
+    g_tab_n = n_fft;
+  }
+  *tab = g_tab;
+  return 0;
+}
+
+extern "C" int32_t diffsep_stft_pack(const float* xt, const float* mix, void* y, int32_t B, int32_t S, int64_t T,
+                                     int32_t n_fft, int32_t hop, float exponent, float factor, int32_t W, int32_t Cpad,
+                                     int32_t centered_shift, int32_t dtype, void* workspace, int64_t workspace_bytes,
+                                     void* stream) {
+  DS_CHECK(xt && mix && y && workspace, "stft_pack: null pointer");
+  DS_CHECK(workspace_bytes >= ds_stft_workspace_bytes(B, S, T, n_fft, hop), "stft_pack: workspace too small");
+  float* tab;
+  if (unit_tab(n_fft, &tab)) return 1;
+  return ds_launch_stft_pack(xt, mix, y, B, S, T, n_fft, hop, exponent, factor, W, Cpad, centered_shift, dtype, tab,
+                             (float*)workspace, (hipStream_t)stream);
+}
+
+extern "C" int32_t diffsep_istft_unpack(const void* x, float* out, int32_t B, int32_t S, int64_t T, int32_t n_fft,
+                                        int32_t hop, float exponent, float factor, int32_t W, int32_t Cpad,
+                                        int32_t dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+  DS_CHECK(x && out && workspace, "istft_unpack: null pointer");
+  DS_CHECK(workspace_bytes >= ds_istft_workspace_bytes(B, S, T, n_fft, hop), "istft_unpack: workspace too small");
+  float* tab;
+  if (unit_tab(n_fft, &tab)) return 1;
+  return ds_launch_istft(x, out, B, S, T, n_fft, hop, exponent, factor, W, Cpad, dtype, tab, (float*)workspace,
+                         (hipStream_t)stream);
+}
+
+
+extern "C" int32_t diffsep_sde_sigma_mix(const float* mix, float* sigma_mix, int32_t B, int64_t T, int32_t avg_len,
+                                         void* stream) {
+  DS_CHECK(mix && sigma_mix, "sde_sigma_mix: null pointer");
+  return ds_launch_sigma_mix(mix, sigma_mix, B, T, avg_len, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_sde_prior(const diffsep_sde_config* sde, const float* y, const float* z, float* x, int32_t B,
+                                     int32_t S, int64_t T, const float* sigma_mix, void* stream) {
+  DS_CHECK(sde && y && z && x, "sde_prior: null pointer");
+  return ds_launch_sde_prior(to_sdep(sde), y, z, x, B, S, T, sigma_mix, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_sde_corrector_update(const diffsep_sde_config* sde, float snr, const float* x, const float* t,
+                                                const float* score, const float* z, float* x_out, float* x_mean_out,
+                                                int32_t B, int32_t S, int64_t T, const float* sigma_mix, int32_t variant,
+                                                void* stream) {
+  DS_CHECK(sde && x && t && score && x_out, "sde_corrector_update: null pointer");
+  return ds_launch_sde_corrector(to_sdep(sde), snr, x, t, score, z, x_out, x_mean_out, B, S, T, sigma_mix, variant,
+                                 (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_sde_predictor_update(const diffsep_sde_config* sde, int32_t N, const float* x, const float* t,
+                                                const float* score, const float* z, float* x_out, float* x_mean_out,
+                                                int32_t B, int32_t S, int64_t T, const float* sigma_mix,
+                                                int32_t probability_flow, void* stream) {
+  DS_CHECK(sde && x && t && score && x_out, "sde_predictor_update: null pointer");
+  return ds_launch_sde_predictor(to_sdep(sde), N, x, t, score, z, x_out, x_mean_out, B, S, T, sigma_mix,
+                                 probability_flow, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_sde_coefficients(const diffsep_sde_config* sde, const float* x, const float* t,
+                                            const float* sigma_mix, float* drift_out, float* diffusion_out, int32_t B,
+                                            int32_t S, int64_t T, float f_scale, float g_scale, void* stream) {
+  DS_CHECK(sde && x && t && drift_out && diffusion_out, "sde_coefficients: null pointer");
+  return ds_launch_sde_coeff(to_sdep(sde), x, t, sigma_mix, drift_out, diffusion_out, B, S, T, f_scale, g_scale,
+                             (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_sde_mean(const diffsep_sde_config* sde, const float* x0, const float* t, float* mean_out,
+                                    int32_t B, int32_t S, int64_t T, void* stream) {
+  DS_CHECK(sde && x0 && t && mean_out, "sde_mean: null pointer");
+  return ds_launch_sde_mean(to_sdep(sde), x0, t, mean_out, B, S, T, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_sde_std(const diffsep_sde_config* sde, const float* t, const float* sigma_mix, float* std_out,
+                                   int32_t B, int32_t S, int64_t T, void* stream) {
+  DS_CHECK(sde && t && std_out, "sde_std: null pointer");
+  return ds_launch_sde_std(to_sdep(sde), t, sigma_mix, std_out, B, S, T, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_sde_mult_std(const float* std, const float* x, float* out, int32_t B, int32_t S, int64_t T,
+                                        int32_t per_sample, void* stream) {
+  DS_CHECK(std && x && out, "sde_mult_std: null pointer");
+  return ds_launch_sde_mult_std(std, x, out, B, S, T, per_sample, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_sde_reverse_drift(const float* f, const float* G, const float* score, float* rev_f_out,
+                                             int32_t B, int64_t n_per_batch, int32_t g_full, int32_t probability_flow,
+                                             void* stream) {
+  DS_CHECK(f && G && score && rev_f_out, "sde_reverse_drift: null pointer");
+  return ds_launch_sde_reverse(f, G, score, rev_f_out, B, n_per_batch, g_full, probability_flow, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_sde_langevin_update(float snr, const float* x, const float* score, const float* z,
+                                               float* x_out, float* x_mean_out, int32_t B, int64_t n_per_batch,
+                                               void* workspace, int64_t workspace_bytes, void* stream) {
+  DS_CHECK(x && score && z && x_out && workspace, "sde_langevin_update: null pointer");
+  DS_CHECK(workspace_bytes >= 16 * (int64_t)B + 16, "sde_langevin_update: workspace too small");
+  return ds_launch_langevin(snr, x, score, z, x_out, x_mean_out, B, n_per_batch, workspace, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_normalize_batch(const float* mix, float* mix_norm, float* mean, float* std, int32_t B,
+                                           int64_t T, void* stream) {
+  DS_CHECK(mix && mix_norm, "normalize_batch: null pointer");
+  return ds_launch_normalize(mix, mix_norm, mean, std, B, T, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_scale_output(const float* mix, float* sep, int32_t B, int32_t S, int64_t T, void* stream) {
+  DS_CHECK(mix && sep, "scale_output: null pointer");
+  return ds_launch_scale_output(mix, sep, B, S, T, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_gram(const float* ref, const float* est, double* out, int32_t B, int32_t S, int64_t T,
+                                void* stream) {
+  DS_CHECK(ref && est && out, "gram: null pointer");
+  return ds_launch_gram(ref, est, out, B, S, T, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream) {
+  DS_CHECK(out, "randn: null pointer");
+  return ds_launch_randn(out, n, seed, stream_id, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_randn_batch(float* out, int32_t B, int32_t S, int64_t T, const uint64_t* seeds,
+                                       const int32_t* lengths, uint64_t stream_id, void* stream) {
+  DS_CHECK(out && seeds && lengths && B >= 1 && S >= 1 && T >= 1, "randn_batch: bad argument");
+  return ds_launch_randn_batch(out, B, S, T, seeds, lengths, stream_id, (hipStream_t)stream);
+}
+extern "C" int32_t diffsep_convert(const void* src, void* dst, int64_t n, int32_t sd, int32_t dd, void* stream) {
+  DS_CHECK(src && dst, "convert: null pointer");
+  return ds_launch_convert(src, dst, n, sd, dd, (hipStream_t)stream);
+}
