@@ -15,7 +15,8 @@ Output tree (evaluate.py:306-323,436-443): `<output_dir>/<exp>_<ckpt>_<tag_inf>/
 `wav/<split>/NNN_{mix,enh0,enh1,tgt0,tgt1}.wav` (scaled to peak 0.95 together, estimates in the permutation that matches
 the targets) for the first --save-n utterances (default: all).  Not produced: `fig/` (matplotlib spectrogram plots of the
 intermediate states) and the PESQ field (ITU-T P.862 C code, third-party `pesq`; null, named under `not_computed`).  STOI /
-ESTOI is computed (diffsep_amd.metrics.stoi) on loader threads.
+ESTOI is computed on loader threads (diffsep_amd.metrics.stoi, `--stoi-on host`, the default) or on the GPU
+(diffsep_amd.metrics.stoi_batch, `--stoi-on device`: no waveform leaves the device unless it is saved).
 
 Utterances are sharded over ranks in contiguous ranges (evaluate_mp.py:495-503); each rank separates its
 share, records {batch_idx, si_sdr, si_sir, si_sar, pesq, stoi, nfe, runtime, len_s} per utterance (evaluate.py:394-405;
@@ -57,6 +58,11 @@ def compute_metrics(est, ref, n_src=None):
     return [{"si_sdr": [[float(v) for v in sdr[b, :k]]], "si_sir": [[float(v) for v in sir[b, :k]]],
              "si_sar": [[float(v) for v in sar[b, :k]]], "perm": [int(v) for v in perm[b]]}
             for b in range(sdr.shape[0])]
+
+
+def needs_host_waveforms(args, group):
+    """does finish() have to copy this batch's waveforms to the host?  Only to save them, or to score STOI there."""
+    return (not args.no_stoi and args.stoi_on == "host") or args.save_n is None or any(i < args.save_n for i in group)
 
 
 def load_dataset(args, fs):
@@ -180,7 +186,12 @@ def build_parser():
     ap.add_argument("--flat-output", action="store_true",
                     help="write <split>.json / <split>_summary.json / wav/ directly into --output_dir instead of the reference's "
                          "<output_dir>/<exp>_<ckpt>_<tag_inf>/ folder")
-    ap.add_argument("--no-stoi", action="store_true", help="skip STOI (host-side, ~0.1 s per utterance and source on one core)")
+    ap.add_argument("--no-stoi", action="store_true",
+                    help="skip STOI (--stoi-on host: ~0.02 - 0.1 s per utterance and source on one core of the loader pool; "
+                         "--stoi-on device: a few kernel launches per batch)")
+    ap.add_argument("--stoi-on", choices=["host", "device"], default="host",
+                    help="where STOI / ESTOI is computed: host = numpy on the loader threads (needs the waveforms on the host); "
+                         "device = the HIP kernels of diffsep_stoi on the worker's stream (B x S numbers cross PCIe)")
     ap.add_argument("--seed", type=int, default=0, help="torch.manual_seed before the first utterance: the i-th "
                                                          "utterance gets the i-th draw as its device RNG seed")
     ap.add_argument("--balance", action="store_true",
@@ -408,7 +419,12 @@ def run_split(args, split, data, fs, models, streams, loader, output_dir, world,
         runtime = 0.0 if t0 is None else (time.perf_counter() - t0) / len(group)
         with torch.cuda.stream(streams[w]):
             mets = compute_metrics(est, tgt_n, n_src)
-        need_host = (not args.no_stoi) or args.save_n is None or any(i < args.save_n for i in group)
+        need_host = needs_host_waveforms(args, group)
+        stoi_dev = None
+        if not args.no_stoi and args.stoi_on == "device":  # every source against its permuted estimate, whole batch at once
+            with torch.cuda.stream(streams[w]):
+                stoi_dev = metrics.stoi_batch(tgt_n, est, fs, extended=not args.stoi_no_extended, lengths=lens,
+                                              perm=[m["perm"] for m in mets])
         est_h = tgt_h = mix_h = None
         if need_host:
             with torch.cuda.stream(streams[w]):
@@ -419,9 +435,11 @@ def run_split(args, split, data, fs, models, streams, loader, output_dir, world,
             records.append(rec)
             perm = mets[b]["perm"]
             k_src = len(perm) if n_src is None else n_src
+            if stoi_dev is not None:
+                rec["stoi"] = [float(v) for v in stoi_dev[b, :k_src]]
             if need_host:
                 est_b = est_h[b, perm, :lens[b]]  # "fix the permutation" (evaluate.py:392): estimates in the targets' order
-                if not args.no_stoi:
+                if not args.no_stoi and args.stoi_on == "host":
                     stoi_jobs.append((rec, loader.submit(stoi_of, tgt_h[b, :k_src, :lens[b]].numpy(), est_b[:k_src].numpy())))
                 if args.save_n is None or i < args.save_n:  # (evaluate.py:341; figures are not produced)
                     save_samples(mix_h[b, :, :lens[b]], est_b, tgt_h[b, :, :lens[b]], output_dir / "wav" / split, i, fs)
@@ -462,7 +480,7 @@ def run_split(args, split, data, fs, models, streams, loader, output_dir, world,
                         # PESQ is ITU-T P.862 reference C code behind the third-party `pesq` package: not restated here
                         # (DESIGN.md section 7); STOI / ESTOI is diffsep_amd.metrics.stoi (published algorithm, restated)
                         "not_computed": ["pesq"] + (["stoi"] if args.no_stoi else []),
-                        "stoi_extended": not args.stoi_no_extended, "pesq_mode": args.pesq_mode})
+                        "stoi_on": args.stoi_on, "stoi_extended": not args.stoi_no_extended, "pesq_mode": args.pesq_mode})
         with open(output_dir / f"{split}_summary.json", "w") as f:
             json.dump(summary, f, indent=2)
         print(json.dumps(summary))

@@ -179,3 +179,14 @@ def stoi(ref, est, fs, extended=True):
     yp = yp / (np.linalg.norm(yp, axis=2, keepdims=True) + _EPS)
     xz = xz / (np.linalg.norm(xz, axis=2, keepdims=True) + _EPS)
     return float(np.sum(yp * xz) / (n * _STOI_BANDS))
+
+
+def stoi_batch(ref, est, fs, extended=True, lengths=None, perm=None):
+    """stoi() of every source of a zero-padded batch, computed on the device (ops.stoi, csrc/stoi.hip): ref, est [B,S,T]
+    device tensors -> [B,S] float64 numpy array; estimate row perm[b][i] (default i) against reference row i over the first
+    lengths[b] (default T) samples.  One pinned, non-blocking readback of B * S numbers on the current stream."""
+    d = ops.stoi(ref, est, fs, extended=extended, lengths=lengths, perm=perm)
+    h = torch.empty(d.shape, dtype=d.dtype, pin_memory=True)
+    h.copy_(d, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return h.numpy().copy()

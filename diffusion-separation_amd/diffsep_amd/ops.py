@@ -403,6 +403,44 @@ def gram(ref, est):
     return out
 
 
+def _dev_i32(v, device):
+    """host list / array or tensor -> contiguous int32 device tensor (host values through pinned memory on the current
+    stream: a pageable copy would stall every other stream's work)"""
+    if isinstance(v, torch.Tensor) and v.is_cuda:
+        return v.to(torch.int32).contiguous()
+    h = torch.as_tensor(np.ascontiguousarray(np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v, dtype=np.int32)))
+    return h.pin_memory().to(device, non_blocking=True)
+
+
+def stoi_workspace_bytes(B, S, T, fs):
+    """bytes of workspace diffsep_stoi needs (host arithmetic; raises for a sample rate or shape it refuses)"""
+    n = lib().diffsep_stoi_workspace_bytes(int(B), int(S), int(T), int(fs))
+    check(0 if n >= 0 else 1)
+    return int(n)
+
+
+def stoi(ref, est, fs, extended=True, lengths=None, perm=None):
+    """STOI (extended: ESTOI) of every source of a zero-padded batch on the device: ref, est [B,S,T] float32 device tensors ->
+    float64 [B,S] device tensor; estimate row perm[b][i] (default i) against reference row i over the first lengths[b]
+    (default T) samples.  The algorithm of metrics.stoi in float64 (csrc/stoi.hip); asynchronous on the current stream."""
+    if ref.shape != est.shape or ref.dim() != 3:
+        raise ValueError("stoi: ref and est must be [B,S,T] tensors of one shape")
+    B, S, T = ref.shape
+    ref, est = ref.float().contiguous(), est.float().contiguous()
+    nbytes = stoi_workspace_bytes(B, S, T, fs)
+    ln = None if lengths is None else _dev_i32(lengths, ref.device)
+    pm = None if perm is None else _dev_i32(perm, ref.device)
+    if ln is not None and ln.numel() != B:
+        raise ValueError("stoi: lengths must have B entries")
+    if pm is not None and tuple(pm.shape) != (B, S):
+        raise ValueError("stoi: perm must be [B,S]")
+    out = torch.empty((B, S), dtype=torch.float64, device=ref.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=ref.device)
+    check(lib().diffsep_stoi(_ptr(ref), _ptr(est), _ptr(out), B, S, T, _ptr(ln), _ptr(pm), int(fs), int(bool(extended)),
+                             _ptr(ws), nbytes, _stream_ptr()))
+    return out
+
+
 def _ode_ptrs(K):
     return (C.c_void_p * max(1, len(K)))(*[k.data_ptr() for k in K])
 

@@ -479,6 +479,22 @@ int32_t diffsep_scale_output(const float* mix, float* sep, int32_t B, int32_t S,
  * { ref ref^T, ref est^T, est est^T }.  SI-SDR / SI-SIR / SI-SAR and the best permutation follow from these alone. */
 int32_t diffsep_gram(const float* ref, const float* est, double* out, int32_t B, int32_t S, int64_t T, void* stream);
 
+/* STOI / ESTOI of every source of a zero-padded batch (evaluate.py:113-130: pystoi's stoi(ref, est, fs, extended) per source;
+ * C. H. Taal, R. C. Hendriks, R. Heusdens, J. Jensen, "An Algorithm for Intelligibility Prediction of Time-Frequency Weighted
+ * Noisy Speech", IEEE TASLP 2011; J. Jensen, C. H. Taal, "An Algorithm for Predicting the Intelligibility of Speech Masked by
+ * Modulated Noise Maskers", IEEE/ACM TASLP 2016).  ref, est [B,S,T] float32; out [B][S] float64: estimate row perm[b][i]
+ * (NULL: i) scored against reference row i over the first lengths[b] (NULL: T) samples, in float64 from the samples on:
+ * polyphase resampling to 10 kHz (Kaiser-windowed sinc, 60 dB), silent-frame removal (40 dB), 15 one-third octave bands of
+ * 256-sample Hann frames, 30-frame segments; fewer than 30 frames left: 1e-5.  extended != 0: ESTOI.  lengths, perm: device
+ * int32.  Row (b, i) does not depend on the rest of the batch or on the stream (fixed-order reductions).  fs: any rate whose
+ * reduced 10000 / fs = p / q has p, q <= 1000 (8000, 10000, 16000, 44100, 48000 ...); others are refused.
+ * Caller-owned workspace of diffsep_stoi_workspace_bytes(B, S, T, fs) bytes (host arithmetic only; -1 and an error message for
+ * a bad shape or rate). */
+int64_t diffsep_stoi_workspace_bytes(int32_t B, int32_t S, int64_t T, int32_t fs);
+int32_t diffsep_stoi(const float* ref, const float* est, double* out, int32_t B, int32_t S, int64_t T,
+                     const int32_t* lengths, const int32_t* perm, int32_t fs, int32_t extended, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
 /* on-device standard normal draws (Philox4x32-10 + Box-Muller); used when noise == NULL. */
 int32_t diffsep_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);
 /* the same for a zero-padded batch of utterances with their own seeds and lengths (device arrays [B]): row (b, s) of
