@@ -32,18 +32,28 @@ the batch is zero-padded on the right to its longest member, the engine keeps ev
 (diffsep_sampler_ext.lengths_host) and draws its noise from the utterance's own seed, so an utterance's record does
 not depend on which batch, stream or rank it was separated in (bit-for-bit with --dtype f32; to the rounding of the
 GroupNorm sums of the weight-stationary bf16 convolution otherwise).
+
+--streams K such calls are in flight on K engines / K HIP streams.  What that takes (hardware queues, engines before
+streams, workspace reserve, per-utterance seeds and normalisation, pinned uploads, the launch / collect ring, the overflow
+re-run) is inflight.py's, shared with separate.py.  Here: main() sets the run up, a SplitRun holds one split's state and
+stages / launches / collects a batch and writes the two JSON files, run_split() is the warm-up and the timed region.
 """
 import argparse
 import json
 import os
 import time
+from collections import namedtuple
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass, field
 from pathlib import Path
+from typing import Callable
 
 import torch
 import torch.distributed as dist
 
-from . import datasets, metrics, ops, synth, wavio
+from . import datasets, inflight, metrics, synth, wavio
 from .dist_utils import gather_objects, rank_indices
+from .inflight import plan_batches  # (its callers import it from here)
 from .pl_model import DiffSepModel, cfg_get, default_config, enhancement_config
 
 
@@ -89,19 +99,6 @@ def load_dataset(args, fs):
         mix, tgt = synth.synth_mixture(i, T=lens[i], fs=fs, n_src=args.n_speakers)
         return torch.from_numpy(mix), torch.from_numpy(tgt)
     return n, get, lens
-
-
-def plan_batches(indices, lengths, width_of, batch):
-    """Group utterance indices into engine batches: equal padded width W, at most `batch` per call, longest first
-    inside a width (deterministic: ties by index).  Returns a list of index lists."""
-    by_w = {}
-    for i in indices:
-        by_w.setdefault(width_of(lengths[i]), []).append(i)
-    out = []
-    for w in sorted(by_w):
-        g = sorted(by_w[w], key=lambda i: (-lengths[i], i))
-        out += [g[k:k + batch] for k in range(0, len(g), batch)]
-    return out
 
 
 def _hparams_datasets(args, fs_model, splits):
@@ -179,10 +176,7 @@ def build_parser():
                     help="--synthetic: utterance lengths spread over [--samples, --samples-max] instead of one length")
     ap.add_argument("--n-speakers", type=int, default=2)
     ap.add_argument("--cut", default="max", choices=["min", "max"])
-    ap.add_argument("--dtype", default="auto", choices=["auto", "f16", "bf16", "f32", "split", "hybrid"],
-                    help="auto (default): f16 for backbones up to nf = 64, hybrid for wider ones; f16: 16-bit tensors in IEEE half precision, 50 dB from the fp32 result after 60 network "
-                         "evaluations; bf16: the same kernels on bfloat16 tensors (32 dB); split / f32: fp32 tensors (bf16x3 / "
-                         "exact fp32 matrix products); hybrid: f16 with the first reverse steps on a split engine")
+    inflight.add_precision_arguments(ap)  # --dtype, --fp32-steps
     ap.add_argument("--flat-output", action="store_true",
                     help="write <split>.json / <split>_summary.json / wav/ directly into --output_dir instead of the reference's "
                          "<output_dir>/<exp>_<ckpt>_<tag_inf>/ folder")
@@ -203,8 +197,6 @@ def build_parser():
     ap.add_argument("--streams", type=int, default=4,
                     help="engine calls (batches) in flight per GPU: K engines on K HIP streams; the records do not "
                          "depend on K.  'runtime' of an utterance is its batch's latency / batch size.")
-    ap.add_argument("--fp32-steps", type=int, default=None,
-                    help="with --dtype hybrid: the first K reverse steps run on the fp32 engine (default: pl_model.HYBRID_HEAD_STEPS)")
     return ap
 
 
@@ -224,10 +216,7 @@ def main(argv=None):
     if args.ckpt is None and not args.synthetic_weights and not no_proc:
         ap.error("a checkpoint (or --synthetic-weights NF) is required")
     if args.streams > 1:
-        # HIP maps streams onto GPU_MAX_HW_QUEUES (default 4) hardware queues, one of which the null stream holds:
-        # with the default, two of four worker streams share a queue (measured 10.7 instead of 18.5 utt/s).  Read
-        # by the HIP runtime when it initialises, i.e. this must precede the first torch.cuda call.
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+        inflight.default_hw_queues()  # (before the first torch.cuda call)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -244,8 +233,7 @@ def main(argv=None):
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     n_workers = max(2, min(os.cpu_count() or 2, 16) if args.dl_workers is None else args.dl_workers)
 
-    K = max(1, args.streams)
-    models, model = [], None
+    model = None
     if not no_proc:
         if args.synthetic_weights or args.ckpt is None:
             cfg = (enhancement_config(nf=args.synthetic_weights or 128) if args.enhance
@@ -254,24 +242,9 @@ def main(argv=None):
         else:
             model = DiffSepModel.load_from_checkpoint(args.ckpt, dtype=args.dtype, head_steps=args.fp32_steps)
         model.eval()
-        # one engine (weights repacked on the device + workspace) per stream over ONE set of parameters
-        models = [model] + [model.replica() for _ in range(K - 1)]
-        for m in models:
-            if K > 1:
-                m.set_throughput_mode(True)
-            # engines are created BEFORE the worker streams: HIP hands out hardware queues in stream-creation order, and
-            # engines created lazily in between left the workers sharing queues (measured 7.0 instead of 17 utt/s, K=4)
-            m.score_model.engine()
-            if m.tail_engine() is not None:
-                m.tail_engine()
+    models, streams = inflight.setup_workers(model, max(1, args.streams))  # (__no_proc__: no models, streams only)
     fs_model = cfg_get(model.config, "model.fs", 8000) if model is not None else None
-    N = cs = snr = None
-    if model is not None:
-        N = cfg_get(model.config, "model.sampler.N", 30) if args.N is None else args.N
-        cs = cfg_get(model.config, "model.sampler.corrector_steps", 1) if args.corrector_steps is None else args.corrector_steps
-        snr = cfg_get(model.config, "model.sampler.snr", 0.5) if args.snr is None else args.snr
-    denoise = args.denoise
-    n_src = 1 if args.enhance else None  # (evaluate.py:268-271)
+    N, cs, snr = inflight.sampler_settings(model.config, args) if model is not None else (None, None, None)
 
     # ---- the output folder (evaluate.py:257-262,306-323)
     if args.flat_output:
@@ -279,7 +252,7 @@ def main(argv=None):
     elif no_proc:
         output_dir = args.output_dir / ("mix" if args.tag is None else args.tag)
     else:
-        tag_inf = f"N-{N}_snr-{snr}_corrstep-{cs}_denoise-{denoise}_schedule-{args.schedule}"
+        tag_inf = f"N-{N}_snr-{snr}_corrstep-{cs}_denoise-{args.denoise}_schedule-{args.schedule}"
         if args.tag is not None:
             output_dir = args.output_dir / f"{args.tag}_{tag_inf}"
         elif args.ckpt is not None and not args.synthetic_weights:
@@ -298,22 +271,22 @@ def main(argv=None):
         else:
             from_hparams = _hparams_datasets(args, fs_model, splits)
 
-    streams = [torch.cuda.Stream() for _ in range(K)]
-    from concurrent.futures import ThreadPoolExecutor
     # the reference's DataLoader has worker processes; here loader threads read / synthesise and pad the next batches while the
     # GPU separates the current ones (wav decoding and numpy release the GIL), and score STOI of the finished ones
     loader = ThreadPoolExecutor(max_workers=n_workers)
+    common = dict(args=args, models=models, streams=streams, loader=loader, sampler_kw=dict(N=N, corrector_steps=cs, snr=snr),
+                  output_dir=output_dir, rank=rank, world=world)
     for split in splits:
         if from_hparams is not None:
             ds = from_hparams[split]
-            n_ = len(ds) if args.limit is None else min(len(ds), args.limit)
-            data = (n_, (lambda i, ds=ds: tuple(t[..., : ds.num_samples(i)] for t in ds[i])), [ds.num_samples(i) for i in range(n_)])
+            n = len(ds) if args.limit is None else min(len(ds), args.limit)
+            get, lengths = (lambda i, ds=ds: tuple(t[..., : ds.num_samples(i)] for t in ds[i])), [ds.num_samples(i) for i in range(n)]
             fs = ds.fs
         else:
             args_split = argparse.Namespace(**{**vars(args), "split": split})
             fs = fs_model if fs_model is not None else 8000
-            data = load_dataset(args_split, fs)
-        run_split(args, split, data, fs, models, streams, loader, output_dir, world, rank, N, cs, snr, denoise, n_src, no_proc)
+            n, get, lengths = load_dataset(args_split, fs)
+        run_split(SplitRun(**common, split=split, fs=fs, n=n, get=get, lengths=lengths))
     loader.shutdown()
     if world > 1:
         dist.barrier()
@@ -321,169 +294,172 @@ def main(argv=None):
     return output_dir
 
 
-def run_split(args, split, data, fs, models, streams, loader, output_dir, world, rank, N, cs, snr, denoise, n_src, no_proc):
-    n, get, lengths = data
-    K = len(streams)
-    model = models[0] if models else None
-    if rank == 0:
-        print(f"Processing {split}: {n} samples")
-    if no_proc:
-        width_of = lambda T: 64 * ((1 + (T + 382) // 128 + 63) // 64)
-        bucket = lambda W: 128 * W - 383
-    else:
-        eng0 = model.score_model.engine()
-        width_of, bucket = eng0.padded_frames, eng0.bucket_length
-    # the reference's contiguous ranges (evaluate_mp.py:495-503), or sorted by length and dealt round-robin
-    mine = rank_indices(n, world, rank, lengths, args.balance)
-    batches = plan_batches(mine, lengths, width_of, max(1, args.batch))
-    if batches and not no_proc:  # workspace for the largest call now: growing it later would stall every stream
-        bmax = max(len(g) for g in batches)
-        tmax = bucket(width_of(max(lengths[i] for i in mine)))
-        for m in models:
-            m.score_model.engine().reserve(bmax, tmax)
-            if m.tail_engine() is not None:
-                m.tail_engine().reserve(bmax, tmax)
-    # utterance i of the data set gets the i-th draw of a generator seeded with --seed as its device RNG seed: the
-    # records do not depend on the number of streams, of ranks, or on how the utterances are batched or dealt
-    seeds = torch.randint(0, 2 ** 62, (max(n, 1),), generator=torch.Generator().manual_seed(args.seed)).tolist()
-    records = []
-    fallbacks = []  # batches repeated on the split-precision engine after non-finite f16 samples
-    pending = [None] * K  # per worker: the batch whose sampler is running on its stream
-    stoi_jobs = []  # (record, future of the per-source STOI list)
+# One engine call in flight: what collect needs (utterance indices, their lengths in samples, ..., t0 = host time at which the
+# sampler was enqueued, None when nothing was separated) and every tensor the asynchronous sampler reads (they stay referenced
+# until the worker's stream has drained).
+_Batch = namedtuple("_Batch", "group lens mix mix_n tgt_n est nfe t0 sampler")
 
-    def host_stage(group):
+
+@dataclass
+class SplitRun:
+    """One split on one rank: what main() set up, the split's data, the rank's plan, and what the batches leave behind."""
+    args: argparse.Namespace
+    models: list   # one per stream (none with __no_proc__: the mixture itself is scored)
+    streams: list
+    loader: ThreadPoolExecutor
+    sampler_kw: dict  # N, corrector_steps, snr
+    output_dir: Path
+    rank: int
+    world: int
+    split: str
+    fs: int
+    n: int  # utterances of the split; get(i) -> (mix [1,T], tgt [S,T]) CPU tensors; lengths in samples
+    get: Callable
+    lengths: list
+    records: list = field(default_factory=list)
+    stoi_jobs: list = field(default_factory=list)  # (record, future of the per-source STOI list)
+    fallbacks: list = field(default_factory=list)  # batches repeated on the split-precision engine after non-finite f16 samples
+    ahead: dict = field(default_factory=dict)  # batch number -> future of its host_stage()
+
+    def __post_init__(self):
+        a = self.args
+        self.no_proc = not self.models
+        self.n_src = 1 if a.enhance else None  # (evaluate.py:268-271)
+        if self.no_proc:
+            self.width_of = lambda T: 64 * ((1 + (T + 382) // 128 + 63) // 64)
+            self.bucket = lambda W: 128 * W - 383
+        else:
+            eng0 = self.models[0].score_model.engine()
+            self.width_of, self.bucket = eng0.padded_frames, eng0.bucket_length
+        # the reference's contiguous ranges (evaluate_mp.py:495-503), or sorted by length and dealt round-robin (SURVEY 8e)
+        self.mine = rank_indices(self.n, self.world, self.rank, self.lengths, a.balance)
+        self.batches = plan_batches(self.mine, self.lengths, self.width_of, max(1, a.batch))
+        self.seeds = inflight.utterance_seeds(self.n, a.seed)
+
+    def host_stage(self, group):
         """load and pad one batch on the host (runs on a loader thread, ahead of the GPU): mix / tgt + lengths"""
-        items = [get(i) for i in group]
+        items = [self.get(i) for i in group]
         # padded to the longest length of the batch's width bucket: one workspace plan / captured graph per (B, W)
-        mix, tgt, lens = datasets.pad_batch(items, side="right", to=bucket(width_of(max(lengths[i] for i in group))))
+        mix, tgt, lens = datasets.pad_batch(items, side="right",
+                                            to=self.bucket(self.width_of(max(self.lengths[i] for i in group))))
         return mix.contiguous(), tgt.contiguous(), lens
 
-    ahead = {}
+    def prefetch(self, j):
+        for jj in range(j, min(j + 2 * len(self.streams) + 2, len(self.batches))):
+            if jj not in self.ahead:
+                self.ahead[jj] = self.loader.submit(self.host_stage, self.batches[jj])
 
-    def prefetch(j):
-        for jj in range(j, min(j + 2 * K + 2, len(batches))):
-            if jj not in ahead:
-                ahead[jj] = loader.submit(host_stage, batches[jj])
-
-    def stage(group, w, j=None):
-        """upload and normalise one batch on worker w's stream -> (mix, mix_n, tgt_n, lens)"""
-        mix, tgt, lens = ahead.pop(j).result() if j in ahead else host_stage(group)
-        # pinned staging + asynchronous copies (a pageable host->device copy serialises the whole device); pinned memory is
-        # allocated on THIS thread: the loader threads make no HIP runtime call
-        mix = mix.pin_memory().to("cuda", non_blocking=True)
-        tgt = tgt.pin_memory().to("cuda", non_blocking=True)
-        if no_proc:  # (evaluate.py:349-355: the raw mixture against the raw targets)
+    def stage(self, w, j, group):
+        """upload and normalise one batch on the current (worker w's) stream -> (mix, mix_n, tgt_n, lens)"""
+        mix, tgt, lens = self.ahead.pop(j).result() if j in self.ahead else self.host_stage(group)
+        mix, tgt = inflight.upload(mix), inflight.upload(tgt)
+        if self.no_proc:  # (evaluate.py:349-355: the raw mixture against the raw targets)
             return mix, mix, tgt, lens
-        mix_n, tgt_n = torch.zeros_like(mix), torch.zeros_like(tgt)
-        for b, L in enumerate(lens):  # every utterance is normalised over ITS samples (pl_model.py:81-88)
-            (m_b, t_b), *_ = models[w].normalize_batch((mix[b:b + 1, :, :L], tgt[b:b + 1, :, :L]))
-            mix_n[b, :, :L], tgt_n[b, :, :L] = m_b[0], t_b[0]
-        return mix, mix_n, tgt_n, lens
+        return (mix, *inflight.normalize_padded(self.models[w], lens, mix, tgt), lens)
 
-    def launch(group, w, j=None):
-        mix, mix_n, tgt_n, lens = stage(group, w, j)
-        if no_proc:
+    def sampler_for(self, model, group, lens, mix_n):
+        return model.get_pc_sampler("reverse_diffusion", "ald2", mix_n, **self.sampler_kw, denoise=self.args.denoise,
+                                    intermediate=False, schedule=self.args.schedule, lengths=lens,
+                                    seeds=[self.seeds[i] for i in group], check_finite=False)
+
+    def launch(self, w, j, group):
+        """enqueue batch j (None: a warm-up call, nothing was prefetched for it) on the current (worker w's) stream"""
+        if j is not None:
+            self.prefetch(j)
+        mix, mix_n, tgt_n, lens = self.stage(w, j, group)
+        if self.no_proc:
             est = mix_n.expand(-1, tgt_n.shape[1], -1).contiguous()  # x_result = broadcast_to(mix, target.shape)
-            return (group, lens, tgt_n, est, 0, None, (mix, mix_n, None))
-        sampler = models[w].get_pc_sampler("reverse_diffusion", "ald2", mix_n, N=N, corrector_steps=cs, snr=snr,
-                                           denoise=denoise, intermediate=False, schedule=args.schedule,
-                                           lengths=lens, seeds=[seeds[i] for i in group], check_finite=False)
-        if K == 1:
+            return _Batch(group, lens, mix, mix_n, tgt_n, est, 0, None, None)
+        sampler = self.sampler_for(self.models[w], group, lens, mix_n)
+        if len(self.streams) == 1:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
         est, nfe, *_ = sampler()  # enqueues the whole sampler on the worker's stream
-        # (every tensor the asynchronous sampler reads stays referenced until the worker's stream has drained)
-        return (group, lens, tgt_n, est, nfe, t0, (mix, mix_n, sampler))
+        return _Batch(group, lens, mix, mix_n, tgt_n, est, nfe, t0, sampler)
 
-    def stoi_of(tgt_rows, est_rows):
-        return [metrics.stoi(t_, e_, fs, extended=not args.stoi_no_extended) for t_, e_ in zip(tgt_rows, est_rows)]
+    def reissue(self, fb, b):
+        self.fallbacks.append(list(b.group))
+        return self.sampler_for(fb, b.group, b.lens, b.mix_n)()
 
-    def finish(w):
-        if pending[w] is None:
-            return
-        group, lens, tgt_n, est, nfe, t0, _alive = pending[w]
-        pending[w] = None
-        streams[w].synchronize()
-        # half precision overflows at 65504: a batch with non-finite samples is repeated on the model's split-precision twin
-        # (DiffSepModel.rerun_if_nonfinite — the one place that decides; raises if that is non-finite too)
-        def rerun(fb):
-            with torch.cuda.stream(streams[w]):
-                r = fb.get_pc_sampler("reverse_diffusion", "ald2", _alive[1], N=N, corrector_steps=cs, snr=snr, denoise=denoise,
-                                      intermediate=False, schedule=args.schedule, lengths=lens,
-                                      seeds=[seeds[i] for i in group], check_finite=False)()
-            streams[w].synchronize()
-            fallbacks.append(list(group))
-            return r
-        if not no_proc:
-            est, nfe, *_ = models[w].rerun_if_nonfinite((est, nfe), rerun, what=f"utterances {group[:3]}...")
-        runtime = 0.0 if t0 is None else (time.perf_counter() - t0) / len(group)
-        with torch.cuda.stream(streams[w]):
-            mets = compute_metrics(est, tgt_n, n_src)
-        need_host = needs_host_waveforms(args, group)
+    def collect(self, w, b):
+        """batch b, whose sampler has drained from worker w's stream, into records (+ STOI jobs, saved samples)"""
+        a, stream, (group, lens, tgt_n, est, nfe) = self.args, self.streams[w], (b.group, b.lens, b.tgt_n, b.est, b.nfe)
+        if not self.no_proc:
+            est, nfe, *_ = inflight.finite_or_rerun(self.models[w], stream, (est, nfe), lambda fb: self.reissue(fb, b),
+                                                    what=f"utterances {group[:3]}...")
+        runtime = 0.0 if b.t0 is None else (time.perf_counter() - b.t0) / len(group)
+        with torch.cuda.stream(stream):
+            mets = compute_metrics(est, tgt_n, self.n_src)
+        need_host = needs_host_waveforms(a, group)
         stoi_dev = None
-        if not args.no_stoi and args.stoi_on == "device":  # every source against its permuted estimate, whole batch at once
-            with torch.cuda.stream(streams[w]):
-                stoi_dev = metrics.stoi_batch(tgt_n, est, fs, extended=not args.stoi_no_extended, lengths=lens,
+        if not a.no_stoi and a.stoi_on == "device":  # every source against its permuted estimate, whole batch at once
+            with torch.cuda.stream(stream):
+                stoi_dev = metrics.stoi_batch(tgt_n, est, self.fs, extended=not a.stoi_no_extended, lengths=lens,
                                               perm=[m["perm"] for m in mets])
-        est_h = tgt_h = mix_h = None
         if need_host:
-            with torch.cuda.stream(streams[w]):
-                est_h, tgt_h, mix_h = est.cpu(), tgt_n.cpu(), _alive[1].cpu()
-        for b, i in enumerate(group):
-            rec = {"batch_idx": i, **mets[b], "pesq": None, "stoi": None, "nfe": int(nfe), "runtime": runtime,
-                   "len_s": lens[b] / fs}
-            records.append(rec)
-            perm = mets[b]["perm"]
-            k_src = len(perm) if n_src is None else n_src
+            with torch.cuda.stream(stream):
+                est_h, tgt_h, mix_h = est.cpu(), tgt_n.cpu(), b.mix_n.cpu()
+        for k, i in enumerate(group):
+            rec = {"batch_idx": i, **mets[k], "pesq": None, "stoi": None, "nfe": int(nfe), "runtime": runtime,
+                   "len_s": lens[k] / self.fs}
+            self.records.append(rec)
+            perm = mets[k]["perm"]
+            k_src = len(perm) if self.n_src is None else self.n_src
             if stoi_dev is not None:
-                rec["stoi"] = [float(v) for v in stoi_dev[b, :k_src]]
+                rec["stoi"] = [float(v) for v in stoi_dev[k, :k_src]]
             if need_host:
-                est_b = est_h[b, perm, :lens[b]]  # "fix the permutation" (evaluate.py:392): estimates in the targets' order
-                if not args.no_stoi and args.stoi_on == "host":
-                    stoi_jobs.append((rec, loader.submit(stoi_of, tgt_h[b, :k_src, :lens[b]].numpy(), est_b[:k_src].numpy())))
-                if args.save_n is None or i < args.save_n:  # (evaluate.py:341; figures are not produced)
-                    save_samples(mix_h[b, :, :lens[b]], est_b, tgt_h[b, :, :lens[b]], output_dir / "wav" / split, i, fs)
+                est_k = est_h[k, perm, :lens[k]]  # "fix the permutation" (evaluate.py:392): estimates in the targets' order
+                if not a.no_stoi and a.stoi_on == "host":
+                    self.stoi_jobs.append((rec, self.loader.submit(_stoi_rows, tgt_h[k, :k_src, :lens[k]].numpy(),
+                                                                   est_k[:k_src].numpy(), self.fs, not a.stoi_no_extended)))
+                if a.save_n is None or i < a.save_n:  # (evaluate.py:341; figures are not produced)
+                    save_samples(mix_h[k, :, :lens[k]], est_k, tgt_h[k, :, :lens[k]], self.output_dir / "wav" / self.split, i, self.fs)
 
-    # warm every worker up on the first batch's shape (workspace plan, graph capture) outside the timed region
-    if batches and not no_proc:
-        for w in range(K):
-            with torch.cuda.stream(streams[w]):
-                launch(batches[0], w)
-        torch.cuda.synchronize()
-    # One host thread drives all K streams (a thread per stream was measured SLOWER: 10.7 instead of 17 utt/s at K = 4;
-    # concurrent launches serialise inside the HIP runtime and a launch that waits for queue space holds them all up).
-    t_all = time.perf_counter()
-    prefetch(0)
-    for j, group in enumerate(batches):
-        w = j % K
-        finish(w)  # the worker's previous batch (oldest in flight)
-        prefetch(j)
-        with torch.cuda.stream(streams[w]):
-            pending[w] = launch(group, w, j)
-    for w in range(K):
-        finish(w)
-    torch.cuda.synchronize()
-    wall = time.perf_counter() - t_all
-    for rec, fut in stoi_jobs:
-        rec["stoi"] = fut.result()
-    allrec = gather_objects(records)
-    if rank == 0:
+    def write_results(self, allrec, wall):
+        """rank 0: <split>.json (every rank's records, by utterance) and <split>_summary.json; wall: this rank's timed region"""
+        a, model = self.args, self.models[0] if self.models else None
         flat = sorted([r for part in allrec for r in part], key=lambda r: r["batch_idx"])
-        with open(output_dir / f"{split}.json", "w") as f:
+        with open(self.output_dir / f"{self.split}.json", "w") as f:
             json.dump(flat, f, indent=2)
         summary = datasets.summarize([{k: v for k, v in r.items() if k not in ("batch_idx", "perm")} for r in flat])
         tot_rt = sum(r["runtime"] for r in flat)
-        summary.update({"rtf": tot_rt / max(sum(r["len_s"] for r in flat), 1e-9), "world_size": world,
-                        "streams": K, "batch": args.batch, "engine_calls_rank0": len(batches),
+        summary.update({"rtf": tot_rt / max(sum(r["len_s"] for r in flat), 1e-9), "world_size": self.world,
+                        "streams": len(self.streams), "batch": a.batch, "engine_calls_rank0": len(self.batches),
                         "dtype": model.dtype if model is not None else None,
-                        "utt_per_s_rank0": len(mine) / max(wall, 1e-9), "split_fallback_batches_rank0": len(fallbacks),
+                        "utt_per_s_rank0": len(self.mine) / max(wall, 1e-9), "split_fallback_batches_rank0": len(self.fallbacks),
                         # PESQ is ITU-T P.862 reference C code behind the third-party `pesq` package: not restated here
                         # (DESIGN.md section 7); STOI / ESTOI is diffsep_amd.metrics.stoi (published algorithm, restated)
-                        "not_computed": ["pesq"] + (["stoi"] if args.no_stoi else []),
-                        "stoi_on": args.stoi_on, "stoi_extended": not args.stoi_no_extended, "pesq_mode": args.pesq_mode})
-        with open(output_dir / f"{split}_summary.json", "w") as f:
+                        "not_computed": ["pesq"] + (["stoi"] if a.no_stoi else []),
+                        "stoi_on": a.stoi_on, "stoi_extended": not a.stoi_no_extended, "pesq_mode": a.pesq_mode})
+        with open(self.output_dir / f"{self.split}_summary.json", "w") as f:
             json.dump(summary, f, indent=2)
         print(json.dumps(summary))
+
+
+def _stoi_rows(tgt_rows, est_rows, fs, extended):
+    return [metrics.stoi(t_, e_, fs, extended=extended) for t_, e_ in zip(tgt_rows, est_rows)]
+
+
+def run_split(run):
+    if run.rank == 0:
+        print(f"Processing {run.split}: {run.n} samples")
+    inflight.reserve_largest(run.models, run.batches, run.lengths)
+    # warm every worker up on the first batch's shape (workspace plan, graph capture) outside the timed region
+    if run.batches and not run.no_proc:
+        for w, stream in enumerate(run.streams):
+            with torch.cuda.stream(stream):
+                run.launch(w, None, run.batches[0])
+        torch.cuda.synchronize()
+    t_all = time.perf_counter()
+    run.prefetch(0)
+    inflight.Ring(run.streams, run.launch, run.collect).run(run.batches)
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t_all
+    for rec, fut in run.stoi_jobs:
+        rec["stoi"] = fut.result()
+    allrec = gather_objects(run.records)
+    if run.rank == 0:
+        run.write_results(allrec, wall)
 
 
 if __name__ == "__main__":
