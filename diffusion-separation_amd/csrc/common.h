@@ -350,6 +350,47 @@ __device__ inline float sde_g_of_t(const SdeP& s, float t) {
   const float r = s.sigma_max / s.sigma_min;
   return s.sigma_min * powf(r, t) * sqrtf(2.0f * logf(r));
 }
+// ev1, ev2 of the perturbation covariance in the operation order of MixSDE._cov_eigval (sdes/sdes.py:296-309); shared by the
+// sampler updates / sde_std_kernel (sde.hip) and the score-matching loss (score_loss.hip): the same roundings everywhere
+__device__ inline void mix_eig(const SdeP& s, float t, float& ev1, float& ev2) {
+  const float r = s.sigma_max / s.sigma_min;
+  const float logsig = logf(r);
+  const float mult = s.sigma_min * s.sigma_min;
+  const float srp = powf(r, 2.0f * t);
+  ev1 = mult * (srp - 1.0f);
+  const float ex = expf(-2.0f * s.d_lambda * t);
+  const float denom = 1.0f + s.d_lambda / logsig;
+  ev2 = mult * (srp - ex) / denom;
+}
+// Philox4x32-10 + Box-Muller: values 4 q .. 4 q + 3 of the stream diffsep_randn(seed, stream id) draws (randn_kernel, sde.hip,
+// holds the same sequence of operations)
+__device__ inline void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0, uint32_t k1) {
+  const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+  const uint32_t n1 = (uint32_t)p1;
+  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+  const uint32_t n3 = (uint32_t)p0;
+  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+}
+__device__ inline void philox_randn4(uint64_t q, uint64_t seed, uint64_t sid, float* v) {
+  uint32_t c0 = (uint32_t)q, c1 = (uint32_t)(q >> 32), c2 = (uint32_t)sid, c3 = (uint32_t)(sid >> 32);
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c0, c1, c2, c3, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  const float u0 = ((float)(c0 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u1 = ((float)(c1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u2 = ((float)(c2 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u3 = ((float)(c3 >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
+  sincosf(6.28318530718f * u1, &v[1], &v[0]);
+  sincosf(6.28318530718f * u3, &v[3], &v[2]);
+  v[0] *= r0; v[1] *= r0; v[2] *= r1; v[3] *= r1;
+}
 // -lambda P x at one time index (x [S] -> f [S])   MixSDE.sde drift (sdes/sdes.py:275-284).  sde_coeff_kernel and the
 // ODE drift (ode.hip) both go through these two helpers: the same operations, the same roundings.
 __device__ inline void sde_mix_drift(const SdeP& s, const float* xv, float* f, int S) {

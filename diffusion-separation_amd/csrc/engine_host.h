@@ -386,5 +386,7 @@ int attention_core(const Tn& q, const void* k, const void* vt, const Tn& o, int 
                    hipStream_t st, int split = 0);
 int ensure_plan(diffsep_engine* e, int B, long T, hipStream_t st);
 int run_nfe(diffsep_engine* e, int B, long T, hipStream_t st);
+// sampler.hip: zero the tail t >= lens[b] of [B][rows][T] rows (the mixture of a mixed-length batch)
+int ds_launch_mask_tail(float* v, int B, int rows, long T, const int* lens, hipStream_t st);
 
 #pragma GCC visibility pop

@@ -20,6 +20,12 @@ __global__ __launch_bounds__(256) void mask_tail_kernel(float* __restrict__ v, i
   for (int r = 0; r < rows; ++r) v[((long)b * rows + r) * T + t] = 0.f;
 }
 
+int ds_launch_mask_tail(float* v, int B, int rows, long T, const int* lens, hipStream_t st) {
+  hipLaunchKernelGGL(mask_tail_kernel, dim3(cdiv(T, 256), B), dim3(256), 0, st, v, rows, T, lens);
+  DS_LAUNCH_CHECK();
+  return 0;
+}
+
 // What both samplers ask of the SDE description (`who`: the entry point's name in the message)
 static int check_sde(const diffsep_engine* e, const diffsep_sde_config* sde, const char* who) {
   const std::string w(who);

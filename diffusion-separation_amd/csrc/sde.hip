@@ -8,19 +8,7 @@
 //   g(t)= smin r^t sqrt(2 ln r);  G = g sqrt(dt), dt = 1/N (quirk Q1)                     sdes.py:275-284, 93-107
 #include "common.h"
 
-struct MixCoef { float a, p; };  // sqrt(ev1), sqrt(ev2)
-
-__device__ inline void mix_eig(const SdeP& s, float t, float& ev1, float& ev2) {
-  const float r = s.sigma_max / s.sigma_min;
-  const float logsig = logf(r);
-  const float mult = s.sigma_min * s.sigma_min;
-  const float srp = powf(r, 2.0f * t);
-  ev1 = mult * (srp - 1.0f);
-  const float ex = expf(-2.0f * s.d_lambda * t);
-  const float denom = 1.0f + s.d_lambda / logsig;
-  ev2 = mult * (srp - ex) / denom;
-}
-
+// (mix_eig: the eigenvalues ev1, ev2 of the perturbation covariance, common.h)
 // PriorMixSDE._std_sigma_mix  sdes.py:477-489: 0.5 * sqrt(clamp(avg_pool1d(mix^2, k, stride 1, pad k/2), 1e-4)),
 // zero padding counted in the average; for even k the extra trailing output is dropped.
 __global__ __launch_bounds__(256) void sde_sigma_mix_kernel(const float* __restrict__ mix, float* __restrict__ out,
@@ -498,16 +486,7 @@ int ds_launch_gram(const float* ref, const float* est, double* out, int B, int S
   return 0;
 }
 
-// ------------------------------------------------------------------ Philox4x32-10 + Box–Muller
-__device__ inline void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-  const uint32_t n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-  const uint32_t n3 = (uint32_t)p0;
-  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
+// ------------------------------------------------------------------ Philox4x32-10 + Box–Muller (philox_round: common.h)
 __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, long n, uint64_t seed, uint64_t sid) {
   const long q = (long)blockIdx.x * 256 + threadIdx.x;  // one thread = 4 outputs
   if (q * 4 >= n) return;

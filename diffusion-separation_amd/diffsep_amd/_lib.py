@@ -55,6 +55,13 @@ class OdeInfo(C.Structure):  # diffsep_ode_info
                 ("t_final", C.c_double)]
 
 
+PIT_NONE, PIT_TRUE_MIX, PIT_MEAN0 = 0, 1, 2
+
+
+class LossConfig(C.Structure):  # diffsep_loss_config
+    _fields_ = [("pit_mode", C.c_int32), ("redefine_z", C.c_int32)]
+
+
 class ProfRecord(C.Structure):  # diffsep_prof_record
     _fields_ = [("kernel", C.c_char * 128), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32),
                 ("Cout", C.c_int32), ("taps", C.c_int32), ("skip_cin", C.c_int32), ("has_res", C.c_int32),
@@ -132,6 +139,14 @@ _SIGS = {
     "diffsep_sde_mean": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _I, _I, _L, _P]),
     "diffsep_sde_std": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _I, _I, _L, _P]),
     "diffsep_sde_mult_std": (_I, [_P, _P, _P, _I, _I, _L, _I, _P]),
+    "diffsep_sde_mult_std_inv": (_I, [_P, _P, _P, _I, _I, _L, _I, _P]),
+    "diffsep_sde_perturb": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _I, _P, _U64, _U64, _P, _P, _I, _I, _L, _P]),
+    "diffsep_score_loss_workspace_bytes": (_L, [_I, _I, _L]),
+    "diffsep_score_loss_reduce": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _L, _P,
+                                       _L, _P]),
+    "diffsep_score_loss": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(LossConfig), _P, _P, _P, _P, _P, _U64, _P, _P, _P, _P, _P,
+                                _P, _I, _L, _P, _L, _P]),
+    "diffsep_score_loss_validate": (_I, [C.POINTER(ModelConfig), C.POINTER(LossConfig), _I, _L, _P, _L]),
     "diffsep_sde_reverse_drift": (_I, [_P, _P, _P, _P, _I, _L, _I, _I, _P]),
     "diffsep_sde_langevin_update": (_I, [_F, _P, _P, _P, _P, _P, _I, _L, _P, _L, _P]),
     "diffsep_normalize_batch": (_I, [_P, _P, _P, _P, _I, _L, _P]),

@@ -51,7 +51,7 @@ from typing import Callable
 import torch
 import torch.distributed as dist
 
-from . import datasets, inflight, metrics, synth, wavio
+from . import datasets, inflight, metrics, ops, synth, wavio
 from .dist_utils import gather_objects, rank_indices
 from .inflight import plan_batches  # (its callers import it from here)
 from .pl_model import DiffSepModel, cfg_get, default_config, enhancement_config
@@ -186,6 +186,10 @@ def build_parser():
     ap.add_argument("--stoi-on", choices=["host", "device"], default="host",
                     help="where STOI / ESTOI is computed: host = numpy on the loader threads (needs the waveforms on the host); "
                          "device = the HIP kernels of diffsep_stoi on the worker's stream (B x S numbers cross PCIe)")
+    ap.add_argument("--score-loss", type=int, default=0, metavar="K",
+                    help="also record every utterance's denoising score-matching loss (the reference's val/score_loss): the mean "
+                         "of K plain losses at times linspace(t_eps, 1, K) with device noise keyed by the utterance's seed, one "
+                         "network evaluation each, in the batch that is separated (default 0: off)")
     ap.add_argument("--seed", type=int, default=0, help="torch.manual_seed before the first utterance: the i-th "
                                                          "utterance gets the i-th draw as its device RNG seed")
     ap.add_argument("--balance", action="store_true",
@@ -297,7 +301,7 @@ def main(argv=None):
 # One engine call in flight: what collect needs (utterance indices, their lengths in samples, ..., t0 = host time at which the
 # sampler was enqueued, None when nothing was separated) and every tensor the asynchronous sampler reads (they stay referenced
 # until the worker's stream has drained).
-_Batch = namedtuple("_Batch", "group lens mix mix_n tgt_n est nfe t0 sampler")
+_Batch = namedtuple("_Batch", "group lens mix mix_n tgt_n est nfe t0 sampler sloss", defaults=(None,))
 
 
 @dataclass
@@ -362,6 +366,22 @@ class SplitRun:
                                     intermediate=False, schedule=self.args.schedule, lengths=lens,
                                     seeds=[self.seeds[i] for i in group], check_finite=False)
 
+    def score_loss(self, model, group, lens, mix_n, tgt_n):
+        """mean over K times of the plain score-matching loss of every utterance of the batch -> float64 [B] device tensor,
+        enqueued on the current stream (diffsep_score_loss with lengths: a row does not depend on the batch it rides in)"""
+        K = self.args.score_loss
+        B, S, T = tgt_n.shape
+        seeds = [self.seeds[i] for i in group]
+        eng, sde = model.score_model.engine(), model.sde.engine_config()
+        total = torch.zeros(B, dtype=torch.float64, device=tgt_n.device)
+        for k, t in enumerate(torch.linspace(float(model.t_eps), float(model.sde.T), K).tolist()):
+            # (stream ids from 2^32: the sampler's own draws of these seeds count up from 0)
+            z = ops.randn_batch(B, S, T, seeds, lens, (1 << 32) + k, device=tgt_n.device)
+            out, _, _ = ops.score_loss(eng, sde, mix_n, tgt_n, torch.full((B,), t, dtype=torch.float32, device=tgt_n.device),
+                                       z=z, lengths=lens)
+            total += out[:, 0]
+        return total / K
+
     def launch(self, w, j, group):
         """enqueue batch j (None: a warm-up call, nothing was prefetched for it) on the current (worker w's) stream"""
         if j is not None:
@@ -370,12 +390,13 @@ class SplitRun:
         if self.no_proc:
             est = mix_n.expand(-1, tgt_n.shape[1], -1).contiguous()  # x_result = broadcast_to(mix, target.shape)
             return _Batch(group, lens, mix, mix_n, tgt_n, est, 0, None, None)
+        sloss = self.score_loss(self.models[w], group, lens, mix_n, tgt_n) if self.args.score_loss > 0 else None
         sampler = self.sampler_for(self.models[w], group, lens, mix_n)
         if len(self.streams) == 1:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
         est, nfe, *_ = sampler()  # enqueues the whole sampler on the worker's stream
-        return _Batch(group, lens, mix, mix_n, tgt_n, est, nfe, t0, sampler)
+        return _Batch(group, lens, mix, mix_n, tgt_n, est, nfe, t0, sampler, sloss)
 
     def reissue(self, fb, b):
         self.fallbacks.append(list(b.group))
@@ -399,9 +420,15 @@ class SplitRun:
         if need_host:
             with torch.cuda.stream(stream):
                 est_h, tgt_h, mix_h = est.cpu(), tgt_n.cpu(), b.mix_n.cpu()
+        sloss = None
+        if b.sloss is not None:
+            with torch.cuda.stream(stream):
+                sloss = b.sloss.cpu().tolist()
         for k, i in enumerate(group):
             rec = {"batch_idx": i, **mets[k], "pesq": None, "stoi": None, "nfe": int(nfe), "runtime": runtime,
                    "len_s": lens[k] / self.fs}
+            if sloss is not None:
+                rec["score_loss"] = float(sloss[k])
             self.records.append(rec)
             perm = mets[k]["perm"]
             k_src = len(perm) if self.n_src is None else self.n_src

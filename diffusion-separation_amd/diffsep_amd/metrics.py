@@ -190,3 +190,14 @@ def stoi_batch(ref, est, fs, extended=True, lengths=None, perm=None):
     h.copy_(d, non_blocking=True)
     torch.cuda.current_stream().synchronize()
     return h.numpy().copy()
+
+
+def si_sdr_loss(est, ref, zero_mean=True, clamp_db=30.0, sign_flip=True):
+    """SISDRLoss(zero_mean, clamp_db, sign_flip), mean-reduced (reference models/losses.py:8-37 over
+    fast_bss_eval.si_sdr_pit_loss): the SI-SDR of the best source permutation from the Gram matrices above, averaged over
+    sources and batch; sign_flip=True returns the SI-SDR itself, False its negative.  A float64 scalar tensor."""
+    if zero_mean:
+        est, ref = est - est.mean(dim=-1, keepdim=True), ref - ref.mean(dim=-1, keepdim=True)
+    sdr, _, _, _ = si_bss_eval_sources(ref.contiguous(), est.contiguous(), clamp_db=float(clamp_db) if clamp_db else 100.0)
+    v = float(np.mean(sdr))
+    return torch.tensor(v if sign_flip else -v, dtype=torch.float64)

@@ -1,11 +1,12 @@
 """Unit-op wrappers over the C-ABI (parity tests call the kernels through these).
 Activations are NHWC torch tensors on the GPU; bf16 is torch.bfloat16 storage."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
 
-from ._lib import F32_SPLIT, F32, BF16, ODE_WORKSPACE_BYTES, SdeConfig, SDE_MIX, check, lib
+from ._lib import F32_SPLIT, F32, BF16, ODE_WORKSPACE_BYTES, LossConfig, SdeConfig, SDE_MIX, check, lib
 from .engine import _ptr, _stream_ptr
 
 
@@ -332,6 +333,16 @@ def sde_mult_std(std, x):
     return out
 
 
+def sde_mult_std_inv(std, x):
+    """std^-1 x for a dense std [B,S,S] or [B,S,S,T] and x [B,S,T] (MixSDE / PriorMixSDE.mult_std_inv)."""
+    B, S, T = x.shape
+    per = std.dim() == 4
+    assert std.shape == ((B, S, S, T) if per else (B, S, S)), "std must be [B,S,S] or [B,S,S,T]"
+    out = torch.empty_like(x)
+    check(lib().diffsep_sde_mult_std_inv(_ptr(std.contiguous()), _ptr(x), _ptr(out), B, S, T, int(per), _stream_ptr()))
+    return out
+
+
 def sde_reverse_drift(f, G, score, probability_flow=False):
     """rev_f = f - G^2 score (x 0.5 for the probability-flow ODE); G [B] or the shape of f."""
     B = f.shape[0]
@@ -439,6 +450,89 @@ def stoi(ref, est, fs, extended=True, lengths=None, perm=None):
     check(lib().diffsep_stoi(_ptr(ref), _ptr(est), _ptr(out), B, S, T, _ptr(ln), _ptr(pm), int(fs), int(bool(extended)),
                              _ptr(ws), nbytes, _stream_ptr()))
     return out
+
+
+PIT_MODES = {None: 0, "none": 0, "true_mix": 1, "init_hack_pit": 1, "mean0": 2, "allthetime": 2}
+
+
+def _f32c(v):
+    return None if v is None else v.float().contiguous()
+
+
+def sde_perturb(sde, x0, mix, t, z=None, sigma_mix=None, beta=None, redefine_z=False, lengths=None, seed=0, stream_id=0,
+                z_out=None):
+    """diffsep_sde_perturb — sample_prior of every init_hack mode in one pass:
+    x_t = beta true_mix + (1 - beta) mean + L z,  z_out = z + (redefine_z ? beta L^-1 (true_mix - mean) : 0).
+    z=None: Philox draws of diffsep_randn(seed, stream_id) laid out as [B,S,T].  Returns (x_t, z_out); z_out may be z."""
+    x0, mix, t, z, sigma_mix, beta = (_f32c(v) for v in (x0, mix, t, z, sigma_mix, beta))
+    B, S, T = x0.shape
+    assert mix.shape == (B, 1, T) and t.shape == (B,)
+    ln = None if lengths is None else _dev_i32(lengths, x0.device)
+    x_t = torch.empty_like(x0)
+    z_out = torch.empty_like(x0) if z_out is None else z_out
+    sc = _sde(sde)
+    check(lib().diffsep_sde_perturb(C.byref(sc), _ptr(x0), _ptr(mix), _ptr(t), _ptr(z), _ptr(sigma_mix), _ptr(beta),
+                                    int(bool(redefine_z)), _ptr(ln), int(seed) % (1 << 64), int(stream_id), _ptr(x_t),
+                                    _ptr(z_out), B, S, T, _stream_ptr()))
+    return x_t, z_out
+
+
+def score_loss_workspace_bytes(B, S, T):
+    """bytes of workspace the loss entries need (host arithmetic; raises for a shape they refuse)"""
+    n = lib().diffsep_score_loss_workspace_bytes(int(B), int(S), int(T))
+    check(0 if n >= 0 else 1)
+    return int(n)
+
+
+def score_loss_reduce(sde, score, z, t, x0=None, mix=None, sigma_mix=None, lengths=None, pit=None, want_coef=False):
+    """diffsep_score_loss_reduce: float64 [B,P] device tensor of mean_{s, t < len}((L score + z_p)^2), P = 1 (pit=None) or S!
+    (pit="true_mix" / "mean0": z_p = z + L^-1 (anchor - mean_p)), plus (best [B] float64, argbest [B] int32); want_coef adds
+    the kernels' (exp(-lambda t), sqrt(ev1), sqrt(ev2)) as a float32 [B,3] tensor."""
+    score, z, t, x0, mix, sigma_mix = (_f32c(v) for v in (score, z, t, x0, mix, sigma_mix))
+    B, S, T = score.shape
+    mode = PIT_MODES[pit]
+    P = math.factorial(S) if mode else 1
+    ln = None if lengths is None else _dev_i32(lengths, score.device)
+    out = torch.empty((B, P), dtype=torch.float64, device=score.device)
+    best = torch.empty(B, dtype=torch.float64, device=score.device)
+    arg = torch.empty(B, dtype=torch.int32, device=score.device)
+    coef = torch.empty((B, 3), dtype=torch.float32, device=score.device) if want_coef else None
+    nbytes = score_loss_workspace_bytes(B, S, T)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=score.device)
+    sc = _sde(sde)
+    check(lib().diffsep_score_loss_reduce(C.byref(sc), _ptr(score), _ptr(z), _ptr(x0), _ptr(mix), _ptr(t), _ptr(sigma_mix),
+                                          _ptr(ln), mode, _ptr(out), _ptr(best), _ptr(arg), _ptr(coef), B, S, T, _ptr(ws),
+                                          nbytes, _stream_ptr()))
+    return (out, best, arg, coef) if want_coef else (out, best, arg)
+
+
+def score_loss(engine, sde, mix_norm, target, t, beta=None, z=None, seed=0, lengths=None, pit=None, redefine_z=False,
+               debug=False):
+    """diffsep_score_loss on an Engine: perturb -> one score evaluation -> reduce, asynchronous on the current stream.
+    Returns (out [B,P] float64, best [B] float64, argbest [B] int32) and, with debug, (x_t, score) [B,S,T] as well."""
+    mix_norm, target, t, beta, z = (_f32c(v) for v in (mix_norm, target, t, beta, z))
+    B, S, T = target.shape
+    assert mix_norm.shape == (B, 1, T) and t.shape == (B,) and S == engine.S
+    mode = PIT_MODES[pit]
+    P = math.factorial(S) if mode else 1
+    dev = target.device
+    out = torch.empty((B, P), dtype=torch.float64, device=dev)
+    best = torch.empty(B, dtype=torch.float64, device=dev)
+    arg = torch.empty(B, dtype=torch.int32, device=dev)
+    x_t = torch.empty_like(target) if debug else None
+    score = torch.empty_like(target) if debug else None
+    la = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64)
+    assert la is None or la.shape == (B,), "lengths must be [B]"
+    nbytes = score_loss_workspace_bytes(B, S, T)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    sc, lc = _sde(sde), LossConfig(mode, int(bool(redefine_z)))
+    with torch.cuda.device(engine.device):
+        check(engine._L.diffsep_score_loss(engine._h, C.byref(sc), C.byref(lc), _ptr(mix_norm), _ptr(target), _ptr(t),
+                                           _ptr(beta), _ptr(z), int(seed) % (1 << 64),
+                                           la.ctypes.data_as(C.c_void_p) if la is not None else None, _ptr(out), _ptr(best),
+                                           _ptr(arg), _ptr(x_t), _ptr(score), B, T, _ptr(ws), nbytes,
+                                           _stream_ptr(engine.device)), engine._L)
+    return (out, best, arg, x_t, score) if debug else (out, best, arg)
 
 
 def _ode_ptrs(K):

@@ -160,6 +160,25 @@ class MixSDE(SDE):
         """std @ x   sdes/sdes.py:326-328 (PriorMixSDE: einsum "bcdt,bdt->bct", :534-537)"""
         return ops.sde_mult_std(std, x.contiguous())
 
+    @staticmethod
+    def mult_std_inv(std, x):
+        """std^-1 x   sdes/sdes.py:330-332 (torch.linalg.solve) / PriorMixSDE :534-558 (the explicit 2x2 formula for two
+        sources, a solve per sample otherwise): LU with partial pivoting in registers, any dense std."""
+        return ops.sde_mult_std_inv(std, x.contiguous())
+
+    def sample_time_varprop(self, n, t_eps=0.0, device=None):
+        """Rejection sampler of times with density proportional to the noise std (sdes/sdes.py:259-273), on device tensors
+        drawn from torch's generator."""
+        L_max = float(self._var(torch.tensor([self.T], device=device)).sqrt())
+        n_acc, stack = 0, []
+        while n_acc < n:
+            t = torch.zeros(3 * (n - n_acc), device=device).uniform_(t_eps, self.T)
+            u = torch.zeros(3 * (n - n_acc), device=device).uniform_(0, L_max)
+            t_acc = t[u < self._var(t).sqrt()]
+            n_acc += t_acc.shape[0]
+            stack.append(t_acc)
+        return torch.cat(stack)[:n]
+
     def prior_sampling(self, shape, y):
         """x_T = 0.5 y + L(T) z   (sdes/sdes.py:334-346); z: sdes/noise.py (device generator, seeded by torch's)."""
         if tuple(shape) != tuple(y.shape):

@@ -455,6 +455,12 @@ int32_t diffsep_sde_std(const diffsep_sde_config* sde, const float* t, const flo
  * (einsum "bcdt,bdt->bct", :534-537; per_sample = 1, std [B,S,S,T]) for any dense std. */
 int32_t diffsep_sde_mult_std(const float* std, const float* x, float* out, int32_t B, int32_t S, int64_t T,
                              int32_t per_sample, void* stream);
+/* MixSDE.mult_std_inv (torch.linalg.solve(std, x), sdes/sdes.py:330-332; per_sample = 0, std [B,S,S]) /
+ * PriorMixSDE.mult_std_inv (:534-558; per_sample = 1, std [B,S,S,T]) for any dense std: the reference's explicit 2x2 formula
+ * for S = 2 with a per-sample std, LU with partial pivoting in registers otherwise.  (The fused loss kernels below do not
+ * solve: for the SDE's own std the inverse is A / sqrt(ev1) + Pn / sqrt(ev2), divided by sigma_mix.) */
+int32_t diffsep_sde_mult_std_inv(const float* std, const float* x, float* out, int32_t B, int32_t S, int64_t T,
+                                 int32_t per_sample, void* stream);
 /* RSDE.discretize (sdes/sdes.py:163-171) given the forward discretisation: rev_f = f - G^2 score (x 0.5 when
  * probability_flow); G is [B] (g_full = 0) or [B, n_per_batch] (g_full = 1). */
 int32_t diffsep_sde_reverse_drift(const float* f, const float* G, const float* score, float* rev_f_out, int32_t B,
@@ -494,6 +500,58 @@ int64_t diffsep_stoi_workspace_bytes(int32_t B, int32_t S, int64_t T, int32_t fs
 int32_t diffsep_stoi(const float* ref, const float* est, double* out, int32_t B, int32_t S, int64_t T,
                      const int32_t* lengths, const int32_t* perm, int32_t fs, int32_t extended, void* workspace,
                      int64_t workspace_bytes, void* stream);
+
+/* ---- the denoising score-matching loss (forward values only): DiffSepModel.sample_prior (pl_model.py:179-247),
+ * compute_score_loss (:411-424), compute_score_loss_init_hack_pit (:370-405), compute_score_loss_with_pit_allthetime
+ * (:327-368).  With true_mix = mix / S, mean = (A + exp(-lambda t) Pn) x0 and L the marginal std (times sigma_mix for
+ * PriorMixSDE):
+ * perturb — sample_prior for init_hack in {false, 1, 2, 3, 4} in one pass:
+ *   x_t = beta true_mix + (1 - beta) mean + L z,   z_out = z + (redefine_z ? beta L^-1 (true_mix - mean) : 0)
+ *   x0 [B,S,T], mix [B,1,T] (both normalised), t [B], beta [B] (NULL: 0), sigma_mix [B,T] (PriorMixSDE) or NULL;
+ *   z [B,S,T], or NULL: Philox draws of the stream (seed, stream_id) laid out as [B,S,T], the bits of diffsep_randn with the
+ *   same keys; z_out may be z.  lengths (device int32 [B], nullable): samples at or beyond lengths[b] come out exactly zero.
+ *   beta = 0: plain; hack 1: beta = (t >= T - t_rev_init), redefine; hack 2: beta = clamp((t - Tm) / (T - Tm), 0, 1);
+ *   hack 3: the same, redefine; hack 4: beta = select (t already set to T there), redefine. */
+int32_t diffsep_sde_perturb(const diffsep_sde_config* sde, const float* x0, const float* mix, const float* t, const float* z,
+                            const float* sigma_mix, const float* beta, int32_t redefine_z, const int32_t* lengths,
+                            uint64_t seed, uint64_t stream_id, float* x_t, float* z_out, int32_t B, int32_t S, int64_t T,
+                            void* stream);
+/* loss_reduce — out [B][P] float64 = mean over (s, t < lengths[b]) of ((L score)[s,t] + z_p[s,t])^2 (pl_model.py:418-422).
+ *   pit_mode DIFFSEP_PIT_NONE: P = 1, z_p = z.  Otherwise P = S!, the source permutations in itertools.permutations order, and
+ *   z_p = z + L^-1 (anchor - mean_p), mean_p the marginal mean of x0[:, p, :]; anchor = true_mix (DIFFSEP_PIT_TRUE_MIX,
+ *   pl_model.py:383-401) or the mean of the unpermuted target (DIFFSEP_PIT_MEAN0, :347-364).  x0 and mix may be NULL without
+ *   PIT.  Per-sample arithmetic in fp32, squares and sums in float64; per-block partial sums in the caller's workspace, then
+ *   one finishing block per utterance: row b depends neither on the batch it rides in, nor on the stream, nor on repetition.
+ *   best [B] float64 = min over p, argbest [B] int32 (first minimum); coef_out [B][3] float32 = (exp(-lambda t), sqrt(ev1),
+ *   sqrt(ev2)) as the kernels use them; all three nullable.  Workspace: diffsep_score_loss_workspace_bytes (host arithmetic
+ *   only; -1 and a message for a bad shape). */
+#define DIFFSEP_PIT_NONE 0
+#define DIFFSEP_PIT_TRUE_MIX 1
+#define DIFFSEP_PIT_MEAN0 2
+int64_t diffsep_score_loss_workspace_bytes(int32_t B, int32_t S, int64_t T);
+int32_t diffsep_score_loss_reduce(const diffsep_sde_config* sde, const float* score, const float* z, const float* x0,
+                                  const float* mix, const float* t, const float* sigma_mix, const int32_t* lengths,
+                                  int32_t pit_mode, double* out, double* best, int32_t* argbest, float* coef_out, int32_t B,
+                                  int32_t S, int64_t T, void* workspace, int64_t workspace_bytes, void* stream);
+/* perturb -> one score evaluation on the engine -> loss_reduce, asynchronous on `stream` with no host synchronisation in
+ * between: compute_score_loss and the two PIT forms, which here cost ONE network evaluation (every permutation sees the same
+ * x_t).  mix_norm [B,1,T], target [B,S,T] (normalised), t [B], beta [B] (nullable), z [B,S,T] or NULL (Philox draws keyed by
+ * seed, stream id 0).  lengths_host [B] (nullable) follows the rule of diffsep_sampler_ext: every utterance must have the padded
+ * frame count of T, otherwise the call is refused; each row then equals the B = 1 call on that utterance alone (fp32 engine).
+ * out [B][P], best / argbest as above; x_t_out, score_out [B,S,T]: nullable debug outputs. */
+typedef struct {
+  int32_t pit_mode;   /* DIFFSEP_PIT_* */
+  int32_t redefine_z; /* the noise redefinition of init_hack 1, 3, 4 (without PIT) */
+} diffsep_loss_config;
+int32_t diffsep_score_loss(diffsep_engine* e, const diffsep_sde_config* sde, const diffsep_loss_config* cfg,
+                           const float* mix_norm, const float* target, const float* t, const float* beta, const float* z,
+                           uint64_t seed, const int64_t* lengths_host, double* out, double* best, int32_t* argbest,
+                           float* x_t_out, float* score_out, int32_t B, int64_t T, void* workspace, int64_t workspace_bytes,
+                           void* stream);
+/* The argument checks of the call above that need no GPU (number of sources, pit_mode, lengths against the padded frame count
+ * of T, workspace size), from the model configuration alone; the call runs them first. */
+int32_t diffsep_score_loss_validate(const diffsep_model_config* cfg, const diffsep_loss_config* loss, int32_t B, int64_t T,
+                                    const int64_t* lengths_host, int64_t workspace_bytes);
 
 /* on-device standard normal draws (Philox4x32-10 + Box-Muller); used when noise == NULL. */
 int32_t diffsep_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);
