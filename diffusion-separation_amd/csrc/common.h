@@ -230,7 +230,7 @@ struct ConvArgs {
   int split;                             // fp32 only: 3 bf16 MFMAs per k-block on hi / lo halves (2^-17 products) instead of fp32 MFMAs
   unsigned opts;                         // DS_OPT_* dispatch switches (an engine's copy, or ds_default_opts() at the unit entry points)
 };
-// Dispatch switches of the convolution launchers (A/B and test aids; DESIGN.md section 6b).  The process defaults are read from
+// Dispatch switches of the convolution launchers (A/B and test aids; DESIGN.md section 7).  The process defaults are read from
 // the environment ONCE (DIFFSEP_NO_RW, DIFFSEP_NO_RW128, DIFFSEP_RW_SMALL, DIFFSEP_NO_RW_RES) and changed with
 // diffsep_set_option; an engine copies them at creation (diffsep_engine_set_option changes its copy and drops its captured
 // graphs), so a launch decision never reads the environment.
@@ -253,13 +253,29 @@ struct ConvArgs {
 #define DS_OPT_NO_WFRAG 32u   // the engine does not hand the fragment-major weight copies to the register-weight kernel (A/B)
 unsigned ds_default_opts();
 int ds_num_cus();  // compute units of the current device (cached per device ordinal)
-int ds_launch_conv(const ConvArgs& a, hipStream_t st);
+// Kernel classes of the per-launch profile (the C-ABI's arrays, bench.py and the tests index by these numbers): the generic
+// conv_mfma tiles for 3x3 (8 x 32 x 64 couts and siblings; 8 x 32 x 32 couts; 8 x 8 x 64) and for 1x1 / GEMM, conv3x3_ws.hip (64 -> 64,
+// first layer, pyramid heads), _small, _rw, the fused attention block (launched by engine.hip), _sw, _sws
+enum { DS_CLS_CONV_N64 = 0, DS_CLS_CONV_N32, DS_CLS_CONV_8X8, DS_CLS_GEMM_N64, DS_CLS_GEMM_N32, DS_CLS_GEMM_8X8, DS_CLS_WS,
+       DS_CLS_SMALL, DS_CLS_RW, DS_CLS_ATTN, DS_CLS_SW, DS_CLS_SWS, DS_NCLS };
+// Where a convolution launch goes: ds_conv_plan (conv_mfma.hip; DESIGN.md section 7b is its table) is the ONE place that orders the
+// kernels, reads the DS_OPT_* switches and weighs tile counts against ds_num_cus(); the kernels' ds_conv_*_supported say only what they can run.
+enum class ConvRoute { GENERIC, WS, THIN_IN, THIN_OUT, SMALL, RW, SW, SWS };
+struct ConvPlan {
+  ConvRoute route;
+  int cls;       // DS_CLS_*
+  int tile;      // GENERIC: the conv_mfma tile (DS_CLS_CONV_N64 .. DS_CLS_GEMM_8X8), else -1
+  int sw_rows;   // conv3x3_sw.hip can run it: rows per wave of its 128-cout tiles (8 or 4; the unit entry point launches with it too)
+  bool rw_ok;    // conv3x3_rw.hip can run it and its tile-count policy takes it (the route is RW unless SW comes first)
+  bool skip_ok;  // the routed kernel has a folded 1x1 skip path (every 3x3 route but the 32-cout generic tile)
+};
+ConvPlan ds_conv_plan(const ConvArgs& a);
+int ds_launch_conv(const ConvArgs& a, hipStream_t st);                    // validate, plan, launch
+int ds_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st);  // ... with the caller's ds_conv_plan(a)
 // name (with its template arguments) of the kernel instantiation the calling thread's last ds_launch_conv ran
 const char* ds_last_conv_kernel();
 void ds_set_last_conv_kernel(const char* name);
-int ds_conv_config_id(const ConvArgs& a);
 int ds_conv_chunk(int taps, int dtype);
-bool ds_conv_skip_supported(int H, int W, int Cout, int dtype);
 // layout of the fragment-major copies: element (cout co, tap, input channel ch) of a [Cout][taps][Cin] weight tensor lives at
 //   ((((ch / 64 * taps + tap) * 4 + ch % 64 / 16) * (Cout / 32) + co / 32) * 64 + (ch % 16 / 8) * 32 + co % 32) * 8 + ch % 8
 // (k-step = (64-channel chunk, tap, 16-channel block); then cout group, lane = (k-half, cout), 8 channels)
@@ -269,15 +285,14 @@ __host__ __device__ inline long ds_rw_frag_index(int co, int tap, int ch, int ta
 inline bool ds_rw_frag_shape(int taps, int Cin, int Cout) {  // the weight shapes conv3x3_rw.hip can take (3x3 and folded 1x1 skip)
   return (Cout == 64 || Cout == 128) && (Cin == 64 || Cin == 128) && (taps == 1 || !(Cout == 128 && Cin == 64));
 }
-bool ds_conv_rw_eligible(const ConvArgs& a);   // conv3x3_rw.hip: register-resident weights, 64 / 128 -> 64 bf16, >= 32-row images
+bool ds_conv_rw_supported(const ConvArgs& a);  // conv3x3_rw.hip: register-resident weights, 64 / 128 -> 64 and 128 -> 128, 16-bit, >= 32-row images
 int ds_launch_conv_rw(const ConvArgs& a, hipStream_t st);
 // the weight shapes conv3x3_sw.hip streams (fragment-major copies of 3x3 weights and folded 1x1 skips)
 // (Cout 64 too: ds_conv_sw_supported takes e.g. the 192 -> 64 layer of the 128-row level, which is no register-weight shape; until
 // round 6 those copies existed only because the split kernel's shape test below happened to cover them)
 inline bool ds_sw_frag_shape(int taps, int Cin, int Cout) { return (Cout == 64 || Cout == 128 || Cout == 256) && Cin % 64 == 0 && Cin >= 64 && Cin <= 512; }
-bool ds_conv_sw_supported(const ConvArgs& a);  // conv3x3_sw.hip: streamed weights, 64 .. 256 -> 128 n couts, 16-bit
-bool ds_conv_sw_eligible(const ConvArgs& a);   // ... and dispatched there
-int ds_launch_conv_sw(const ConvArgs& a, hipStream_t st);
+bool ds_conv_sw_supported(const ConvArgs& a);  // conv3x3_sw.hip: streamed weights, 64 .. 512 -> 128 / 256 (and 192 -> 64), 16-bit
+int ds_launch_conv_sw(const ConvArgs& a, int rows, hipStream_t st);  // rows: ConvPlan.sw_rows
 // conv3x3_sws.hip: the split mode's streamed-weight kernel (fp32 tensors, hi / lo bfloat16 planes).  Element (cout co, tap, input
 // channel ch) of a [Cout][taps][Cin] weight tensor, plane 0 = bf16(w), plane 1 = bf16(w - plane 0), lives at
 //   ((((ch / 32 * taps + tap) * 2 + ch % 32 / 16) * 2 + plane) * (Cout / 32) + co / 32) * 64 + (ch % 16 / 8) * 32 + co % 32) * 8 + ch % 8
@@ -286,15 +301,14 @@ __host__ __device__ inline long ds_sws_frag_index(int co, int tap, int ch, int t
 }
 inline bool ds_sws_frag_shape(int taps, int Cin, int Cout) { return (Cout == 64 || Cout == 128 || Cout == 256) && Cin % 64 == 0 && Cin >= 64 && Cin <= 256; }
 bool ds_conv_sws_supported(const ConvArgs& a);
-bool ds_conv_sws_eligible(const ConvArgs& a);
 int ds_launch_conv_sws(const ConvArgs& a, hipStream_t st);
-bool ds_conv_ws_eligible(const ConvArgs& a);   // conv3x3_ws.hip: weight-stationary 64 -> 64 bf16 kernel
+bool ds_conv_ws_supported(const ConvArgs& a);   // conv3x3_ws.hip: weight-stationary 64 -> 64 bf16 kernel
 int ds_launch_conv_ws(const ConvArgs& a, hipStream_t st);
-bool ds_conv_thin_eligible(const ConvArgs& a);   // conv3x3_ws.hip: the 8 -> 64 first layer
-int ds_launch_conv_thin(const ConvArgs& a, hipStream_t st);
-bool ds_conv_thin_out_eligible(const ConvArgs& a);   // conv3x3_ws.hip: the <= 8-cout pyramid heads
+bool ds_conv_thin_in_supported(const ConvArgs& a);  // conv3x3_ws.hip: the 8 -> 64 first layer
+int ds_launch_conv_thin_in(const ConvArgs& a, hipStream_t st);
+bool ds_conv_thin_out_supported(const ConvArgs& a);  // conv3x3_ws.hip: the <= 8-cout pyramid heads
 int ds_launch_conv_thin_out(const ConvArgs& a, hipStream_t st);
-bool ds_conv_small_eligible(const ConvArgs& a);  // conv3x3_small.hip: <= 16-row images, 16-cout slabs, bf16
+bool ds_conv_small_supported(const ConvArgs& a);  // conv3x3_small.hip: <= 16-row images, 16-cout slabs, 16-bit or split
 int ds_launch_conv_small(const ConvArgs& a, hipStream_t st);
 
 // attn_fused.hip: AttnBlockpp as one kernel (16-bit storage, 128 channels, <= 256 pixels per sample).  Weights in the

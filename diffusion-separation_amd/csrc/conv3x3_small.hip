@@ -29,7 +29,7 @@
 // 128 bf16 channels), values split into hi / lo bf16 planes on the way to LDS, three MFMAs per k-block, fp32 epilogue
 // (the split engine's <= 16-row levels: 31 -> ~14 us per launch, one batch alone 759 -> 702 ms).
 //
-// Same ConvArgs contract as ds_launch_conv (common.h); ds_conv_small_eligible says which launches come here.
+// Same ConvArgs contract as ds_launch_conv (common.h); ds_conv_small_supported says which launches it can take.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -584,7 +584,7 @@ static bool small_sources_multiple_of(const ConvArgs& a, int pc) {
   }
   return true;
 }
-bool ds_conv_small_eligible(const ConvArgs& a) {
+bool ds_conv_small_supported(const ConvArgs& a) {
   // bf16, or fp32 tensors in split mode (the exact fp32 engine keeps the generic kernel's fp32 MFMAs)
   if (!(a.dtype == DS_BF16 || (a.dtype == DS_F32 && a.split)) || a.taps != 9 || a.w_bs != 0 || a.bias_mode != 0 || a.div_b) return false;
   if (!(a.W < 32 || a.H < 8) || a.H > 16) return false;

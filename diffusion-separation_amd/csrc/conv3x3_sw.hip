@@ -873,21 +873,12 @@ int sw_dispatch128(const SwK& k, const ConvArgs& a, int nch, int nsk, int mode, 
 #undef SW_CASE
   return -1;
 }
-// rows per wave of a 128-cout launch: 8 x 32 tiles where every compute unit gets one, 4 x 32 tiles on smaller levels (nf = 64 at
-// 32^2, B = 16: 128 blocks; half the stream reuse, but twice the blocks), 0 = neither
-int sw_rpw(const ConvArgs& a) {
-  const bool h8 = a.H % 8 == 0;
-  const long t4 = (long)a.B * (a.H / 4) * (a.W / TW) * (a.Cout / 128);
-  if (h8 && !(a.opts & DS_OPT_SW_ROWS4) && (t4 >= 2L * ds_num_cus() || (a.opts & DS_OPT_RW_SMALL))) return 8;
-  return (2 * t4 >= ds_num_cus() || (a.opts & DS_OPT_RW_SMALL)) ? 4 : 0;
-}
-
 }  // namespace
 
 // The layers this kernel can take: 16-bit 3x3, Cout = 128 / 256 (Cin = 64 .. 512 in 64-channel chunks: one tensor or the in-place
 // concat of two, split on a chunk boundary; input raw or GroupNorm + SiLU; optional folded 1x1 skip on 64 .. 512 raw channels, or
 // a residual against the identity copy ConvArgs.ident_frag) or Cout = 64 with Cin = 192; whole tiles; fragment-major weight
-// copies at hand.
+// copies at hand.  Which of them it is given, and on which tile: ds_conv_plan.
 bool ds_conv_sw_supported(const ConvArgs& a) {
   if (!(a.dtype == DS_BF16 && a.taps == 9 && (a.Cout == 64 || a.Cout == 128 || a.Cout == 256) && a.Cin % KC == 0 && a.Cin >= KC &&
         a.Cin <= 8 * KC && a.w_frag && a.w_bs == 0 && a.bias_mode == 0 && !a.div_b && a.W % TW == 0 && a.H % 4 == 0 && a.H >= 4 &&
@@ -911,21 +902,9 @@ bool ds_conv_sw_supported(const ConvArgs& a) {
   }
   return sw_shape(a.Cout, a.Cin / KC, nsk, gn ? 2 : 0);
 }
-// ... and the launches it is given: what neither the register-weight kernel nor (small images) the small-image kernel holds, on
-// levels with at least one 8 x 32 tile per compute unit and cout block — and the register-weight kernel's own 128-cout launches
-// with fewer than two such tiles per unit, where its 295 KB weight prologue per block serves one or two tiles (nf = 64 at 64^2,
-// B = 16: 26.6 against 28.0 us, with a folded 64 / 128-channel skip 28.4 / 29.1 against 38 us; option no_sw_rw for the A/B)
-bool ds_conv_sw_eligible(const ConvArgs& a) {
-  if ((a.opts & DS_OPT_NO_SW) || !ds_conv_sw_supported(a)) return false;
-  if (a.Cout == 64) return (long)a.B * (a.H / 8) * (a.W / TW) >= ds_num_cus() || (a.opts & DS_OPT_RW_SMALL);
-  const int rpw = sw_rpw(a);
-  if (rpw == 0 || (rpw == 4 && (a.opts & DS_OPT_NO_SW_ROWS4))) return false;
-  const long tiles = (long)a.B * (a.H / 8) * (a.W / TW) * (a.Cout / 128);
-  if (ds_conv_rw_eligible(a)) return !(a.opts & DS_OPT_NO_SW_RW) && tiles < 2L * ds_num_cus();
-  return true;
-}
 
-int ds_launch_conv_sw(const ConvArgs& a, hipStream_t st) {
+// rows: rows per wave of the 128-cout tiles, 8 (H % 8 == 0) or 4 (ConvPlan.sw_rows; the one 64-cout instantiation has 4)
+int ds_launch_conv_sw(const ConvArgs& a, int rows, hipStream_t st) {
   SwK k;
   k.x = reinterpret_cast<const bf16_t*>(a.x); k.x_bs = a.x_bs; k.ldx = a.ldx; k.C1 = a.x2 ? a.C1 : a.Cin;
   k.x2 = reinterpret_cast<const bf16_t*>(a.x2); k.x2_bs = a.x2_bs; k.ldx2 = a.x2 ? a.ldx2 : a.ldx;
@@ -959,15 +938,14 @@ int ds_launch_conv_sw(const ConvArgs& a, hipStream_t st) {
 #endif
   const int mode = ((a.gn_scale || a.gn_acc1) && a.gn_act) ? 2 : 0;
   const int nch = a.Cin / KC;
+  DS_CHECK(rows == 4 || (rows == 8 && a.H % 8 == 0), "conv3x3_sw: rows per wave must be 4, or 8 on whole 8-row tiles");
   int rc = -1;
   if (a.Cout == 64) {
     k.ncb = 1;
     if (nch == 3 && nsk == 0 && mode == 2) rc = sw_launch<3, 0, 2, 4, 2>(k, a, st);
   } else {
     k.ncb = a.Cout / 128;
-    const int rpw = sw_rpw(a);
-    // (the unit entry point reaches here whatever the dispatch rule says: 8-row tiles whenever the image has them)
-    rc = (rpw == 8 || (rpw == 0 && a.H % 8 == 0 && !(a.opts & DS_OPT_SW_ROWS4))) ? sw_dispatch128<8>(k, a, nch, nsk, mode, st) : sw_dispatch128<4>(k, a, nch, nsk, mode, st);
+    rc = rows == 8 ? sw_dispatch128<8>(k, a, nch, nsk, mode, st) : sw_dispatch128<4>(k, a, nch, nsk, mode, st);
   }
   DS_CHECK(rc >= 0, "conv3x3_sw: shape outside the instantiated set");
   return rc;

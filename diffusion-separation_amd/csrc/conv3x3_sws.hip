@@ -537,7 +537,7 @@ int sws_dispatch(const SwsK& k, const ConvArgs& a, int nch, int nsk, int mode, h
 
 // The launches this kernel takes: fp32 tensors in split mode, 3x3, 64 / 128 / 256 couts, input channels and skip channels in the
 // instantiated set (sws_dispatch), whole tiles (W % 32 == 0, H % 8 == 0), fragment-major hi / lo weight copies at hand; a residual
-// needs the identity copy (ConvArgs.ident_frag).
+// needs the identity copy (ConvArgs.ident_frag).  Which of them it is given: ds_conv_plan.
 static bool sws_shape(int Cout, int nch, int nsk, int mode) {
   if (!(Cout == 64 || Cout == 128 || Cout == 256)) return false;  // (256: two cout blocks of 128)
   if (mode == 0) return nsk == 0 && (nch == 2 || nch == 4 || nch == 8);
@@ -565,13 +565,6 @@ bool ds_conv_sws_supported(const ConvArgs& a) {
     nsk = a.Cout / KC;
   }
   return sws_shape(a.Cout, a.Cin / KC, nsk, gn ? 2 : 0);
-}
-bool ds_conv_sws_eligible(const ConvArgs& a) {
-  if ((a.opts & DS_OPT_NO_SWS) || !ds_conv_sws_supported(a)) return false;
-  // at least one tile per two compute units (nf = 64 at 32^2, B = 16: 128 blocks of 1728 MFMAs per wave, ~40 us, against 93 us on
-  // the generic tile, which splits the same work over 256 blocks but re-streams and re-splits the weights through LDS)
-  const long tiles = (long)a.B * (a.H / (a.Cout == 64 ? 8 : 4)) * (a.W / TW) * (a.Cout == 64 ? 1 : a.Cout / 128);
-  return 2 * tiles >= ds_num_cus() || (a.opts & DS_OPT_RW_SMALL);
 }
 
 int ds_launch_conv_sws(const ConvArgs& a, hipStream_t st) {

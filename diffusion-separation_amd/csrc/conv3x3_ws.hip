@@ -864,9 +864,8 @@ __global__ __launch_bounds__(512, WPE) void conv3x3_thin_out_kernel(ThinOutK p) 
 }
 
 int ws_blocks_per_image(const ConvArgs& a) {
-  const int cus = ds_num_cus();
   const int tiles = (a.H / TH) * (a.W / TW);
-  int g = cus / a.B;
+  int g = ds_num_cus() / a.B;
   if (g < 1) g = 1;
   if (g > tiles) g = tiles;
   return g;
@@ -874,8 +873,8 @@ int ws_blocks_per_image(const ConvArgs& a) {
 
 }  // namespace
 
-// The layers this kernel takes over from conv_mfma.hip.
-bool ds_conv_ws_eligible(const ConvArgs& a) {
+// The layers this kernel can take over from conv_mfma.hip.
+bool ds_conv_ws_supported(const ConvArgs& a) {
   if (!(a.dtype == DS_BF16 && a.taps == 9 && a.Cin == C && a.Cout == C && !a.x2 && a.w_bs == 0 &&
         (a.w_chunked == 0 || a.w_chunked == KC) && a.bias_mode == 0 && !a.div_b && a.H % TH == 0 && a.W % TW == 0 &&
         a.ldx >= C && a.ldy >= C && (!a.res || a.ldr >= C)))
@@ -925,13 +924,13 @@ int ds_launch_conv_ws(const ConvArgs& a, hipStream_t st) {
 }
 
 // The first layer of the network: 8 (padded) input channels, no GroupNorm, no residual.
-bool ds_conv_thin_eligible(const ConvArgs& a) {
+bool ds_conv_thin_in_supported(const ConvArgs& a) {
   return a.dtype == DS_BF16 && a.taps == 9 && a.Cin == 8 && a.Cout == C && !a.x2 && !a.sx && a.w_bs == 0 &&
          a.w_chunked == 0 && !a.gn_scale && !a.gn_acc1 && !a.res && !a.bias_b && a.bias_mode == 0 && !a.div_b &&
          a.out_scale == 1.f && a.H % TH == 0 && a.W % TW == 0 && a.ldx % 8 == 0 && a.ldy >= C;
 }
 
-int ds_launch_conv_thin(const ConvArgs& a, hipStream_t st) {
+int ds_launch_conv_thin_in(const ConvArgs& a, hipStream_t st) {
   ThinK k;
   k.x = reinterpret_cast<const bf16_t*>(a.x); k.x_bs = a.x_bs; k.ldx = a.ldx;
   k.w = reinterpret_cast<const bf16_t*>(a.w);
@@ -949,7 +948,7 @@ int ds_launch_conv_thin(const ConvArgs& a, hipStream_t st) {
 }
 
 // The output-pyramid heads: <= 8 couts, 64-channel multiples in, GroupNorm (+ SiLU) on the input, optional residual.
-bool ds_conv_thin_out_eligible(const ConvArgs& a) {
+bool ds_conv_thin_out_supported(const ConvArgs& a) {
   return a.dtype == DS_BF16 && a.taps == 9 && a.Cout <= 8 && a.Cin % 64 == 0 && a.Cin <= 512 && !a.x2 && !a.sx && a.w_bs == 0 &&
          ((a.w_chunked & (a.w_chunked - 1)) == 0) && (a.w_chunked == 0 || a.w_chunked >= 8) && !a.bias_b && a.bias_mode == 0 &&
          !a.div_b && a.out_scale == 1.f && !a.stats_acc && a.H % TH == 0 && a.W % TW == 0 && a.ldx % 8 == 0 && a.ldy >= 8 &&

@@ -904,11 +904,11 @@ const char* ds_last_conv_kernel() { return g_last_conv_kernel; }
 void ds_set_last_conv_kernel(const char* name) { g_last_conv_kernel = name; }
 
 template <typename T, int SP = 0>
-static int launch_typed(const ConvArgs& a, hipStream_t st) {
+static int launch_typed(const ConvArgs& a, int tile, hipStream_t st) {
   constexpr int KC9 = (sizeof(T) == 4) ? 16 : 32;
   constexpr int KC1 = (sizeof(T) == 4) ? 32 : 64;
-  switch (ds_conv_config_id(a)) {
-    case 0: {
+  switch (tile) {
+    case DS_CLS_CONV_N64: {
       // few tiles (the 32^2 level: 128 blocks of 8 x 32 pixels on 256 CUs): half-width tiles fill the chip
       // (one batch alone 325.6 -> 320.6 ms, four in flight unchanged)
       const long blocks = (long)cdiv(a.W, 32) * cdiv(a.H, 8) * cdiv(a.Cout, 64) * a.B;
@@ -927,26 +927,17 @@ static int launch_typed(const ConvArgs& a, hipStream_t st) {
       }
       return launch_cfg<T, 9, 8, 32, 64, 2, 2, KC9, 1, 2, SP>(a, st);
     }
-    case 1: return launch_cfg<T, 9, 8, 32, 32, 2, 1, KC9, 1, 2, SP>(a, st);
-    case 2: {  // small images: a chain of dependent chunk round trips (1.7 us each) -> chunks twice as deep (+1 %)
+    case DS_CLS_CONV_N32: return launch_cfg<T, 9, 8, 32, 32, 2, 1, KC9, 1, 2, SP>(a, st);
+    case DS_CLS_CONV_8X8: {  // small images: a chain of dependent chunk round trips (1.7 us each) -> chunks twice as deep (+1 %)
       const bool deep = a.Cin % (2 * KC9) == 0 && (!a.x2 || a.C1 % (2 * KC9) == 0) &&
                         (!a.sx || (a.sCin % (2 * KC9) == 0 && (!a.sx2 || a.sC1 % (2 * KC9) == 0)));
       if (deep) return launch_cfg<T, 9, 8, 8, 64, 1, 1, KC9 * 2, 1, 2, SP>(a, st);
       return launch_cfg<T, 9, 8, 8, 64, 1, 1, KC9, 1, 2, SP>(a, st);
     }
-    case 3: return launch_cfg<T, 1, 8, 32, 64, 2, 2, KC1, 1, 2, SP>(a, st);
-    case 4: return launch_cfg<T, 1, 8, 32, 32, 2, 1, KC1, 1, 2, SP>(a, st);
+    case DS_CLS_GEMM_N64: return launch_cfg<T, 1, 8, 32, 64, 2, 2, KC1, 1, 2, SP>(a, st);
+    case DS_CLS_GEMM_N32: return launch_cfg<T, 1, 8, 32, 32, 2, 1, KC1, 1, 2, SP>(a, st);
     default: return launch_cfg<T, 1, 8, 8, 64, 1, 1, KC1, 1, 2, SP>(a, st);
   }
-}
-
-// whether the instantiation that would run a 3x3 launch of this shape can take the fused 1x1 skip convolution
-bool ds_conv_skip_supported(int H, int W, int Cout, int dtype) {
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.H = H; a.W = W; a.Cout = Cout; a.taps = 9; a.dtype = dtype; a.sx = &a;
-  const int id = ds_conv_config_id(a);
-  return id == 0 || id == 2;  // (bf16 small images go to conv3x3_small.hip, which takes the skip too: checked there)
 }
 
 // chunk width (channels per K stage) of the kernel that would run this problem: the kc of chunk-major weights
@@ -955,26 +946,59 @@ int ds_conv_chunk(int taps, int dtype) {
   return taps == 9 ? 32 : 64;
 }
 
-// Which instantiation ds_launch_conv picks (profiling label): 0/1/2 = 3x3 {8x32xBN64, 8x32xBN32, 8x8xBN64},
-// 3/4/5 = the same tiles for 1x1 / GEMM, 6 = the weight-stationary 64 -> 64 kernel (conv3x3_ws.hip), 7 = the
-// small-image kernel (conv3x3_small.hip), 8 = the register-weight kernel (conv3x3_rw.hip), 10 = the streamed-weight kernel
-// (conv3x3_sw.hip), 11 = its split-mode sibling (conv3x3_sws.hip).  (9 = the fused attention block, launched by engine.hip.)
-int ds_conv_config_id(const ConvArgs& a) {
-  if (ds_conv_sws_eligible(a)) return 11;
-  if (ds_conv_sw_eligible(a)) return 10;
-  if (ds_conv_rw_eligible(a)) return 8;
-  if (ds_conv_ws_eligible(a) || ds_conv_thin_eligible(a) || ds_conv_thin_out_eligible(a)) return 6;
-  if (ds_conv_small_eligible(a)) return 7;
-  if (a.taps == 9) {
-    if (a.W >= 32 && a.H >= 8) return a.Cout <= 32 ? 1 : 0;
-    return 2;
+// ---------------------------------------------------------------- dispatch
+// Which kernel runs a launch, top to bottom (DESIGN.md section 7b holds the same table).  t8 / t4 = tiles of 8 x 32 / 4 x 32 pixels
+// times 128-cout blocks over the whole batch: the persistent kernels pay a weight prologue per BLOCK, so each is given a level only
+// where its blocks fill the compute units (option rw_small lifts every such threshold: unit tests of small shapes).
+ConvPlan ds_conv_plan(const ConvArgs& a) {
+  const unsigned o = a.opts;
+  const bool any_size = o & DS_OPT_RW_SMALL;
+  const long cus = ds_num_cus(), ncb = a.Cout >= 128 ? a.Cout / 128 : 1;
+  const long t8 = (long)a.B * (a.H / 8) * (a.W / 32) * ncb, t4 = (long)a.B * (a.H / 4) * (a.W / 32) * ncb;
+  ConvPlan p = {ConvRoute::GENERIC, -1, -1, 0, false, false};
+  auto routed = [&](ConvRoute r, int cls) {
+    p.route = r; p.cls = cls; p.tile = r == ConvRoute::GENERIC ? cls : -1; p.skip_ok = a.taps == 9 && cls != DS_CLS_CONV_N32;
+    return p;
+  };
+  // split mode's streamed weights: at least one tile per two compute units (nf = 64 at 32^2, B = 16: 128 blocks of 1728 MFMAs per
+  // wave, ~40 us, against 93 us on the generic tile, which re-streams and re-splits the weights through LDS)
+  if (!(o & DS_OPT_NO_SWS) && ds_conv_sws_supported(a) && (2 * (a.Cout == 64 ? t8 : t4) >= cus || any_size))
+    return routed(ConvRoute::SWS, DS_CLS_SWS);
+  // register-resident weights.  128 couts: one 4 x 32 tile per unit (below, at 32^2 with B = 16, the 295 KB weight prologue serves
+  // one tile and half the chip idles: the generic tile is as fast, 22.6 vs 23.6 us).  64 couts: one 8 x 32 tile per unit (at 128^2:
+  // Conv_0 41.8 vs 46.5 us on the weight-stationary kernel, + residual 45.0 vs 48.2, + skip 46.1 vs 52.0); a residual rides as an
+  // identity-weight skip chunk (138 vs 159 us at 256^2; option no_rw_res)
+  p.rw_ok = !(o & DS_OPT_NO_RW) && ds_conv_rw_supported(a) &&
+            (a.Cout == 128 ? !(o & DS_OPT_NO_RW128) && (t4 >= cus || any_size)
+                           : !(a.res && (o & DS_OPT_NO_RW_RES)) && (t8 >= cus || any_size));
+  // streamed weights, ahead of the register-weight kernel: what that one does not take — and its own 128-cout launches with fewer
+  // than two 8 x 32 tiles per unit, where its prologue serves one or two tiles (nf = 64 at 64^2, B = 16: 26.6 against 28.0 us, with
+  // a folded skip 28.4 / 29.1 against 38 us; option no_sw_rw).  128-cout tiles: 8 rows from two 4-row tiles per unit up, else 4 rows
+  // down to one per two units (nf = 64 at 32^2, B = 16: half the stream reuse, twice the blocks; option no_sw_rows4); rows == 0: not
+  // routed here, but the unit entry point still launches it.  The one 64-cout instantiation: one 8 x 32 tile per unit.
+  if (ds_conv_sw_supported(a)) {
+    const bool rows8 = a.H % 8 == 0 && !(o & DS_OPT_SW_ROWS4);
+    const int rows = a.Cout == 64 ? 4 : rows8 && (t4 >= 2 * cus || any_size) ? 8 : (2 * t4 >= cus || any_size) ? 4 : 0;
+    p.sw_rows = rows ? rows : (rows8 ? 8 : 4);
+    const bool take = a.Cout == 64 ? t8 >= cus || any_size
+                                   : rows && !(rows == 4 && (o & DS_OPT_NO_SW_ROWS4)) && (!p.rw_ok || (!(o & DS_OPT_NO_SW_RW) && t8 < 2 * cus));
+    if (take && !(o & DS_OPT_NO_SW)) return routed(ConvRoute::SW, DS_CLS_SW);
   }
+  if (p.rw_ok) return routed(ConvRoute::RW, DS_CLS_RW);
+  if (ds_conv_ws_supported(a)) return routed(ConvRoute::WS, DS_CLS_WS);
+  if (ds_conv_thin_in_supported(a)) return routed(ConvRoute::THIN_IN, DS_CLS_WS);
+  if (ds_conv_thin_out_supported(a)) return routed(ConvRoute::THIN_OUT, DS_CLS_WS);
+  if (ds_conv_small_supported(a)) return routed(ConvRoute::SMALL, DS_CLS_SMALL);
+  if (a.taps == 9)
+    return routed(ConvRoute::GENERIC, !(a.W >= 32 && a.H >= 8) ? DS_CLS_CONV_8X8 : a.Cout <= 32 ? DS_CLS_CONV_N32 : DS_CLS_CONV_N64);
   // small-M problems with a wide N (the STFT GEMM: M = 512 bins, N = frames) still want the 256-row tile
-  if ((long)a.H * a.W >= 1024 || ((long)a.H * a.W >= 256 && a.Cout >= 1024)) return a.Cout <= 32 ? 4 : 3;
-  return 5;
+  if ((long)a.H * a.W >= 1024 || ((long)a.H * a.W >= 256 && a.Cout >= 1024))
+    return routed(ConvRoute::GENERIC, a.Cout <= 32 ? DS_CLS_GEMM_N32 : DS_CLS_GEMM_N64);
+  return routed(ConvRoute::GENERIC, DS_CLS_GEMM_8X8);
 }
 
-int ds_launch_conv(const ConvArgs& a, hipStream_t st) {
+int ds_launch_conv(const ConvArgs& a, hipStream_t st) { return ds_launch_conv(a, ds_conv_plan(a), st); }
+int ds_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
   DS_CHECK(a.taps == 1 || a.taps == 9, "conv: taps must be 1 or 9");
   DS_CHECK(a.Cin % 8 == 0 && a.ldx % 8 == 0, "conv: Cin and ldx must be multiples of 8");
   DS_CHECK(a.B > 0 && a.H > 0 && a.W > 0 && a.Cout > 0, "conv: empty problem");
@@ -989,14 +1013,17 @@ int ds_launch_conv(const ConvArgs& a, hipStream_t st) {
     DS_CHECK(M * mld * esz < 2147483647L, "conv: image too large for 32-bit buffer offsets");
     DS_CHECK((long)a.Cout * a.taps * a.Cin * esz < 2147483647L, "conv: weight tensor too large");
   }
-  if (ds_conv_sws_eligible(a)) return ds_launch_conv_sws(a, st);
-  if (ds_conv_sw_eligible(a)) return ds_launch_conv_sw(a, st);
-  if (ds_conv_rw_eligible(a)) return ds_launch_conv_rw(a, st);
-  if (ds_conv_ws_eligible(a)) return ds_launch_conv_ws(a, st);
-  if (ds_conv_thin_eligible(a)) return ds_launch_conv_thin(a, st);
-  if (ds_conv_thin_out_eligible(a)) return ds_launch_conv_thin_out(a, st);
-  if (ds_conv_small_eligible(a)) return ds_launch_conv_small(a, st);
-  if (a.dtype == DS_F32) return a.split ? launch_typed<float, 1>(a, st) : launch_typed<float, 0>(a, st);
-  if (a.dtype == DS_BF16) return launch_typed<bf16_t>(a, st);
+  switch (p.route) {
+    case ConvRoute::SWS: return ds_launch_conv_sws(a, st);
+    case ConvRoute::SW: return ds_launch_conv_sw(a, p.sw_rows, st);
+    case ConvRoute::RW: return ds_launch_conv_rw(a, st);
+    case ConvRoute::WS: return ds_launch_conv_ws(a, st);
+    case ConvRoute::THIN_IN: return ds_launch_conv_thin_in(a, st);
+    case ConvRoute::THIN_OUT: return ds_launch_conv_thin_out(a, st);
+    case ConvRoute::SMALL: return ds_launch_conv_small(a, st);
+    case ConvRoute::GENERIC: break;
+  }
+  if (a.dtype == DS_F32) return a.split ? launch_typed<float, 1>(a, p.tile, st) : launch_typed<float, 0>(a, p.tile, st);
+  if (a.dtype == DS_BF16) return launch_typed<bf16_t>(a, p.tile, st);
   DS_CHECK(false, "conv: unknown dtype");
 }

@@ -77,7 +77,6 @@ extern "C" int32_t diffsep_set_option(const char* name, int64_t value) {
 }
 
 // ------------------------------------------------------------------ arena
-#define DS_NCLS 12
 static Tn cat_view(const Tn& a, const Tn& b) {
   Tn t = a;
   t.C = a.C + b.C; t.C1 = a.C; t.p2 = b.p; t.ld2 = b.ld;
@@ -158,12 +157,12 @@ struct Conv {
   const SkipConv* skip = nullptr;
   bool want_stats = false;           // the output gets GroupNorm accumulators (y.sa)
 };
-static int conv(diffsep_engine* e, const Conv& c, Tn& y, int B, hipStream_t st) {
+// The launcher's view of a Conv writing into y (no launch, no allocation: stats_acc is conv()'s to set)
+static ConvArgs conv_args(const diffsep_engine* e, const Conv& c, const Tn& y, int B) {
   const Tn& x = c.x;
   ConvArgs a;
   memset(&a, 0, sizeof(a));
-  a.B = B; a.Cout = c.Cout; a.taps = c.taps; a.dtype = e->cfg.dtype; a.split = e->split;
-  a.opts = e->opts;
+  a.B = B; a.Cout = c.Cout; a.taps = c.taps; a.dtype = e->cfg.dtype; a.split = e->split; a.opts = e->opts;
   conv_input(a, x);
   if (c.gn) {
     a.gn_scale = c.gn->scale; a.gn_shift = c.gn->shift; a.gn_act = 1;
@@ -185,17 +184,23 @@ static int conv(diffsep_engine* e, const Conv& c, Tn& y, int B, hipStream_t st) 
     a.sw = c.skip->w; a.sw_chunked = c.skip->chunk;
     a.sw_frag = use_frag ? c.skip->w_frag : nullptr;
   }
+  return a;
+}
+static int conv(diffsep_engine* e, const Conv& c, Tn& y, int B, hipStream_t st) {
+  ConvArgs a = conv_args(e, c, y, B);
   if (c.want_stats) {  // the consumer's GroupNorm reads these partials instead of re-reading the tensor
     y.sa = e_alloc_stats(e, (size_t)B * c.Cout * 2 * sizeof(long long));
     if (!y.sa) return 1;
     a.stats_acc = y.sa;
-    if (e->dbg_alloc && !e->dry)
-      fprintf(stderr, "[diffsep stats] %ld Cin %d Cout %d taps %d HxW %dx%d res %d skip %d bias_b %d cfg %d\n",
-              (long)((char*)y.sa - e->stats_ptr), x.C, c.Cout, c.taps, x.H, x.W, c.res != nullptr, c.skip != nullptr,
-              c.bias_b != nullptr, ds_conv_config_id(a));
   }
-  if (e->dry || ablated(e, x.H)) return 0;
-  if (!e->prof) return ds_launch_conv(a, st);
+  const ConvPlan p = ds_conv_plan(a);  // (the one plan of this launch: its kernel, its profile class)
+  DS_CHECK(!a.sx || p.skip_ok, "internal: fused skip conv on an unsupported tile");
+  if (c.want_stats && e->dbg_alloc && !e->dry)
+    fprintf(stderr, "[diffsep stats] %ld Cin %d Cout %d taps %d HxW %dx%d res %d skip %d bias_b %d cfg %d\n",
+            (long)((char*)y.sa - e->stats_ptr), a.Cin, c.Cout, c.taps, a.H, a.W, c.res != nullptr, c.skip != nullptr,
+            c.bias_b != nullptr, p.cls);
+  if (e->dry || ablated(e, a.H)) return 0;
+  if (!e->prof) return ds_launch_conv(a, p, st);
   diffsep_engine::ProfRec r;
   r.flops = 2.0 * ((double)a.taps * a.Cin + (a.sx ? a.sCin : 0)) * a.Cout * (double)a.H * a.W * a.B;
   {  // algorithmic HBM bytes: input (+ fused skip input) + output (+ residual) once each, weights once
@@ -204,9 +209,9 @@ static int conv(diffsep_engine* e, const Conv& c, Tn& y, int B, hipStream_t st) 
                          ((double)a.Cin + a.Cout + (a.res ? a.Cout : 0) + (a.sx ? a.sCin : 0)) +
                      ((double)a.taps * a.Cin + (a.sx ? a.sCin : 0)) * a.Cout);
   }
-  r.cls = ds_conv_config_id(a);
+  r.cls = p.cls;
   r.B = a.B; r.H = a.H; r.W = a.W; r.Cin = a.Cin; r.Cout = a.Cout; r.taps = a.taps; r.sCin = a.sx ? a.sCin : 0; r.res = a.res != nullptr;
-  const int rc = prof_launch(e, st, r, [&]() { return ds_launch_conv(a, st); });
+  const int rc = prof_launch(e, st, r, [&]() { return ds_launch_conv(a, p, st); });
   e->prof_recs.back().kernel = ds_last_conv_kernel();  // (the instantiation the dispatch chose)
   return rc;
 }
@@ -285,9 +290,8 @@ int res_block(diffsep_engine* e, const Module& m, const Tn& x, const float* temb
   // 269 + 318 for the pair, 155 against 77 + 89 at 128^2 — the pair stays at 256 rows; Conv_1 with the WHOLE 256-channel skip
   // folded 438 us at 256^2 against 319 + 193 (3x3 with half of the skip + the 1x1 launch on the other half), 103 against 91 + 47 at
   // 128^2 — one launch at every size.  Option no_sw: the route of round 4.
-  if (e->cfg.dtype == DS_BF16 && mode == 0 && x.p2 && m.pf0a >= 0 && x.C1 == 128 && x.sa && x.sa2 && x.W % 32 == 0 && x.H % 8 == 0 &&
-      x.H >= ((e->opts & DS_OPT_NO_SW) ? 128 : 256) && (long)B * (x.H / 4) * (x.W / 32) >= ds_num_cus() &&
-      !(e->opts & (DS_OPT_NO_RW | DS_OPT_NO_RW128 | DS_OPT_NO_SPLIT256 | DS_OPT_NO_WFRAG))) {
+  if (e->cfg.dtype == DS_BF16 && mode == 0 && x.p2 && m.pf0a >= 0 && x.C1 == 128 && x.sa && x.sa2 &&
+      x.H >= ((e->opts & DS_OPT_NO_SW) ? 128 : 256) && !(e->opts & (DS_OPT_NO_SPLIT256 | DS_OPT_NO_WFRAG))) {
     Tn xa = x, xb = x;
     xa.C = 128; xa.p2 = nullptr; xa.C1 = 0; xa.ld2 = 0; xa.sa2 = nullptr;
     xb.p = x.p2; xb.ld = x.ld2; xb.C = 128; xb.p2 = nullptr; xb.C1 = 0; xb.ld2 = 0; xb.sa = x.sa2; xb.sa2 = nullptr;
@@ -296,25 +300,32 @@ int res_block(diffsep_engine* e, const Module& m, const Tn& x, const float* temb
     ga.groups = gn_group_count(x.C) / 2;  // (of the 128-channel half)
     ga.inv_count = gn_inv_count((long)x.H * x.W, x.C, gn_group_count(x.C));
     gb = ga; gb.acc1 = xb.sa; gb.gamma = ga.gamma + 128; gb.beta = ga.beta + 128;
-    Tn h1p = e_tensor(e, B, Ho, Wo, m.out_ch), h1 = e_tensor(e, B, Ho, Wo, m.out_ch);
-    const long half0 = 4L * 9 * m.out_ch * 32;  // chunk-major [Cin / 32][9][Cout][32]: the first source = the first 4 chunks
     Conv c0a(xa, PK(e, m.pk0), m.out_ch, 9);
     c0a.w_frag = PKF(e, m.pf0a); c0a.gn = &ga; c0a.bias = P(e, m.conv0_b); c0a.bias_b = temb; c0a.bias_b_ld = e->arch.dense_total;
-    if (conv(e, c0a, h1p, B, st)) return 1;
-    Conv c0b(xb, PK(e, m.pk0 + half0), m.out_ch, 9);
-    c0b.w_frag = PKF(e, m.pf0b); c0b.gn = &gb; c0b.res = &h1p; c0b.want_stats = true;
-    if (conv(e, c0b, h1, B, st)) return 1;
-    if (gn_stats(e, h1, P(e, m.gn1_w), P(e, m.gn1_b), B, a1, st, true)) return 1;
-    out = e_tensor(e, B, Ho, Wo, m.out_ch);
-    if (!(e->opts & DS_OPT_NO_SW) && m.pf2 >= 0) return conv1_folded_skip(e, m, h1, x, a1, out, B, st);
-    Tn outp = e_tensor(e, B, Ho, Wo, m.out_ch);
-    const SkipConv sk = {&xa, PK(e, m.pk2), weight_chunk(9, 128, 0, e->cfg.dtype), PKF(e, m.pf2a)};
-    Conv c1(h1, PK(e, m.pk1), m.out_ch, 9);
-    c1.w_frag = PKF(e, m.pf1); c1.gn = &a1; c1.skip = &sk; c1.bias = P(e, m.conv1_b); c1.bias_b = P(e, m.conv2_b);
-    if (conv(e, c1, outp, B, st)) return 1;
-    Conv c2b(xb, PK(e, m.pk2b), m.out_ch, 1);
-    c2b.res = &outp; c2b.scale = kInvSqrt2; c2b.want_stats = true;
-    return conv(e, c2b, out, B, st);
+    // ... and only where the register-weight kernel's rule takes such a half (whole tiles, one 4 x 32 tile per CU, no_rw / no_rw128
+    // off; the streamed-weight kernel may still come first) — without rw_small, the unit tests' way past the tile counts
+    Tn h1p; h1p.C = h1p.ld = m.out_ch; h1p.H = Ho; h1p.W = Wo;  // (its shape is all the plan reads)
+    ConvArgs half = conv_args(e, c0a, h1p, B); half.opts &= ~DS_OPT_RW_SMALL;
+    if (ds_conv_plan(half).rw_ok) {
+      h1p = e_tensor(e, B, Ho, Wo, m.out_ch);
+      Tn h1 = e_tensor(e, B, Ho, Wo, m.out_ch);
+      const long half0 = 4L * 9 * m.out_ch * 32;  // chunk-major [Cin / 32][9][Cout][32]: the first source = the first 4 chunks
+      if (conv(e, c0a, h1p, B, st)) return 1;
+      Conv c0b(xb, PK(e, m.pk0 + half0), m.out_ch, 9);
+      c0b.w_frag = PKF(e, m.pf0b); c0b.gn = &gb; c0b.res = &h1p; c0b.want_stats = true;
+      if (conv(e, c0b, h1, B, st)) return 1;
+      if (gn_stats(e, h1, P(e, m.gn1_w), P(e, m.gn1_b), B, a1, st, true)) return 1;
+      out = e_tensor(e, B, Ho, Wo, m.out_ch);
+      if (!(e->opts & DS_OPT_NO_SW) && m.pf2 >= 0) return conv1_folded_skip(e, m, h1, x, a1, out, B, st);
+      Tn outp = e_tensor(e, B, Ho, Wo, m.out_ch);
+      const SkipConv sk = {&xa, PK(e, m.pk2), weight_chunk(9, 128, 0, e->cfg.dtype), PKF(e, m.pf2a)};
+      Conv c1(h1, PK(e, m.pk1), m.out_ch, 9);
+      c1.w_frag = PKF(e, m.pf1); c1.gn = &a1; c1.skip = &sk; c1.bias = P(e, m.conv1_b); c1.bias_b = P(e, m.conv2_b);
+      if (conv(e, c1, outp, B, st)) return 1;
+      Conv c2b(xb, PK(e, m.pk2b), m.out_ch, 1);
+      c2b.res = &outp; c2b.scale = kInvSqrt2; c2b.want_stats = true;
+      return conv(e, c2b, out, B, st);
+    }
   }
   if (gn_stats(e, x, P(e, m.gn0_w), P(e, m.gn0_b), B, a0, st, mode == 0)) return 1;  // resampling needs the arrays
   Tn h1 = e_tensor(e, B, Ho, Wo, m.out_ch);
@@ -332,10 +343,7 @@ int res_block(diffsep_engine* e, const Module& m, const Tn& x, const float* temb
   if (conv(e, c0, h1, B, st)) return 1;
   if (gn_stats(e, h1, P(e, m.gn1_w), P(e, m.gn1_b), B, a1, st, true)) return 1;
   out = e_tensor(e, B, Ho, Wo, m.out_ch);
-  if (m.has_conv2 && fuse_skip(m)) {
-    DS_CHECK(ds_conv_skip_supported(Ho, Wo, m.out_ch, e->cfg.dtype), "internal: fused skip conv on an unsupported tile");
-    return conv1_folded_skip(e, m, h1, xr, a1, out, B, st);
-  }
+  if (m.has_conv2 && fuse_skip(m)) return conv1_folded_skip(e, m, h1, xr, a1, out, B, st);  // (conv() checks the tile takes it)
   Tn skip = xr;
   if (m.has_conv2) {  // narrow blocks (<= 32 couts use the 32-cout tile, which has no skip path): separate 1x1 launch
     skip = e_tensor(e, B, Ho, Wo, m.out_ch);
@@ -399,11 +407,11 @@ int attn_block(diffsep_engine* e, const Module& m, const Tn& x, int B, Tn& out, 
     a.y = out.p; a.y_bs = (long)L * out.ld; a.ldy = out.ld;
     a.stats = out.sa;
     a.B = B; a.L = L; a.C = C;
-    diffsep_engine::ProfRec r;  // (per-launch timing like the convolutions: class 9)
+    diffsep_engine::ProfRec r;  // (per-launch timing like the convolutions)
     // V^T, Q' and the output projection (2 L C^2 each), scores and P V (2 L^2 C each); input + output + three matrices once
     r.flops = (double)B * (6.0 * L * C * C + 4.0 * (double)L * L * C);
     r.bytes = (double)e->esz * (2.0 * B * L * C + 3.0 * C * C);
-    r.cls = 9; r.B = B; r.H = x.H; r.W = x.W; r.Cin = C; r.Cout = C; r.taps = 1; r.res = 1;
+    r.cls = DS_CLS_ATTN; r.B = B; r.H = x.H; r.W = x.W; r.Cin = C; r.Cout = C; r.taps = 1; r.res = 1;
     r.kernel = "attn_fused_kernel";
     return prof_launch(e, st, r, [&]() { return ds_launch_attn_fused(a, st); });
   }
@@ -863,11 +871,9 @@ extern "C" int64_t diffsep_engine_get_option(const diffsep_engine* e, const char
   return -1;
 }
 
-// Per-launch timing of the MFMA contraction kernels inside the real launch sequence: between
-// profile_begin and profile_end every conv/GEMM launch is bracketed by HIP events on its stream
-// (graph replay is bypassed meanwhile).  Arrays have 10 entries (the last: the fused attention block): 3x3 {8x32xBN64, 8x32xBN32, 8x8xBN64},
-// then the same three tiles for 1x1/GEMM, the weight-stationary 64 -> 64 3x3 kernel, the small-image 3x3 kernel, the
-// register-weight 3x3 kernel.  flops = algorithmic 2*taps*Cin*Cout*H*W*B (unpadded).
+// Per-launch timing of the MFMA contraction kernels inside the real launch sequence: between profile_begin and profile_end every
+// conv/GEMM launch is bracketed by HIP events on its stream (graph replay is bypassed meanwhile).  The arrays are indexed by
+// kernel class (DS_CLS_*, common.h).  flops = algorithmic 2*taps*Cin*Cout*H*W*B (unpadded).
 extern "C" int32_t diffsep_engine_profile_begin(diffsep_engine* e) {
   DS_CHECK(e, "null engine");
   e->prof = true;

@@ -145,7 +145,7 @@ extern "C" int32_t diffsep_conv3x3_streamed(const void* x, const void* x2, int32
   }
   DS_CHECK(ds_conv_sw_supported(a), "conv3x3_streamed: shape outside the kernel's instantiations (16-bit, Cout = 128 / 256, Cin = 64 .. 256 "
                                     "by 64, W % 32 == 0, H % 4 == 0; a skip needs GroupNorm and Cin = 128; raw input: Cin <= 128; Cout = 64: Cin = 192)");
-  return ds_launch_conv_sw(a, (hipStream_t)stream);
+  return ds_launch_conv_sw(a, ds_conv_plan(a).sw_rows, (hipStream_t)stream);  // (the plan's tile rows, whatever its route)
 }
 extern "C" int64_t diffsep_frag_index(int32_t cout, int32_t tap, int32_t cin, int32_t taps, int32_t Cout) {
   return ds_rw_frag_index(cout, tap, cin, taps, Cout);

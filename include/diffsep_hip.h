@@ -249,7 +249,7 @@ int32_t diffsep_ode_error_norm(const diffsep_sde_config* sde, const float* x, co
 /* Use hipGraph replay of the per-NFE launch sequence inside diffsep_pc_sample (default 1). */
 int32_t diffsep_engine_set_graph(diffsep_engine* e, int32_t enable);
 
-/* Options (no counterpart in the reference: A/B switches, test aids and the bound of the graph cache; DESIGN.md section 6b).
+/* Options (no counterpart in the reference: A/B switches, test aids and the bound of the graph cache; DESIGN.md section 7).
  * Process-wide defaults of the kernel-dispatch switches "no_rw", "no_rw128", "rw_small", "no_rw_res" (0 / 1): read from the
  * environment variables DIFFSEP_NO_RW, DIFFSEP_NO_RW128, DIFFSEP_RW_SMALL, DIFFSEP_NO_RW_RES ONCE, changed here; they apply to
  * the unit entry points (diffsep_conv2d, ...) and are copied by every engine created afterwards. */
