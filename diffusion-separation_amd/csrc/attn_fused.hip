@@ -26,7 +26,7 @@
 // Both paths are compared with the CPU oracle at the 16-bit tolerance (tests/test_round4_gpu.py: the fused one is the closer).
 #include <type_traits>
 
-#include "common.h"
+#include "conv_device.h"
 
 #ifdef ATTN_TIMING  // profiling build only (tools/attn_timing.sh): per-phase cycle totals of wave 0 of every block
 __device__ unsigned long long g_attn_dbg[16];
@@ -46,7 +46,6 @@ extern "C" int diffsep_attn_debug_read(unsigned long long* out, int reset) {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 constexpr int C = 128, NKB = C / 16, NT_ = 512, LMAX = 256;
 constexpr int PH = C * 2 + 16;         // sH pitch: pixel row of 128 channels (+16 B: 16 consecutive rows = 16 distinct bank slots)
 constexpr int PV = LMAX * 2 + 16;      // sVt pitch: channel row of 256 pixels
@@ -140,11 +139,7 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
       long long ssum = 0, ssq = 0;
 #pragma unroll
       for (int j = 0; j < 8; ++j) { ssum += vs[j]; ssq += vq[j]; }
-      const double mean = (double)ssum * (1.0 / DS_STAT_SUM_SCALE) * (double)p.gn_inv_count;
-      double var = (double)ssq * (1.0 / DS_STAT_SQ_SCALE) * (double)p.gn_inv_count - mean * mean;
-      if (var < 0.0) var = 0.0;
-      sc = (float)(1.0 / sqrt(var + (double)p.gn_eps)) * (p.gn_gamma ? p.gn_gamma[tid] : 1.f);
-      sh = (p.gn_beta ? p.gn_beta[tid] : 0.f) - (float)mean * sc;
+      ds_gn_affine_from_acc(ssum, ssq, p.gn_inv_count, p.gn_eps, p.gn_gamma ? p.gn_gamma[tid] : 1.f, p.gn_beta ? p.gn_beta[tid] : 0.f, sc, sh);
     } else {
       sc = p.gn_scale[(long)b * C + tid];
       sh = p.gn_shift[(long)b * C + tid];
@@ -382,7 +377,7 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
       double a = 0.0;
 #pragma unroll 8
       for (int g = 0; g < NT_ / PPP; ++g) a += (double)sP[(g * C + c) * 2 + st];
-      ds_stat_add(p.stats + ((long)b * C + c) * 2 + st, (long long)llrint(a * (st ? DS_STAT_SQ_SCALE : DS_STAT_SUM_SCALE)));
+      ds_stat_flush(p.stats + ((long)b * C + c) * 2, st, a);
     }
   }
   AT_MARK(11)

@@ -1,4 +1,5 @@
-// common.h — shared device helpers for the gfx950 kernels (wave64, NHWC activations).
+// common.h — what every source shares: the storage-format helpers of the gfx950 kernels (wave64, NHWC activations), error
+// plumbing and the launcher prototypes.  The convolution kernels' own device helpers live in conv_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,13 +15,8 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 #define DS_BF16 1
 #define DS_F32_SPLIT 2  // boundary value only: fp32 tensors, MFMA products as 3 bf16 MFMAs (ConvArgs.split); kernels see DS_F32
 #define DS_MAX_SRC 4
-// fixed-point scales of the GroupNorm channel-sum accumulators (int64): sums 2^-24, sums of squares 2^-16
-#define DS_STAT_SUM_SCALE 16777216.0
-#define DS_STAT_SQ_SCALE 65536.0
-// Add into an accumulator (device-scope integer atomic: associative, so totals are bit-reproducible).
-__device__ inline void ds_stat_add(long long* acc, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(acc), (unsigned long long)v);
-}
+// (the GroupNorm channel-sum accumulators — int64 fixed point: their scales, the write-back and the scale / shift computed from
+// them — are device-side only: conv_device.h)
 
 // ---------------------------------------------------------------- error plumbing (host)
 void ds_set_error(const std::string& s);
@@ -218,7 +214,7 @@ struct ConvArgs {
   const void* res; long res_bs; int ldr; // residual added before out_scale, or null
   float out_scale;
   void* y; long y_bs; int ldy;
-  // optional [B][Cout][2] accumulators (sum, sum of squares of the output, fixed point DS_STAT_*_SCALE, int64):
+  // optional [B][Cout][2] accumulators (sum, sum of squares of the output; int64 fixed point, conv_device.h):
   // every block ADDS its tile's totals with integer atomics (bit-reproducible); the caller zeroes them first
   long long* stats_acc;
   // GroupNorm of the INPUT straight from such accumulators (of x and x2) instead of gn_scale / gn_shift:

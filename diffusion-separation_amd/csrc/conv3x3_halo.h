@@ -1,13 +1,13 @@
 // conv3x3_halo.h — what the persistent halo-tile 3x3 convolutions share word for word: conv3x3_rw.hip (register-resident
 // weights), conv3x3_sw.hip (streamed weights) and conv3x3_sws.hip (split mode).  Included once by each of them, before its own
-// code: the per-phase timing scaffolding of the profiling builds, the buffer helpers and the tile constants.  Everything lives
-// in an anonymous namespace except the profiling build's counters (g_<name>_dbg) and read-back function, which keep the names
-// and external linkage they had in each kernel file.
+// code: the per-phase timing scaffolding of the profiling builds and the tile constants (the buffer helpers and everything else
+// that is not specific to the halo tile come with conv_device.h).  The constants live in an anonymous namespace; the profiling
+// build's counters (g_<name>_dbg) and read-back function keep the names and external linkage they had in each kernel file.
 #pragma once
 
 #include <type_traits>
 
-#include "common.h"
+#include "conv_device.h"
 
 // ---- profiling build only (the including file defines HALO_TIMING as rw / sw / sws): per-phase cycle totals of wave 0,
 // read back through diffsep_<name>_debug_read
@@ -31,18 +31,6 @@ extern "C" int HALO_CAT(diffsep_, HALO_TIMING, _debug_read)(unsigned long long* 
 #endif
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ inline __amdgpu_buffer_rsrc_t rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-__device__ inline u32x4_t ld16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-}
-// block barrier that orders LDS traffic only (a __syncthreads() would also drain the global prefetch)
-__device__ inline void sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int TW = 32, HW_ = TW + 2;  // tile width, halo row
 constexpr int AROW = 128 + 16;        // 144 B: LDS pitch of a halo pixel's 128-byte chunk line (16 consecutive rows = 16 distinct bank slots)

@@ -169,11 +169,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
         long long t_ssum = 0, t_ssq = 0;
 #pragma unroll
         for (int j = 0; j < CPG_MAX; ++j) { t_ssum += t_s[j]; t_ssq += t_q[j]; }
-        const double mean = (double)t_ssum * (1.0 / DS_STAT_SUM_SCALE) * (double)p.gn_inv_count;
-        double var = (double)t_ssq * (1.0 / DS_STAT_SQ_SCALE) * (double)p.gn_inv_count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        sc = (float)(1.0 / sqrt(var + (double)p.gn_eps)) * t_gam;
-        sh = t_bet - (float)mean * sc;
+        ds_gn_affine_from_acc(t_ssum, t_ssq, p.gn_inv_count, p.gn_eps, t_gam, t_bet, sc, sh);
       }
       sTab[tid] = sc;
       sTab[CIN + tid] = sh;
@@ -242,12 +238,12 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
         const int chb = c * KC + kb * 16;  // first channel of the k-block (this lane: + 8 h)
         const unsigned so = wfm ? (unsigned)(ks * NCG * 1024)
                                 : (wc ? (unsigned)((((chb >> 5) * 9 + tap) * CO * 32 + (chb & 31)) * 2) : (unsigned)((tap * CIN + chb) * 2));
-        put_w(ks, ld16(rw, vlane, so));
+        put_w(ks, ld16v(rw, vlane, so));
       } else {
         const int chb = (ks - NCH * KSC) * 16;
         const unsigned so = sfm ? (unsigned)((ks - NCH * KSC) * NCG * 1024)
                                 : (sc_ ? (unsigned)((((chb >> p.sw_shift) * CO) * kcs + (chb & (kcs - 1))) * 2) : (unsigned)(chb * 2));
-        u32x4_t f = ld16(rsw, vl2, so);
+        u32x4_t f = ld16v(rsw, vl2, so);
         if (!p.sw) {  // residual as a skip with identity weights: channel chb + 8 h + j feeds cout co with weight 1
           const int d = co - (chb + 8 * h);  // the lane's 8 channels hold the 1 at position d (if 0 <= d < 8)
 #pragma unroll
@@ -304,14 +300,14 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
     if (k < NI) {  // a pixel of the tile itself: inside the image whenever the tile is (a tile past the block's range has a
                    // pixel index beyond every tensor: the hardware returns zeros)
       const unsigned off = __umul24((unsigned)(g.pix0 + k * p.W + ixp), ld2) + co2;
-      pa[k] = ld16(r, off, 0);
+      pa[k] = ld16v(r, off, 0);
       return;
     }
     const unsigned off = __umul24((unsigned)(rel + g.pix0), ld2) + co2;
 #ifdef RW_TIMING
-    pa[k] = ld16(r, (piece_ok(P_, g, k) && !(p.dbg & 2)) ? off : OOB, 0);
+    pa[k] = ld16v(r, (piece_ok(P_, g, k) && !(p.dbg & 2)) ? off : OOB, 0);
 #else
-    pa[k] = ld16(r, piece_ok(P_, g, k) ? off : OOB, 0);
+    pa[k] = ld16v(r, piece_ok(P_, g, k) ? off : OOB, 0);
 #endif
   };
   // every input of the launch is activated (no raw skip / residual chunk shares the accumulators): the activation may
@@ -877,7 +873,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
           const int t = (wpg * NCG + wcg) * 64 + hh * 32 + l;
           a += (double)red[t * RED_ROW + st * 16 + 4 * q + i];
         }
-      ds_stat_add(p.stats + ((long)b * CO + co) * 2 + st, (long long)llrint(a * (st ? DS_STAT_SQ_SCALE : DS_STAT_SUM_SCALE)));
+      ds_stat_flush(p.stats + ((long)b * CO + co) * 2, st, a);
     }
   }
   RT_MARK(5)

@@ -34,7 +34,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "conv_device.h"
 
 #ifdef SM_TIMING  // profiling build only (tools/small_timing.sh): per-phase cycle totals of wave 0 of every block
 __device__ unsigned long long g_sm_dbg[16];
@@ -55,27 +55,6 @@ extern "C" int diffsep_small_debug_read(unsigned long long* out, int reset) {
 #endif
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ inline __amdgpu_buffer_rsrc_t rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-__device__ inline uint4 ld16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ inline uint2 ld8(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-  const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, 0, 0);
-  return make_uint2(v.x, v.y);
-}
-__device__ inline void st8(__amdgpu_buffer_rsrc_t r, unsigned voff, uint2 d) {
-  const u32x2_t v = {d.x, d.y};
-  __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, 0, 0);
-}
 
 constexpr int GN_MAX = 512;         // channels of the lazy GroupNorm table
 
@@ -110,46 +89,6 @@ __device__ inline float row16_sum(float v) {
   v = dpp_add<0x4e>(v);   // quad_perm [2,3,0,1]
   v = dpp_add<0xb1>(v);   // quad_perm [1,0,3,2]
   return v;
-}
-
-// GN affine (+ SiLU) on 8 bf16 channels
-template <bool ACT>
-__device__ inline uint4 gn8(const uint4& u, const float* sc, const float* sh) {
-  float f[8];
-  f[0] = h_lo(u.x); f[1] = h_hi(u.x);
-  f[2] = h_lo(u.y); f[3] = h_hi(u.y);
-  f[4] = h_lo(u.z); f[5] = h_hi(u.z);
-  f[6] = h_lo(u.w); f[7] = h_hi(u.w);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float v = f[j] * sc[j] + sh[j];
-    f[j] = ACT ? silu_t<bf16_t>(v) : v;
-  }
-  uint4 o;
-  o.x = pack_h2(f[0], f[1]);
-  o.y = pack_h2(f[2], f[3]);
-  o.z = pack_h2(f[4], f[5]);
-  o.w = pack_h2(f[6], f[7]);
-  return o;
-}
-
-// fp32 storage (DIFFSEP_F32_SPLIT): GN affine (+ SiLU) on 4 fp32 channels, and the hi / lo bf16 split of conv_mfma.hip
-template <bool ACT>
-__device__ inline uint4 gn4(const uint4& u, const float* sc, const float* sh) {
-  float f[4] = {__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float v = f[j] * sc[j] + sh[j];
-    f[j] = ACT ? silu_t<float>(v) : v;
-  }
-  return make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
-}
-__device__ inline void split4(const uint4& v, uint2& hi, uint2& lo) {
-  const float f0 = __uint_as_float(v.x), f1 = __uint_as_float(v.y), f2 = __uint_as_float(v.z), f3 = __uint_as_float(v.w);
-  hi.x = pack_bf16x2(f0, f1);
-  hi.y = pack_bf16x2(f2, f3);
-  lo.x = pack_bf16x2(f0 - bf_lo(hi.x), f1 - bf_hi(hi.x));
-  lo.y = pack_bf16x2(f2 - bf_lo(hi.y), f3 - bf_hi(hi.y));
 }
 
 // tile shapes by image width: 16 columns x 8 rows on 8 waves, 8 x 8 on 8 waves (4 of them multiply: 512 threads keep the two
@@ -422,6 +361,7 @@ __global__ __launch_bounds__(SmTile<GW>::NT, 2) void conv3x3_small_kernel(SmK p)
           ssum += tmp[2 * (g0 + j)];
           ssq += tmp[2 * (g0 + j) + 1];
         }
+        // (ds_gn_affine_from_acc of conv_device.h written out: behind a function boundary this kernel compiles to another instruction stream)
         const double mean = (double)ssum * (1.0 / DS_STAT_SUM_SCALE) * (double)p.gn_inv_count;
         double var = (double)ssq * (1.0 / DS_STAT_SQ_SCALE) * (double)p.gn_inv_count - mean * mean;
         if (var < 0.0) var = 0.0;
@@ -536,6 +476,7 @@ __global__ __launch_bounds__(SmTile<GW>::NT, 2) void conv3x3_small_kernel(SmK p)
         s2 += (double)sr[(w * NS + tid) * 2 + 1];
       }
       long long* o = p.stats + ((long)b * p.Cout + co0 + tid) * 2;
+      // (both slots of a channel from one thread: ds_stat_flush of conv_device.h, slot by slot, written out)
       ds_stat_add(o, (long long)llrint(a * DS_STAT_SUM_SCALE));
       ds_stat_add(o + 1, (long long)llrint(s2 * DS_STAT_SQ_SCALE));
     }

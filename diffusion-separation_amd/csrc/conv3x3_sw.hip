@@ -179,11 +179,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
           long long t_ssum = 0, t_ssq = 0;
 #pragma unroll
           for (int j = 0; j < CPG_MAX; ++j) { t_ssum += t_s[e][j]; t_ssq += t_q[e][j]; }
-          const double mean = (double)t_ssum * (1.0 / DS_STAT_SUM_SCALE) * (double)p.gn_inv_count;
-          double var = (double)t_ssq * (1.0 / DS_STAT_SQ_SCALE) * (double)p.gn_inv_count - mean * mean;
-          if (var < 0.0) var = 0.0;
-          sc = (float)(1.0 / sqrt(var + (double)p.gn_eps)) * t_gam[e];
-          sh = t_bet[e] - (float)mean * sc;
+          ds_gn_affine_from_acc(t_ssum, t_ssq, p.gn_inv_count, p.gn_eps, t_gam[e], t_bet[e], sc, sh);
         }
         sTab[c] = sc;
         sTab[CIN + c] = sh;
@@ -233,8 +229,8 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
   auto load_frag = [&](int s) __attribute__((always_inline)) {  // (s: compile time)
     constexpr typename G::FragTab FT = G::frag_tab();  // (a constant table: the index is a constant once the K loop is unrolled)
     const int f = FT.v[s];
-    if (f >= 0) ring[s % RING] = ld16(rw, vfrag, (unsigned)f * p.frag_step);
-    else ring[s % RING] = ld16(rsw, vfrag, (unsigned)(-1 - f) * p.frag_step);
+    if (f >= 0) ring[s % RING] = ld16v(rw, vfrag, (unsigned)f * p.frag_step);
+    else ring[s % RING] = ld16v(rsw, vfrag, (unsigned)(-1 - f) * p.frag_step);
   };
 
   // ---- staging state: pa[] holds the chunk AFTER the one in LDS (in flight or landed)
@@ -278,14 +274,14 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
     if (k < NI) {  // a pixel of the tile itself: inside the image whenever the tile is (a tile past the block's range has a
                    // pixel index beyond every tensor: the hardware returns zeros)
       const unsigned off = __umul24((unsigned)(g.pix0 + k * p.W + ixp), ld2) + co2;
-      pa[k] = ld16(r, off, 0);
+      pa[k] = ld16v(r, off, 0);
       return;
     }
     const unsigned off = __umul24((unsigned)(rel + g.pix0), ld2) + co2;
 #ifdef SW_TIMING
-    pa[k] = ld16(r, (piece_ok(P_, g, k) && !(p.dbg & 2)) ? off : OOB, 0);
+    pa[k] = ld16v(r, (piece_ok(P_, g, k) && !(p.dbg & 2)) ? off : OOB, 0);
 #else
-    pa[k] = ld16(r, piece_ok(P_, g, k) ? off : OOB, 0);
+    pa[k] = ld16v(r, piece_ok(P_, g, k) ? off : OOB, 0);
 #endif
   };
   // every input of the launch is activated (no raw skip / residual chunk shares the accumulators): the activation may
@@ -821,7 +817,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
           const int t = (wpg * NCG + wcg) * 64 + hh * 32 + l;
           a += (double)red[t * RED_ROW + st * 16 + 4 * q + i];
         }
-      ds_stat_add(p.stats + ((long)b * p.cout + cb * CO + co) * 2 + st, (long long)llrint(a * (st ? DS_STAT_SQ_SCALE : DS_STAT_SUM_SCALE)));
+      ds_stat_flush(p.stats + ((long)b * p.cout + cb * CO + co) * 2, st, a);
     }
   }
   RT_MARK(5)

@@ -31,7 +31,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 constexpr int KC = 32;                // channels per chunk: a pixel's chunk is ONE full 128-byte line of fp32 values
 constexpr int NKB = KC / 16;          // 16-channel k-blocks per tap
 constexpr int KSC = 9 * NKB;          // k-steps of a 3x3 chunk
@@ -103,14 +102,6 @@ struct SwsGeom {
   static_assert(NT * 36 * 4 <= LDS_TOTAL, "the statistics reduce reuses the block's LDS");
 };
 
-// fp32 value = hi + lo with hi, lo bfloat16 (round to nearest even both): as split4 of conv_mfma.hip
-__device__ inline void split4(const float (&f)[4], u32x2_t& hi, u32x2_t& lo) {
-  hi.x = pack_bf16x2(f[0], f[1]);
-  hi.y = pack_bf16x2(f[2], f[3]);
-  lo.x = pack_bf16x2(f[0] - bf_lo(hi.x), f[1] - bf_hi(hi.x));
-  lo.y = pack_bf16x2(f[2] - bf_lo(hi.y), f[3] - bf_hi(hi.y));
-}
-
 // MODE: 0 raw input, 2 GroupNorm + SiLU
 template <int NCH, int NSK, int MODE, int NCG>
 __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
@@ -167,11 +158,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
         long long t_ssum = 0, t_ssq = 0;
 #pragma unroll
         for (int j = 0; j < CPG_MAX; ++j) { t_ssum += t_s[j]; t_ssq += t_q[j]; }
-        const double mean = (double)t_ssum * (1.0 / DS_STAT_SUM_SCALE) * (double)p.gn_inv_count;
-        double var = (double)t_ssq * (1.0 / DS_STAT_SQ_SCALE) * (double)p.gn_inv_count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        sc = (float)(1.0 / sqrt(var + (double)p.gn_eps)) * t_gam;
-        sh = t_bet - (float)mean * sc;
+        ds_gn_affine_from_acc(t_ssum, t_ssq, p.gn_inv_count, p.gn_eps, t_gam, t_bet, sc, sh);
       }
       sTab[tid] = sc;
       sTab[CIN + tid] = sh;
@@ -220,11 +207,11 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
     constexpr typename G::FragTab FT = G::frag_tab();
     const int f = FT.v[s];
     if (f >= 0) {
-      rhi[s % RING] = ld16(rw, vfrag, (unsigned)f * p.frag_step);
-      rlo[s % RING] = ld16(rw, vfrag, (unsigned)f * p.frag_step + lo_step);
+      rhi[s % RING] = ld16v(rw, vfrag, (unsigned)f * p.frag_step);
+      rlo[s % RING] = ld16v(rw, vfrag, (unsigned)f * p.frag_step + lo_step);
     } else {
-      rhi[s % RING] = ld16(rsw, vfrag, (unsigned)(-1 - f) * p.frag_step);
-      rlo[s % RING] = ld16(rsw, vfrag, (unsigned)(-1 - f) * p.frag_step + lo_step);
+      rhi[s % RING] = ld16v(rsw, vfrag, (unsigned)(-1 - f) * p.frag_step);
+      rlo[s % RING] = ld16v(rsw, vfrag, (unsigned)(-1 - f) * p.frag_step + lo_step);
     }
   };
 
@@ -264,11 +251,11 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
     }
     if (k < NI) {
       const unsigned off = __umul24((unsigned)(g.pix0 + k * p.W + ixp), ld4) + co4;
-      pa[k] = ld16(r, off, 0);
+      pa[k] = ld16v(r, off, 0);
       return;
     }
     const unsigned off = __umul24((unsigned)(rel + g.pix0), ld4) + co4;
-    pa[k] = ld16(r, piece_ok(P_, g, k) ? off : OOB, 0);
+    pa[k] = ld16v(r, piece_ok(P_, g, k) ? off : OOB, 0);
   };
   // every input of the launch is activated: the activation may leave a constant factor (-1 / ln 2) to the epilogue
   constexpr bool FOLD = MODE == 2 && NSK == 0;
@@ -491,7 +478,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
           const int t = (wpg * NCG + wcg) * 64 + hh * 32 + l;
           a += (double)red[t * RED_ROW + st * 16 + 4 * q + i];
         }
-      ds_stat_add(p.stats + ((long)b * p.cout + cb * CO + co) * 2 + st, (long long)llrint(a * (st ? DS_STAT_SQ_SCALE : DS_STAT_SUM_SCALE)));
+      ds_stat_flush(p.stats + ((long)b * p.cout + cb * CO + co) * 2, st, a);
     }
   }
   RT_MARK(5)

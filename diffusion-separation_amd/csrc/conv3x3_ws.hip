@@ -32,7 +32,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "conv_device.h"
 
 #ifdef WS_TIMING  // profiling build only: per-phase cycle totals of wave 0 (group 0) and wave 4 (group 1)
 __device__ unsigned long long g_ws_dbg[32];
@@ -65,31 +65,6 @@ __device__ inline f32x16 mfma_h32x(bf16x8 a, bf16x8 b, f32x16 c, int, int, int) 
 __device__ inline f32x4_acc mfma_h16x(bf16x8 a, bf16x8 b, f32x4_acc c, int, int, int) {
   return mfma_h16(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, b), c);
 }
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ inline __amdgpu_buffer_rsrc_t rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-__device__ inline uint4 ld16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-__device__ inline uint2 ld8(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-  const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, 0, 0);
-  return make_uint2(v.x, v.y);
-}
-__device__ inline void st8(__amdgpu_buffer_rsrc_t r, unsigned voff, uint2 d) {
-  const u32x2_t v = {d.x, d.y};
-  __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, 0, 0);
-}
-
-// Block barrier that only orders LDS traffic.  __syncthreads() is a workgroup-scope fence: it drains vmcnt, i.e. it
-// would wait for the global prefetch loads issued just before it and serialize them with the barrier.
-__device__ inline void sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int C = 64;                 // input and output channels
 constexpr int TH = 8, TW = 32;        // output tile
@@ -127,49 +102,6 @@ struct WsK {
   const bf16_t* sw; int sw_chunked, sw_shift;
   int H, W, G, tiles_x, tiles_per_img;
 };
-
-// GN affine (+ SiLU) on 8 bf16 channels
-template <bool ACT>
-__device__ inline uint4 gn8(const uint4& u, const float* sc, const float* sh) {
-#if defined(DS_HALF_F16) && !defined(DS_GN8_F32)
-  // half-precision build, round 5: affine + SiLU in packed half precision, 8 instructions per dword (as the register-weight
-  // convolution: DESIGN.md section 2 for what it costs in agreement — in front of a convolution, nothing measurable)
-  if constexpr (ACT) {
-    auto one = [&](unsigned w, int d) __attribute__((always_inline)) {
-      const unsigned ps = pack_h2(sc[2 * d], sc[2 * d + 1]), pb = pack_h2(sh[2 * d], sh[2 * d + 1]);
-      unsigned z, xx, e, dd, r, o;
-      asm("v_pk_fma_f16 %0, %1, %2, %3" : "=v"(z) : "v"(w), "v"(ps), "v"(pb));
-      asm("v_pk_mul_f16 %0, %1, %2" : "=v"(xx) : "v"(z), "s"(0xbdc5bdc5u));  // x -log2(e)
-      asm("v_exp_f16 %0, %1" : "=v"(e) : "v"(xx));
-      asm("v_exp_f16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1" : "+v"(e) : "v"(xx));
-      asm("v_pk_add_f16 %0, %1, %2" : "=v"(dd) : "v"(e), "s"(0x3c003c00u));
-      asm("v_rcp_f16 %0, %1" : "=v"(r) : "v"(dd));
-      asm("v_rcp_f16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1" : "+v"(r) : "v"(dd));
-      asm("v_pk_mul_f16 %0, %1, %2" : "=v"(o) : "v"(z), "v"(r));
-      return o;
-    };
-    uint4 o;
-    o.x = one(u.x, 0); o.y = one(u.y, 1); o.z = one(u.z, 2); o.w = one(u.w, 3);
-    return o;
-  }
-#endif
-  float f[8];
-  f[0] = h_lo(u.x); f[1] = h_hi(u.x);
-  f[2] = h_lo(u.y); f[3] = h_hi(u.y);
-  f[4] = h_lo(u.z); f[5] = h_hi(u.z);
-  f[6] = h_lo(u.w); f[7] = h_hi(u.w);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float v = f[j] * sc[j] + sh[j];
-    f[j] = ACT ? silu_t<bf16_t>(v) : v;
-  }
-  uint4 o;
-  o.x = pack_h2(f[0], f[1]);
-  o.y = pack_h2(f[2], f[3]);
-  o.z = pack_h2(f[4], f[5]);
-  o.w = pack_h2(f[6], f[7]);
-  return o;
-}
 
 // ---- the kernel: all 8 waves in the same phase.  A wave owns ONE pixel row x 64 couts
 // (36 MFMAs per chunk); the halo chunks go through a 2-slot ring with ONE barrier per chunk; the chunk in flight
@@ -225,6 +157,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws1_kernel(WsK p) {
           ssum += p.gn_acc[((long)b * C + g0 + j) * 2];
           ssq += p.gn_acc[((long)b * C + g0 + j) * 2 + 1];
         }
+        // (ds_gn_affine_from_acc of conv_device.h written out: behind a function boundary this kernel compiles to another instruction stream)
         const double mean = (double)ssum * (1.0 / DS_STAT_SUM_SCALE) * (double)p.gn_inv_count;
         double var = (double)ssq * (1.0 / DS_STAT_SQ_SCALE) * (double)p.gn_inv_count - mean * mean;
         if (var < 0.0) var = 0.0;
@@ -299,7 +232,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws1_kernel(WsK p) {
 #ifdef ABL2_NOACT
     return;
 #endif
-    uint4 r = gn8<MODE == 2>(pa[set][k], gsc, gsh);
+    uint4 r = gn8<MODE == 2, true>(pa[set][k], gsc, gsh);
     asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
     pa[set][k].x = pval[set][k] ? r.x : pa[set][k].x;
     pa[set][k].y = pval[set][k] ? r.y : pa[set][k].y;
@@ -545,6 +478,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws1_kernel(WsK p) {
       double a = 0.0;
 #pragma unroll 8
       for (int i = 0; i < 64; ++i) a += (double)src[i * 8 * RED_ROW];
+      // (ds_stat_flush of conv_device.h written out, as the GroupNorm expression of this file is)
       ds_stat_add(p.stats + ((long)b * C + co) * 2 + st, (long long)llrint(a * (st ? DS_STAT_SQ_SCALE : DS_STAT_SUM_SCALE)));
     }
   }
@@ -673,6 +607,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_thin_in_kernel(ThinK p) {
       double a = 0.0;
 #pragma unroll 8
       for (int i = 0; i < 64; ++i) a += (double)src[i * 8 * RED_ROW];
+      // (ds_stat_flush of conv_device.h written out, as the GroupNorm expression of this file is)
       ds_stat_add(p.stats + ((long)b * C + co) * 2 + st, (long long)llrint(a * (st ? DS_STAT_SQ_SCALE : DS_STAT_SUM_SCALE)));
     }
   }
@@ -791,6 +726,7 @@ __global__ __launch_bounds__(512, WPE) void conv3x3_thin_out_kernel(ThinOutK p) 
               ssum += p.gn_acc[((long)b * p.Cin + g0 + j) * 2];
               ssq += p.gn_acc[((long)b * p.Cin + g0 + j) * 2 + 1];
             }
+            // (ds_gn_affine_from_acc of conv_device.h written out: behind a function boundary this kernel compiles to another instruction stream)
             const double mean = (double)ssum * (1.0 / DS_STAT_SUM_SCALE) * (double)p.gn_inv_count;
             double var = (double)ssq * (1.0 / DS_STAT_SQ_SCALE) * (double)p.gn_inv_count - mean * mean;
             if (var < 0.0) var = 0.0;
@@ -813,7 +749,7 @@ __global__ __launch_bounds__(512, WPE) void conv3x3_thin_out_kernel(ThinOutK p) 
         const int v = tid + 512 * k;
         if (v < HP * 8) {
           uint4 r = pv[k];
-          if (ok[k]) r = p.act ? gn8<true>(pv[k], gsc, gsh) : gn8<false>(pv[k], gsc, gsh);
+          if (ok[k]) r = p.act ? gn8<true, true>(pv[k], gsc, gsh) : gn8<false>(pv[k], gsc, gsh);
           *reinterpret_cast<uint4*>(sX + (v >> 3) * TO_PROW + slot * 16) = r;
         }
       }

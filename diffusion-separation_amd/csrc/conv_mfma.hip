@@ -30,7 +30,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "conv_device.h"
 
 #ifdef CONV_TIMING  // profiling build only (tools/conv_timing.sh): per-phase cycle totals of wave 0 of every block
 __device__ unsigned long long g_conv_dbg[16];
@@ -72,51 +72,12 @@ struct MmaBf {  // true bfloat16 operands: the hi / lo planes of the split mode
   __device__ static inline void run(const uint4& a, const uint4& b, f32x16& c) { c = mfma_bf32(a, b, c); }
 };
 
-// fp32 value = hi + lo with hi, lo bf16 (|error| <= 2^-17 |v|): the operands of the "split" mode, in which an fp32 conv
-// runs as three bf16 MFMAs per k-block (hi*hi + hi*lo + lo*hi, fp32 accumulation) instead of eight fp32 MFMAs
-__device__ inline void split4(const uint4& v, uint2& hi, uint2& lo) {
-  const float f0 = __uint_as_float(v.x), f1 = __uint_as_float(v.y), f2 = __uint_as_float(v.z), f3 = __uint_as_float(v.w);
-  hi.x = pack_bf16x2(f0, f1);
-  hi.y = pack_bf16x2(f2, f3);
-  lo.x = pack_bf16x2(f0 - bf_lo(hi.x), f1 - bf_hi(hi.x));
-  lo.y = pack_bf16x2(f2 - bf_lo(hi.y), f3 - bf_hi(hi.y));
+// GN-apply (+SiLU) on one 16-byte vector of KV channels of the storage type
+template <typename T, bool ACT>
+__device__ inline uint4 gn_vec(const uint4& u, const float* sc, const float* sh) {
+  if constexpr (sizeof(T) == 4) return gn4<ACT>(u, sc, sh);
+  else return gn8<ACT>(u, sc, sh);
 }
-
-// GN-apply (+SiLU) on one 16-byte vector of KV channels
-template <typename T> struct GnVec;
-template <> struct GnVec<float> {
-  template <bool ACT>
-  __device__ static inline uint4 run(const uint4& u, const float* sc, const float* sh) {
-    float f[4] = {__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float v = f[j] * sc[j] + sh[j];
-      f[j] = ACT ? silu_t<float>(v) : v;
-    }
-    return make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
-  }
-};
-template <> struct GnVec<bf16_t> {
-  template <bool ACT>
-  __device__ static inline uint4 run(const uint4& u, const float* sc, const float* sh) {
-    float f[8];
-    f[0] = h_lo(u.x); f[1] = h_hi(u.x);
-    f[2] = h_lo(u.y); f[3] = h_hi(u.y);
-    f[4] = h_lo(u.z); f[5] = h_hi(u.z);
-    f[6] = h_lo(u.w); f[7] = h_hi(u.w);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float v = f[j] * sc[j] + sh[j];
-      f[j] = ACT ? silu_t<bf16_t>(v) : v;
-    }
-    uint4 o;
-    o.x = pack_h2(f[0], f[1]);
-    o.y = pack_h2(f[2], f[3]);
-    o.z = pack_h2(f[4], f[5]);
-    o.w = pack_h2(f[6], f[7]);
-    return o;
-  }
-};
 
 // 8 channels held as raw 16-byte vectors -> floats
 template <typename T> __device__ inline void unpack8(const uint4* u, float* f);
@@ -189,25 +150,13 @@ struct ConvGeom {
   static constexpr bool SKIP_OK = TAPS == 9 && (NT / NVEC) <= BN && BN % (NT / NVEC) == 0;
 };
 
-// ---- buffer addressing (SRSRC): a wave-uniform descriptor + a 32-bit per-lane byte offset + a uniform
-// scalar offset.  Lanes that must not touch memory get an offset >= num_records: the hardware returns 0 for
-// such loads and drops such stores, so the halo zero padding, ragged tiles and channel tails cost no
-// branches, no exec masking and no zero-initialisation.  The per-lane offsets are loop invariant: inside the
+// ---- buffer addressing: rsrc / ld16 / OOB of conv_device.h.  The per-lane offsets are loop invariant: inside the
 // K loop a load is ONE instruction (the chunk's channel offset travels in the scalar offset).
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-#define DS_OOB 0x80000000u
-__device__ inline __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
 #ifndef DS_A_AUX
 #define DS_A_AUX 0  // cache-policy bits of the activation tile loads (experiment: 2 = nt)
 #endif
 __device__ inline uint4 buf_load16a(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
   const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, DS_A_AUX);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ inline uint4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 __device__ inline void buf_store16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, const uint4& d) {
@@ -257,11 +206,11 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
   float* sGN = reinterpret_cast<float*>(smem + G::LDS);  // [Cin] scale, [Cin] shift (accumulator mode)
   const int C1 = p.C1, C2 = p.Cin - p.C1;
   const __amdgpu_buffer_rsrc_t rx1 =
-      make_rsrc(reinterpret_cast<const T*>(p.x) + (long)b * p.x_bs, (unsigned)M * p.ldx * ESZ);
-  const __amdgpu_buffer_rsrc_t rx2 = make_rsrc(
+      rsrc(reinterpret_cast<const T*>(p.x) + (long)b * p.x_bs, (unsigned)M * p.ldx * ESZ);
+  const __amdgpu_buffer_rsrc_t rx2 = rsrc(
       p.x2 ? reinterpret_cast<const T*>(p.x2) + (long)b * p.x2_bs : reinterpret_cast<const T*>(p.x), (unsigned)M * (p.x2 ? p.ldx2 : p.ldx) * ESZ);
   const __amdgpu_buffer_rsrc_t rw =
-      make_rsrc(reinterpret_cast<const T*>(p.w) + (long)b * p.w_bs, (unsigned)p.Cout * TAPS * p.Cin * ESZ);
+      rsrc(reinterpret_cast<const T*>(p.w) + (long)b * p.w_bs, (unsigned)p.Cout * TAPS * p.Cin * ESZ);
 
   // ---- per-thread staging descriptors.  Vector i = tid + 256 k of a stage: row (pixel / weight row)
   // row0 + k*RPS, 16-byte slot tid % NVEC: LDS offsets are linear in k (immediates), global byte offsets
@@ -310,7 +259,7 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
     }
   }
   auto voa = [&](int k, int ld) __attribute__((always_inline)) { return (unsigned)((pixi_[k] * ld + vch) * ESZ); };
-  // byte offsets of the thread's weight vectors (row = cout, tap): DS_OOB past Cout.  When a pass of the block covers whole
+  // byte offsets of the thread's weight vectors (row = cout, tap): OOB past Cout.  When a pass of the block covers whole
   // taps the offsets are base + k * step (one register + a scalar instead of NB registers: the 8 x 32 x 64 tile sat at 256
   // VGPRs with 5 of them in scratch memory, and a scratch reload next to in-flight loads is a full vmcnt(0))
   constexpr bool VOB_LIN = B_TAPSTEP;
@@ -341,13 +290,13 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
     const bool ok = b_in(k) && n0 + col < p.Cout && tap < TAPS;
     // weights: [Cout][tap][Cin] or, chunk-major, [Cin / KC][tap][Cout][KC] (a stage's rows are then contiguous:
     // full 128-byte lines per request instead of 64-byte pieces)
-    vob[k] = !ok ? DS_OOB
+    vob[k] = !ok ? OOB
                  : p.w_chunked ? (unsigned)((((vch >> p.w_shift) * TAPS + tap) * p.Cout + n0 + col) * p.w_chunked +
                                             (vch & (p.w_chunked - 1))) * ESZ
                                : (unsigned)(((n0 + col) * TAPS + tap) * p.Cin + vch) * ESZ;
   }
   auto vobk = [&](int k) __attribute__((always_inline)) {
-    if constexpr (VOB_LIN) return (vcol_ok && vtap0 + k * (RPS / BN) < TAPS) ? vob[0] + (unsigned)k * vob_step : DS_OOB;
+    if constexpr (VOB_LIN) return (vcol_ok && vtap0 + k * (RPS / BN) < TAPS) ? vob[0] + (unsigned)k * vob_step : OOB;
     else return vob[k];
   };
 
@@ -394,14 +343,14 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
       const int width = (second ? sC2 : sC1) - cb;
       const int wb = second ? sC1 + cb : cb;
       ch_ok = vch < width;
-      const __amdgpu_buffer_rsrc_t rs = make_rsrc(
+      const __amdgpu_buffer_rsrc_t rs = rsrc(
           second ? reinterpret_cast<const T*>(p.sx2) + (long)b * p.sx2_bs : reinterpret_cast<const T*>(p.sx) + (long)b * p.sx_bs,
           (unsigned)M * (second ? p.ldsx2 : p.ldsx) * ESZ);
-      const __amdgpu_buffer_rsrc_t rsw = make_rsrc(p.sw, (unsigned)p.Cout * p.sCin * ESZ);
+      const __amdgpu_buffer_rsrc_t rsw = rsrc(p.sw, (unsigned)p.Cout * p.sCin * ESZ);
       const int lds_ = second ? p.ldsx2 : p.ldsx;
       const unsigned so = (unsigned)cb * ESZ;
 #pragma unroll
-      for (int k = 0; k < NA; ++k) pa[k] = buf_load16(rs, (ch_ok && ain[k]) ? voa(k, lds_) : DS_OOB, so);
+      for (int k = 0; k < NA; ++k) pa[k] = ld16(rs, (ch_ok && ain[k]) ? voa(k, lds_) : OOB, so);
 #pragma unroll
       for (int q = 0; q < QS; ++q) {
         const int col = row0 + q * RPS;  // (RPS == BN: row0 < BN)
@@ -409,7 +358,7 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
         const unsigned vo = p.sw_chunked ? (unsigned)((((wb + vch) >> p.sw_shift) * p.Cout + n0 + col) * p.sw_chunked +
                                                       ((wb + vch) & (p.sw_chunked - 1))) * ESZ
                                          : (unsigned)((n0 + col) * p.sCin + wb + vch) * ESZ;
-        pb[KSKIP + q] = buf_load16(rsw, okw ? vo : DS_OOB, 0);
+        pb[KSKIP + q] = ld16(rsw, okw ? vo : OOB, 0);
       }
       return;
     }
@@ -434,17 +383,17 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
         for (int k = 0; k < NA; ++k) pa[k] = buf_load16a(rx2, voa(k, ld_), so);
       }
 #pragma unroll
-      for (int k = 0; k < NB; ++k) pb[k] = buf_load16(rw, vobk(k), sw);
+      for (int k = 0; k < NB; ++k) pb[k] = ld16(rw, vobk(k), sw);
     } else {  // channel tail of a source: lanes past the end read zeros
       if (!second) {
 #pragma unroll
-        for (int k = 0; k < NA; ++k) pa[k] = buf_load16(rx1, ch_ok ? voa(k, ld_) : DS_OOB, so);
+        for (int k = 0; k < NA; ++k) pa[k] = ld16(rx1, ch_ok ? voa(k, ld_) : OOB, so);
       } else {
 #pragma unroll
-        for (int k = 0; k < NA; ++k) pa[k] = buf_load16(rx2, ch_ok ? voa(k, ld_) : DS_OOB, so);
+        for (int k = 0; k < NA; ++k) pa[k] = ld16(rx2, ch_ok ? voa(k, ld_) : OOB, so);
       }
 #pragma unroll
-      for (int k = 0; k < NB; ++k) pb[k] = buf_load16(rw, ch_ok ? vobk(k) : DS_OOB, sw);
+      for (int k = 0; k < NB; ++k) pb[k] = ld16(rw, ch_ok ? vobk(k) : OOB, sw);
     }
   };
   auto load_gn = [&](int c) __attribute__((always_inline)) {  // scale / shift of this thread's KV channels of chunk c
@@ -484,6 +433,7 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
         ssum += tmp[2 * (g0 + j)];
         ssq += tmp[2 * (g0 + j) + 1];
       }
+      // (ds_gn_affine_from_acc of conv_device.h written out: behind a function boundary this kernel compiles to another instruction stream)
       const double mean = (double)ssum * (1.0 / DS_STAT_SUM_SCALE) * (double)p.gn_inv_count;
       double var = (double)ssq * (1.0 / DS_STAT_SQ_SCALE) * (double)p.gn_inv_count - mean * mean;
       if (var < 0.0) var = 0.0;
@@ -533,7 +483,7 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
       return;
 #endif
       if constexpr (MODE != 0) {
-        uint4 r = GnVec<T>::template run<MODE == 2>(pa[k], gsc, gsh);
+        uint4 r = gn_vec<T, MODE == 2>(pa[k], gsc, gsh);
         // keep the arithmetic unconditional (a branch here would cut the MFMA loop into pieces)
         asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
         const bool ok = aval[k] && ch_ok;
@@ -639,8 +589,8 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
   // ---- epilogue: accumulators -> LDS (fp32, [pixel][cout]) -> bias / temb / residual / scale -> 16-byte
   // stores, in EP passes over the wave's M blocks (a smaller staging buffer lets more blocks share a CU).
   const __amdgpu_buffer_rsrc_t ry =
-      make_rsrc(reinterpret_cast<T*>(p.y) + (long)b * p.y_bs, (unsigned)M * p.ldy * ESZ);
-  const __amdgpu_buffer_rsrc_t rr = make_rsrc(
+      rsrc(reinterpret_cast<T*>(p.y) + (long)b * p.y_bs, (unsigned)M * p.ldy * ESZ);
+  const __amdgpu_buffer_rsrc_t rr = rsrc(
       p.res ? reinterpret_cast<const T*>(p.res) + (long)b * p.res_bs : reinterpret_cast<const T*>(p.y),
       p.res ? (unsigned)M * p.ldr * ESZ : 0u);  // no residual: zero records -> every load returns 0
 #ifdef ABL_NOEPI
@@ -740,10 +690,10 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
         if (co >= cout8) m = -1;
       }
       mrow[it] = m;
-      voy[it] = m >= 0 ? (unsigned)(m * p.ldy + co) * ESZ : DS_OOB;
-      vor[it] = m >= 0 ? (unsigned)(m * p.ldr + co) * ESZ : DS_OOB;
+      voy[it] = m >= 0 ? (unsigned)(m * p.ldy + co) * ESZ : OOB;
+      vor[it] = m >= 0 ? (unsigned)(m * p.ldr + co) * ESZ : OOB;
 #pragma unroll
-      for (int q = 0; q < RV; ++q) rraw[it][q] = buf_load16(rr, vor[it], 16u * q);
+      for (int q = 0; q < RV; ++q) rraw[it][q] = ld16(rr, vor[it], 16u * q);
     }
     __syncthreads();
     CT_MARK(7)
@@ -839,6 +789,7 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
       }
       // integer (fixed-point) atomics: associative, so the image totals are bit-reproducible whatever the order
       long long* o = p.stats + ((long)b * p.Cout + n0 + tid) * 2;
+      // (both slots of a channel from one thread: ds_stat_flush of conv_device.h, slot by slot, written out)
       ds_stat_add(o, (long long)llrint(a * DS_STAT_SUM_SCALE));
       ds_stat_add(o + 1, (long long)llrint(q * DS_STAT_SQ_SCALE));
     }

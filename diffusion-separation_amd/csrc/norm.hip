@@ -6,7 +6,7 @@
 // upsample_2d / downsample_2d  up_or_down_sampling.py:206-273 (closed forms: SURVEY.md §8a-15).
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_device.h"
 
 // ------------------------------------------------------------------ GroupNorm statistics
 // grid (nblk, B); each block reduces `ppb` pixels of one batch entry for all C channels.
@@ -103,9 +103,10 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restri
   }
 }
 
-// GroupNorm scale/shift from the channel-sum accumulators the conv epilogues fill (fixed point, common.h) — only
+// GroupNorm scale/shift from the channel-sum accumulators the conv epilogues fill (fixed point, conv_device.h) — only
 // for consumers that are not convolutions (the FIR resampling / attention GroupNorm kernels); the convolutions
-// build the same table in their own prologue.  grid (B) x 256 threads; two sources = in-place concat.
+// build the same table in their own prologue (ds_gn_affine_from_acc, conv_device.h).  grid (B) x 256 threads; two sources =
+// in-place concat.
 __global__ __launch_bounds__(256) void gn_finalize_acc_kernel(const long long* __restrict__ a1, int C1,
                                                               const long long* __restrict__ a2, int C2, int groups,
                                                               double inv_count, float eps,
@@ -122,6 +123,7 @@ __global__ __launch_bounds__(256) void gn_finalize_acc_kernel(const long long* _
       ssum += __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       ssq += __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    // (ds_gn_affine_from_acc of conv_device.h written out: behind a function boundary this kernel compiles to another instruction stream)
     const double mean = (double)ssum * (1.0 / DS_STAT_SUM_SCALE) * inv_count;
     double var = (double)ssq * (1.0 / DS_STAT_SQ_SCALE) * inv_count - mean * mean;
     if (var < 0.0) var = 0.0;
@@ -136,7 +138,10 @@ int ds_launch_gn_finalize_acc(const long long* a1, int C1, const long long* a2, 
                               hipStream_t st) {
   const int C = C1 + C2;
   DS_CHECK(C % groups == 0 && groups > 0, "groupnorm(acc): bad group count");
-  const double inv_count = 1.0 / ((double)npix * (double)(C / groups));
+  // rounded to float and widened again: the reciprocal the convolutions' argument structs carry (gn_inv_count, engine_host.h).
+  // With the double reciprocal the table differed in the last bits from a convolution's own whenever npix * C / groups is no
+  // power of two (e.g. 16 x 12 x 8)
+  const double inv_count = (double)(float)(1.0 / ((double)npix * (double)(C / groups)));
   hipLaunchKernelGGL(gn_finalize_acc_kernel, dim3(B), dim3(256), 0, st, a1, C1, a2, C2, groups, inv_count, eps, gamma,
                      beta, scale, shift);
   DS_LAUNCH_CHECK();

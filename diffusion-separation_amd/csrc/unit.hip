@@ -90,6 +90,18 @@ extern "C" int32_t diffsep_conv2d_fused(const void* x, const void* x2, int32_t C
   a.dtype = ds.dtype; a.split = ds.split;
   return ds_launch_conv(a, (hipStream_t)stream);
 }
+// name (with template arguments) of the kernel the calling thread's last convolution launch ran: lets a test that aims at one
+// route fail when the dispatch silently took another
+extern "C" const char* diffsep_last_conv_kernel() { return ds_last_conv_kernel(); }
+// scale / shift [B][C1 + C2] from the accumulators of one tensor or of the in-place concat of two (the launch the engine puts in
+// front of consumers that are not convolutions)
+extern "C" int32_t diffsep_gn_finalize_acc(const int64_t* acc1, int32_t C1, const int64_t* acc2, int32_t C2, int32_t B,
+                                           int64_t npix, int32_t groups, float eps, const float* gamma, const float* beta,
+                                           float* scale, float* shift, void* stream) {
+  DS_CHECK(acc1 && scale && shift && C1 > 0 && (acc2 ? C2 > 0 : C2 == 0) && B > 0 && npix > 0, "gn_finalize_acc: bad argument");
+  return ds_launch_gn_finalize_acc((const long long*)acc1, C1, (const long long*)acc2, C2, B, npix, groups, eps, gamma, beta,
+                                   scale, shift, (hipStream_t)stream);
+}
 // (the plain convolution: no concat, no GroupNorm, no statistics, row-major weights)
 extern "C" int32_t diffsep_conv2d(const void* x, const void* w, const float* bias, const float* bias_b, const void* res,
                                   void* y, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t ksize,
@@ -106,8 +118,11 @@ extern "C" int32_t diffsep_conv3x3_streamed(const void* x, const void* x2, int32
                                             const float* bias_b, const void* sx, const void* sx2, int32_t sC1,
                                             int32_t sCin, const void* sw_frag, void* y, int32_t B, int32_t H, int32_t W,
                                             int32_t Cin, int32_t Cout, float out_scale, int32_t dtype, int64_t* stats,
-                                            const void* res, const void* ident_frag, void* stream) {
+                                            const void* res, const void* ident_frag, const int64_t* gn_acc1,
+                                            const int64_t* gn_acc2, const float* gn_gamma, const float* gn_beta,
+                                            int32_t gn_groups, void* stream) {
   DS_CHECK(x && w_frag && y, "conv3x3_streamed: null pointer");
+  DS_CHECK(!gn_acc1 || (!gn_scale && gn_groups > 0 && Cin % gn_groups == 0 && (!x2 || gn_acc2)), "conv3x3_streamed: bad GroupNorm accumulators");
   DS_CHECK(!res || (ident_frag && !sx), "conv3x3_streamed: a residual needs the identity copy and no skip");
   DS_CHECK(B > 0 && H > 0 && W > 0, "conv3x3_streamed: empty problem");
   DS_CHECK(!x2 || (C1 > 0 && C1 < Cin), "conv3x3_streamed: bad concat split");
@@ -120,7 +135,11 @@ extern "C" int32_t diffsep_conv3x3_streamed(const void* x, const void* x2, int32
   Tn xin = view(x, H, W, Cin, c1);
   xin.p2 = const_cast<void*>(x2); xin.ld2 = Cin - c1; xin.C1 = x2 ? C1 : 0;
   conv_input(a, xin);
-  a.gn_scale = gn_scale; a.gn_shift = gn_shift; a.gn_act = gn_scale ? 1 : 0;
+  a.gn_scale = gn_scale; a.gn_shift = gn_shift; a.gn_act = (gn_scale || gn_acc1) ? 1 : 0;
+  if (gn_acc1) {  // GroupNorm of the input from its producers' accumulators, as diffsep_conv2d_fused
+    a.gn_acc1 = (const long long*)gn_acc1; a.gn_acc2 = (const long long*)gn_acc2; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta;
+    a.gn_groups = gn_groups; a.gn_eps = 1e-6f; a.gn_inv_count = gn_inv_count((long)H * W, Cin, gn_groups);
+  }
   a.w = w_frag; a.w_frag = w_frag; a.w_bs = 0;
   a.bias = bias; a.bias_b = bias_b; a.bias_b_ld = Cout; a.bias_mode = 0;
   if (sx) {
@@ -152,6 +171,28 @@ extern "C" int64_t diffsep_frag_index(int32_t cout, int32_t tap, int32_t cin, in
 }
 extern "C" int64_t diffsep_frag_index_split(int32_t cout, int32_t tap, int32_t cin, int32_t taps, int32_t Cout, int32_t plane) {
   return ds_sws_frag_index(cout, tap, cin, taps, Cout, plane);
+}
+
+// Unit entry of the fused attention kernel (attn_fused.hip) on caller-supplied operands: x, y dense [B][L][C] 16-bit, the three
+// weight matrices in the fragment-major order of diffsep_frag_index(row, 0, column, 1, C) (wqk = Wk^T Wq), GroupNorm of x from its
+// producer's accumulators (gn_acc + gamma / beta / groups) or from gn_scale / gn_shift [B][C].
+extern "C" int32_t diffsep_attn_fused(const void* x, const int64_t* gn_acc, const float* gn_gamma, const float* gn_beta,
+                                      int32_t gn_groups, const float* gn_scale, const float* gn_shift, const void* wqk,
+                                      const void* wv, const void* wo, const float* bqk, const float* bv, const float* bo,
+                                      void* y, int64_t* stats, int32_t B, int32_t L, int32_t C, void* stream) {
+  DS_CHECK(B > 0 && ds_attn_fused_eligible(DS_BF16, C, L), "attn_fused: 128 channels, 16 .. 256 pixels by 16");
+  DS_CHECK(!gn_acc || (gn_groups > 0 && C % gn_groups == 0 && C / gn_groups <= 8), "attn_fused: bad GroupNorm group count");
+  AttnFusedArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.x_bs = (long)L * C; a.ldx = C;
+  a.gn_acc = (const long long*)gn_acc; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.gn_scale = gn_scale; a.gn_shift = gn_shift;
+  if (gn_acc) { a.gn_groups = gn_groups; a.gn_inv_count = gn_inv_count(L, C, gn_groups); a.gn_eps = 1e-6f; }
+  a.wqk = wqk; a.wv = wv; a.wo = wo; a.bqk = bqk; a.bv = bv; a.bo = bo;
+  a.y = y; a.y_bs = (long)L * C; a.ldy = C;
+  a.stats = (long long*)stats;
+  a.B = B; a.L = L; a.C = C;
+  ds_set_last_conv_kernel("attn_fused_kernel");  // (the name the engine's profile records give this launch)
+  return ds_launch_attn_fused(a, (hipStream_t)stream);
 }
 
 extern "C" int32_t diffsep_conv2d_chunk(int32_t ksize, int32_t dtype) { return ds_conv_chunk(ksize == 3 ? 9 : 1, dtype); }

@@ -91,11 +91,12 @@ def pack_frag_weight_split(w):
 
 
 def conv3x3_streamed(x, w_frag, cout, x2=None, gn=None, bias=None, bias_b=None, skip=None, out_scale=1.0, stats=False, out=None,
-                     res=None, ident_frag=None):
+                     res=None, ident_frag=None, gn_acc=None):
     """The streamed-weight 3x3 kernels as units (diffsep_conv3x3_streamed).  x [B,H,W,C1] (+ x2 [B,H,W,C2]) dense; 16-bit tensors:
     conv3x3_sw.hip with pack_frag_weight copies; float32 tensors: the split mode's conv3x3_sws.hip with pack_frag_weight_split
     copies (res + ident_frag: residual against the identity copy).  gn = (scale, shift) [B,Cin] f32 -> SiLU(GroupNorm(.)) on the
-    fly; skip = (sx, sx2 | None, sw_frag): folded 1x1 on raw channels."""
+    fly, or gn_acc = (acc1, acc2 | None, gamma, beta, groups): the same from the producers' accumulators, as conv2d_fused;
+    skip = (sx, sx2 | None, sw_frag): folded 1x1 on raw channels."""
     B, H, W, C1 = x.shape
     Cin = C1 + (x2.shape[-1] if x2 is not None else 0)
     y = torch.zeros((B, H, W, cout), dtype=x.dtype, device=x.device) if out is None else out
@@ -108,11 +109,13 @@ def conv3x3_streamed(x, w_frag, cout, x2=None, gn=None, bias=None, bias_b=None, 
     sx, sx2, swf = skip if skip is not None else (None, None, None)
     sC1 = sx.shape[-1] if sx is not None else 0
     sCin = sC1 + (sx2.shape[-1] if sx2 is not None else 0)
+    a1, a2, gam, bet, grp = gn_acc if gn_acc is not None else (None, None, None, None, 0)
     split = x.dtype == torch.float32
     L = lib("bf16") if split else _L(x)
     check(L.diffsep_conv3x3_streamed(_ptr(x), _ptr(x2), C1, _ptr(sc), _ptr(sh), _ptr(w_frag), _ptr(bias), _ptr(bias_b),
                                      _ptr(sx), _ptr(sx2), sC1, sCin, _ptr(swf), _ptr(y), B, H, W, Cin, cout, out_scale,
-                                     F32_SPLIT if split else _dt(x), _ptr(st), _ptr(res), _ptr(ident_frag), _stream_ptr()), L)
+                                     F32_SPLIT if split else _dt(x), _ptr(st), _ptr(res), _ptr(ident_frag), _ptr(a1), _ptr(a2), _ptr(gam),
+                                     _ptr(bet), grp, _stream_ptr()), L)
     return (y, st) if stats is not False else y
 
 
@@ -195,6 +198,38 @@ def stats_to_float(st):
     out[..., 0] /= STAT_SUM_SCALE
     out[..., 1] /= STAT_SQ_SCALE
     return out
+
+
+def groupnorm_from_acc(sa, sb, gamma, beta, groups, npix, eps=1e-6):
+    """scale, shift [B,C] fp32 from the int64 accumulators sa [B,C1,2] (+ sb [B,C2,2] | None: the concat of two tensors of npix
+    pixels) through the finalize launch: the table a convolution given gn_acc=... builds in its own prologue, bit for bit
+    (tests/test_gn_table_gpu.py)."""
+    B, C1 = sa.shape[:2]
+    C2 = sb.shape[1] if sb is not None else 0
+    scale = torch.empty((B, C1 + C2), dtype=torch.float32, device=sa.device)
+    shift = torch.empty_like(scale)
+    check(lib().diffsep_gn_finalize_acc(_ptr(sa), C1, _ptr(sb), C2, B, npix, groups, eps, _ptr(gamma), _ptr(beta), _ptr(scale),
+                                        _ptr(shift), _stream_ptr()))
+    return scale, shift
+
+
+def attn_fused(x, wqk, wv, wo, bqk, bv, bo, gn=None, gn_acc=None, stats=False):
+    """The fused attention block's kernel as a unit (diffsep_attn_fused): x [B,L,128] 16-bit, wqk / wv / wo [128*128] in the
+    fragment-major order of pack_frag_weight (1x1), biases [128] f32; gn = (scale, shift) [B,128] or gn_acc = (acc, gamma, beta,
+    groups)."""
+    B, L, Cc = x.shape
+    y = torch.empty_like(x)
+    st = torch.zeros((B, Cc, 2), dtype=torch.int64, device=x.device) if stats else None
+    sc, sh = gn if gn is not None else (None, None)
+    acc, gam, bet, grp = gn_acc if gn_acc is not None else (None, None, None, 0)
+    check(_L(x).diffsep_attn_fused(_ptr(x), _ptr(acc), _ptr(gam), _ptr(bet), grp, _ptr(sc), _ptr(sh), _ptr(wqk), _ptr(wv), _ptr(wo),
+                                   _ptr(bqk), _ptr(bv), _ptr(bo), _ptr(y), _ptr(st), B, L, Cc, _stream_ptr()), _L(x))
+    return (y, st) if stats else y
+
+
+def last_conv_kernel(kind="bf16"):
+    """name of the kernel instantiation the calling thread's last convolution launch ran in library `kind`"""
+    return lib(kind).diffsep_last_conv_kernel().decode()
 
 
 def attention(q, k, vt, split=False):

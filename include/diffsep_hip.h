@@ -343,6 +343,16 @@ int32_t diffsep_conv2d_fused(const void* x, const void* x2, int32_t C1, const fl
  * [Cin_pad / kc][k*k][Cout][kc] (the layout the engine keeps its weights in: one K stage of the kernel is then
  * contiguous in memory and is fetched in full 128-byte lines). */
 int32_t diffsep_conv2d_chunk(int32_t ksize, int32_t dtype);
+/* Name, with its template arguments, of the kernel instantiation that the calling thread's last convolution launch ran
+ * (thread-local; "" before the first launch). */
+const char* diffsep_last_conv_kernel(void);
+/* GroupNorm scale / shift [B][C1 + C2] fp32 from the int64 channel-sum accumulators [B][C][2] that the convolutions' `stats`
+ * fill (acc2 nullable: the in-place concat of two tensors); npix = H * W of the tensor.  The expression, and the float-rounded
+ * 1 / (npix * C / groups), that the convolutions evaluate when they are given `gn_acc1` instead of `gn_scale` / `gn_shift`:
+ * both tables hold the same bits (tests/test_gn_table_gpu.py). */
+int32_t diffsep_gn_finalize_acc(const int64_t* acc1, int32_t C1, const int64_t* acc2, int32_t C2, int32_t B, int64_t npix,
+                                int32_t groups, float eps, const float* gamma, const float* beta, float* scale, float* shift,
+                                void* stream);
 /* The streamed-weight 3x3 kernel (csrc/conv3x3_sw.hip; the 128-cout layers with 192 / 256 input channels or a folded 1x1 skip
  * on up to 256 raw channels: ncsnpp.py:409-417, layerspp.py:291-323) as a unit, whatever the dispatch would pick.  Dense NHWC
  * 16-bit tensors: x [B][H][W][C1 or Cin], x2 (nullable) the other Cin - C1 channels; act(GroupNorm(.)) from per-(b, c)
@@ -357,12 +367,23 @@ int32_t diffsep_conv2d_chunk(int32_t ksize, int32_t dtype);
  * plane).  `res` (nullable, no skip beside it; 16-bit: Cout = 128): residual [B][H][W][Cout] added before out_scale — it rides
  * through the matrix cores against `ident_frag`, the fragment copy (of that mode) of the Cout x Cout identity (taps = 1).
  * 16-bit tile shapes: 8 x 32 pixels x 128 couts, 4 x 32 x 128 where H % 8 != 0 (and, in the engine, on levels with fewer 8-row
- * tiles than compute units), 8 x 32 x 64 for the one 64-cout layer the register-weight kernel does not hold (Cin = 192). */
+ * tiles than compute units), 8 x 32 x 64 for the one 64-cout layer the register-weight kernel does not hold (Cin = 192).
+ * gn_acc1 (nullable, instead of gn_scale / gn_shift; gn_acc2 for x2), gn_gamma, gn_beta, gn_groups: GroupNorm of the input from
+ * its producers' accumulators, as in diffsep_conv2d_fused. */
 int32_t diffsep_conv3x3_streamed(const void* x, const void* x2, int32_t C1, const float* gn_scale, const float* gn_shift,
                                  const void* w_frag, const float* bias, const float* bias_b, const void* sx, const void* sx2,
                                  int32_t sC1, int32_t sCin, const void* sw_frag, void* y, int32_t B, int32_t H, int32_t W,
                                  int32_t Cin, int32_t Cout, float out_scale, int32_t dtype, int64_t* stats, const void* res,
-                                 const void* ident_frag, void* stream);
+                                 const void* ident_frag, const int64_t* gn_acc1, const int64_t* gn_acc2, const float* gn_gamma,
+                                 const float* gn_beta, int32_t gn_groups, void* stream);
+/* The fused attention kernel (csrc/attn_fused.hip) as a unit: x, y dense [B][L][C] 16-bit, C = 128, L = 16 .. 256 by 16; wqk
+ * (= Wk^T Wq), wv, wo in the order of diffsep_frag_index(row, 0, column, 1, C); bqk = Wk^T b_q, bv, bo [C] fp32.  GroupNorm of x
+ * (no activation) from gn_acc [B][C][2] + gn_gamma / gn_beta / gn_groups, or from gn_scale / gn_shift [B][C] when gn_acc is NULL.
+ * stats (nullable): accumulators of y. */
+int32_t diffsep_attn_fused(const void* x, const int64_t* gn_acc, const float* gn_gamma, const float* gn_beta, int32_t gn_groups,
+                           const float* gn_scale, const float* gn_shift, const void* wqk, const void* wv, const void* wo,
+                           const float* bqk, const float* bv, const float* bo, void* y, int64_t* stats, int32_t B, int32_t L,
+                           int32_t C, void* stream);
 int64_t diffsep_frag_index(int32_t cout, int32_t tap, int32_t cin, int32_t taps, int32_t Cout);
 int64_t diffsep_frag_index_split(int32_t cout, int32_t tap, int32_t cin, int32_t taps, int32_t Cout, int32_t plane);
 /* `stats` (nullable): channel-sum accumulators of the OUTPUT for the next GroupNorm, [B][Cout][2] int64 fixed point
