@@ -410,6 +410,7 @@ int ds_launch_attn_fused(const AttnFusedArgs& a, hipStream_t st) {
 #define ATTN_GO(LT_)                                                                     \
   do {                                                                                   \
     DS_FUNC_LDS_ONCE(attn_fused_kernel<LT_>, LDS_BYTES);                                 \
+    ds_set_last_conv_kernel("attn_fused_kernel<" #LT_ ">");                              \
     hipLaunchKernelGGL(attn_fused_kernel<LT_>, dim3(a.B), dim3(NT_), LDS_BYTES, st, k);  \
     DS_LAUNCH_CHECK();                                                                   \
     return 0;                                                                            \

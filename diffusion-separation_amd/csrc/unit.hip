@@ -191,7 +191,6 @@ extern "C" int32_t diffsep_attn_fused(const void* x, const int64_t* gn_acc, cons
   a.y = y; a.y_bs = (long)L * C; a.ldy = C;
   a.stats = (long long*)stats;
   a.B = B; a.L = L; a.C = C;
-  ds_set_last_conv_kernel("attn_fused_kernel");  // (the name the engine's profile records give this launch)
   return ds_launch_attn_fused(a, (hipStream_t)stream);
 }
 

@@ -213,18 +213,28 @@ def groupnorm_from_acc(sa, sb, gamma, beta, groups, npix, eps=1e-6):
     return scale, shift
 
 
-def attn_fused(x, wqk, wv, wo, bqk, bv, bo, gn=None, gn_acc=None, stats=False):
+def attn_fused(x, wqk, wv, wo, bqk, bv, bo, gn=None, gn_acc=None, stats=False, out=None):
     """The fused attention block's kernel as a unit (diffsep_attn_fused): x [B,L,128] 16-bit, wqk / wv / wo [128*128] in the
     fragment-major order of pack_frag_weight (1x1), biases [128] f32; gn = (scale, shift) [B,128] or gn_acc = (acc, gamma, beta,
-    groups)."""
+    groups).  stats=True additionally returns the int64 accumulators [B,128,2] of the output, stats=<tensor> adds into it, as
+    conv2d_fused; out=<tensor>: the output buffer (dense, x's type, at least B samples of [L,128]: the first B are written)."""
     B, L, Cc = x.shape
-    y = torch.empty_like(x)
-    st = torch.zeros((B, Cc, 2), dtype=torch.int64, device=x.device) if stats else None
+    if out is not None and (out.dtype != x.dtype or out.device != x.device or not out.is_contiguous() or out.dim() != 3
+                            or out.shape[0] < B or tuple(out.shape[1:]) != (L, Cc)):
+        raise ValueError("attn_fused: out must be a dense [>= B, L, C] tensor of x's type on x's device")
+    y = torch.empty_like(x) if out is None else out
+    st = None
+    if stats is True:
+        st = torch.zeros((B, Cc, 2), dtype=torch.int64, device=x.device)
+    elif stats is not False:
+        st = stats
+        if st.dtype != torch.int64 or not st.is_contiguous() or st.dim() != 3 or st.shape[0] < B or tuple(st.shape[1:]) != (Cc, 2):
+            raise ValueError("attn_fused: stats must be a dense int64 [>= B, C, 2] tensor")
     sc, sh = gn if gn is not None else (None, None)
     acc, gam, bet, grp = gn_acc if gn_acc is not None else (None, None, None, 0)
     check(_L(x).diffsep_attn_fused(_ptr(x), _ptr(acc), _ptr(gam), _ptr(bet), grp, _ptr(sc), _ptr(sh), _ptr(wqk), _ptr(wv), _ptr(wo),
                                    _ptr(bqk), _ptr(bv), _ptr(bo), _ptr(y), _ptr(st), B, L, Cc, _stream_ptr()), _L(x))
-    return (y, st) if stats else y
+    return (y, st) if stats is not False else y
 
 
 def last_conv_kernel(kind="bf16"):

@@ -344,7 +344,8 @@ int32_t diffsep_conv2d_fused(const void* x, const void* x2, int32_t C1, const fl
  * contiguous in memory and is fetched in full 128-byte lines). */
 int32_t diffsep_conv2d_chunk(int32_t ksize, int32_t dtype);
 /* Name, with its template arguments, of the kernel instantiation that the calling thread's last convolution launch ran
- * (thread-local; "" before the first launch). */
+ * (thread-local; "" before the first launch).  The fused attention kernel counts as one, from the unit entry point and from
+ * the engine's block code alike: "attn_fused_kernel<LT>" with LT = 1, 2, 4, 8 tiles of 32 pixels. */
 const char* diffsep_last_conv_kernel(void);
 /* GroupNorm scale / shift [B][C1 + C2] fp32 from the int64 channel-sum accumulators [B][C][2] that the convolutions' `stats`
  * fill (acc2 nullable: the in-place concat of two tensors); npix = H * W of the tensor.  The expression, and the float-rounded

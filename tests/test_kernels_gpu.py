@@ -163,6 +163,32 @@ def test_attention(dtype, tol, L, C):
     assert rel_rms(o.float(), ref) < tol
 
 
+@pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-5), (torch.bfloat16, 2e-2), (torch.float16, 2.5e-3)],
+                         ids=["float32", "bfloat16", "float16"])  # (float16: the bfloat16 bound by the ulp ratio 2^-3)
+@pytest.mark.parametrize("B,L,gain", [(2, 12, 1.0), (2, 20, 1.0), (2, 68, 1.0), (16, 20, 30.0)])
+def test_attention_ragged_key_count(dtype, tol, B, L, gain):
+    # the unfused path (scores, softmax_kernel, P V) where L is no multiple of 8: the score / probability rows are padded to
+    # Lp > L columns, which must contribute nothing (V^T's padding columns hold 100 here); L = 68: a lane's softmax loop runs
+    # twice.  Reference: float64 softmax over the L keys only, on the stored operands.  gain = 30: logits of +-100 (above 88
+    # in about 15 of the 320 rows: exp overflows fp32 there unless the row maximum is subtracted); few keys per row, so that
+    # the storage rounding of such scores (ulp 0.5 in bfloat16) stays about half the bound, and many rows
+    C = 128
+    q, k, v = (rnd(f"atr.{n}{L}.{B}", (B, L, C)) for n in "qkv")
+    q = q * gain
+    qd, kd, vd = q.to(dtype).double(), k.to(dtype).double(), v.to(dtype).double()
+    w = torch.softmax(torch.einsum("bic,bjc->bij", qd, kd) * C ** -0.5, dim=-1)
+    ref = torch.einsum("bij,bjc->bic", w, vd)
+    Lp = (L + 7) // 8 * 8
+    assert Lp > L
+    vt = torch.full((B, C, Lp), 100.0)
+    vt[:, :, :L] = v.transpose(1, 2)
+    o = ops.attention(q.to(DEV, dtype), k.to(DEV, dtype), vt.to(DEV, dtype))
+    assert bool(torch.isfinite(o.float()).all())
+    r = rel_rms(o.float(), ref)
+    print(f"\n[attention {dtype} B{B} L{L} x{gain:g}] {r:.2e} rel rms (limit {tol:g})")
+    assert r < tol
+
+
 @pytest.mark.parametrize("T", [4000, 31999, 32000, 32001, 130])
 def test_stft_pack_matches_oracle(T):
     cfg = O.default_config(16, 2)
