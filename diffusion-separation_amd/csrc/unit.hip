@@ -166,6 +166,48 @@ extern "C" int32_t diffsep_conv3x3_streamed(const void* x, const void* x2, int32
                                     "by 64, W % 32 == 0, H % 4 == 0; a skip needs GroupNorm and Cin = 128; raw input: Cin <= 128; Cout = 64: Cin = 192)");
   return ds_launch_conv_sw(a, ds_conv_plan(a).sw_rows, (hipStream_t)stream);  // (the plan's tile rows, whatever its route)
 }
+// Unit entry of the register-weight 3x3 kernel (conv3x3_rw.hip), whatever the dispatch would have chosen for the shape, with the
+// folded 1x1 skip that diffsep_conv2d_fused has no arguments for: dense NHWC 16-bit tensors, w as in diffsep_conv2d_fused
+// ([Cout][9][Cin], or chunk-major with w_chunk), sw [Cout][sCin] row-major.
+extern "C" int32_t diffsep_conv3x3_regweight(const void* x, const void* x2, int32_t C1, const float* gn_scale,
+                                             const float* gn_shift, const void* w, int32_t w_chunk, const float* bias,
+                                             const float* bias_b, const void* sx, const void* sx2, int32_t sC1, int32_t sCin,
+                                             const void* sw, const void* res, void* y, int32_t B, int32_t H, int32_t W,
+                                             int32_t Cin, int32_t Cout, float out_scale, int32_t dtype, int64_t* stats,
+                                             void* stream) {
+  DS_CHECK(x && w && y, "conv3x3_regweight: null pointer");
+  DS_CHECK(B > 0 && H > 0 && W > 0, "conv3x3_regweight: empty problem");
+  DS_CHECK(!x2 || (C1 > 0 && C1 < Cin), "conv3x3_regweight: bad concat split");
+  DS_CHECK(!sx || (sw && !res && sCin > 0 && (!sx2 || (sC1 > 0 && sC1 < sCin))), "conv3x3_regweight: bad skip operands");
+  DS_CHECK((long)H * W * (Cin > Cout ? Cin : Cout) * 2 < 2147483647L, "conv3x3_regweight: image too large for 32-bit buffer offsets");
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.opts = ds_default_opts();
+  a.stats_acc = (long long*)stats;
+  const int c1 = x2 ? C1 : Cin;  // dense sources: each one's leading dimension is its channel count
+  Tn xin = view(x, H, W, Cin, c1);
+  xin.p2 = const_cast<void*>(x2); xin.ld2 = Cin - c1; xin.C1 = x2 ? C1 : 0;
+  conv_input(a, xin);
+  a.gn_scale = gn_scale; a.gn_shift = gn_shift; a.gn_act = gn_scale ? 1 : 0;
+  a.w = w; a.w_bs = 0; a.w_chunked = w_chunk;
+  a.bias = bias; a.bias_b = bias_b; a.bias_b_ld = Cout; a.bias_mode = 0;
+  if (sx) {
+    const int s1 = sx2 ? sC1 : sCin;
+    Tn sin = view(sx, H, W, sCin, s1);
+    sin.p2 = const_cast<void*>(sx2); sin.ld2 = sCin - s1; sin.C1 = sx2 ? sC1 : 0;
+    conv_skip_input(a, sin);
+    a.sw = sw; a.sw_chunked = 0;
+  }
+  conv_residual(a, view(res, H, W, Cout, Cout));
+  a.out_scale = out_scale;
+  conv_output(a, view(y, H, W, Cout, Cout));
+  a.B = B; a.Cout = Cout; a.taps = 9;
+  const DtypeSplit ds = split_dtype(dtype);
+  a.dtype = ds.dtype; a.split = ds.split;
+  DS_CHECK(!a.split && ds_conv_rw_supported(a), "conv3x3_regweight: shape outside the kernel's instantiations (16-bit, 64 / 128 -> 64 or "
+                                                "128 -> 128, H >= 32, H % 8 == 0, W % 32 == 0; skip: 64 / 128 (/ 192 at 64 -> 64) raw channels)");
+  return ds_launch_conv_rw(a, (hipStream_t)stream);
+}
 extern "C" int64_t diffsep_frag_index(int32_t cout, int32_t tap, int32_t cin, int32_t taps, int32_t Cout) {
   return ds_rw_frag_index(cout, tap, cin, taps, Cout);
 }

@@ -126,6 +126,8 @@ _SIGS = {
     "diffsep_gn_finalize_acc": (_I, [_P, _I, _P, _I, _I, _L, _I, _F, _P, _P, _P, _P, _P]),
     "diffsep_conv3x3_streamed": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P,
                                       _P, _P, _P, _P, _P, _I, _P]),
+    "diffsep_conv3x3_regweight": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P,
+                                       _P]),
     "diffsep_attn_fused": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "diffsep_frag_index": (_L, [_I, _I, _I, _I, _I]),
     "diffsep_frag_index_split": (_L, [_I, _I, _I, _I, _I, _I]),

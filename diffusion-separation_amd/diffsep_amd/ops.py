@@ -119,6 +119,25 @@ def conv3x3_streamed(x, w_frag, cout, x2=None, gn=None, bias=None, bias_b=None, 
     return (y, st) if stats is not False else y
 
 
+def conv3x3_regweight(x, wpacked, cout, x2=None, gn=None, bias=None, bias_b=None, skip=None, res=None, out_scale=1.0, stats=False,
+                      w_chunk=0):
+    """The register-weight 3x3 kernel as a unit (diffsep_conv3x3_regweight), with its folded 1x1 skip: x (+ x2) dense 16-bit,
+    wpacked from pack_conv_weight; gn = (scale, shift) -> SiLU(GroupNorm(.)) on the fly; skip = (sx, sx2 | None, sw [cout, sCin]
+    in x's type): raw channels through the centre tap; res: residual (no skip beside it)."""
+    B, H, W, C1 = x.shape
+    Cin = C1 + (x2.shape[-1] if x2 is not None else 0)
+    y = torch.zeros((B, H, W, cout), dtype=x.dtype, device=x.device)
+    sc, sh = gn if gn is not None else (None, None)
+    st = torch.zeros((B, cout, 2), dtype=torch.int64, device=x.device) if stats else None
+    sx, sx2, sw = skip if skip is not None else (None, None, None)
+    sC1 = sx.shape[-1] if sx is not None else 0
+    sCin = sC1 + (sx2.shape[-1] if sx2 is not None else 0)
+    check(_L(x).diffsep_conv3x3_regweight(_ptr(x), _ptr(x2), C1, _ptr(sc), _ptr(sh), _ptr(wpacked), w_chunk, _ptr(bias), _ptr(bias_b),
+                                          _ptr(sx), _ptr(sx2), sC1, sCin, _ptr(sw), _ptr(res), _ptr(y), B, H, W, Cin, cout, out_scale,
+                                          _dt(x), _ptr(st), _stream_ptr()), _L(x))
+    return (y, st) if stats else y
+
+
 def conv2d_chunk(ksize, dtype):
     return lib().diffsep_conv2d_chunk(ksize, F32 if dtype == torch.float32 else BF16)  # (the same in both builds)
 

@@ -377,6 +377,15 @@ int32_t diffsep_conv3x3_streamed(const void* x, const void* x2, int32_t C1, cons
                                  int32_t Cin, int32_t Cout, float out_scale, int32_t dtype, int64_t* stats, const void* res,
                                  const void* ident_frag, const int64_t* gn_acc1, const int64_t* gn_acc2, const float* gn_gamma,
                                  const float* gn_beta, int32_t gn_groups, void* stream);
+/* The register-weight 3x3 kernel (csrc/conv3x3_rw.hip) as a unit, whatever the dispatch would choose, with its folded 1x1 skip:
+ * dense NHWC 16-bit tensors, 64 / cat -> 64 or 128 -> 128 couts, H >= 32, H % 8 == 0, W % 32 == 0.  w as in diffsep_conv2d_fused
+ * (row-major, or chunk-major with w_chunk); sx (+ sx2, split at sC1) [B][H][W][sCin] raw skip channels (64 / 128, 192 at
+ * 64 -> 64) against sw [Cout][sCin] row-major, added before out_scale; res (nullable, no skip beside it) likewise. */
+int32_t diffsep_conv3x3_regweight(const void* x, const void* x2, int32_t C1, const float* gn_scale, const float* gn_shift,
+                                  const void* w, int32_t w_chunk, const float* bias, const float* bias_b, const void* sx,
+                                  const void* sx2, int32_t sC1, int32_t sCin, const void* sw, const void* res, void* y, int32_t B,
+                                  int32_t H, int32_t W, int32_t Cin, int32_t Cout, float out_scale, int32_t dtype, int64_t* stats,
+                                  void* stream);
 /* The fused attention kernel (csrc/attn_fused.hip) as a unit: x, y dense [B][L][C] 16-bit, C = 128, L = 16 .. 256 by 16; wqk
  * (= Wk^T Wq), wv, wo in the order of diffsep_frag_index(row, 0, column, 1, C); bqk = Wk^T b_q, bv, bo [C] fp32.  GroupNorm of x
  * (no activation) from gn_acc [B][C][2] + gn_gamma / gn_beta / gn_groups, or from gn_scale / gn_shift [B][C] when gn_acc is NULL.

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import convcheck as CC
 import diffsep_oracle as O
 from diffsep_amd import _lib, ops, synth
 from diffsep_amd.engine import Engine, pack_state_dict, param_table
@@ -75,6 +76,15 @@ def test_f16_convolutions_match_torch(B, C1, C2, Cout, H, W, k, res):
                              gn_act=1 if gn else 0, res=r, out_scale=0.70710678 if res else 1.0, cout_pad=cp, stats=True)
     assert y.dtype == H16
     assert rel_rms(y.float()[..., :Cout], ref) < 1e-3
+    # the per-element bound of tests/convcheck.py; the packed-half staging model where the kernel that ran stages that way
+    name = ops.last_conv_kernel("f16")
+    packed = None
+    if gn and name.startswith("conv3x3_ws1_kernel"):
+        packed = "pk"
+    elif gn and name.startswith("conv3x3_rw_kernel"):
+        packed = "pk" if res else "pk_fold"
+    CC.ConvCheck((a, bt), (sc, sh, 1) if gn else None, w, H16, bias=bias, res=r, out_scale=0.70710678 if res else 1.0,
+                 packed=packed)(y, f"f16 {name} {C1}+{C2}->{Cout} {B}x{H}x{W} k{k}")
     s = ops.stats_to_float(st)
     assert torch.allclose(s[..., 0].cpu(), ref.double().sum((1, 2)), rtol=5e-4, atol=5e-4 * H * W)
 

@@ -1,6 +1,14 @@
 """GPU parity of every HIP kernel (through the C-ABI) against the CPU oracle / torch fp32 ops and
 the committed reference golden vectors.  Tolerances: fp32 kernels ~1e-5 relative RMS (summation
-order only); bf16 kernels ~1e-2 (storage rounding), stated per test."""
+order only); bf16 kernels ~1e-2 (storage rounding), stated per test.
+
+The 3x3 convolution kernels (from test_weight_stationary_conv3x3_64_to_64 down) also carry the two instruments of
+tests/convcheck.py.  (1) Exact integers (test_conv_exact_integers): torch.equal on the output and the int64 statistics for raw,
+affine and affine + SiLU launches of the weight-stationary, small-image, pyramid-head, first-layer and generic bf16 kernels; sees
+any wrong tap, halo, seam, slab, padding or statistic on one element, cannot see rounding or the SiLU at ordinary arguments.
+(2) The per-element bound (ConvCheck in the matches-torch tests, test_conv_activation_probe): every output element within its own
+derived rounding budget of a float64 reference; sees a local fault above about one storage ulp of the summed inputs, nothing
+smaller."""
 import math
 
 import numpy as np
@@ -8,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import convcheck as CC
 import diffsep_oracle as O
 from diffsep_amd import ops, synth
 
@@ -409,12 +418,15 @@ def test_weight_stationary_conv3x3_64_to_64(B, H, W, act):
     y, st = ops.conv2d_fused(x, ops.pack_conv_weight(w, dt).to(DEV), bias, 64, 3, gn=None if act is None else (sc, sh),
                              gn_act=act or 0, bias_b=bb, res=res, out_scale=0.70710678, stats=True)
     assert rel_rms(y.float(), ref) < 4e-3
+    CC.ConvCheck((x, None), None if act is None else (sc, sh, act), w, dt, bias=bias, bb=bb, res=res, out_scale=0.70710678)(
+        y, f"ws {B}x{H}x{W} act {act}")
     s = ops.stats_to_float(st)
     assert torch.allclose(s[..., 0].cpu(), ref.double().sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
     assert torch.allclose(s[..., 1].cpu(), (ref.double() ** 2).sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
     y2 = ops.conv2d_fused(x, ops.pack_conv_weight(w, dt).to(DEV), None, 64, 3)  # no bias / residual / statistics
     ref2 = F.conv2d(x.float().cpu().permute(0, 3, 1, 2), wq, None, padding=1).permute(0, 2, 3, 1)
     assert rel_rms(y2.float(), ref2) < 4e-3
+    CC.ConvCheck((x, None), None, w, dt)(y2, f"ws {B}x{H}x{W} plain")
 
 
 @pytest.mark.parametrize("dtype,tol", DT)
@@ -507,11 +519,15 @@ def test_small_image_conv3x3(C1, C2, Cout, H, W, act, lazy):
     hn = hn.to(dt).float()  # the kernel rounds the activated input to bf16 before the MFMA
     ref = F.conv2d(hn.permute(0, 3, 1, 2), w.to(dt).float(), bias.cpu(), padding=1).permute(0, 2, 3, 1)
     ref = (ref + bb.cpu()[:, None, None, :] + res.float().cpu()) * 0.70710678
+    # (from accumulators: the table the kernel builds in its prologue, bit for bit: tests/test_gn_table_gpu.py)
+    tab = None if act is None else (kw["gn"] if "gn" in kw else ops.groupnorm_from_acc(*kw["gn_acc"], H * W))
+    chk = CC.ConvCheck((xa, xb), None if tab is None else (tab[0], tab[1], act), w, dt, bias=bias, bb=bb, res=res, out_scale=0.70710678)
     for chunk in (0, 32):
         wp = ops.pack_conv_weight(w, dt, chunk=chunk).to(DEV)
         y, st = ops.conv2d_fused(xa, wp, bias, Cout, 3, x2=xb, bias_b=bb, res=res, out_scale=0.70710678, stats=True,
                                  w_chunk=chunk, **kw)
         assert rel_rms(y.float().cpu(), ref) < 4e-3
+        chk(y, f"small {tag}->{Cout} act {act} lazy {lazy} chunk {chunk}")
         s = ops.stats_to_float(st).cpu()
         assert torch.allclose(s[..., 0], ref.double().sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
         assert torch.allclose(s[..., 1], (ref.double() ** 2).sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
@@ -543,6 +559,7 @@ def test_small_image_pyramid_head_conv3x3(C, Cout, H, W, chunk):
     y[..., Cout:] = 0  # (the engine's arena is zeroed: padding channels are never written)
     ops.conv2d_fused(x, wp, bias, Cout, 3, gn=(sc, sh), gn_act=1, res=res, cout_pad=cp, out=y, w_chunk=chunk)
     assert rel_rms(y[..., :Cout].float().cpu(), ref) < 4e-3
+    CC.ConvCheck((x, None), (sc, sh, 1), w, dt, bias=bias, res=res)(y, f"small head {tag} chunk {chunk}")
     assert Cout == cp or float(y[..., Cout:].abs().max()) == 0.0
 
 
@@ -560,6 +577,7 @@ def test_first_layer_conv3x3_8_to_64(B, H, W, cin):
     y, st = ops.conv2d_fused(x, ops.pack_conv_weight(w, dt).to(DEV), bias, 64, 3, stats=True)
     ref = F.conv2d(x.float().cpu().permute(0, 3, 1, 2), w.to(dt).float(), bias.cpu(), padding=1).permute(0, 2, 3, 1)
     assert rel_rms(y.float().cpu(), ref) < 4e-3
+    CC.ConvCheck((x, None), None, w, dt, bias=bias)(y, f"first layer {B}x{H}x{W} cin {cin}")
     s = ops.stats_to_float(st).cpu()
     assert torch.allclose(s[..., 0], ref.double().sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
     assert torch.allclose(s[..., 1], (ref.double() ** 2).sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
@@ -598,10 +616,13 @@ def test_pyramid_head_conv3x3_to_8_channels(Cin, Cout, B, H, W, act, lazy, with_
     ref = F.conv2d(hn.permute(0, 3, 1, 2), w.to(dt).float(), bias.cpu(), padding=1).permute(0, 2, 3, 1)
     if with_res:
         ref = ref + res.float().cpu()[..., :Cout]
+    tab = kw["gn"] if "gn" in kw else ops.groupnorm_from_acc(*kw["gn_acc"], H * W)
+    chk = CC.ConvCheck((x, None), (tab[0], tab[1], act), w, dt, bias=bias, res=res if with_res else None)
     for chunk in (0, 32):
         y = ops.conv2d_fused(x, ops.pack_conv_weight(w, dt, chunk=chunk).to(DEV), bias, Cout, 3, res=res if with_res else None,
                              cout_pad=8, w_chunk=chunk, **kw)
         assert rel_rms(y.float().cpu()[..., :Cout], ref) < 4e-3
+        chk(y, f"pyramid head {tag} act {act} lazy {lazy} chunk {chunk}")
         if Cout < 8:
             assert not bool(y[..., Cout:].any())
 
@@ -626,6 +647,85 @@ def test_wide_tile_conv3x3_128_couts(Cin, Cout, H, W):
     y, st = ops.conv2d_fused(x, ops.pack_conv_weight(w, dt, chunk=32).to(DEV), bias, Cout, 3, gn=(sc, sh), gn_act=1,
                              bias_b=bb, res=res, out_scale=0.70710678, stats=True, w_chunk=32)
     assert rel_rms(y.float().cpu(), ref) < 4e-3
+    CC.ConvCheck((x, None), (sc, sh, 1), w, dt, bias=bias, bb=bb, res=res, out_scale=0.70710678)(y, f"wide tile {Cin}->{Cout} {H}x{W}")
     s = ops.stats_to_float(st).cpu()
     assert torch.allclose(s[..., 0], ref.double().sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
     assert torch.allclose(s[..., 1], (ref.double() ** 2).sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
+
+
+# ---- exact integers (tests/convcheck.py): bit for bit on the output and on the statistics
+# (family, kernel, C1, C2, Cout, (B, H, W) | "multi", modes, residual, statistics, real input channels)
+ALL3 = ("raw", "affine", "silu")
+CONV_EXACT = [
+    ("ws", "conv3x3_ws1_kernel<", 64, 0, 64, (2, 16, 64), ALL3, True, True, None),
+    ("ws", "conv3x3_ws1_kernel<", 64, 0, 64, (5, 8, 32), ALL3, True, True, None),
+    ("ws", "conv3x3_ws1_kernel<", 64, 0, 64, "multi", ALL3, True, True, None),
+    ("small", "conv3x3_small_kernel<", 128, 0, 128, (3, 16, 16), ALL3, True, True, None),
+    ("small", "conv3x3_small_kernel<", 64, 192, 48, (3, 16, 12), ALL3, True, True, None),
+    ("small", "conv3x3_small_kernel<", 256, 256, 256, (3, 4, 1), ALL3, True, True, None),
+    ("small head", "conv3x3_small_kernel<", 128, 0, 6, (3, 8, 8), ("silu",), True, False, None),
+    ("thin out", "conv3x3_thin_out_kernel", 128, 0, 6, (3, 8, 64), ("affine", "silu"), True, False, None),
+    ("thin in", "conv3x3_thin_in_kernel", 8, 0, 64, (3, 8, 96), ("raw",), False, True, 6),
+    ("generic", "conv_mfma_kernel", 192, 0, 128, (1, 9, 33), ALL3, True, True, None),
+]
+
+
+@pytest.mark.parametrize("family,kernel,C1,C2,CO,shape,modes,with_res,stats,cin_real", CONV_EXACT,
+                         ids=[f"{c[0]}-{c[2]}+{c[3]}-{c[4]}-{c[5]}".replace(" ", "") for c in CONV_EXACT])
+def test_conv_exact_integers(family, kernel, C1, C2, CO, shape, modes, with_res, stats, cin_real):
+    """integer data on which every product, partial sum, output and statistic is exact: torch.equal, both weight layouts, the
+    padding channels of the <= 8-cout heads stay zero.  "multi": the smallest batch at which one block of an image gets two 8 x 32
+    tiles and another one."""
+    dt = torch.bfloat16
+    if shape == "multi":
+        H, W = 16, 96
+        B = CC.multi_tile_batch(H, W, 8, 32, CC.device_cus())
+        print(f"\n[{family} exact] multi-tile batch B = {B} at {H} x {W} on {CC.device_cus()} compute units")
+        if B * H * W * CO > 2e7:
+            pytest.skip(f"multi-tile batch B = {B}: more than 2e7 output elements")
+    else:
+        B, H, W = shape
+    cp = (CO + 7) // 8 * 8
+    for mode in modes:
+        thin = family.startswith("thin")  # (neither a scale nor a per-sample bias in these two kernels)
+        c = CC.exact_case(f"cx{family}{C1}{C2}{CO}{B}{H}{W}{mode}", B, H, W, C1, C2, CO, mode, res=with_res, cin_real=cin_real,
+                          out_scale=1.0 if thin else 0.5, with_bb=not thin)
+        a, bt = c.a.to(DEV, dt), (c.b.to(DEV, dt) if C2 else None)
+        gn = None if mode == "raw" else (c.sc.to(DEV), c.sh.to(DEV))
+        res = F.pad(c.res, (0, cp - CO)).to(DEV, dt) if with_res else None
+        for chunk in (0, 32) if (C1 + C2) % 32 == 0 and C1 % 32 == 0 else (0,):
+            wp = ops.pack_conv_weight(c.w, dt, chunk=chunk).to(DEV)
+            out = ops.conv2d_fused(a, wp, c.bias.to(DEV), CO, 3, x2=bt, gn=gn, gn_act=1 if mode == "silu" else 0,
+                                   bias_b=None if thin else c.bb.to(DEV), res=res, out_scale=c.out_scale, cout_pad=cp, stats=stats, w_chunk=chunk)
+            y, st = out if stats else (out, None)
+            assert ops.last_conv_kernel().startswith(kernel), ops.last_conv_kernel()
+            CC.check_exact(c, y, st, dt, f"{family} {C1}+{C2}->{CO} {B}x{H}x{W} {mode} chunk {chunk}")
+
+
+@pytest.mark.parametrize("family,kernel,C,H,W,kind", [("ws", "conv3x3_ws1_kernel<", 64, 16, 64, "bf16"), ("ws", "conv3x3_ws1_kernel<", 64, 16, 64, "f16"),
+                                                      ("small", "conv3x3_small_kernel<", 128, 8, 8, "bf16"),
+                                                      ("generic", "conv_mfma_kernel", 192, 9, 33, "bf16")])
+def test_conv_activation_probe(family, kernel, C, H, W, kind):
+    """one-hot weights: the kernel outputs its activated input (gn8 staging; packed half in the weight-stationary kernel of the
+    half-precision build); arguments over [-12, 12] and near zero against the input-error model of the bound"""
+    dt = torch.float16 if kind == "f16" else torch.bfloat16
+    x, sc, sh, w = CC.probe_inputs(f"cp{family}", 2, H, W, C)
+    a = x.to(DEV, dt)
+    y = ops.conv2d_fused(a, ops.pack_conv_weight(w, dt).to(DEV), None, C, 3, gn=(sc.to(DEV), sh.to(DEV)), gn_act=1)
+    assert ops.last_conv_kernel(kind).startswith(kernel), ops.last_conv_kernel(kind)
+    CC.ConvCheck((a, None), (sc, sh, 1), w, dt, packed="pk" if (kind == "f16" and family == "ws") else None, exact_out=True)(
+        y, f"{family} probe {kind}")
+
+
+def test_thin_out_activation_probe():
+    """the pyramid-head kernel (conv3x3_thin_out_kernel, its own gn8 staging): cout c reads cin 4 + c at the centre tap (four
+    channels of arguments near zero, four over [-12, 12]); no output scale, so the output is the staged value itself"""
+    dt = torch.bfloat16
+    B, H, W, C = 2, 8, 64, 64
+    x, sc, sh, _ = CC.probe_inputs("cpthin", B, H, W, C)
+    w = torch.zeros(8, C, 3, 3)
+    w[torch.arange(8), 4 + torch.arange(8), 1, 1] = 1.0
+    a = x.to(DEV, dt)
+    y = ops.conv2d_fused(a, ops.pack_conv_weight(w, dt).to(DEV), None, 8, 3, gn=(sc.to(DEV), sh.to(DEV)), gn_act=1, cout_pad=8)
+    assert ops.last_conv_kernel().startswith("conv3x3_thin_out_kernel"), ops.last_conv_kernel()
+    CC.ConvCheck((a, None), (sc, sh, 1), w, dt, exact_out=True)(y, "thin out probe")

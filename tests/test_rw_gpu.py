@@ -1,7 +1,15 @@
 """GPU parity of the register-weight 3x3 kernel (conv3x3_rw.hip: 64 / cat(64, 64) -> 64 couts at >= 32-row images, bf16)
 through the C-ABI against torch fp32 on the CPU (same bf16-rounded operands) and, for whole residual blocks with the
 folded 1x1 skip, against the CPU oracle.  Tolerance: 4e-3 relative RMS per convolution (bf16 storage of the activated
-input and of the output), 1.5e-2 per residual block."""
+input and of the output), 1.5e-2 per residual block.
+
+Next to the relative-RMS gates stand the two instruments of tests/convcheck.py.  (1) Exact integers (test_rw_exact_integers):
+torch.equal on the output and the int64 statistics, raw launches in both weight layouts and GroupNorm + SiLU launches with a
+residual; sees any wrong tap, halo, seam, tile share or statistic on a single element, cannot see rounding or the SiLU at ordinary
+arguments; activated launches WITHOUT a residual or skip fold -1 / ln 2 into the staged value and cannot be bit exact; the folded
+1x1 skip on 64 / 128 / 192 raw channels runs through the kernel's unit entry (test_rw_exact_integers_folded_skip).  (2) The per-element bound (ConvCheck in both
+matches-torch tests, test_rw_activation_probe): every output element within its own derived rounding budget of a float64
+reference; sees a local fault of more than about one storage ulp of the summed inputs, cannot see less than that."""
 import math
 
 import numpy as np
@@ -9,6 +17,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import convcheck as CC
 import diffsep_oracle as O
 from diffsep_amd import ops, synth
 
@@ -66,11 +75,13 @@ def test_rw_conv3x3_matches_torch(B, H, W, C1, C2, act):
     wq = w.to(DT).float()
     ref = F.conv2d(xf.cpu().permute(0, 3, 1, 2), wq, bias.cpu(), padding=1).permute(0, 2, 3, 1)
     ref = (ref + bb.cpu()[:, None, None, :] + (res.float().cpu() if res is not None else 0.0)) * 0.70710678
+    chk = CC.ConvCheck((a, bt), None if act is None else (sc, sh, 1), w, DT, bias=bias, bb=bb, res=res, out_scale=0.70710678)
     for chunk in (0, ops.conv2d_chunk(3, DT)):
         wp = ops.pack_conv_weight(w, DT, chunk=chunk).to(DEV) if chunk else ops.pack_conv_weight(w, DT).to(DEV)
         y, st = ops.conv2d_fused(a, wp, bias, 64, 3, x2=bt, gn=None if act is None else (sc, sh), gn_act=act or 0,
                                  bias_b=bb, res=res, out_scale=0.70710678, stats=True, w_chunk=chunk)
         assert rel_rms(y.float(), ref) < 4e-3
+        chk(y, f"rw {C1}+{C2}->64 {B}x{H}x{W} act {act} chunk {chunk}")
         s = ops.stats_to_float(st)
         assert torch.allclose(s[..., 0].cpu(), ref.double().sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
         assert torch.allclose(s[..., 1].cpu(), (ref.double() ** 2).sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
@@ -79,6 +90,7 @@ def test_rw_conv3x3_matches_torch(B, H, W, C1, C2, act):
     xr = torch.cat([a.float(), bt.float()], -1) if C2 else a.float()
     ref2 = F.conv2d(xr.cpu().permute(0, 3, 1, 2), wq, None, padding=1).permute(0, 2, 3, 1)
     assert rel_rms(y2.float(), ref2) < 4e-3
+    CC.ConvCheck((a, bt), None, w, DT)(y2, f"rw {C1}+{C2}->64 {B}x{H}x{W} plain")
 
 
 # ---- 128 -> 128 couts: 4 cout groups on one 4 x 32 pixel group (tiles of 4 rows), skip / residual fragments in LDS
@@ -105,11 +117,13 @@ def test_rw128_conv3x3_matches_torch(B, H, W, C1, C2, extra):
         ref = ref + res.float().cpu()
         kw = dict(res=res)
     ref = ref * 0.70710678
+    chk = CC.ConvCheck((a, bt), (sc, sh, 1), w, DT, bias=bias, bb=bb, res=kw.get("res"), out_scale=0.70710678)
     for chunk in (0, ops.conv2d_chunk(3, DT)):
         wp = ops.pack_conv_weight(w, DT, chunk=chunk).to(DEV) if chunk else ops.pack_conv_weight(w, DT).to(DEV)
         y, st = ops.conv2d_fused(a, wp, bias, CO, 3, x2=bt, gn=(sc, sh), gn_act=1, bias_b=bb, out_scale=0.70710678, stats=True,
                                  w_chunk=chunk, **kw)
         assert rel_rms(y.float(), ref) < 4e-3
+        chk(y, f"rw128 {C1}+{C2} {B}x{H}x{W} {extra} chunk {chunk}")
         s = ops.stats_to_float(st)
         assert torch.allclose(s[..., 0].cpu(), ref.double().sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
         assert torch.allclose(s[..., 1].cpu(), (ref.double() ** 2).sum((1, 2)), rtol=2e-3, atol=2e-3 * H * W)
@@ -117,6 +131,82 @@ def test_rw128_conv3x3_matches_torch(B, H, W, C1, C2, extra):
         y2 = ops.conv2d_fused(a, ops.pack_conv_weight(w, DT).to(DEV), None, CO, 3, x2=bt)
         ref2 = F.conv2d(xf.cpu().permute(0, 3, 1, 2), wq, None, padding=1).permute(0, 2, 3, 1)
         assert rel_rms(y2.float(), ref2) < 4e-3
+        CC.ConvCheck((a, bt), None, w, DT)(y2, f"rw128 {C1}+{C2} {B}x{H}x{W} raw")
+
+
+# ---- exact integers (tests/convcheck.py): bit for bit on the output and on the statistics
+# (C1, C2, Cout, tile rows, multi-tile image); tile rows = (4 / NCG) * RPW of the instantiation ds_launch_conv_rw picks (RPW = 4
+# always: 8 rows at 64 couts, 4 rows at 128), asserted below from the name of the kernel that ran
+RW_EXACT = [(64, 0, 64, 8, (64, 96)), (64, 64, 64, 8, (64, 96)), (128, 0, 128, 4, (32, 32))]
+
+
+@pytest.mark.parametrize("shape", [(2, 32, 32), (2, 40, 64), (3, 64, 96), "multi"], ids=str)
+@pytest.mark.parametrize("C1,C2,CO,th,mimg", RW_EXACT)
+def test_rw_exact_integers(C1, C2, CO, th, mimg, shape):
+    """raw launches (both weight layouts) and, where the kernel takes a residual, GroupNorm + SiLU + residual launches on integer
+    data: torch.equal on y and on both accumulators.  "multi": the smallest batch at which one block of an image gets two tiles
+    and another one (from the tile size and the device's compute-unit count)."""
+    if shape == "multi":
+        H, W = mimg
+        B = CC.multi_tile_batch(H, W, th, 32, CC.device_cus())
+        print(f"\n[rw exact {C1}+{C2}->{CO}] multi-tile batch B = {B} at {H} x {W} on {CC.device_cus()} compute units")
+        if B * H * W * CO > 2e7:
+            pytest.skip(f"multi-tile batch B = {B}: more than 2e7 output elements")
+    else:
+        B, H, W = shape
+    modes = [("raw", False)] + ([("silu", True)] if (C1 + C2 == 64 or CO == 128) else [])
+    for mode, with_res in modes:
+        c = CC.exact_case(f"rwx{C1}{C2}{CO}{B}{H}{W}{mode}", B, H, W, C1, C2, CO, mode, res=with_res, big=B > 8)
+        a, bt = c.a.to(DEV, DT), (c.b.to(DEV, DT) if C2 else None)
+        gn = None if mode == "raw" else (c.sc.to(DEV), c.sh.to(DEV))
+        res = c.res.to(DEV, DT) if with_res else None
+        for chunk in (0, ops.conv2d_chunk(3, DT)):
+            wp = ops.pack_conv_weight(c.w, DT, chunk=chunk).to(DEV)
+            y, st = ops.conv2d_fused(a, wp, c.bias.to(DEV), CO, 3, x2=bt, gn=gn, gn_act=1 if gn else 0, bias_b=c.bb.to(DEV), res=res,
+                                     out_scale=0.5, stats=True, w_chunk=chunk)
+            name = ops.last_conv_kernel()
+            assert name.startswith("conv3x3_rw_kernel<"), name
+            if shape == "multi":  # the tile height the batch was worked out from is the one that ran: <NCH,RPW,NSK,MODE,NCG>,
+                t = name[name.index("<") + 1:-1].split(",")  # rows = (4 / NCG) * RPW (RwGeom in conv3x3_rw.hip)
+                assert (4 // int(t[4])) * int(t[1]) == th, name
+            CC.check_exact(c, y, st, DT, f"rw {C1}+{C2}->{CO} {B}x{H}x{W} {mode} chunk {chunk}")
+
+
+# the folded 1x1 skip (raw channels through the centre tap; NSK = 1, 2, 3 skip chunks with real weights) through the kernel's
+# unit entry: (Cin, Cout, skip channels (first, second))
+RW_SKIP = [(64, 64, (64, 0)), (64, 64, (64, 64)), (64, 64, (64, 128)), (128, 128, (128, 0)), (128, 128, (64, 64))]
+
+
+@pytest.mark.parametrize("B,H,W", [(2, 32, 32), (2, 40, 64)])
+@pytest.mark.parametrize("C,CO,skip", RW_SKIP)
+def test_rw_exact_integers_folded_skip(C, CO, skip, B, H, W):
+    """GroupNorm + SiLU launch with a folded skip on 64 / 128 / 192 raw channels (one tensor or the concat of two), both weight
+    layouts: torch.equal on y and on both accumulators; the skip keeps the staged value silu(v) itself"""
+    c = CC.exact_case(f"rwk{C}{CO}{skip}{B}{H}{W}", B, H, W, C, 0, CO, "silu", skip=skip)
+    a = c.a.to(DEV, DT)
+    sa, sb, sw = c.skip
+    sk = (sa.to(DEV, DT), sb.to(DEV, DT) if sb is not None else None, sw.reshape(CO, -1).to(DEV, DT).contiguous())
+    for chunk in (0, ops.conv2d_chunk(3, DT)):
+        wp = ops.pack_conv_weight(c.w, DT, chunk=chunk).to(DEV)
+        y, st = ops.conv3x3_regweight(a, wp, CO, gn=(c.sc.to(DEV), c.sh.to(DEV)), bias=c.bias.to(DEV), bias_b=c.bb.to(DEV), skip=sk,
+                                      out_scale=0.5, stats=True, w_chunk=chunk)
+        name = ops.last_conv_kernel()
+        assert name.startswith("conv3x3_rw_kernel<") and name.split(",")[2] == str(sum(skip) // 64), name
+        CC.check_exact(c, y, st, DT, f"{name} skip {skip} {B}x{H}x{W} chunk {chunk}")
+
+
+@pytest.mark.parametrize("C,CO,with_res", [(64, 64, True), (64, 64, False), (128, 128, True)])
+def test_rw_activation_probe(C, CO, with_res):
+    """one-hot weights: the kernel outputs its activated input; arguments over [-12, 12] and near zero against the input-error
+    model of the bound (u_in, d_abs).  With a (zero) residual the staged value is silu(v) itself and the output is exactly it;
+    without, the folded factor adds the output rounding."""
+    B, H, W = 2, 32, 32
+    x, sc, sh, w = CC.probe_inputs(f"rwp{C}", B, H, W, C)
+    a = x.to(DEV, DT)
+    res = torch.zeros(B, H, W, CO).to(DEV, DT) if with_res else None
+    y = ops.conv2d_fused(a, ops.pack_conv_weight(w, DT).to(DEV), None, CO, 3, gn=(sc.to(DEV), sh.to(DEV)), gn_act=1, res=res)
+    assert ops.last_conv_kernel().startswith("conv3x3_rw_kernel<")
+    CC.ConvCheck((a, None), (sc, sh, 1), w, DT, exact_out=with_res)(y, f"rw probe {C} residual {with_res}")
 
 
 def test_rw_conv3x3_zero_padding_is_exact():

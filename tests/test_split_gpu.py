@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import convcheck as CC
 import diffsep_oracle as O
 from diffsep_amd import _lib, ops, synth
 from test_engine_gpu import DEV, SDE, _g9_inputs, diff_rms, engine, rel_rms, rms, rnd, si_sdr
@@ -43,6 +44,10 @@ def test_split_conv_launches_vs_torch_fp32(C1, C2, Cout, H, W, k):
         y_exact, _ = ops.conv2d_fused(xa, wp, bias, Cout, k, **kw)
         assert rel_rms(y_exact, ref) < 2e-6
         assert rel_rms(y, ref) < 2e-5, "bf16x3 products: 2^-17 per operand"
+        # the per-element bounds of tests/convcheck.py: 2^-16 per product in split mode, accumulation order alone in plain fp32
+        kwc = dict(bias=bias, bb=bb, res=res, out_scale=0.70710678)
+        CC.ConvCheck((xa, xb), (sc, sh, 1), w, torch.float32, split=True, **kwc)(y, f"split generic {tag} chunk {chunk}")
+        CC.ConvCheck((xa, xb), (sc, sh, 1), w, torch.float32, **kwc)(y_exact, f"fp32 generic {tag} chunk {chunk}")
         s = ops.stats_to_float(st).cpu()
         assert torch.allclose(s[..., 0], ref.double().sum((1, 2)), rtol=1e-4, atol=1e-4 * H * W)
 

@@ -2,7 +2,16 @@
 to 256 raw channels, 16-bit storage) through the C-ABI unit entry diffsep_conv3x3_streamed against torch fp32 on the CPU (same
 16-bit-rounded operands), and of the engine's dispatch to it (whole residual blocks against the CPU oracle).
 Tolerance: 4e-3 relative RMS per convolution (16-bit storage of the activated input and of the output; 6e-3 with bfloat16 weights
-and a 256-channel skip), 1.5e-2 per residual block.  Reference layers: layers.py:141-156, layerspp.py:291-323, ncsnpp.py:409-417."""
+and a 256-channel skip), 1.5e-2 per residual block.  Reference layers: layers.py:141-156, layerspp.py:291-323, ncsnpp.py:409-417.
+
+Next to those gates stand the two instruments of tests/convcheck.py.  (1) Exact integers (test_sw_exact_integers,
+test_sw_exact_integers_four_row_tiles, test_sws_exact_integers): torch.equal on the output and the int64 statistics for raw
+launches and for GroupNorm + SiLU launches with a residual or a folded skip; sees any wrong tap, halo, seam, cout block, tile
+share or statistic on one element, cannot see rounding or the SiLU at ordinary arguments.  Activated launches WITHOUT skip or
+residual (the concat inputs among them) stage silu(v) / -ln 2 and multiply back in the epilogue: not bit exact by construction.
+(2) The per-element bound (ConvCheck in both matches-torch tests, the activation probes): every output element within its own
+derived rounding budget of a float64 reference, in the half-precision build with the packed-half staging model; sees a local
+fault above about one storage ulp of the summed inputs, nothing smaller."""
 import math
 
 import numpy as np
@@ -10,6 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import convcheck as CC
 from diffsep_amd import _lib, ops, synth
 
 pytestmark = pytest.mark.gpu
@@ -112,6 +122,11 @@ def test_sw_conv3x3_matches_torch(dt, B, H, W, C1, C2, raw, skip, CO):
                                  bias_b=bb, skip=sk, out_scale=0.70710678, stats=True, res=res, ident_frag=ident)
     tol = 4e-3 if dt == torch.float16 else 8e-3
     assert rel_rms(y.float(), ref) < tol
+    packed = None if (raw or dt != torch.float16) else ("pk" if skip is not None else "pk_fold")
+    skw = None if sk is None else (sk[0], sk[1], sw)
+    what = f"sw {dt} {C1}+{C2}->{CO} {B}x{H}x{W} skip {skip}"
+    CC.ConvCheck((a, bt), None if raw else (sc, sh, 1), w, dt, bias=bias, bb=bb, res=res, skip=skw, out_scale=0.70710678,
+                 packed=packed)(y, what)
     s = ops.stats_to_float(st)
     assert torch.allclose(s[..., 0].cpu(), ref.double().sum((1, 2)), rtol=3e-3, atol=3e-3 * H * W)
     assert torch.allclose(s[..., 1].cpu(), (ref.double() ** 2).sum((1, 2)), rtol=4e-3, atol=4e-3 * H * W)
@@ -120,6 +135,7 @@ def test_sw_conv3x3_matches_torch(dt, B, H, W, C1, C2, raw, skip, CO):
                               ident_frag=ident)
     ref2 = (ref / 0.70710678) - bias.cpu() - bb.cpu()[:, None, None, :]
     assert rel_rms(y2.float(), ref2) < tol
+    CC.ConvCheck((a, bt), None if raw else (sc, sh, 1), w, dt, res=res, skip=skw, packed=packed)(y2, what + " plain")
     # the same launch twice: bit-identical (fixed summation order, integer statistics)
     y3, st3 = ops.conv3x3_streamed(a, ops.pack_frag_weight(w, dt).to(DEV), CO, x2=bt, gn=None if raw else (sc, sh), bias=bias,
                                    bias_b=bb, skip=sk, out_scale=0.70710678, stats=True, res=res, ident_frag=ident)
@@ -136,6 +152,85 @@ def test_sw_four_row_tiles_on_every_shape():
                 test_sw_conv3x3_matches_torch(torch.float16, B, H, W, *case)
     finally:
         _lib.check(L.diffsep_set_option(b"sw_rows4", 0), L)
+
+
+# ---- exact integers (tests/convcheck.py): bit for bit on the output and on the statistics
+# raw; raw concat cat(64, 64) (the concat staging path: an ACTIVATED concat such as cat(128, 64) has no skip beside it, so it folds
+# -1 / ln 2 into the staged value and cannot be bit exact; a raw launch takes one or two 64-channel chunks); residual; skip on
+# cat(128, 64); the two-cout-block case and the 256-channel case of CASES in one: 256 -> 256 with a 512-channel skip
+SW_EXACT = [(64, 0, True, None, 128), (128, 0, True, None, 128), (64, 64, True, None, 128), (128, 0, False, "res", 128),
+            (128, 0, False, (128, 64), 128), (256, 0, False, (256, 256), 256)]
+# one case each from SPLIT_CASES: raw, concat (raw cat(128, 128) -> 256: also two cout blocks), "res" (64 and 128 couts), skip
+SWS_EXACT = [(128, 0, True, None, 128), (128, 128, True, None, 256), (64, 0, False, "res", 64), (128, 0, False, (128, 64), 128),
+             (128, 0, False, "res", 128)]
+
+
+def _streamed_exact(dt, B, H, W, C1, C2, raw, skip, CO, kernel):
+    split = dt == torch.float32
+    pack = ops.pack_frag_weight_split if split else (lambda t: ops.pack_frag_weight(t, dt))
+    c = CC.exact_case(f"swx{C1}{C2}{CO}{B}{H}{W}{skip}", B, H, W, C1, C2, CO, "raw" if raw else "silu", res=skip == "res",
+                      skip=skip if isinstance(skip, tuple) else None)
+    a, bt = c.a.to(DEV, dt), (c.b.to(DEV, dt) if C2 else None)
+    sk = None if c.skip is None else (c.skip[0].to(DEV, dt), c.skip[1].to(DEV, dt) if c.skip[1] is not None else None, pack(c.skip[2]).to(DEV))
+    res = c.res.to(DEV, dt) if c.res is not None else None
+    ident = pack(torch.eye(CO).reshape(CO, CO, 1, 1)).to(DEV) if res is not None else None
+    y, st = ops.conv3x3_streamed(a, pack(c.w).to(DEV), CO, x2=bt, gn=None if raw else (c.sc.to(DEV), c.sh.to(DEV)), bias=c.bias.to(DEV),
+                                 bias_b=c.bb.to(DEV), skip=sk, out_scale=0.5, stats=True, res=res, ident_frag=ident)
+    name = ops.last_conv_kernel("f16" if dt == torch.float16 else "bf16")
+    assert name.startswith(kernel), name
+    CC.check_exact(c, y, st, dt, f"{name} {dt} {C1}+{C2}->{CO} {B}x{H}x{W} skip {skip}")
+    return name
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("B,H,W", [(2, 8, 32), (3, 12, 64), (5, 24, 32), (3, 64, 96)])
+@pytest.mark.parametrize("C1,C2,raw,skip,CO", SW_EXACT)
+def test_sw_exact_integers(dt, B, H, W, C1, C2, raw, skip, CO):
+    _streamed_exact(dt, B, H, W, C1, C2, raw, skip, CO, "conv3x3_sw_kernel<")
+
+
+def test_sw_exact_integers_four_row_tiles():
+    L = _lib.lib("f16")
+    _lib.check(L.diffsep_set_option(b"sw_rows4", 1), L)
+    try:
+        for case in SW_EXACT[1:5]:
+            name = _streamed_exact(torch.float16, 3, 64, 96, *case, "conv3x3_sw_kernel<")
+            assert name.split(",")[3] == "4", name  # (the RPW argument: four rows)
+    finally:
+        _lib.check(L.diffsep_set_option(b"sw_rows4", 0), L)
+
+
+@pytest.mark.parametrize("B,H,W", [(2, 8, 32), (3, 12, 64), (5, 24, 32), (3, 64, 96)])
+@pytest.mark.parametrize("C1,C2,raw,skip,CO", SWS_EXACT)
+def test_sws_exact_integers(B, H, W, C1, C2, raw, skip, CO):
+    """fp32 tensors in split mode: the integers are exact in the hi plane, so the lo plane must contribute exactly 0.  The sw
+    shapes; at (3, 12, 64) the split kernel, which has 8-row tiles only (ds_conv_sws_supported: a.H % 8 == 0), must refuse."""
+    if H % 8:
+        with pytest.raises(RuntimeError):
+            _streamed_exact(torch.float32, B, H, W, C1, C2, raw, skip, CO, "conv3x3_sws_kernel<")
+        return
+    _streamed_exact(torch.float32, B, H, W, C1, C2, raw, skip, CO, "conv3x3_sws_kernel<")
+
+
+@pytest.mark.parametrize("dt,with_res", [(torch.bfloat16, True), (torch.bfloat16, False), (torch.float16, True), (torch.float16, False),
+                                         (torch.float32, True), (torch.float32, False)])
+def test_streamed_activation_probe(dt, with_res):
+    """one-hot weights: the kernel outputs its activated input; arguments over [-12, 12] and near zero against the input-error
+    model of the bound (fp32 staging in the bfloat16 and split kernels, packed half in the half-precision build; with a zero
+    residual the staged value is silu(v) itself, without it the folded factor)"""
+    B, H, W, C = 2, 8, 32, 128
+    split = dt == torch.float32
+    pack = ops.pack_frag_weight_split if split else (lambda t: ops.pack_frag_weight(t, dt))
+    x, sc, sh, w = CC.probe_inputs(f"swp{with_res}", B, H, W, C)
+    a = x.to(DEV, dt)
+    res = torch.zeros(B, H, W, C).to(DEV, dt) if with_res else None
+    ident = pack(torch.eye(C).reshape(C, C, 1, 1)).to(DEV) if with_res else None
+    y = ops.conv3x3_streamed(a, pack(w).to(DEV), C, gn=(sc.to(DEV), sh.to(DEV)), res=res, ident_frag=ident)
+    name = ops.last_conv_kernel("f16" if dt == torch.float16 else "bf16")
+    assert name.startswith("conv3x3_sws_kernel<" if split else "conv3x3_sw_kernel<"), name
+    packed = None if dt != torch.float16 else ("pk" if with_res else "pk_fold")
+    CC.ConvCheck((a, None), (sc, sh, 1), w, dt, split=split, packed=packed, exact_out=with_res and not split)(
+        y, f"streamed probe {dt} residual {with_res}")
 
 
 def test_sw_rejects_what_it_does_not_instantiate():
@@ -200,6 +295,9 @@ def test_sws_split_conv3x3_matches_torch_fp32(B, H, W, C1, C2, raw, skip, CO):
                                  stats=True, res=res, ident_frag=ident)
     r = rel_rms(y, ref)
     assert r < 2e-5, r
+    CC.ConvCheck((a, bt), None if raw else (sc, sh, 1), w, torch.float32, bias=bias, bb=bb, res=res,
+                 skip=None if sk is None else (sk[0], sk[1], sw), out_scale=0.70710678, split=True)(
+        y, f"sws {C1}+{C2}->{CO} {B}x{H}x{W} skip {skip}")
     s = ops.stats_to_float(st)
     assert torch.allclose(s[..., 0].cpu(), ref.sum((1, 2)), rtol=1e-4, atol=1e-4 * H * W)
     assert torch.allclose(s[..., 1].cpu(), (ref ** 2).sum((1, 2)), rtol=1e-4, atol=1e-4 * H * W)
