@@ -336,8 +336,19 @@ int ds_launch_gn_finalize_acc(const long long* a1, int C1, const long long* a2, 
                               float eps, const float* gamma, const float* beta, float* scale, float* shift,
                               hipStream_t st);
 // mode: 0 none, 1 up, 2 down. scale/shift null => identity & no activation (pure FIR on x -> xr only).
+// Where such a launch goes: ds_gn_route (norm.hip; DESIGN.md section 7c is its table) orders the kernels and holds their size
+// thresholds; ds_gn_route_runs says only what a kernel can run (shape, type, build).  rs: output rows per strip of the two
+// FIR-down kernels (DOWN_STRIP 4 | 8, DOWN_TILED 4 | 8), else 0.  cus: compute units to weigh block counts against (<= 0: the
+// current device's, asked for only where a threshold needs it).
+enum class GnRoute { APPLY = 1, BLOCK2X2, DOWN_STRIP, DOWN_TILED, UP_TILED };
+struct GnPlan { GnRoute route; int rs; };
+bool ds_gn_route_runs(GnRoute r, int mode, bool affine, int dtype, int H, int W, int C, int ldx, int ldy, int ldxr, bool has_xr);
+GnPlan ds_gn_route(int mode, bool affine, int dtype, int B, int H, int W, int C, int ldx, int ldy, int ldxr, bool has_xr, int cus);
+const char* ds_gn_kernel_name(const GnPlan& p, int mode, bool affine, int dtype);  // what the launch leaves in ds_last_conv_kernel()
 int ds_launch_gn_apply(const void* x, int ldx, const float* scale, const float* shift, int C, void* y, int ldy,
-                       void* xr, int ldxr, int B, int H, int W, int act, int mode, int dtype, hipStream_t st);
+                       void* xr, int ldxr, int B, int H, int W, int act, int mode, int dtype, hipStream_t st);  // validate, route, launch
+int ds_launch_gn_apply(const GnPlan& p, const void* x, int ldx, const float* scale, const float* shift, int C, void* y, int ldy,
+                       void* xr, int ldxr, int B, int H, int W, int act, int mode, int dtype, hipStream_t st);  // ... on the caller's plan
 int ds_launch_concat(const void* a, int lda, int Ca, const void* b, int ldb, int Cb, void* y, int ldy, long npix,
                      int dtype, hipStream_t st);
 int ds_launch_softmax(const void* x, void* y, long rows, int L, int ld, int dtype, hipStream_t st);

@@ -730,9 +730,83 @@ __global__ __launch_bounds__(256, UP_MINW) void gn_resample_up_tiled_kernel(cons
 template <typename T>
 static constexpr int gn_resample_up_tiled_lds() { return 6 * 10 * 8 * (32 + 8 * (int)sizeof(T)); }
 
+// ---- where a GroupNorm-apply / FIR launch goes: ds_gn_route is the ONE place that orders the kernels above and holds their size
+// thresholds (host arithmetic only: it touches no device unless it has to ask for the compute-unit count); ds_gn_route_runs says
+// what a kernel can run at all (its shape preconditions), which is all a forced route of the unit entry point has to meet.
+bool ds_gn_route_runs(GnRoute r, int mode, bool aff, int dtype, int H, int W, int C, int ldx, int ldy, int ldxr, bool has_xr) {
+  const bool h16 = dtype != DS_F32;
+  switch (r) {
+    case GnRoute::APPLY: return true;
+    case GnRoute::BLOCK2X2: return aff && (mode == 1 || (mode == 2 && H % 4 == 0 && W % 4 == 0));
+    case GnRoute::DOWN_STRIP: return h16 && aff && mode == 2 && H % 2 == 0 && W % 4 == 0;
+    case GnRoute::DOWN_TILED:
+#if defined(DS_HALF_F16) && !defined(DS_NO_FIR_TILED)
+      return h16 && aff && mode == 2 && H % 2 == 0 && W % 32 == 0 && C % 64 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && (!has_xr || ldxr % 8 == 0);
+#else
+      return false;  // (the row-tile kernel exists in the half-precision build only)
+#endif
+    case GnRoute::UP_TILED: return aff && mode == 1 && C % 64 == 0;
+  }
+  return false;
+}
+
+#ifndef FD_RS_MAX
+#define FD_RS_MAX 8  // (16: 99.9 -> 97.0 us at 256^2 C = 64 and 68.7 -> 62.3 at 128^2 C = 128 incl. the statistics passes; tools/fir_ab.sh)
+#endif
+
+GnPlan ds_gn_route(int mode, bool aff, int dtype, int B, int H, int W, int C, int ldx, int ldy, int ldxr, bool has_xr, int cus) {
+  const long tot2 = (mode == 1 ? (long)B * H * W : (long)B * (H / 4) * (W / 4)) * (C >> 3);
+  auto runs = [&](GnRoute r) { return ds_gn_route_runs(r, mode, aff, dtype, H, W, C, ldx, ldy, ldxr, has_xr); };
+  // 2 x 2 output blocks per thread: fewer SiLU evaluations and loads per output, but a thread of the down mode walks
+  // 36 input vectors — on the small levels (a few blocks' worth of threads) that is a 20 us latency chain, and the
+  // one-output-per-thread kernel with 4x the threads takes 6 - 11 us (at 131072 block-threads: 26 vs 30 us, the blocks win)
+  // large levels, FIR up: one activation per input element (LDS-staged tiles of 8 channel groups)
+  if (runs(GnRoute::UP_TILED) && tot2 >= 262144) return {GnRoute::UP_TILED, 0};
+  if (dtype != DS_F32) {
+    // large levels, FIR down, 16-bit tensors: column pairs walking down strips of 8 output rows (every input row read once)
+    // (half-precision build) row tiles through LDS: one activation per input element, 16 output columns x 64 channels per block
+    if (runs(GnRoute::DOWN_TILED) && (long)B * H * W * C >= (1l << 21)) {
+      const int Ho_ = H / 2, tiles_x = W / 32, ncgb = C / 64;
+      // strips of RS output rows: as long as the strips still give every CU ~2 blocks
+      if (cus <= 0) cus = ds_num_cus();
+      int rs = FD_RS_MAX;
+      while (rs > 4 && (long)B * tiles_x * cdiv(Ho_, rs) * ncgb < 2 * cus) rs >>= 1;
+      return {GnRoute::DOWN_TILED, rs};
+    }
+    if (runs(GnRoute::DOWN_STRIP) && tot2 >= 131072) {
+      const long per_row = (long)B * (W / 4) * (C >> 3);
+      // strips of 8 output rows where that still gives every CU two blocks (256^2: 131072 threads); strips of 4 below (nf = 64 at
+      // 128^2: 32768 threads of 8-row strips were 128 blocks, 63 us with the statistics passes; 4-row strips 50, 2-row 53, the
+      // 2 x 2-block kernel 55)
+      return {GnRoute::DOWN_STRIP, per_row * cdiv(H / 2, 8) >= 131072 ? 8 : 4};
+    }
+  }
+  if (runs(GnRoute::BLOCK2X2) && (mode == 1 || tot2 >= 131072)) return {GnRoute::BLOCK2X2, 0};
+  return {GnRoute::APPLY, 0};
+}
+
+// the name a launch on plan `p` records (ds_set_last_conv_kernel; each launch site below carries its own literal, the GPU tests
+// hold the two together)
+const char* ds_gn_kernel_name(const GnPlan& p, int mode, bool aff, int dtype) {
+  const bool f32 = dtype == DS_F32;
+  switch (p.route) {
+    case GnRoute::UP_TILED: return f32 ? "gn_resample_up_tiled_kernel<f32>" : "gn_resample_up_tiled_kernel<" DS_HALF_NAME ">";
+    case GnRoute::DOWN_TILED: return p.rs == 16 ? "gn_fir_down_tiled_kernel<16>" : (p.rs == 8 ? "gn_fir_down_tiled_kernel<8>" : "gn_fir_down_tiled_kernel<4>");
+    case GnRoute::DOWN_STRIP: return p.rs == 8 ? "gn_fir_down_strip_kernel<8>" : "gn_fir_down_strip_kernel<4>";
+    case GnRoute::BLOCK2X2:
+      if (mode == 1) return f32 ? "gn_resample2x2_kernel<f32,1>" : "gn_resample2x2_kernel<" DS_HALF_NAME ",1>";
+      return f32 ? "gn_resample2x2_kernel<f32,2>" : "gn_resample2x2_kernel<" DS_HALF_NAME ",2>";
+    case GnRoute::APPLY:
+      if (mode == 0) return aff ? "gn_apply_kernel<0,affine>" : "gn_apply_kernel<0,raw>";
+      if (mode == 1) return aff ? "gn_apply_kernel<1,affine>" : "gn_apply_kernel<1,raw>";
+      return aff ? "gn_apply_kernel<2,affine>" : "gn_apply_kernel<2,raw>";
+  }
+  return "";
+}
+
 template <typename T>
-static int gn_apply_typed(const void* x, int ldx, const float* scale, const float* shift, int C, void* y, int ldy,
-                          void* xr, int ldxr, int B, int H, int W, int act, int mode, hipStream_t st) {
+static int gn_launch_typed(const GnPlan& p, const void* x, int ldx, const float* scale, const float* shift, int C, void* y, int ldy,
+                           void* xr, int ldxr, int B, int H, int W, int act, int mode, hipStream_t st) {
   const int Ho = mode == 1 ? 2 * H : (mode == 2 ? H / 2 : H);
   const int Wo = mode == 1 ? 2 * W : (mode == 2 ? W / 2 : W);
   const long total = (long)B * Ho * Wo * (C >> 3);
@@ -741,94 +815,100 @@ static int gn_apply_typed(const void* x, int ldx, const float* scale, const floa
   if (nb < 1) nb = 1;
   const bool aff = scale != nullptr;
   const long tot2 = (mode == 1 ? (long)B * H * W : (long)B * (H / 4) * (W / 4)) * (C >> 3);
-  // 2 x 2 output blocks per thread: fewer SiLU evaluations and loads per output, but a thread of the down mode walks
-  // 36 input vectors — on the small levels (a few blocks' worth of threads) that is a 20 us latency chain, and the
-  // one-output-per-thread kernel with 4x the threads takes 6 - 11 us (at 131072 block-threads: 26 vs 30 us, the blocks win)
-  // large levels, FIR up: one activation per input element (LDS-staged tiles of 8 channel groups)
-  if (aff && mode == 1 && C % 64 == 0 && tot2 >= 262144) {
+  if (p.route == GnRoute::UP_TILED) {
     const int th = cdiv(H, 4), tw = cdiv(W, 8);
     const long nblk = (long)B * th * tw * (C / 64);
     DS_FUNC_LDS_ONCE((gn_resample_up_tiled_kernel<T>), gn_resample_up_tiled_lds<T>());
     hipLaunchKernelGGL((gn_resample_up_tiled_kernel<T>), dim3((unsigned)nblk), dim3(256), gn_resample_up_tiled_lds<T>(), st,
                        (const T*)x, ldx, scale, shift, C, (T*)y, ldy, (T*)xr, ldxr, B, H, W, act, tw, th);
     DS_LAUNCH_CHECK();
+    ds_set_last_conv_kernel(sizeof(T) == 4 ? "gn_resample_up_tiled_kernel<f32>" : "gn_resample_up_tiled_kernel<" DS_HALF_NAME ">");
     return 0;
   }
   if constexpr (sizeof(T) == 2) {
-    // large levels, FIR down, 16-bit tensors: column pairs walking down strips of 8 output rows (every input row read once)
 #if defined(DS_HALF_F16) && !defined(DS_NO_FIR_TILED)
-    // (half-precision build) row tiles through LDS: one activation per input element, 16 output columns x 64 channels per block
-    if (aff && mode == 2 && H % 2 == 0 && W % 32 == 0 && C % 64 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && (!xr || ldxr % 8 == 0) &&
-        (long)B * H * W * C >= (1l << 21)) {
-      const int Ho_ = H / 2, tiles_x = W / 32, ncgb = C / 64;
-      // strips of RS output rows: as long as the strips still give every CU ~2 blocks
-#ifndef FD_RS_MAX
-#define FD_RS_MAX 8  // (16: 99.9 -> 97.0 us at 256^2 C = 64 and 68.7 -> 62.3 at 128^2 C = 128 incl. the statistics passes; tools/fir_ab.sh)
-#endif
-      int rs = FD_RS_MAX;
-      while (rs > 4 && (long)B * tiles_x * cdiv(Ho_, rs) * ncgb < 2 * ds_num_cus()) rs >>= 1;
+    if (p.route == GnRoute::DOWN_TILED) {
+      const int Ho_ = H / 2, tiles_x = W / 32, ncgb = C / 64, rs = p.rs;
       const int strips = cdiv(Ho_, rs);
       const unsigned nblk = (unsigned)((long)B * tiles_x * strips * ncgb);
-#define FD(RS_) hipLaunchKernelGGL((gn_fir_down_tiled_kernel<RS_>), dim3(nblk), dim3(256), 0, st, (const bf16_t*)x, ldx, scale, shift, C, \
-                                   (bf16_t*)y, ldy, (bf16_t*)xr, ldxr, B, H, W, act, tiles_x, strips)
+#define FD(RS_)                                                                                                                          \
+  do {                                                                                                                                   \
+    hipLaunchKernelGGL((gn_fir_down_tiled_kernel<RS_>), dim3(nblk), dim3(256), 0, st, (const bf16_t*)x, ldx, scale, shift, C, (bf16_t*)y, \
+                       ldy, (bf16_t*)xr, ldxr, B, H, W, act, tiles_x, strips);                                                           \
+    ds_set_last_conv_kernel("gn_fir_down_tiled_kernel<" #RS_ ">");                                                                       \
+  } while (0)
       if (rs == 16) FD(16); else if (rs == 8) FD(8); else FD(4);
 #undef FD
       DS_LAUNCH_CHECK();
       return 0;
     }
 #endif
-    if (aff && mode == 2 && H % 2 == 0 && W % 4 == 0 && tot2 >= 131072) {
+    if (p.route == GnRoute::DOWN_STRIP) {
       const long per_row = (long)B * (W / 4) * (C >> 3);
-      // strips of 8 output rows where that still gives every CU two blocks (256^2: 131072 threads); strips of 4 below (nf = 64 at
-      // 128^2: 32768 threads of 8-row strips were 128 blocks, 63 us with the statistics passes; 4-row strips 50, 2-row 53, the
-      // 2 x 2-block kernel 55)
-      if (per_row * cdiv(H / 2, 8) >= 131072) {
+      if (p.rs == 8) {
         constexpr int RS = 8;
         const long tot3 = per_row * cdiv(H / 2, RS);
         hipLaunchKernelGGL((gn_fir_down_strip_kernel<RS>), dim3((unsigned)cdiv(tot3, 256)), dim3(256), 0, st, (const bf16_t*)x, ldx, scale,
                            shift, C, (bf16_t*)y, ldy, (bf16_t*)xr, ldxr, B, H, W, act);
+        ds_set_last_conv_kernel("gn_fir_down_strip_kernel<8>");
       } else {
         constexpr int RS = 4;
         const long tot3 = per_row * cdiv(H / 2, RS);
         hipLaunchKernelGGL((gn_fir_down_strip_kernel<RS>), dim3((unsigned)cdiv(tot3, 256)), dim3(256), 0, st, (const bf16_t*)x, ldx, scale,
                            shift, C, (bf16_t*)y, ldy, (bf16_t*)xr, ldxr, B, H, W, act);
+        ds_set_last_conv_kernel("gn_fir_down_strip_kernel<4>");
       }
       DS_LAUNCH_CHECK();
       return 0;
     }
   }
-  if (aff && (mode == 1 || (mode == 2 && H % 4 == 0 && W % 4 == 0 && tot2 >= 131072))) {
+  DS_CHECK(p.route == GnRoute::BLOCK2X2 || p.route == GnRoute::APPLY, "gn_apply: internal: route without a kernel for this type");
+  if (p.route == GnRoute::BLOCK2X2) {
     long nb2 = (tot2 + 255) / 256;
     if (nb2 > 16384) nb2 = 16384;
     if (nb2 < 1) nb2 = 1;
-    if (mode == 1)
+    if (mode == 1) {
       hipLaunchKernelGGL((gn_resample2x2_kernel<T, 1>), dim3((unsigned)nb2), dim3(256), 0, st, (const T*)x, ldx, scale,
                          shift, C, (T*)y, ldy, (T*)xr, ldxr, B, H, W, act);
-    else
+      ds_set_last_conv_kernel(sizeof(T) == 4 ? "gn_resample2x2_kernel<f32,1>" : "gn_resample2x2_kernel<" DS_HALF_NAME ",1>");
+    } else {
       hipLaunchKernelGGL((gn_resample2x2_kernel<T, 2>), dim3((unsigned)nb2), dim3(256), 0, st, (const T*)x, ldx, scale,
                          shift, C, (T*)y, ldy, (T*)xr, ldxr, B, H, W, act);
+      ds_set_last_conv_kernel(sizeof(T) == 4 ? "gn_resample2x2_kernel<f32,2>" : "gn_resample2x2_kernel<" DS_HALF_NAME ",2>");
+    }
     DS_LAUNCH_CHECK();
     return 0;
   }
-#define GA(M, A)                                                                                                    \
-  hipLaunchKernelGGL((gn_apply_kernel<T, M, A>), dim3((unsigned)nb), dim3(256), 0, st, (const T*)x, ldx, scale, shift, \
-                     C, (T*)y, ldy, (T*)xr, ldxr, B, H, W, act)
-  if (mode == 0) { if (aff) GA(0, true); else GA(0, false); }
-  else if (mode == 1) { if (aff) GA(1, true); else GA(1, false); }
-  else { if (aff) GA(2, true); else GA(2, false); }
+#define GA(M, A, N)                                                                                                  \
+  do {                                                                                                               \
+    hipLaunchKernelGGL((gn_apply_kernel<T, M, A>), dim3((unsigned)nb), dim3(256), 0, st, (const T*)x, ldx, scale, shift, \
+                       C, (T*)y, ldy, (T*)xr, ldxr, B, H, W, act);                                                   \
+    ds_set_last_conv_kernel("gn_apply_kernel<" #M "," N ">");                                                        \
+  } while (0)
+  if (mode == 0) { if (aff) GA(0, true, "affine"); else GA(0, false, "raw"); }
+  else if (mode == 1) { if (aff) GA(1, true, "affine"); else GA(1, false, "raw"); }
+  else { if (aff) GA(2, true, "affine"); else GA(2, false, "raw"); }
 #undef GA
   DS_LAUNCH_CHECK();
   return 0;
 }
 
-int ds_launch_gn_apply(const void* x, int ldx, const float* scale, const float* shift, int C, void* y, int ldy,
+int ds_launch_gn_apply(const GnPlan& p, const void* x, int ldx, const float* scale, const float* shift, int C, void* y, int ldy,
                        void* xr, int ldxr, int B, int H, int W, int act, int mode, int dtype, hipStream_t st) {
   DS_CHECK(C % 8 == 0, "gn_apply: C must be a multiple of 8");
   DS_CHECK(mode >= 0 && mode <= 2, "gn_apply: bad resample mode");
   DS_CHECK(mode != 2 || (H % 2 == 0 && W % 2 == 0), "gn_apply: FIR down needs even H, W");
   DS_CHECK(scale != nullptr || (mode != 0 && xr != nullptr), "gn_apply: nothing to do");
-  if (dtype == DS_F32) return gn_apply_typed<float>(x, ldx, scale, shift, C, y, ldy, xr, ldxr, B, H, W, act, mode, st);
-  return gn_apply_typed<bf16_t>(x, ldx, scale, shift, C, y, ldy, xr, ldxr, B, H, W, act, mode, st);
+  DS_CHECK(ds_gn_route_runs(p.route, mode, scale != nullptr, dtype, H, W, C, ldx, ldy, ldxr, xr != nullptr),
+           "gn_apply: the routed kernel cannot run this shape");
+  if (dtype == DS_F32) return gn_launch_typed<float>(p, x, ldx, scale, shift, C, y, ldy, xr, ldxr, B, H, W, act, mode, st);
+  return gn_launch_typed<bf16_t>(p, x, ldx, scale, shift, C, y, ldy, xr, ldxr, B, H, W, act, mode, st);
+}
+
+int ds_launch_gn_apply(const void* x, int ldx, const float* scale, const float* shift, int C, void* y, int ldy,
+                       void* xr, int ldxr, int B, int H, int W, int act, int mode, int dtype, hipStream_t st) {
+  const GnPlan p = ds_gn_route(mode, scale != nullptr, dtype, B, H, W, C, ldx, ldy, ldxr, xr != nullptr, /*cus: the device's*/ 0);
+  return ds_launch_gn_apply(p, x, ldx, scale, shift, C, y, ldy, xr, ldxr, B, H, W, act, mode, dtype, st);
 }
 
 // ------------------------------------------------------------------ channel concat  cat([a, b], dim=C)

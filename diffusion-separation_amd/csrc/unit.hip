@@ -40,6 +40,61 @@ extern "C" int32_t diffsep_groupnorm_act(const void* x, const float* gamma, cons
   return ds_launch_gn_apply(x, ldx, scale, shift, C, y, ldy, xr, ldxr, B, H, W, act, resample, dtype, st);
 }
 
+// The GroupNorm-apply / FIR kernels of norm.hip as units on a caller's scale / shift table [B][C] (nullable: the pyramid's pure FIR
+// of x into xr), with leading dimensions of the caller's choice.  route = DIFFSEP_GN_AUTO: the dispatch's choice (ds_gn_route,
+// what the engine runs); any other DIFFSEP_GN_* code forces that kernel wherever its SHAPE preconditions hold (ds_gn_route_runs)
+// and lifts only the dispatch's size thresholds.
+static int gn_forced_plan(int route, GnPlan* p) {
+  switch (route) {
+    case DIFFSEP_GN_APPLY: *p = {GnRoute::APPLY, 0}; return 0;
+    case DIFFSEP_GN_BLOCK2X2: *p = {GnRoute::BLOCK2X2, 0}; return 0;
+    case DIFFSEP_GN_DOWN_STRIP4: *p = {GnRoute::DOWN_STRIP, 4}; return 0;
+    case DIFFSEP_GN_DOWN_STRIP8: *p = {GnRoute::DOWN_STRIP, 8}; return 0;
+    case DIFFSEP_GN_DOWN_TILED4: *p = {GnRoute::DOWN_TILED, 4}; return 0;
+    case DIFFSEP_GN_DOWN_TILED8: *p = {GnRoute::DOWN_TILED, 8}; return 0;
+    case DIFFSEP_GN_UP_TILED: *p = {GnRoute::UP_TILED, 0}; return 0;
+  }
+  return 1;
+}
+static int gn_unit_shape(int32_t B, int32_t H, int32_t W, int32_t C, int32_t ldx, int32_t ldy, int32_t ldxr, bool has_y, bool has_xr,
+                         int32_t mode, int32_t dtype) {
+  DS_CHECK(dtype == DS_F32 || dtype == DS_BF16, "gn_apply: bad dtype");
+  DS_CHECK(B >= 1 && H >= 1 && W >= 1 && C >= 8 && C % 8 == 0, "gn_apply: bad shape (C a multiple of 8)");
+  DS_CHECK(mode >= 0 && mode <= 2 && (mode != 2 || (H % 2 == 0 && W % 2 == 0)), "gn_apply: bad resample mode (FIR down needs even H, W)");
+  const int al = dtype == DS_F32 ? 4 : 8;  // (16-byte vectors)
+  DS_CHECK(ldx >= C && ldx % al == 0, "gn_apply: ldx must be >= C and a multiple of 16 bytes");
+  DS_CHECK(!has_y || (ldy >= C && ldy % al == 0), "gn_apply: ldy must be >= C and a multiple of 16 bytes");
+  DS_CHECK(!has_xr || (ldxr >= C && ldxr % al == 0), "gn_apply: ldxr must be >= C and a multiple of 16 bytes");
+  return 0;
+}
+extern "C" int32_t diffsep_gn_apply(const void* x, const float* scale, const float* shift, void* y, void* xr, int32_t B, int32_t H,
+                                    int32_t W, int32_t C, int32_t ldx, int32_t ldy, int32_t ldxr, int32_t act, int32_t mode,
+                                    int32_t dtype, int32_t route, void* stream) {
+  DS_CHECK(x && (scale != nullptr) == (shift != nullptr), "gn_apply: null pointer (scale and shift come together)");
+  DS_CHECK((scale != nullptr) == (y != nullptr), "gn_apply: y is written with a table and only with one");
+  DS_CHECK(scale || (mode != 0 && xr), "gn_apply: nothing to do");
+  DS_CHECK(mode != 0 || !xr, "gn_apply: xr is the resampled raw tensor (mode 1 / 2)");
+  if (gn_unit_shape(B, H, W, C, ldx, ldy, ldxr, y != nullptr, xr != nullptr, mode, dtype)) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  if (route == DIFFSEP_GN_AUTO)
+    return ds_launch_gn_apply(x, ldx, scale, shift, C, y, ldy, xr, ldxr, B, H, W, act, mode, dtype, st);
+  GnPlan p;
+  DS_CHECK(!gn_forced_plan(route, &p), "gn_apply: unknown route code");
+  DS_CHECK(ds_gn_route_runs(p.route, mode, scale != nullptr, dtype, H, W, C, ldx, ldy, ldxr, xr != nullptr),
+           "gn_apply: the forced kernel's shape preconditions do not hold (2 x 2 blocks: table, up or H % 4 == W % 4 == 0 down; strips: "
+           "16-bit, table, down, W % 4 == 0; row tiles: half-precision build, 16-bit, table, down, W % 32 == 0, C % 64 == 0, ld % 8 == 0; "
+           "up tiles: table, up, C % 64 == 0)");
+  return ds_launch_gn_apply(p, x, ldx, scale, shift, C, y, ldy, xr, ldxr, B, H, W, act, mode, dtype, st);
+}
+// the route function alone, nothing launched: the name diffsep_gn_apply(route = DIFFSEP_GN_AUTO) would leave in
+// diffsep_last_conv_kernel() for this launch on a device of `cus` compute units (<= 0: the current device's); NULL on a bad shape
+extern "C" const char* diffsep_gn_route_name(int32_t mode, int32_t affine, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C,
+                                             int32_t ldx, int32_t ldy, int32_t ldxr, int32_t has_xr, int32_t cus) {
+  if (gn_unit_shape(B, H, W, C, ldx, ldy, ldxr, affine != 0, has_xr != 0, mode, dtype)) return nullptr;
+  const GnPlan p = ds_gn_route(mode, affine != 0, dtype, B, H, W, C, ldx, ldy, ldxr, has_xr != 0, cus);
+  return ds_gn_kernel_name(p, mode, affine != 0, dtype);
+}
+
 // dense-or-strided NHWC view of a caller's tensor
 static Tn view(const void* p, int H, int W, int C, int ld) {
   Tn t;

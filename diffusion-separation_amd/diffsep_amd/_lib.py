@@ -55,6 +55,10 @@ class OdeInfo(C.Structure):  # diffsep_ode_info
                 ("t_final", C.c_double)]
 
 
+# route codes of diffsep_gn_apply (DIFFSEP_GN_* of include/diffsep_hip.h): the dispatch's choice, or one kernel of csrc/norm.hip
+GN_ROUTES = {"auto": 0, "apply": 1, "block2x2": 2, "down_strip4": 3, "down_strip8": 4, "down_tiled4": 5, "down_tiled8": 6,
+             "up_tiled": 7}
+
 PIT_NONE, PIT_TRUE_MIX, PIT_MEAN0 = 0, 1, 2
 
 
@@ -124,6 +128,8 @@ _SIGS = {
     "diffsep_conv2d_chunk": (_I, [_I, _I]),
     "diffsep_last_conv_kernel": (C.c_char_p, []),
     "diffsep_gn_finalize_acc": (_I, [_P, _I, _P, _I, _I, _L, _I, _F, _P, _P, _P, _P, _P]),
+    "diffsep_gn_apply": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "diffsep_gn_route_name": (C.c_char_p, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "diffsep_conv3x3_streamed": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P,
                                       _P, _P, _P, _P, _P, _I, _P]),
     "diffsep_conv3x3_regweight": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P,

@@ -6,7 +6,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import F32_SPLIT, F32, BF16, ODE_WORKSPACE_BYTES, LossConfig, SdeConfig, SDE_MIX, check, lib
+from ._lib import F32_SPLIT, F32, BF16, GN_ROUTES, ODE_WORKSPACE_BYTES, LossConfig, SdeConfig, SDE_MIX, check, lib
 from .engine import _ptr, _stream_ptr
 
 
@@ -159,6 +159,36 @@ def groupnorm_act(x, gamma, beta, groups, eps=1e-6, act=1, resample=0, want_xr=F
     check(_L(x).diffsep_groupnorm_act(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(xr), B, H, W, Cc, Cc, Cc, Cc,
                                       groups, eps, act, resample, _dt(x), _ptr(ws), ws.numel(), _stream_ptr()), _L(x))
     return (y, xr) if want_xr else y
+
+
+def gn_apply(x, scale, shift, act, resample, want_y=True, want_xr=False, route=None, pad=(0, 0, 0)):
+    """The GroupNorm-apply / FIR kernels as units on a caller's table (diffsep_gn_apply): y = FIR(act(x * scale + shift)), xr =
+    FIR(x); x [B,H,W,C], scale / shift [B,C] f32 or None (the pyramid's pure FIR: want_y=False, want_xr=True).  resample 0 / 1 /
+    2 = none / x2 up / x2 down.  route: None = the dispatch's choice, or a key of _lib.GN_ROUTES to force that kernel (an error
+    where its shape preconditions do not hold).  pad = extra lanes (ldx, ldy, ldxr) - C of the buffers this wrapper allocates; all
+    of x's buffer but x itself, and both outputs entirely, are prefilled with NaN.  Returns (y, xr, ybuf, xrbuf): views of the
+    first C lanes and the full buffers (None where not wanted)."""
+    B, H, W, Cc = x.shape
+    Ho, Wo = {0: (H, W), 1: (2 * H, 2 * W), 2: (H // 2, W // 2)}[resample]
+    nan = float("nan")
+    xb = torch.full((B, H, W, Cc + pad[0]), nan, dtype=x.dtype, device=x.device)
+    xb[..., :Cc] = x
+    yb = torch.full((B, Ho, Wo, Cc + pad[1]), nan, dtype=x.dtype, device=x.device) if want_y else None
+    xrb = torch.full((B, Ho, Wo, Cc + pad[2]), nan, dtype=x.dtype, device=x.device) if want_xr else None
+    check(_L(x).diffsep_gn_apply(_ptr(xb), _ptr(scale), _ptr(shift), _ptr(yb), _ptr(xrb), B, H, W, Cc, Cc + pad[0], Cc + pad[1],
+                                 Cc + pad[2], int(act), resample, _dt(x), GN_ROUTES[route or "auto"], _stream_ptr()), _L(x))
+    return (yb[..., :Cc] if want_y else None, xrb[..., :Cc] if want_xr else None, yb, xrb)
+
+
+def gn_route_name(kind, resample, affine, dtype, B, H, W, C, pad=(0, 0, 0), has_xr=True, cus=256):
+    """name of the kernel the dispatch picks for a GroupNorm-apply / FIR launch in library `kind` on a device of `cus` compute
+    units (diffsep_gn_route_name: host arithmetic, nothing is launched and no device is needed); dtype: torch type of the tensors"""
+    l = lib(kind)
+    name = l.diffsep_gn_route_name(resample, int(affine), F32 if dtype == torch.float32 else BF16, B, H, W, C, C + pad[0], C + pad[1],
+                                   C + pad[2], int(has_xr), cus)
+    if name is None:
+        check(1, l)
+    return name.decode()
 
 
 def conv2d(x, wpacked, bias, cout, ksize, bias_b=None, res=None, out_scale=1.0, cout_pad=None):

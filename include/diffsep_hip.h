@@ -345,7 +345,9 @@ int32_t diffsep_conv2d_fused(const void* x, const void* x2, int32_t C1, const fl
 int32_t diffsep_conv2d_chunk(int32_t ksize, int32_t dtype);
 /* Name, with its template arguments, of the kernel instantiation that the calling thread's last convolution launch ran
  * (thread-local; "" before the first launch).  The fused attention kernel counts as one, from the unit entry point and from
- * the engine's block code alike: "attn_fused_kernel<LT>" with LT = 1, 2, 4, 8 tiles of 32 pixels. */
+ * the engine's block code alike: "attn_fused_kernel<LT>" with LT = 1, 2, 4, 8 tiles of 32 pixels.  So does every GroupNorm-apply /
+ * FIR resampling launch of csrc/norm.hip: "gn_apply_kernel<MODE,affine|raw>", "gn_resample2x2_kernel<T,MODE>",
+ * "gn_fir_down_strip_kernel<RS>", "gn_fir_down_tiled_kernel<RS>", "gn_resample_up_tiled_kernel<T>" (T = f32 | bf16 | f16). */
 const char* diffsep_last_conv_kernel(void);
 /* GroupNorm scale / shift [B][C1 + C2] fp32 from the int64 channel-sum accumulators [B][C][2] that the convolutions' `stats`
  * fill (acc2 nullable: the in-place concat of two tensors); npix = H * W of the tensor.  The expression, and the float-rounded
@@ -354,6 +356,33 @@ const char* diffsep_last_conv_kernel(void);
 int32_t diffsep_gn_finalize_acc(const int64_t* acc1, int32_t C1, const int64_t* acc2, int32_t C2, int32_t B, int64_t npix,
                                 int32_t groups, float eps, const float* gamma, const float* beta, float* scale, float* shift,
                                 void* stream);
+/* The GroupNorm-apply / FIR x2 resampling kernels (csrc/norm.hip) as units on a CALLER'S table: y = FIR(act(x * scale[b,c] +
+ * shift[b,c])) and xr = FIR(x) (mode 0: no FIR, no xr; 1: x2 up; 2: x2 down; zero padding of BOTH tensors after the activation),
+ * x [B][H][W][ldx], y / xr [B][H'][W'][ldy / ldxr], C channels written, the other lanes untouched.  scale = shift = y = NULL: the
+ * pyramid's pure FIR of x into xr.  act: 0 none, 1 SiLU.  The launch leaves its kernel's name in diffsep_last_conv_kernel().
+ * route = DIFFSEP_GN_AUTO: the kernel the dispatch picks for the shape (what the engine runs).  Any other code forces that kernel
+ * wherever its SHAPE preconditions hold — an error otherwise — and lifts only the dispatch's size thresholds:
+ *   BLOCK2X2 (gn_resample2x2_kernel): table; up, or down with H % 4 == 0 and W % 4 == 0
+ *   DOWN_STRIP4 / 8 (gn_fir_down_strip_kernel<4 | 8>): 16-bit, table, down, W % 4 == 0
+ *   DOWN_TILED4 / 8 (gn_fir_down_tiled_kernel<4 | 8>): libdiffsep_hip_f16.so only, 16-bit, table, down, W % 32 == 0, C % 64 == 0,
+ *                                                      ldx, ldy, ldxr multiples of 8
+ *   UP_TILED (gn_resample_up_tiled_kernel): table, up, C % 64 == 0 */
+#define DIFFSEP_GN_AUTO 0
+#define DIFFSEP_GN_APPLY 1
+#define DIFFSEP_GN_BLOCK2X2 2
+#define DIFFSEP_GN_DOWN_STRIP4 3
+#define DIFFSEP_GN_DOWN_STRIP8 4
+#define DIFFSEP_GN_DOWN_TILED4 5
+#define DIFFSEP_GN_DOWN_TILED8 6
+#define DIFFSEP_GN_UP_TILED 7
+int32_t diffsep_gn_apply(const void* x, const float* scale, const float* shift, void* y, void* xr, int32_t B, int32_t H, int32_t W,
+                         int32_t C, int32_t ldx, int32_t ldy, int32_t ldxr, int32_t act, int32_t mode, int32_t dtype, int32_t route,
+                         void* stream);
+/* The dispatch alone, nothing launched (host arithmetic; needs no device when cus > 0): the kernel name that
+ * diffsep_gn_apply(route = DIFFSEP_GN_AUTO) would leave in diffsep_last_conv_kernel() for this launch on a device of `cus` compute
+ * units (<= 0: the current device's).  NULL (and diffsep_last_error) on a shape the entry point refuses. */
+const char* diffsep_gn_route_name(int32_t mode, int32_t affine, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C,
+                                  int32_t ldx, int32_t ldy, int32_t ldxr, int32_t has_xr, int32_t cus);
 /* The streamed-weight 3x3 kernel (csrc/conv3x3_sw.hip; the 128-cout layers with 192 / 256 input channels or a folded 1x1 skip
  * on up to 256 raw channels: ncsnpp.py:409-417, layerspp.py:291-323) as a unit, whatever the dispatch would pick.  Dense NHWC
  * 16-bit tensors: x [B][H][W][C1 or Cin], x2 (nullable) the other Cin - C1 channels; act(GroupNorm(.)) from per-(b, c)

@@ -97,6 +97,8 @@ def test_f16_elementwise_kernels():
     for resample in (0, 1, 2):
         y, xr = ops.groupnorm_act(x, g, be, 16, 1e-6, act=1, resample=resample, want_xr=True) if resample else \
             (ops.groupnorm_act(x, g, be, 16, 1e-6, act=1), None)
+        # (the kernels this case has in fact been running: 2^16 elements are far below every large-level threshold)
+        assert ops.last_conv_kernel("f16") == ("gn_apply_kernel<0,affine>", "gn_resample2x2_kernel<f16,1>", "gn_apply_kernel<2,affine>")[resample]
         xx = x.float().cpu().permute(0, 3, 1, 2)  # torch fp32 on the CPU
         hn = F.silu(F.group_norm(xx, 16, g.cpu(), be.cpu(), eps=1e-6))
         if resample == 1:
@@ -118,6 +120,11 @@ def test_f16_fir_down_row_tiles(C, H, W):
     x = (rnd(f"h.fd{C}{H}", (B, H, W, C), 1.5) + 0.3).to(DEV, H16)
     g, be = (1.0 + rnd(f"h.fdg{C}", (C,), 0.2)).to(DEV), rnd(f"h.fdb{C}", (C,), 0.1).to(DEV)
     y, xr = ops.groupnorm_act(x, g, be, groups, 1e-6, act=1, resample=2, want_xr=True)
+    # at B = 2 every one of these shapes gives fewer than 2 x 256 blocks of 8-row strips: all five have been running the 4-row
+    # instantiation (8-row strips: tests/test_gn_gpu.py)
+    want = ops.gn_route_name("f16", 2, True, H16, B, H, W, C, cus=CC.device_cus())
+    assert CC.device_cus() != 256 or want == "gn_fir_down_tiled_kernel<4>"
+    assert ops.last_conv_kernel("f16") == want, ops.last_conv_kernel("f16")
     xx = x.float().cpu().permute(0, 3, 1, 2)
     hn = O.fir_down2(F.silu(F.group_norm(xx, groups, g.cpu(), be.cpu(), eps=1e-6)))
     assert y.shape == (B, H // 2, W // 2, C) and xr.shape == y.shape

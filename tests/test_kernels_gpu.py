@@ -121,6 +121,13 @@ def test_conv_f32_is_exact_fmaf_chain_on_integers():
                                             (256, 44, 1032, 2)])
 def test_groupnorm_silu_resample(dtype, tol, C, H, W, resample):
     B = 2
+    # the kernel each case has in fact been running (the route table of tests/test_gncheck_cpu.py; T = f32 | bf16): 256 x 256 x 64
+    # at B = 2 is below the strips' threshold, and no case reaches gn_fir_down_strip_kernel<8> (tests/test_gn_gpu.py does)
+    T = "f32" if dtype == torch.float32 else "bf16"
+    big_down = f"gn_resample2x2_kernel<{T},2>" if dtype == torch.float32 else "gn_fir_down_strip_kernel<4>"
+    kernel = {0: "gn_apply_kernel<0,affine>",
+              1: f"gn_resample_up_tiled_kernel<{T}>" if H >= 100 else f"gn_resample2x2_kernel<{T},1>",
+              2: big_down if (C, H, W) in ((128, 256, 520), (256, 44, 1032)) else "gn_apply_kernel<2,affine>"}[resample]
     x = rnd(f"gn.x{C}{H}{resample}", (B, C, H, W), 1.5) + 0.3
     g = 1.0 + rnd(f"gn.g{C}", (C,), 0.2)
     b = rnd(f"gn.b{C}", (C,), 0.1)
@@ -134,6 +141,7 @@ def test_groupnorm_silu_resample(dtype, tol, C, H, W, resample):
         h, xr_ref = O.fir_down2(h), O.fir_down2(xin)
     y, xr = ops.groupnorm_act(ops.to_nhwc(x).to(DEV, dtype), g.to(DEV), b.to(DEV), groups, 1e-6, 1, resample,
                               want_xr=True)
+    assert ops.last_conv_kernel() == kernel, ops.last_conv_kernel()
     assert rel_rms(ops.to_nchw(y.float()), h) < tol
     if resample:
         assert rel_rms(ops.to_nchw(xr.float()), xr_ref) < tol
