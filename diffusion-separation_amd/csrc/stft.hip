@@ -388,6 +388,7 @@ int ds_launch_stft_pack(const float* xt, const float* mix, void* y, int B, int S
     constexpr int LDS0_ = 2 * NC_ * SF_CH, LDS_ = LDS0_ > SF_LDS_MIN ? LDS0_ : SF_LDS_MIN;                                   \
     DS_FUNC_LDS_ONCE((stft_fused_kernel<NC_>), LDS_);                                                                        \
     hipLaunchKernelGGL((stft_fused_kernel<NC_>), dim3(nblk), dim3(SF_NT), LDS_, st, xt, mix, (bf16_t*)y, T, F, W, exponent, factor, shift, dfrag); \
+    ds_set_last_conv_kernel("stft_fused_kernel<" #NC_ ">");                                                                  \
   }
     if (S == 1) SFK(2) else if (S == 2) SFK(3) else SFK(4)
 #undef SFK
@@ -417,6 +418,8 @@ int ds_launch_stft_pack(const float* xt, const float* mix, void* y, int B, int S
     hipLaunchKernelGGL(stft_pack_kernel<bf16_t>, dim3(cdiv(total, 256)), dim3(256), 0, st, specT, (bf16_t*)y, S, bins,
                        F, W, Cpad, rows_p, exponent, factor, shift, B);
   DS_LAUNCH_CHECK();
+  // (the three-launch routes leave their LAST thin kernel's name, over the DFT GEMM's)
+  ds_set_last_conv_kernel(dtype == DS_F32 ? "stft_pack_kernel<f32>" : "stft_pack_kernel<" DS_HALF_NAME ">");
   return 0;
 }
 
@@ -721,10 +724,13 @@ int ds_launch_istft(const void* x, float* out, int B, int S, long T, int n_fft, 
                     int W, int Cpad, int dtype, const float* tab, float* ws, hipStream_t st, int split, const float* ow,
                     const float* ob, const float* tdiv, int ow_cin) {
   DS_CHECK(n_fft % 2 == 0 && n_fft <= 510, "istft: n_fft must be even and <= 510");
-  DS_CHECK(!ow || (ob && tdiv && ow_cin >= 1 && ow_cin <= 8), "istft: bad fused output layer");
+  DS_CHECK(!ow || (ob && tdiv), "istft: the fused output layer needs its bias and the per-entry divisor");
   DS_CHECK(S >= 1 && S <= DS_MAXC - 1 && Cpad >= 2 * S && Cpad % 8 == 0 && 2 * S <= 8, "istft: bad source / channel count");
   const int F = 1 + (int)((T + n_fft - hop) / hop);
   DS_CHECK(W >= F, "istft: padded width smaller than the frame count");
+  // (every source reads its own two input channels at least: with fewer the fused kernel and istft_unpack_kernel would disagree
+  // on what the missing weights are — identity there, zero here — and no model has such an output layer)
+  DS_CHECK(!ow || (ow_cin >= 2 * S && ow_cin <= 8), "istft: the fused output layer needs 2 * num_sources <= ow_cin <= 8 input channels");
   const int bins = n_fft / 2 + 1;
   if (dtype == DS_BF16 && n_fft == 510 && hop == 128 && Cpad % 8 == 0 && (!ow || ow_cin <= 8) && !(ds_default_opts() & DS_OPT_NO_STFT_FUSED)) {
     const uint4* dfrag = reinterpret_cast<const uint4*>(tab + ds_stft_ifrag_offset(n_fft));
@@ -736,6 +742,7 @@ int ds_launch_istft(const void* x, float* out, int B, int S, long T, int n_fft, 
     DS_FUNC_LDS_ONCE((istft_fused_kernel<NS_, EM_>), NS_ * LDS1);                                                                            \
     hipLaunchKernelGGL((istft_fused_kernel<NS_, EM_>), dim3((unsigned)(B * (S / NS_) * nseg)), dim3(SI_NT), NS_ * LDS1, st, (const bf16_t*)x, out, \
                        S, T, F, W, Cpad, exponent, factor, ow, ob, tdiv, ow_cin, dfrag, tab, nseg);                                       \
+    ds_set_last_conv_kernel("istft_fused_kernel<" #NS_ "," #EM_ ">");                                                                         \
   }
     const int em = exponent == 0.5f ? 0 : (exponent == 1.0f ? 1 : 2);
 #ifdef SI_NS1  // (A/B: one source per block, two blocks per CU)
@@ -770,5 +777,6 @@ int ds_launch_istft(const void* x, float* out, int B, int S, long T, int n_fft, 
   dim3 g2((unsigned)cdiv(T, 256), (unsigned)(B * S));
   hipLaunchKernelGGL(istft_ola_kernel, g2, dim3(256), 0, st, frames, out, T, n_fft, hop, F, tab);
   DS_LAUNCH_CHECK();
+  ds_set_last_conv_kernel("istft_ola_kernel");
   return 0;
 }

@@ -398,27 +398,42 @@ static int unit_tab(int n_fft, float** tab) {
   return 0;
 }
 
-extern "C" int32_t diffsep_stft_pack(const float* xt, const float* mix, void* y, int32_t B, int32_t S, int64_t T,
-                                     int32_t n_fft, int32_t hop, float exponent, float factor, int32_t W, int32_t Cpad,
-                                     int32_t centered_shift, int32_t dtype, void* workspace, int64_t workspace_bytes,
-                                     void* stream) {
+extern "C" int32_t diffsep_stft_pack_ex(const float* xt, const float* mix, void* y, int32_t B, int32_t S, int64_t T,
+                                        int32_t n_fft, int32_t hop, float exponent, float factor, int32_t W, int32_t Cpad,
+                                        int32_t centered_shift, int32_t dtype, void* workspace, int64_t workspace_bytes,
+                                        void* stream, int32_t split) {
   DS_CHECK(xt && mix && y && workspace, "stft_pack: null pointer");
   DS_CHECK(workspace_bytes >= ds_stft_workspace_bytes(B, S, T, n_fft, hop), "stft_pack: workspace too small");
   float* tab;
   if (unit_tab(n_fft, &tab)) return 1;
   return ds_launch_stft_pack(xt, mix, y, B, S, T, n_fft, hop, exponent, factor, W, Cpad, centered_shift, dtype, tab,
-                             (float*)workspace, (hipStream_t)stream);
+                             (float*)workspace, (hipStream_t)stream, split ? 1 : 0);
+}
+extern "C" int32_t diffsep_stft_pack(const float* xt, const float* mix, void* y, int32_t B, int32_t S, int64_t T,
+                                     int32_t n_fft, int32_t hop, float exponent, float factor, int32_t W, int32_t Cpad,
+                                     int32_t centered_shift, int32_t dtype, void* workspace, int64_t workspace_bytes,
+                                     void* stream) {
+  return diffsep_stft_pack_ex(xt, mix, y, B, S, T, n_fft, hop, exponent, factor, W, Cpad, centered_shift, dtype, workspace,
+                              workspace_bytes, stream, 0);
 }
 
-extern "C" int32_t diffsep_istft_unpack(const void* x, float* out, int32_t B, int32_t S, int64_t T, int32_t n_fft,
-                                        int32_t hop, float exponent, float factor, int32_t W, int32_t Cpad,
-                                        int32_t dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+extern "C" int32_t diffsep_istft_unpack_ex(const void* x, float* out, int32_t B, int32_t S, int64_t T, int32_t n_fft,
+                                           int32_t hop, float exponent, float factor, int32_t W, int32_t Cpad,
+                                           int32_t dtype, void* workspace, int64_t workspace_bytes, void* stream,
+                                           int32_t split, const float* ow, const float* ob, const float* tdiv,
+                                           int32_t ow_cin) {
   DS_CHECK(x && out && workspace, "istft_unpack: null pointer");
   DS_CHECK(workspace_bytes >= ds_istft_workspace_bytes(B, S, T, n_fft, hop), "istft_unpack: workspace too small");
   float* tab;
   if (unit_tab(n_fft, &tab)) return 1;
   return ds_launch_istft(x, out, B, S, T, n_fft, hop, exponent, factor, W, Cpad, dtype, tab, (float*)workspace,
-                         (hipStream_t)stream);
+                         (hipStream_t)stream, split ? 1 : 0, ow, ob, tdiv, ow_cin);
+}
+extern "C" int32_t diffsep_istft_unpack(const void* x, float* out, int32_t B, int32_t S, int64_t T, int32_t n_fft,
+                                        int32_t hop, float exponent, float factor, int32_t W, int32_t Cpad,
+                                        int32_t dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+  return diffsep_istft_unpack_ex(x, out, B, S, T, n_fft, hop, exponent, factor, W, Cpad, dtype, workspace, workspace_bytes,
+                                 stream, 0, nullptr, nullptr, nullptr, 0);
 }
 
 

@@ -326,24 +326,40 @@ def attnblock_forward(params, x):
     return y
 
 
-def stft_pack(xt, mix, W, cpad, n_fft=510, hop=128, exponent=0.5, factor=0.33, shift=False, dtype=torch.float32):
+def stft_pack(xt, mix, W, cpad, n_fft=510, hop=128, exponent=0.5, factor=0.33, shift=False, dtype=torch.float32, split=False):
+    """diffsep_stft_pack_ex.  split=True: the DFT matrix product of the three-launch route with bf16x3 products (the fused kernel of
+    the 16-bit types ignores it).  last_conv_kernel() names the kernel afterwards."""
     B, S, T = xt.shape
     y = torch.empty((B, n_fft // 2 + 1, W, cpad), dtype=dtype, device=xt.device)
     F_ = 1 + (T + n_fft - hop) // hop
     ws = torch.empty(2 * ((B * (S + 1) * F_ + 8) * 512 + 64), dtype=torch.float32, device=xt.device)
-    check(_L(y).diffsep_stft_pack(_ptr(xt), _ptr(mix), _ptr(y), B, S, T, n_fft, hop, exponent, factor, W, cpad,
-                                  int(shift), F32 if dtype == torch.float32 else BF16, _ptr(ws), ws.numel() * 4,
-                                  _stream_ptr()), _L(y))
+    check(_L(y).diffsep_stft_pack_ex(_ptr(xt), _ptr(mix), _ptr(y), B, S, T, n_fft, hop, exponent, factor, W, cpad,
+                                     int(shift), F32 if dtype == torch.float32 else BF16, _ptr(ws), ws.numel() * 4,
+                                     _stream_ptr(), int(bool(split))), _L(y))
     return y
 
 
-def istft_unpack(x, S, T, n_fft=510, hop=128, exponent=0.5, factor=0.33):
+def istft_unpack(x, S, T, n_fft=510, hop=128, exponent=0.5, factor=0.33, split=False, ow=None, ob=None, tdiv=None, out=None):
+    """diffsep_istft_unpack_ex.  ow [2S, ow_cin], ob [2S], tdiv [B] (float32, on x's device): the network's output layer
+    v = (ow x) / tdiv[b] + ob applied to every pixel first; all three or none.  out: a float32 [>= B, S, T] tensor to write into."""
     B, H, W, cpad = x.shape
     F_ = 1 + (T + n_fft - hop) // hop
-    out = torch.empty((B, S, T), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((B, S, T), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape[0] < B or tuple(out.shape[1:]) != (S, T):
+        raise ValueError("istft_unpack: out must be a dense float32 [>= B, S, T] tensor")
     ws = torch.empty(2 * (B * S * F_ * 512 + 64), dtype=torch.float32, device=x.device)
-    check(_L(x).diffsep_istft_unpack(_ptr(x), _ptr(out), B, S, T, n_fft, hop, exponent, factor, W, cpad, _dt(x),
-                                     _ptr(ws), ws.numel() * 4, _stream_ptr()), _L(x))
+    ow_cin = 0
+    if ow is not None:
+        if ob is None or tdiv is None:
+            raise ValueError("istft_unpack: ow, ob and tdiv come together")
+        for t_, shp in ((ow, (2 * S, ow.shape[-1])), (ob, (2 * S,)), (tdiv, (B,))):
+            if t_.dtype != torch.float32 or not t_.is_contiguous() or tuple(t_.shape) != shp or t_.device != x.device:
+                raise ValueError("istft_unpack: ow [2S, ow_cin], ob [2S], tdiv [B] must be dense float32 tensors on x's device")
+        ow_cin = ow.shape[1]
+    check(_L(x).diffsep_istft_unpack_ex(_ptr(x), _ptr(out), B, S, T, n_fft, hop, exponent, factor, W, cpad, _dt(x),
+                                        _ptr(ws), ws.numel() * 4, _stream_ptr(), int(bool(split)), _ptr(ow), _ptr(ob),
+                                        _ptr(tdiv), ow_cin), _L(x))
     return out
 
 

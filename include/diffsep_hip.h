@@ -315,6 +315,15 @@ int32_t diffsep_groupnorm_act(const void* x, const float* gamma, const float* be
                               int32_t H, int32_t W, int32_t C, int32_t ldx, int32_t ldy, int32_t ldxr,
                               int32_t groups, float eps, int32_t act, int32_t resample, int32_t dtype,
                               void* workspace, int64_t workspace_bytes, void* stream);
+/* ... with split (as above) and the network's output layer applied on the fly (ow != NULL; all device pointers): x is then the
+ * last pyramid tensor [B,256,W,Cpad] and every pixel becomes v[c] = (sum_{k < ow_cin} ow[c][k] x[k]) / tdiv[b] + ob[c] first.
+ * ow [2S][ow_cin] f32, ob [2S] f32, tdiv [B] f32, 2S <= ow_cin <= 8 (anything else is refused).  ow == NULL: ob, tdiv
+ * and ow_cin are ignored.  Name left behind: "istft_fused_kernel<NS,EM>" (NS = 2 at S = 2, else 1; EM = 0 | 1 | 2: exponent 0.5 |
+ * 1 | other) or the route's last kernel "istft_ola_kernel". */
+int32_t diffsep_istft_unpack_ex(const void* x, float* out, int32_t B, int32_t S, int64_t T, int32_t n_fft,
+                                int32_t hop, float exponent, float factor, int32_t W, int32_t Cpad, int32_t dtype,
+                                void* workspace, int64_t workspace_bytes, void* stream, int32_t split, const float* ow,
+                                const float* ob, const float* tdiv, int32_t ow_cin);
 
 /* 3x3 (pad 1) or 1x1 convolution, NHWC, implicit GEMM on MFMA:
  * y = (conv(x, w) + bias[co] + bias_b[b,co] + res) * out_scale     (layers.py:112-119,141-156;
@@ -464,6 +473,13 @@ int32_t diffsep_stft_pack(const float* xt, const float* mix, void* y, int32_t B,
                           int32_t n_fft, int32_t hop, float exponent, float factor, int32_t W, int32_t Cpad,
                           int32_t centered_shift, int32_t dtype, void* workspace, int64_t workspace_bytes,
                           void* stream);
+/* ... with split != 0: the DFT matrix product of the three-launch route with bf16x3 products (what the bf16 and split engines
+ * pass); the fused kernel (16-bit y, n_fft 510, hop 128, Cpad 8, W % 32 == 0) ignores it.  The launch leaves its kernel's name in
+ * diffsep_last_conv_kernel(): "stft_fused_kernel<S+1>", or the route's last kernel "stft_pack_kernel<f32|bf16|f16>". */
+int32_t diffsep_stft_pack_ex(const float* xt, const float* mix, void* y, int32_t B, int32_t S, int64_t T,
+                             int32_t n_fft, int32_t hop, float exponent, float factor, int32_t W, int32_t Cpad,
+                             int32_t centered_shift, int32_t dtype, void* workspace, int64_t workspace_bytes,
+                             void* stream, int32_t split);
 
 /* post_process (score_models.py:118-124): unpad frames -> channels to complex -> z/|factor| ->
  * |z|^(1/e) e^{j angle} -> iSTFT -> crop to T.  x [B,256,W,Cpad] (first 2S channels used) -> out [B,S,T];

@@ -213,6 +213,7 @@ def test_stft_pack_matches_oracle(T):
     spec, _, n_pad = O.pre_process(cfg, x)
     W = spec.shape[-1]
     y = ops.stft_pack(x[:, :2].contiguous().to(DEV), x[:, 2:].contiguous().to(DEV), W, 8)
+    assert ops.last_conv_kernel() == "stft_pack_kernel<f32>", ops.last_conv_kernel()
     got = ops.to_nchw(y, 6).cpu()
     assert rel_rms(got, spec) < 2e-5
     F_ = W - n_pad
@@ -253,6 +254,7 @@ def test_istft_matches_reference_golden_and_roundtrip(golden):
     g, _ = golden
     yy = rnd("g6.y.4000", (1, 4, 256, 64), 0.2)
     out = ops.istft_unpack(ops.to_nhwc(yy, 8).to(DEV), 2, 4000)
+    assert ops.last_conv_kernel() == "istft_ola_kernel", ops.last_conv_kernel()
     assert rel_rms(out.cpu(), g["g6_post_4000"]) < 2e-5
     # STFT -> iSTFT round trip through both kernels (compress o decompress = id): <= 2e-5
     T = 32000

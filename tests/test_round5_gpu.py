@@ -216,6 +216,7 @@ def test_fused_stft_matches_oracle(dtype, tol, T, S):
     spec, _, n_pad = O.pre_process(cfg, x)
     W = spec.shape[-1]
     y = ops.stft_pack(x[:, :S].contiguous().to(DEV), x[:, S:].contiguous().to(DEV), W, 8, dtype=dtype)
+    assert ops.last_conv_kernel("f16" if dtype == torch.float16 else "bf16") == f"stft_fused_kernel<{S + 1}>"
     assert y.dtype == dtype
     got = ops.to_nchw(y.float(), 2 * (S + 1)).cpu()
     assert rel_rms(got, spec) < tol
@@ -260,7 +261,9 @@ def test_fused_istft_matches_oracle_and_roundtrip(dtype, tol, T, S):
     yy = rnd(f"r5.istft.{T}.{S}", (2, 2 * S, 256, W), 0.2)
     x16 = ops.to_nhwc(yy, 8).to(DEV, dtype)
     out = ops.istft_unpack(x16, S, T)
+    assert ops.last_conv_kernel("f16" if dtype == torch.float16 else "bf16") == f"istft_fused_kernel<{2 if S == 2 else 1},0>"
     ref = ops.istft_unpack(x16.float(), S, T)     # fp32 kernels on the same values
+    assert ops.last_conv_kernel() == "istft_ola_kernel"
     assert out.shape == (2, S, T) and torch.isfinite(out).all()
     assert rel_rms(out, ref) < 3e-5
     if T > 128 * (F_ - 1):                        # beyond the iSTFT length adjust_length pads zeros (score_models.py:99-105)
