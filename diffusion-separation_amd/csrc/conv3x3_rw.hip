@@ -268,8 +268,9 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
     TileG g;
     const int y0 = ty * TH, x0 = tx * TW;
     g.edge = (y0 == 0 ? 1u : 0u) | (y0 + TH == p.H ? 2u : 0u) | (x0 == 0 ? 4u : 0u) | (x0 + TW == p.W ? 8u : 0u);
-    // (0x3fffff rather than M as in conv3x3_sw.hip: safe while the pixel pitch stays under 1 KB, and M moves the register
-    // allocation of the whole kernel — profiles/experiments/README.md, "Sharing the halo-tile pipeline")
+    // (0x3fffff rather than M as in conv3x3_sw.hip: safe while the pixel pitch stays under 1 KB and the image plus a tile below
+    // 0x3fffff pixels — halo_addressing_ok(rw_sentinel) in conv3x3_halo.h, which ds_conv_rw_supported asks — and M moves the
+    // register allocation of the whole kernel — profiles/experiments/README.md, "Sharing the halo-tile pipeline")
     g.pix0 = valid ? y0 * p.W + x0 : 0x3fffff;
     return g;
   };
@@ -880,40 +881,48 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
   RT_FLUSH
 }
 
+// blocks per image: the compute units over the batch, then the A/B options
 int rw_blocks_per_image(const ConvArgs& a, int tiles) {
-  int g = ds_num_cus() / a.B;
-#ifdef RW_TIMING  // (profiling builds only: fewer, fatter blocks)
-  if (getenv("DIFFSEP_RW_G")) g = atoi(getenv("DIFFSEP_RW_G"));
-#endif
+  int g = halo_blocks_wanted(a, 1);
   // option rw_half (A/B, round 5): launches whose blocks would get <= 4 tiles (the 128-row level at B = 16: a 295 KB weight
   // prologue per 4 tiles) run on HALF the CUs with twice the tiles per block — pays only if another stream's kernel takes the rest
   if ((a.opts & DS_OPT_RW_HALF) && g >= 2 && tiles / g <= 4) g /= 2;
   if ((a.opts & DS_OPT_RW_QUARTER) && g >= 4 && tiles / g <= 4) g /= 4;
   if ((a.opts & DS_OPT_RW_BIG_HALF) && g >= 2 && tiles / g > 4) g /= 2;
-  if (g < 1) g = 1;
-  if (g > tiles) g = tiles;
-  return g;
+  return g;  // (halo_launch clamps it to [1, tiles])
 }
 
 template <int NCH, int RPW, int NSK, int MODE, int NCG>
-int rw_launch(const RwK& k0, const ConvArgs& a, hipStream_t st) {
+int rw_launch(const RwK& k, const ConvArgs& a, hipStream_t st) {
   using G = RwGeom<NCH, RPW, NSK, NCG>;
-  RwK k = k0;
-  const int tiles = (a.H / G::TH) * (a.W / TW);
-  k.G = rw_blocks_per_image(a, tiles);
-  k.tiles_x = a.W / TW;
-  k.tiles_per_img = tiles;
-  auto kern = conv3x3_rw_kernel<NCH, RPW, NSK, MODE, NCG>;
-  DS_FUNC_LDS_ONCE(kern, G::LDS_TOTAL);
-  hipLaunchKernelGGL(kern, dim3(a.B * k.G), dim3(NT), G::LDS_TOTAL, st, k);
-  DS_LAUNCH_CHECK();
-  {
-    static char name[64] = {0};
-    if (!name[0]) snprintf(name, sizeof(name), "conv3x3_rw_kernel<%d,%d,%d,%d,%d>", NCH, RPW, NSK, MODE, NCG);
-    ds_set_last_conv_kernel(name);
-  }
-  return 0;
+  static_assert(G::TH <= HALO_TH_MAX, "halo_addressing_ok covers the tile");
+  return halo_launch<conv3x3_rw_kernel<NCH, RPW, NSK, MODE, NCG>>(k, a, G::TH, rw_blocks_per_image(a, halo_tiles(a, G::TH)), 1, G::LDS_TOTAL, st,
+                                                                 "conv3x3_rw_kernel", {NCH, RPW, NSK, MODE, NCG});
 }
+
+// The instantiated set, written ONCE: (Cout, 64-channel chunks of the 3x3 input, of the folded skip / residual, mode).  The shape
+// clause of ds_conv_rw_supported and the dispatch are both generated from it.  64 couts: 64 input channels with 0 .. 3 skip chunks
+// (192 skip channels = the cat(64, 128) block of the 128^2 up path: 36 + 12 fragments fill 192 of the 256 weight registers; a
+// residual is one chunk) or 128 without (no layer of the network has both; the register file would not hold it either).  128 couts
+// = 4 cout groups: the skip / residual fragments live in LDS; every such layer normalises its input.
+#define RW_SHAPES(X)                                                                        \
+  X(64, 1, 0, 0) X(64, 1, 1, 0) X(64, 1, 2, 0) X(64, 1, 3, 0) X(64, 2, 0, 0)                \
+  X(64, 1, 0, 2) X(64, 1, 1, 2) X(64, 1, 2, 2) X(64, 1, 3, 2) X(64, 2, 0, 2)                \
+  X(128, 2, 0, 0) X(128, 2, 0, 2) X(128, 2, 1, 2) X(128, 2, 2, 2)
+#define RW_IS(CO_, NCH_, NSK_, MODE_) cout == CO_ && nch == NCH_ && nsk == NSK_ && mode == MODE_
+bool rw_shape(int cout, int nch, int nsk, int mode) {
+#define RW_CASE(CO_, NCH_, NSK_, MODE_) if (RW_IS(CO_, NCH_, NSK_, MODE_)) return true;
+  RW_SHAPES(RW_CASE)
+#undef RW_CASE
+  return false;
+}
+int rw_dispatch(const RwK& k, const ConvArgs& a, int cout, int nch, int nsk, int mode, hipStream_t st) {
+#define RW_CASE(CO_, NCH_, NSK_, MODE_) if (RW_IS(CO_, NCH_, NSK_, MODE_)) return rw_launch<NCH_, 4, NSK_, MODE_, CO_ / 32>(k, a, st);
+  RW_SHAPES(RW_CASE)
+#undef RW_CASE
+  return -1;
+}
+#undef RW_IS
 
 }  // namespace
 
@@ -922,70 +931,41 @@ int rw_launch(const RwK& k0, const ConvArgs& a, hipStream_t st) {
 // tiles.  Which of them it is given (tile counts against compute units, the A/B switches): ds_conv_plan.
 bool ds_conv_rw_supported(const ConvArgs& a) {
   const int CO = a.Cout;
-  if (!(a.dtype == DS_BF16 && a.taps == 9 && ((CO == 64 && (a.Cin == 64 || a.Cin == 128)) || (CO == 128 && a.Cin == 128)) &&
-        a.w_bs == 0 && (a.w_chunked == 0 || a.w_chunked == 32) && a.bias_mode == 0 && !a.div_b && a.W % TW == 0 && a.H % 8 == 0 &&
-        a.H >= 32 && a.W >= 32 && a.ldy >= CO && a.ldy % 8 == 0 && (!a.res || (a.ldr >= CO && a.ldr % 8 == 0))))
+  if (!(a.dtype == DS_BF16 && a.taps == 9 && a.Cin % KC == 0 && a.w_bs == 0 && (a.w_chunked == 0 || a.w_chunked == 32) &&
+        a.bias_mode == 0 && !a.div_b && a.W % TW == 0 && a.H % 8 == 0 && a.H >= 32 && a.W >= 32 && a.ldy >= CO && a.ldy % 8 == 0 &&
+        (!a.res || (a.ldr >= CO && a.ldr % 8 == 0))))
     return false;
-  if (a.x2 ? !(a.C1 % KC == 0 && a.C1 > 0 && a.C1 < a.Cin && a.ldx % 8 == 0 && a.ldx2 % 8 == 0) : a.ldx % 8 != 0) return false;
-  const bool gn = a.gn_scale || a.gn_acc1;
-  if (gn && !a.gn_act) return false;  // (affine without SiLU does not occur in front of a 3x3 convolution)
-  if (a.gn_acc1 && !(a.gn_groups > 0 && a.Cin % a.gn_groups == 0 && a.Cin / a.gn_groups <= 8 && (!a.x2 || a.gn_acc2))) return false;
+  if (!halo_concat_ok(a, KC, 8) || !halo_gn_ok(a, 8) || !halo_addressing_ok(a, 2, true)) return false;
+  int nsk = 0;
   if (a.sx) {
-    // (192 skip channels = the cat(64, 128) block of the 128^2 up path: 36 + 12 fragments fill 192 of the 256 weight registers)
-    if (!(a.sw && !a.res && (a.sCin == 64 || a.sCin == 128 || (a.sCin == 192 && CO == 64 && a.Cin == 64)) && a.ldsx % 8 == 0 &&
-          (!a.sx2 || (a.sC1 % KC == 0 && a.sC1 > 0 && a.sC1 < a.sCin && a.ldsx2 % 8 == 0)) &&
+    if (!(a.sw && !a.res && a.sCin % KC == 0 && a.sCin >= KC && halo_skip_split_ok(a, KC, 8) &&
           (a.sw_chunked == 0 || ((a.sw_chunked & (a.sw_chunked - 1)) == 0 && a.sw_chunked >= 16))))
       return false;
-    if (a.Cin == 128 && CO == 64) return false;  // (no layer of the network has both; the register file would not hold it either)
+    nsk = a.sCin / KC;
+  } else if (a.res) {
+    nsk = CO / KC;
   }
-  if (a.res && a.Cin == 128 && CO == 64) return false;  // (the residual rides as a skip: same limit)
-  // 128 couts = 4 cout groups: the skip / residual fragments live in LDS; every such layer normalises its input
-  if (CO == 128 && (a.sx || a.res) && !gn) return false;
-  return true;
+  return rw_shape(CO, a.Cin / KC, nsk, (a.gn_scale || a.gn_acc1) ? 2 : 0);
 }
 
 int ds_launch_conv_rw(const ConvArgs& a, hipStream_t st) {
   RwK k;
-  k.x = reinterpret_cast<const bf16_t*>(a.x); k.x_bs = a.x_bs; k.ldx = a.ldx; k.C1 = a.x2 ? a.C1 : a.Cin;
-  k.x2 = reinterpret_cast<const bf16_t*>(a.x2); k.x2_bs = a.x2_bs; k.ldx2 = a.x2 ? a.ldx2 : a.ldx;
+  halo_fill_common(k, a);
   k.w = reinterpret_cast<const bf16_t*>(a.w); k.w_chunked = a.w_chunked;
   k.wfrag = reinterpret_cast<const bf16_t*>(a.w_frag);
   k.swfrag = (a.sx && a.sw) ? reinterpret_cast<const bf16_t*>(a.sw_frag) : nullptr;
-  k.gn_scale = a.gn_scale; k.gn_shift = a.gn_shift;
-  k.gn_acc1 = a.gn_acc1; k.gn_acc2 = a.gn_acc2; k.gn_gamma = a.gn_gamma; k.gn_beta = a.gn_beta;
-  k.gn_groups = a.gn_groups; k.gn_inv_count = a.gn_inv_count; k.gn_eps = a.gn_eps;
-  k.bias = a.bias; k.bias_b = a.bias_b; k.bias_b_ld = a.bias_b_ld;
   k.res = reinterpret_cast<const bf16_t*>(a.res); k.res_bs = a.res_bs; k.ldr = a.ldr;
-  k.out_scale = a.out_scale;
-  k.y = reinterpret_cast<bf16_t*>(a.y); k.y_bs = a.y_bs; k.ldy = a.ldy;
-  k.stats = a.stats_acc;
   k.sx = reinterpret_cast<const bf16_t*>(a.sx); k.sx_bs = a.sx_bs; k.ldsx = a.ldsx; k.sC1 = a.sx2 ? a.sC1 : a.sCin;
   k.sx2 = reinterpret_cast<const bf16_t*>(a.sx2); k.sx2_bs = a.sx2_bs; k.ldsx2 = a.sx2 ? a.ldsx2 : a.ldsx;
   k.sw = reinterpret_cast<const bf16_t*>(a.sw); k.sw_chunked = a.sw_chunked; k.sw_shift = a.sw_chunked ? __builtin_ctz(a.sw_chunked) : 0;
   k.sCin = a.sCin;
-  k.H = a.H; k.W = a.W; k.G = 0; k.tiles_x = 0; k.tiles_per_img = 0;
-#ifdef RW_TIMING  // (profiling builds only: stores / loads outside the tensors)
-  k.dbg = getenv("DIFFSEP_RW_DBG") ? atoi(getenv("DIFFSEP_RW_DBG")) : 0;
-#else
-  k.dbg = 0;
-#endif
   if (a.res) {  // the residual [B][H][W][64] as a folded skip with identity weights (sw = null): exact in the fp32 accumulators
     k.sx = reinterpret_cast<const bf16_t*>(a.res); k.sx_bs = a.res_bs; k.ldsx = a.ldr; k.sC1 = a.Cout;
     k.sx2 = nullptr; k.sx2_bs = 0; k.ldsx2 = a.ldr; k.sw = nullptr; k.sw_chunked = 0; k.sw_shift = 0; k.sCin = a.Cout;
   }
   const int mode = ((a.gn_scale || a.gn_acc1) && a.gn_act) ? 2 : 0;
   const int nsk = a.sx ? a.sCin / KC : (a.res ? a.Cout / KC : 0);
-  if (a.Cout == 128) {  // 128 -> 128: 4 cout groups
-    if (mode == 0) return rw_launch<2, 4, 0, 0, 4>(k, a, st);
-    if (nsk == 0) return rw_launch<2, 4, 0, 2, 4>(k, a, st);
-    if (nsk == 1) return rw_launch<2, 4, 1, 2, 4>(k, a, st);
-    return rw_launch<2, 4, 2, 2, 4>(k, a, st);
-  }
-#define RW_GO(NCH_, NSK_) return mode == 2 ? rw_launch<NCH_, 4, NSK_, 2, 2>(k, a, st) : rw_launch<NCH_, 4, NSK_, 0, 2>(k, a, st)
-  if (a.Cin == 128) RW_GO(2, 0);
-  if (nsk == 0) RW_GO(1, 0);
-  if (nsk == 1) RW_GO(1, 1);
-  if (nsk == 2) RW_GO(1, 2);
-  RW_GO(1, 3);
-#undef RW_GO
+  const int rc = rw_dispatch(k, a, a.Cout, a.Cin / KC, nsk, mode, st);
+  DS_CHECK(rc >= 0, "conv3x3_rw: shape outside the instantiated set");
+  return rc;
 }

@@ -38,23 +38,7 @@ constexpr int NKB = KC / 16;          // 16-channel k-blocks per tap
 constexpr int KSC = 9 * NKB;          // k-steps of a 3x3 chunk
 static_assert(KC * 2 + 16 == AROW && KC / 8 == PPL, "a pixel's chunk is one 128-byte line");
 
-struct SwK {
-  const bf16_t* x; long x_bs; int ldx; int C1;     // channels [0, C1) from x, [C1, Cin) from x2
-  const bf16_t* x2; long x2_bs; int ldx2;
-  const bf16_t* wfrag; const bf16_t* swfrag;       // fragment-major weights (ds_rw_frag_index): [k-step][Cout / 32][lane][8]
-  unsigned frag_step;                              // bytes of one k-step of the fragment-major copies: Cout / 32 KB
-  const float* gn_scale; const float* gn_shift;    // [B][Cin] or null
-  const long long* gn_acc1; const long long* gn_acc2; const float* gn_gamma; const float* gn_beta;
-  int gn_groups; float gn_inv_count; float gn_eps;
-  const float* bias; const float* bias_b; int bias_b_ld;
-  float out_scale;
-  bf16_t* y; long y_bs; int ldy;
-  long long* stats;
-  const bf16_t* sx; long sx_bs; int ldsx; int sC1;  // folded skip: raw channels [0, sC1) from sx, the rest from sx2
-  const bf16_t* sx2; long sx2_bs; int ldsx2;
-  int H, W, G, ncb, cout, tiles_x, tiles_per_img;   // G blocks per image and cout block; ncb cout blocks of 128; cout = 128 ncb
-  int dbg;  // profiling builds: bit 0 = stores fall outside the tensor, bit 1 = loads do
-};
+using SwK = HaloK<bf16_t>;  // (conv3x3_halo.h)
 
 #ifndef SW_D
 #define SW_D 16  // ring depth: k-steps between a fragment's load and its MFMAs (A/B: -DSW_D=..)
@@ -242,8 +226,9 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
     TileG g;
     const int y0 = ty * TH, x0 = tx * TW;
     g.edge = (y0 == 0 ? 1u : 0u) | (y0 + TH == p.H ? 2u : 0u) | (x0 == 0 ? 4u : 0u) | (x0 + TW == p.W ? 8u : 0u);
-    // (no tile: the first pixel PAST the image — every offset pixel x pitch is then >= the tensor's size, and stays below 2^32 for
-    // every pitch; a constant like 0x3fffff times a 1 KB pitch plus a tile offset WRAPS into the tensor)
+    // (no tile: the first pixel PAST the image — every offset pixel x pitch is then >= the tensor's size, and stays below 2^31 for
+    // every pitch the launch uses: halo_addressing_ok in conv3x3_halo.h, which ds_conv_sw_supported asks; a constant like 0x3fffff
+    // times a 1 KB pitch plus a tile offset WRAPS into the tensor)
     g.pix0 = valid ? y0 * p.W + x0 : M;
     return g;
   };
@@ -825,50 +810,45 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
 }
 
 template <int NCH, int NSK, int MODE, int RPW, int NCG>
-int sw_launch(const SwK& k0, const ConvArgs& a, hipStream_t st) {
+int sw_launch(const SwK& k, const ConvArgs& a, hipStream_t st) {
   using G = SwGeom<NCH, NSK, RPW, NCG>;
-  SwK k = k0;
-  const int tiles = (a.H / G::TH) * (a.W / TW);
-  int g = ds_num_cus() / (a.B * k.ncb);
-#ifdef SW_TIMING  // (profiling builds only: fewer, fatter blocks)
-  if (getenv("DIFFSEP_SW_G")) g = atoi(getenv("DIFFSEP_SW_G"));
-#endif
-  if (g < 1) g = 1;
-  if (g > tiles) g = tiles;
-  k.G = g;
-  k.tiles_x = a.W / TW;
-  k.tiles_per_img = tiles;
-  auto kern = conv3x3_sw_kernel<NCH, NSK, MODE, RPW, NCG>;
-  DS_FUNC_LDS_ONCE(kern, G::LDS_TOTAL);
-  hipLaunchKernelGGL(kern, dim3(a.B * k.ncb * k.G), dim3(NT), G::LDS_TOTAL, st, k);
-  DS_LAUNCH_CHECK();
-  {
-    static char name[64] = {0};
-    if (!name[0]) snprintf(name, sizeof(name), "conv3x3_sw_kernel<%d,%d,%d,%d,%d>", NCH, NSK, MODE, RPW, NCG);
-    ds_set_last_conv_kernel(name);
-  }
-  return 0;
+  static_assert(G::TH <= HALO_TH_MAX, "halo_addressing_ok covers the tile");
+  return halo_launch<conv3x3_sw_kernel<NCH, NSK, MODE, RPW, NCG>>(k, a, G::TH, halo_blocks_wanted(a, k.ncb), k.ncb, G::LDS_TOTAL, st,
+                                                                 "conv3x3_sw_kernel", {NCH, NSK, MODE, RPW, NCG});
 }
 
-// the (input chunks, skip chunks, mode) sets instantiated per tile shape
+// The instantiated sets, written ONCE: (input chunks, skip chunks, mode) per tile shape; sw_shape and the dispatch are both
+// generated from them.  128-cout blocks (RPW = 8 or 4, NCG = 4): raw input on 64 / 128 channels; GroupNorm + SiLU on 64 .. 512;
+// with a folded skip or residual on 128 channels (nf = 64) or 256 (nf = 128: the 256-channel blocks).  64 couts (RPW = 4, NCG = 2):
+// cat(128, 64) -> 64 of the 128^2 up path, the one 64-cout layer the register-weight kernel does not hold.
+#define SW_SHAPES_128(X)                                               \
+  X(1, 0, 0) X(2, 0, 0)                                                \
+  X(1, 0, 2) X(2, 0, 2) X(3, 0, 2) X(4, 0, 2) X(6, 0, 2) X(8, 0, 2)    \
+  X(2, 1, 2) X(2, 2, 2) X(2, 3, 2) X(2, 4, 2) X(2, 6, 2)               \
+  X(4, 2, 2) X(4, 4, 2) X(4, 6, 2) X(4, 8, 2)
+#define SW_SHAPES_64(X) X(3, 0, 2)
+#define SW_IS(NCH_, NSK_, MODE_) nch == NCH_ && nsk == NSK_ && mode == MODE_
 bool sw_shape(int cout, int nch, int nsk, int mode) {
-  if (cout == 64) return nch == 3 && nsk == 0 && mode == 2;  // (cat(128, 64) -> 64 of the 128^2 up path: the one 64-cout layer the
-                                                               // register-weight kernel does not hold)
-  if (mode == 0) return nsk == 0 && (nch == 1 || nch == 2);
-  if (nsk == 0) return (nch >= 1 && nch <= 4) || nch == 6 || nch == 8;
-  if (nch == 2) return (nsk >= 1 && nsk <= 4) || nsk == 6;
-  return nch == 4 && (nsk == 2 || nsk == 4 || nsk == 6 || nsk == 8);  // (nf = 128: the 256-channel blocks)
+#define SW_CASE(NCH_, NSK_, MODE_) if (SW_IS(NCH_, NSK_, MODE_)) return true;
+  if (cout == 64) { SW_SHAPES_64(SW_CASE) return false; }
+  SW_SHAPES_128(SW_CASE)
+#undef SW_CASE
+  return false;
 }
 template <int RPW>
 int sw_dispatch128(const SwK& k, const ConvArgs& a, int nch, int nsk, int mode, hipStream_t st) {
-#define SW_CASE(NCH_, NSK_, MODE_) if (nch == NCH_ && nsk == NSK_ && mode == MODE_) return sw_launch<NCH_, NSK_, MODE_, RPW, 4>(k, a, st)
-  SW_CASE(1, 0, 0); SW_CASE(2, 0, 0);
-  SW_CASE(1, 0, 2); SW_CASE(2, 0, 2); SW_CASE(3, 0, 2); SW_CASE(4, 0, 2); SW_CASE(6, 0, 2); SW_CASE(8, 0, 2);
-  SW_CASE(2, 1, 2); SW_CASE(2, 2, 2); SW_CASE(2, 3, 2); SW_CASE(2, 4, 2); SW_CASE(2, 6, 2);
-  SW_CASE(4, 2, 2); SW_CASE(4, 4, 2); SW_CASE(4, 6, 2); SW_CASE(4, 8, 2);
+#define SW_CASE(NCH_, NSK_, MODE_) if (SW_IS(NCH_, NSK_, MODE_)) return sw_launch<NCH_, NSK_, MODE_, RPW, 4>(k, a, st);
+  SW_SHAPES_128(SW_CASE)
 #undef SW_CASE
   return -1;
 }
+int sw_dispatch64(const SwK& k, const ConvArgs& a, int nch, int nsk, int mode, hipStream_t st) {
+#define SW_CASE(NCH_, NSK_, MODE_) if (SW_IS(NCH_, NSK_, MODE_)) return sw_launch<NCH_, NSK_, MODE_, 4, 2>(k, a, st);
+  SW_SHAPES_64(SW_CASE)
+#undef SW_CASE
+  return -1;
+}
+#undef SW_IS
 }  // namespace
 
 // The layers this kernel can take: 16-bit 3x3, Cout = 128 / 256 (Cin = 64 .. 512 in 64-channel chunks: one tensor or the in-place
@@ -881,68 +861,33 @@ bool ds_conv_sw_supported(const ConvArgs& a) {
         a.ldy >= a.Cout && a.ldy % 8 == 0))
     return false;
   if (a.Cout == 64 && a.H % 8 != 0) return false;
-  if (a.x2 ? !(a.C1 % KC == 0 && a.C1 > 0 && a.C1 < a.Cin && a.ldx % 8 == 0 && a.ldx2 % 8 == 0) : a.ldx % 8 != 0) return false;
-  const bool gn = a.gn_scale || a.gn_acc1;
-  if (gn && !a.gn_act) return false;  // (affine without SiLU does not occur in front of a 3x3 convolution)
-  if (a.gn_acc1 && !(a.gn_groups > 0 && a.Cin % a.gn_groups == 0 && a.Cin / a.gn_groups <= (a.Cin > 256 ? 16 : 8) && (!a.x2 || a.gn_acc2)))
-    return false;
+  // (the prologue of the > 256-channel instantiations sums up to 16 channels per GroupNorm group)
+  if (!halo_concat_ok(a, KC, 8) || !halo_gn_ok(a, a.Cin > 256 ? 16 : 8) || !halo_addressing_ok(a, 2, false)) return false;
   int nsk = 0;
   if (a.sx) {
-    if (!(a.sw && a.sw_frag && !a.res && a.sCin % KC == 0 && a.sCin >= KC && a.sCin <= 8 * KC && a.ldsx % 8 == 0 &&
-          (!a.sx2 || (a.sC1 % KC == 0 && a.sC1 > 0 && a.sC1 < a.sCin && a.ldsx2 % 8 == 0))))
-      return false;
+    if (!(a.sw && a.sw_frag && !a.res && a.sCin % KC == 0 && a.sCin >= KC && a.sCin <= 8 * KC && halo_skip_split_ok(a, KC, 8))) return false;
     nsk = a.sCin / KC;
   } else if (a.res) {
     if (!(a.ident_frag && a.Cout >= 128 && a.ldr >= a.Cout && a.ldr % 8 == 0)) return false;
     nsk = a.Cout / KC;
   }
-  return sw_shape(a.Cout, a.Cin / KC, nsk, gn ? 2 : 0);
+  return sw_shape(a.Cout, a.Cin / KC, nsk, (a.gn_scale || a.gn_acc1) ? 2 : 0);
 }
 
 // rows: rows per wave of the 128-cout tiles, 8 (H % 8 == 0) or 4 (ConvPlan.sw_rows; the one 64-cout instantiation has 4)
 int ds_launch_conv_sw(const ConvArgs& a, int rows, hipStream_t st) {
   SwK k;
-  k.x = reinterpret_cast<const bf16_t*>(a.x); k.x_bs = a.x_bs; k.ldx = a.ldx; k.C1 = a.x2 ? a.C1 : a.Cin;
-  k.x2 = reinterpret_cast<const bf16_t*>(a.x2); k.x2_bs = a.x2_bs; k.ldx2 = a.x2 ? a.ldx2 : a.ldx;
+  halo_fill_common(k, a);
   k.wfrag = reinterpret_cast<const bf16_t*>(a.w_frag);
-  k.swfrag = nullptr;
   k.frag_step = (unsigned)(a.Cout / 32) * 1024u;
-  k.gn_scale = a.gn_scale; k.gn_shift = a.gn_shift;
-  k.gn_acc1 = a.gn_acc1; k.gn_acc2 = a.gn_acc2; k.gn_gamma = a.gn_gamma; k.gn_beta = a.gn_beta;
-  k.gn_groups = a.gn_groups; k.gn_inv_count = a.gn_inv_count; k.gn_eps = a.gn_eps;
-  k.bias = a.bias; k.bias_b = a.bias_b; k.bias_b_ld = a.bias_b_ld;
-  k.out_scale = a.out_scale;
-  k.y = reinterpret_cast<bf16_t*>(a.y); k.y_bs = a.y_bs; k.ldy = a.ldy;
-  k.stats = a.stats_acc;
-  k.sx = nullptr; k.sx_bs = 0; k.ldsx = 0; k.sC1 = 0; k.sx2 = nullptr; k.sx2_bs = 0; k.ldsx2 = 0;
-  int nsk = 0;
-  if (a.sx) {
-    k.sx = reinterpret_cast<const bf16_t*>(a.sx); k.sx_bs = a.sx_bs; k.ldsx = a.ldsx; k.sC1 = a.sx2 ? a.sC1 : a.sCin;
-    k.sx2 = reinterpret_cast<const bf16_t*>(a.sx2); k.sx2_bs = a.sx2_bs; k.ldsx2 = a.sx2 ? a.ldsx2 : a.ldsx;
-    k.swfrag = reinterpret_cast<const bf16_t*>(a.sw_frag);
-    nsk = a.sCin / KC;
-  } else if (a.res) {  // the residual [B][H][W][Cout] as a folded skip against the identity matrix (exact in the fp32 accumulators)
-    k.sx = reinterpret_cast<const bf16_t*>(a.res); k.sx_bs = a.res_bs; k.ldsx = a.ldr; k.sC1 = a.Cout; k.ldsx2 = a.ldr;
-    k.swfrag = reinterpret_cast<const bf16_t*>(a.ident_frag);
-    nsk = a.Cout / KC;
-  }
-  k.H = a.H; k.W = a.W; k.G = 0; k.cout = a.Cout; k.tiles_x = 0; k.tiles_per_img = 0;
-#ifdef SW_TIMING  // (profiling builds only: stores / loads outside the tensors)
-  k.dbg = getenv("DIFFSEP_SW_DBG") ? atoi(getenv("DIFFSEP_SW_DBG")) : 0;
-#else
-  k.dbg = 0;
-#endif
+  const int nsk = halo_fill_skip(k, a) / KC;
+  k.cout = a.Cout; k.ncb = a.Cout == 64 ? 1 : a.Cout / 128;
   const int mode = ((a.gn_scale || a.gn_acc1) && a.gn_act) ? 2 : 0;
   const int nch = a.Cin / KC;
   DS_CHECK(rows == 4 || (rows == 8 && a.H % 8 == 0), "conv3x3_sw: rows per wave must be 4, or 8 on whole 8-row tiles");
-  int rc = -1;
-  if (a.Cout == 64) {
-    k.ncb = 1;
-    if (nch == 3 && nsk == 0 && mode == 2) rc = sw_launch<3, 0, 2, 4, 2>(k, a, st);
-  } else {
-    k.ncb = a.Cout / 128;
-    rc = rows == 8 ? sw_dispatch128<8>(k, a, nch, nsk, mode, st) : sw_dispatch128<4>(k, a, nch, nsk, mode, st);
-  }
+  const int rc = a.Cout == 64 ? sw_dispatch64(k, a, nch, nsk, mode, st)
+                 : rows == 8  ? sw_dispatch128<8>(k, a, nch, nsk, mode, st)
+                              : sw_dispatch128<4>(k, a, nch, nsk, mode, st);
   DS_CHECK(rc >= 0, "conv3x3_sw: shape outside the instantiated set");
   return rc;
 }

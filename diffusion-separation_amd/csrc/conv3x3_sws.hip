@@ -42,23 +42,7 @@ constexpr int RPW = 4, RH = RPW / 2;  // pixel rows per wave, rows per half-phas
 #endif
 constexpr int RING = SWS_D;
 
-struct SwsK {
-  const float* x; long x_bs; int ldx; int C1;      // channels [0, C1) from x, [C1, Cin) from x2
-  const float* x2; long x2_bs; int ldx2;
-  const bf16_t* wfrag; const bf16_t* swfrag;       // ds_sws_frag_index order: [k-step][hi | lo][Cout / 32][lane][8]
-  unsigned frag_step;                              // bytes of one k-step: 2 planes x Cout / 32 KB
-  const float* gn_scale; const float* gn_shift;    // [B][Cin] or null
-  const long long* gn_acc1; const long long* gn_acc2; const float* gn_gamma; const float* gn_beta;
-  int gn_groups; float gn_inv_count; float gn_eps;
-  const float* bias; const float* bias_b; int bias_b_ld;
-  float out_scale;
-  float* y; long y_bs; int ldy;
-  long long* stats;
-  const float* sx; long sx_bs; int ldsx; int sC1;  // folded skip / residual: raw channels [0, sC1) from sx, the rest from sx2
-  const float* sx2; long sx2_bs; int ldsx2;
-  int H, W, G, ncb, cout, tiles_x, tiles_per_img;  // G blocks per image and cout block; ncb cout blocks; cout = the layer's
-  int dbg;
-};
+using SwsK = HaloK<float>;  // (conv3x3_halo.h)
 
 // NCH / NSK: 32-channel chunks of the 3x3 input / of the folded 1x1 skip; NCG: cout groups of 32 per block (4: one pixel group,
 // tile 4 x 32; 2: two pixel groups, tile 8 x 32)
@@ -222,8 +206,9 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
     TileG g;
     const int y0 = ty * TH, x0 = tx * TW;
     g.edge = (y0 == 0 ? 1u : 0u) | (y0 + TH == p.H ? 2u : 0u) | (x0 == 0 ? 4u : 0u) | (x0 + TW == p.W ? 8u : 0u);
-    // (no tile: the first pixel PAST the image — every offset pixel x pitch is then >= the tensor's size, and stays below 2^32 for
-    // every pitch; a constant like 0x3fffff times a 1 KB pitch plus a tile offset WRAPS into the tensor)
+    // (no tile: the first pixel PAST the image — every offset pixel x pitch is then >= the tensor's size, and stays below 2^31 for
+    // every pitch the launch uses: halo_addressing_ok in conv3x3_halo.h, which ds_conv_sws_supported asks; a constant like 0x3fffff
+    // times a 1 KB pitch plus a tile offset WRAPS into the tensor)
     g.pix0 = valid ? y0 * p.W + x0 : M;
     return g;
   };
@@ -486,111 +471,66 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
 }
 
 template <int NCH, int NSK, int MODE, int NCG>
-int sws_launch(const SwsK& k0, const ConvArgs& a, hipStream_t st) {
+int sws_launch(const SwsK& k, const ConvArgs& a, hipStream_t st) {
   using G = SwsGeom<NCH, NSK, NCG>;
-  SwsK k = k0;
-  const int tiles = (a.H / G::TH) * (a.W / TW);
-  int g = ds_num_cus() / (a.B * k.ncb);
-  if (g < 1) g = 1;
-  if (g > tiles) g = tiles;
-  k.G = g;
-  k.tiles_x = a.W / TW;
-  k.tiles_per_img = tiles;
-  auto kern = conv3x3_sws_kernel<NCH, NSK, MODE, NCG>;
-  DS_FUNC_LDS_ONCE(kern, G::LDS_TOTAL);
-  hipLaunchKernelGGL(kern, dim3(a.B * k.ncb * k.G), dim3(NT), G::LDS_TOTAL, st, k);
-  DS_LAUNCH_CHECK();
-  {
-    static char name[64] = {0};
-    if (!name[0]) snprintf(name, sizeof(name), "conv3x3_sws_kernel<%d,%d,%d,%d>", NCH, NSK, MODE, NCG);
-    ds_set_last_conv_kernel(name);
-  }
-  return 0;
+  static_assert(G::TH <= HALO_TH_MAX, "halo_addressing_ok covers the tile");
+  return halo_launch<conv3x3_sws_kernel<NCH, NSK, MODE, NCG>>(k, a, G::TH, halo_blocks_wanted(a, k.ncb), k.ncb, G::LDS_TOTAL, st,
+                                                             "conv3x3_sws_kernel", {NCH, NSK, MODE, NCG});
 }
 
-// (Cin / 32, skip or residual channels / 32) pairs instantiated per cout width: the layers of the >= 32-row levels of nf = 64 / 128
+// The instantiated set, written ONCE: (Cin / 32, skip or residual channels / 32, mode), the same for both cout widths (NCG): the
+// layers of the >= 32-row levels of nf = 64 / 128.  sws_shape and the dispatch are both generated from it.
+#define SWS_SHAPES(X)                                                                                                       \
+  X(2, 0, 0) X(4, 0, 0) X(8, 0, 0)            /* raw input (behind a resampling) */                                         \
+  X(2, 0, 2) X(4, 0, 2) X(6, 0, 2) X(8, 0, 2) /* Conv_0 of plain blocks (one tensor or a concat) */                         \
+  X(2, 2, 2) X(2, 4, 2) X(2, 6, 2)            /* 64 -> 64 + residual / skip on 64, 128, 192 raw channels */                 \
+  X(4, 2, 2) X(4, 4, 2) X(4, 6, 2) X(4, 8, 2) /* 128 -> 128 + residual / skip on 64 .. 256 raw channels */
+#define SWS_IS(NCH_, NSK_, MODE_) nch == NCH_ && nsk == NSK_ && mode == MODE_
+bool sws_shape(int nch, int nsk, int mode) {
+#define SWS_CASE(NCH_, NSK_, MODE_) if (SWS_IS(NCH_, NSK_, MODE_)) return true;
+  SWS_SHAPES(SWS_CASE)
+#undef SWS_CASE
+  return false;
+}
 template <int NCG>
 int sws_dispatch(const SwsK& k, const ConvArgs& a, int nch, int nsk, int mode, hipStream_t st) {
-#define SWS_CASE(NCH_, NSK_, MODE_) if (nch == NCH_ && nsk == NSK_ && mode == MODE_) return sws_launch<NCH_, NSK_, MODE_, NCG>(k, a, st)
-  SWS_CASE(2, 0, 0); SWS_CASE(4, 0, 0); SWS_CASE(8, 0, 0);                     // raw input (behind a resampling)
-  SWS_CASE(2, 0, 2); SWS_CASE(4, 0, 2); SWS_CASE(6, 0, 2); SWS_CASE(8, 0, 2);  // Conv_0 of plain blocks (one tensor or a concat)
-  SWS_CASE(2, 2, 2); SWS_CASE(2, 4, 2); SWS_CASE(2, 6, 2);                      // 64 -> 64 + residual / skip on 64, 128, 192 raw channels
-  SWS_CASE(4, 2, 2); SWS_CASE(4, 4, 2); SWS_CASE(4, 6, 2); SWS_CASE(4, 8, 2);  // 128 -> 128 + residual / skip on 64 .. 256 raw channels
+#define SWS_CASE(NCH_, NSK_, MODE_) if (SWS_IS(NCH_, NSK_, MODE_)) return sws_launch<NCH_, NSK_, MODE_, NCG>(k, a, st);
+  SWS_SHAPES(SWS_CASE)
 #undef SWS_CASE
   return -1;
 }
+#undef SWS_IS
 
 }  // namespace
 
-// The launches this kernel takes: fp32 tensors in split mode, 3x3, 64 / 128 / 256 couts, input channels and skip channels in the
-// instantiated set (sws_dispatch), whole tiles (W % 32 == 0, H % 8 == 0), fragment-major hi / lo weight copies at hand; a residual
-// needs the identity copy (ConvArgs.ident_frag).  Which of them it is given: ds_conv_plan.
-static bool sws_shape(int Cout, int nch, int nsk, int mode) {
-  if (!(Cout == 64 || Cout == 128 || Cout == 256)) return false;  // (256: two cout blocks of 128)
-  if (mode == 0) return nsk == 0 && (nch == 2 || nch == 4 || nch == 8);
-  if (nsk == 0) return nch == 2 || nch == 4 || nch == 6 || nch == 8;
-  if (nch == 2) return nsk == 2 || nsk == 4 || nsk == 6;
-  if (nch == 4) return nsk == 2 || nsk == 4 || nsk == 6 || nsk == 8;
-  return false;
-}
+// The launches this kernel takes: fp32 tensors in split mode, 3x3, 64 / 128 / 256 couts (256: two cout blocks of 128), input
+// channels and skip channels in the instantiated set (SWS_SHAPES), whole tiles (W % 32 == 0, H % 8 == 0), fragment-major hi / lo
+// weight copies at hand; a residual needs the identity copy (ConvArgs.ident_frag).  Which of them it is given: ds_conv_plan.
 bool ds_conv_sws_supported(const ConvArgs& a) {
   if (!(a.dtype == DS_F32 && a.split && a.taps == 9 && a.Cin % KC == 0 && a.w_frag && a.w_bs == 0 && a.bias_mode == 0 && !a.div_b &&
-        a.W % TW == 0 && a.H % 8 == 0 && a.H >= 8 && a.ldy >= a.Cout && a.ldy % 4 == 0 && a.Cout <= 256))
+        a.W % TW == 0 && a.H % 8 == 0 && a.H >= 8 && a.ldy >= a.Cout && a.ldy % 4 == 0 && (a.Cout == 64 || a.Cout == 128 || a.Cout == 256)))
     return false;
-  if (a.x2 ? !(a.C1 % KC == 0 && a.C1 > 0 && a.C1 < a.Cin && a.ldx % 4 == 0 && a.ldx2 % 4 == 0) : a.ldx % 4 != 0) return false;
-  const bool gn = a.gn_scale || a.gn_acc1;
-  if (gn && !a.gn_act) return false;
-  if (a.gn_acc1 && !(a.gn_groups > 0 && a.Cin % a.gn_groups == 0 && a.Cin / a.gn_groups <= 8 && (!a.x2 || a.gn_acc2))) return false;
+  if (!halo_concat_ok(a, KC, 4) || !halo_gn_ok(a, 8) || !halo_addressing_ok(a, 4, false)) return false;
   int nsk = 0;
   if (a.sx) {
-    if (!(a.sw && a.sw_frag && !a.res && a.sCin % KC == 0 && a.ldsx % 4 == 0 &&
-          (!a.sx2 || (a.sC1 % KC == 0 && a.sC1 > 0 && a.sC1 < a.sCin && a.ldsx2 % 4 == 0))))
-      return false;
+    if (!(a.sw && a.sw_frag && !a.res && a.sCin % KC == 0 && halo_skip_split_ok(a, KC, 4))) return false;
     nsk = a.sCin / KC;
   } else if (a.res) {
     if (!(a.ident_frag && a.ldr >= a.Cout && a.ldr % 4 == 0)) return false;
     nsk = a.Cout / KC;
   }
-  return sws_shape(a.Cout, a.Cin / KC, nsk, gn ? 2 : 0);
+  return sws_shape(a.Cin / KC, nsk, (a.gn_scale || a.gn_acc1) ? 2 : 0);
 }
 
 int ds_launch_conv_sws(const ConvArgs& a, hipStream_t st) {
   SwsK k;
-  k.x = reinterpret_cast<const float*>(a.x); k.x_bs = a.x_bs; k.ldx = a.ldx; k.C1 = a.x2 ? a.C1 : a.Cin;
-  k.x2 = reinterpret_cast<const float*>(a.x2); k.x2_bs = a.x2_bs; k.ldx2 = a.x2 ? a.ldx2 : a.ldx;
+  halo_fill_common(k, a);
   k.wfrag = reinterpret_cast<const bf16_t*>(a.w_frag);
-  k.swfrag = nullptr;
   k.frag_step = (unsigned)(a.Cout / 32) * 2048u;
-  k.gn_scale = a.gn_scale; k.gn_shift = a.gn_shift;
-  k.gn_acc1 = a.gn_acc1; k.gn_acc2 = a.gn_acc2; k.gn_gamma = a.gn_gamma; k.gn_beta = a.gn_beta;
-  k.gn_groups = a.gn_groups; k.gn_inv_count = a.gn_inv_count; k.gn_eps = a.gn_eps;
-  k.bias = a.bias; k.bias_b = a.bias_b; k.bias_b_ld = a.bias_b_ld;
-  k.out_scale = a.out_scale;
-  k.y = reinterpret_cast<float*>(a.y); k.y_bs = a.y_bs; k.ldy = a.ldy;
-  k.stats = a.stats_acc;
-  k.sx = nullptr; k.sx_bs = 0; k.ldsx = 0; k.sC1 = 0; k.sx2 = nullptr; k.sx2_bs = 0; k.ldsx2 = 0;
-  int nsk = 0;
-  if (a.sx) {
-    k.sx = reinterpret_cast<const float*>(a.sx); k.sx_bs = a.sx_bs; k.ldsx = a.ldsx; k.sC1 = a.sx2 ? a.sC1 : a.sCin;
-    k.sx2 = reinterpret_cast<const float*>(a.sx2); k.sx2_bs = a.sx2_bs; k.ldsx2 = a.sx2 ? a.ldsx2 : a.ldsx;
-    k.swfrag = reinterpret_cast<const bf16_t*>(a.sw_frag);
-    nsk = a.sCin / KC;
-  } else if (a.res) {  // the residual [B][H][W][Cout] as a folded skip against the identity matrix
-    k.sx = reinterpret_cast<const float*>(a.res); k.sx_bs = a.res_bs; k.ldsx = a.ldr; k.sC1 = a.Cout; k.ldsx2 = a.ldr;
-    k.swfrag = reinterpret_cast<const bf16_t*>(a.ident_frag);
-    nsk = a.Cout / KC;
-  }
-  k.H = a.H; k.W = a.W; k.G = 0; k.cout = a.Cout; k.tiles_x = 0; k.tiles_per_img = 0;
-  k.dbg = 0;
+  const int nsk = halo_fill_skip(k, a) / KC;
+  k.cout = a.Cout; k.ncb = a.Cout == 64 ? 1 : a.Cout / 128;
   const int mode = ((a.gn_scale || a.gn_acc1) && a.gn_act) ? 2 : 0;
-  int rc;
-  if (a.Cout == 64) {
-    k.ncb = 1;
-    rc = sws_dispatch<2>(k, a, a.Cin / KC, nsk, mode, st);
-  } else {
-    k.ncb = a.Cout / 128;
-    rc = sws_dispatch<4>(k, a, a.Cin / KC, nsk, mode, st);
-  }
+  const int rc = a.Cout == 64 ? sws_dispatch<2>(k, a, a.Cin / KC, nsk, mode, st) : sws_dispatch<4>(k, a, a.Cin / KC, nsk, mode, st);
   DS_CHECK(rc >= 0, "conv3x3_sws: shape outside the instantiated set");
   return rc;
 }

@@ -961,6 +961,8 @@ int ds_launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
     long mld = a.ldx > a.ldy ? a.ldx : a.ldy;
     if (a.x2 && a.ldx2 > mld) mld = a.ldx2;
     if (a.res && a.ldr > mld) mld = a.ldr;
+    if (a.sx && a.ldsx > mld) mld = a.ldsx;  // (a folded skip's sources are often the widest tensors of the launch)
+    if (a.sx && a.sx2 && a.ldsx2 > mld) mld = a.ldsx2;
     DS_CHECK(M * mld * esz < 2147483647L, "conv: image too large for 32-bit buffer offsets");
     DS_CHECK((long)a.Cout * a.taps * a.Cin * esz < 2147483647L, "conv: weight tensor too large");
   }

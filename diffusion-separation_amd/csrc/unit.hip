@@ -166,6 +166,32 @@ extern "C" int32_t diffsep_conv2d(const void* x, const void* w, const float* bia
                               /*gn_acc1, gn_acc2, gn_gamma, gn_beta, gn_groups*/ nullptr, nullptr, nullptr, nullptr, 0, stream);
 }
 
+// The ConvArgs of the two 3x3 unit entries below, as far as they agree: dense NHWC operands (each tensor's leading dimension is its
+// channel count) — the input or the in-place concat of two, the optional folded-skip sources, the optional residual, the output —
+// B / Cout / taps = 9, the dtype split and the process options.  Weights, GroupNorm, bias, scale and statistics: the caller's.
+static ConvArgs conv3x3_dense_args(const void* x, const void* x2, int C1, const void* sx, const void* sx2, int sC1, int sCin,
+                                   const void* res, void* y, int B, int H, int W, int Cin, int Cout, int dtype) {
+  ConvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.opts = ds_default_opts();
+  const int c1 = x2 ? C1 : Cin;
+  Tn xin = view(x, H, W, Cin, c1);
+  xin.p2 = const_cast<void*>(x2); xin.ld2 = Cin - c1; xin.C1 = x2 ? C1 : 0;
+  conv_input(a, xin);
+  if (sx) {
+    const int s1 = sx2 ? sC1 : sCin;
+    Tn sin = view(sx, H, W, sCin, s1);
+    sin.p2 = const_cast<void*>(sx2); sin.ld2 = sCin - s1; sin.C1 = sx2 ? sC1 : 0;
+    conv_skip_input(a, sin);
+  }
+  conv_residual(a, view(res, H, W, Cout, Cout));
+  conv_output(a, view(y, H, W, Cout, Cout));
+  a.B = B; a.Cout = Cout; a.taps = 9;
+  const DtypeSplit ds = split_dtype(dtype);
+  a.dtype = ds.dtype; a.split = ds.split;
+  return a;
+}
+
 // Unit entry of the streamed-weight 3x3 kernel (conv3x3_sw.hip), whatever the dispatch would have chosen for the shape: dense
 // NHWC tensors, weights already in the fragment-major order of diffsep_frag_index (include/diffsep_hip.h).
 extern "C" int32_t diffsep_conv3x3_streamed(const void* x, const void* x2, int32_t C1, const float* gn_scale,
@@ -182,14 +208,8 @@ extern "C" int32_t diffsep_conv3x3_streamed(const void* x, const void* x2, int32
   DS_CHECK(B > 0 && H > 0 && W > 0, "conv3x3_streamed: empty problem");
   DS_CHECK(!x2 || (C1 > 0 && C1 < Cin), "conv3x3_streamed: bad concat split");
   DS_CHECK(!sx || (sw_frag && sCin > 0 && (!sx2 || (sC1 > 0 && sC1 < sCin))), "conv3x3_streamed: bad skip operands");
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.opts = ds_default_opts();
+  ConvArgs a = conv3x3_dense_args(x, x2, C1, sx, sx2, sC1, sCin, res, y, B, H, W, Cin, Cout, dtype);
   a.stats_acc = (long long*)stats;
-  const int c1 = x2 ? C1 : Cin;  // dense sources: each one's leading dimension is its channel count
-  Tn xin = view(x, H, W, Cin, c1);
-  xin.p2 = const_cast<void*>(x2); xin.ld2 = Cin - c1; xin.C1 = x2 ? C1 : 0;
-  conv_input(a, xin);
   a.gn_scale = gn_scale; a.gn_shift = gn_shift; a.gn_act = (gn_scale || gn_acc1) ? 1 : 0;
   if (gn_acc1) {  // GroupNorm of the input from its producers' accumulators, as diffsep_conv2d_fused
     a.gn_acc1 = (const long long*)gn_acc1; a.gn_acc2 = (const long long*)gn_acc2; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta;
@@ -197,21 +217,10 @@ extern "C" int32_t diffsep_conv3x3_streamed(const void* x, const void* x2, int32
   }
   a.w = w_frag; a.w_frag = w_frag; a.w_bs = 0;
   a.bias = bias; a.bias_b = bias_b; a.bias_b_ld = Cout; a.bias_mode = 0;
-  if (sx) {
-    const int s1 = sx2 ? sC1 : sCin;
-    Tn sin = view(sx, H, W, sCin, s1);
-    sin.p2 = const_cast<void*>(sx2); sin.ld2 = sCin - s1; sin.C1 = sx2 ? sC1 : 0;
-    conv_skip_input(a, sin);
-    a.sw = sw_frag; a.sw_frag = sw_frag;
-  }
+  if (sx) { a.sw = sw_frag; a.sw_frag = sw_frag; }
   a.out_scale = out_scale;
-  conv_output(a, view(y, H, W, Cout, Cout));
-  a.B = B; a.Cout = Cout; a.taps = 9;
-  const DtypeSplit ds = split_dtype(dtype);
-  a.dtype = ds.dtype; a.split = ds.split;
-  DS_CHECK((long)H * W * (Cin > Cout ? Cin : Cout) * 4 < 2147483647L, "conv3x3_streamed: image too large for 32-bit buffer offsets");
-  conv_residual(a, view(res, H, W, Cout, Cout));
   a.ident_frag = ident_frag;
+  // (an image too large for the kernels' 32-bit offsets is no supported shape either: halo_addressing_ok, conv3x3_halo.h)
   if (a.split) {  // fp32 tensors, hi / lo fragment copies: conv3x3_sws.hip
     DS_CHECK(ds_conv_sws_supported(a), "conv3x3_streamed: shape outside the split kernel's instantiations (Cout = 64 / 128 / 256, Cin = 64 .. 256 "
                                        "by 64, W % 32 == 0, H % 8 == 0; skip / residual channels 64 .. 256 by 64 behind GroupNorm; raw input: Cin <= 128)");
@@ -234,31 +243,14 @@ extern "C" int32_t diffsep_conv3x3_regweight(const void* x, const void* x2, int3
   DS_CHECK(B > 0 && H > 0 && W > 0, "conv3x3_regweight: empty problem");
   DS_CHECK(!x2 || (C1 > 0 && C1 < Cin), "conv3x3_regweight: bad concat split");
   DS_CHECK(!sx || (sw && !res && sCin > 0 && (!sx2 || (sC1 > 0 && sC1 < sCin))), "conv3x3_regweight: bad skip operands");
-  DS_CHECK((long)H * W * (Cin > Cout ? Cin : Cout) * 2 < 2147483647L, "conv3x3_regweight: image too large for 32-bit buffer offsets");
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.opts = ds_default_opts();
+  ConvArgs a = conv3x3_dense_args(x, x2, C1, sx, sx2, sC1, sCin, res, y, B, H, W, Cin, Cout, dtype);
   a.stats_acc = (long long*)stats;
-  const int c1 = x2 ? C1 : Cin;  // dense sources: each one's leading dimension is its channel count
-  Tn xin = view(x, H, W, Cin, c1);
-  xin.p2 = const_cast<void*>(x2); xin.ld2 = Cin - c1; xin.C1 = x2 ? C1 : 0;
-  conv_input(a, xin);
   a.gn_scale = gn_scale; a.gn_shift = gn_shift; a.gn_act = gn_scale ? 1 : 0;
   a.w = w; a.w_bs = 0; a.w_chunked = w_chunk;
   a.bias = bias; a.bias_b = bias_b; a.bias_b_ld = Cout; a.bias_mode = 0;
-  if (sx) {
-    const int s1 = sx2 ? sC1 : sCin;
-    Tn sin = view(sx, H, W, sCin, s1);
-    sin.p2 = const_cast<void*>(sx2); sin.ld2 = sCin - s1; sin.C1 = sx2 ? sC1 : 0;
-    conv_skip_input(a, sin);
-    a.sw = sw; a.sw_chunked = 0;
-  }
-  conv_residual(a, view(res, H, W, Cout, Cout));
+  if (sx) { a.sw = sw; a.sw_chunked = 0; }
   a.out_scale = out_scale;
-  conv_output(a, view(y, H, W, Cout, Cout));
-  a.B = B; a.Cout = Cout; a.taps = 9;
-  const DtypeSplit ds = split_dtype(dtype);
-  a.dtype = ds.dtype; a.split = ds.split;
+  // (an image too large for the kernel's 32-bit offsets is no supported shape either: halo_addressing_ok, conv3x3_halo.h)
   DS_CHECK(!a.split && ds_conv_rw_supported(a), "conv3x3_regweight: shape outside the kernel's instantiations (16-bit, 64 / 128 -> 64 or "
                                                 "128 -> 128, H >= 32, H % 8 == 0, W % 32 == 0; skip: 64 / 128 (/ 192 at 64 -> 64) raw channels)");
   return ds_launch_conv_rw(a, (hipStream_t)stream);

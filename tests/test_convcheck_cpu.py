@@ -137,14 +137,20 @@ def test_multi_tile_batch_against_the_launchers():
     import os
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "diffusion-separation_amd", "csrc")
-    rw, ws = (open(os.path.join(csrc, f)).read() for f in ("conv3x3_rw.hip", "conv3x3_ws.hip"))
+    rw, ws, halo = (open(os.path.join(csrc, f)).read() for f in ("conv3x3_rw.hip", "conv3x3_ws.hip", "conv3x3_halo.h"))
+    # (the register-weight launcher takes its start value, its tile count and the clamp from the halo-tile kernels' shared launch tail)
     body = re.search(r"int rw_blocks_per_image\(.*?\n}", rw, re.S).group(0)
-    assert "int g = ds_num_cus() / a.B;" in body and "if (g < 1) g = 1;" in body and "if (g > tiles) g = tiles;" in body
-    assert "const int tiles = (a.H / G::TH) * (a.W / TW);" in rw and "static constexpr int TH = PGN * RPW" in rw
+    assert "int g = halo_blocks_wanted(a, 1);" in body and "rw_blocks_per_image(a, halo_tiles(a, G::TH))" in rw
+    body = re.search(r"inline int halo_blocks_wanted\(.*?\n}", halo, re.S).group(0)
+    assert "const int g = ds_num_cus() / (a.B * ncb);" in body
+    assert "inline int halo_tiles(const ConvArgs& a, int tile_h) { return (a.H / tile_h) * (a.W / TW); }" in halo
+    body = re.search(r"\nint halo_launch\(.*?\n}", halo, re.S).group(0)
+    assert "const int tiles = halo_tiles(a, tile_h);" in body and "k.G = g < 1 ? 1 : (g > tiles ? tiles : g);" in body
+    assert "static constexpr int TH = PGN * RPW" in rw
     body = re.search(r"int ws_blocks_per_image\(.*?\n}", ws, re.S).group(0)
     assert "int g = ds_num_cus() / a.B;" in body and "if (g < 1) g = 1;" in body and "if (g > tiles) g = tiles;" in body
     assert "constexpr int TH = 8, TW = 32;" in ws and "const int tiles = (a.H / TH) * (a.W / TW);" in body
-    assert "constexpr int TW = 32" in open(os.path.join(csrc, "conv3x3_halo.h")).read()
+    assert "constexpr int TW = 32" in halo
 
     def blocks(Bn, tiles, cus):  # the launchers' lines
         g = cus // Bn

@@ -223,6 +223,39 @@ def test_rw_conv3x3_zero_padding_is_exact():
     assert float((y.float().cpu() - ref).abs().max()) < 0.05
 
 
+@pytest.mark.parametrize("dt,kind", [(torch.bfloat16, "bf16"), (torch.float16, "f16")])
+def test_rw_refuses_one_kilobyte_output_pitch(dt, kind):
+    """The kernel marks "no tile" with the constant pixel index 0x3fffff, which is safe only while every pixel pitch stays under
+    1 KB (halo_addressing_ok in conv3x3_halo.h): at cout_pad = 512 (a 1024-byte output pitch) the epilogue of the "previous tile"
+    of a block's first tile would store INTO the image.  So the launch must not reach the kernel: under rw_small (a) another
+    kernel runs, (b) the lanes 64 .. 511 of every pixel keep the marker they were prefilled with, (c) lanes 0 .. 63 equal, bit for
+    bit, the same call with rw_small off, which runs the same fallback kernel.  The dense launch of the same shape still runs on
+    conv3x3_rw_kernel<1,4,0,0,2>: the refusal is the pitch and nothing else."""
+    from diffsep_amd import _lib
+    L = _lib.lib(kind)
+    B, H, W, C, MARK = 2, 32, 32, 64, 3.0
+    x = rnd("rwpitch.x", (B, H, W, C)).to(DEV, dt)
+    wp = ops.pack_conv_weight(rnd("rwpitch.w", (64, C, 3, 3), 1.0 / math.sqrt(9 * C)), dt).to(DEV)
+    try:
+        _lib.check(L.diffsep_set_option(b"rw_small", 1), L)
+        ops.conv2d_fused(x, wp, None, 64, 3, gn_act=0)
+        assert ops.last_conv_kernel(kind) == "conv3x3_rw_kernel<1,4,0,0,2>"
+        y_on = torch.full((B, H, W, 512), MARK, dtype=dt, device=DEV)
+        ops.conv2d_fused(x, wp, None, 64, 3, gn_act=0, cout_pad=512, out=y_on)
+        name_on = ops.last_conv_kernel(kind)
+        _lib.check(L.diffsep_set_option(b"rw_small", 0), L)
+        y_off = torch.full((B, H, W, 512), MARK, dtype=dt, device=DEV)
+        ops.conv2d_fused(x, wp, None, 64, 3, gn_act=0, cout_pad=512, out=y_off)
+        name_off = ops.last_conv_kernel(kind)
+    finally:
+        _lib.check(L.diffsep_set_option(b"rw_small", 1), L)  # (this module's setting: the fixture at the top)
+    assert not name_on.startswith("conv3x3_rw_kernel"), name_on
+    assert name_on == name_off
+    assert bool((y_on[..., 64:] == MARK).all()), "lanes past Cout were written"
+    assert torch.equal(y_on[..., :64], y_off[..., :64])
+    assert bool(y_on[..., :64].float().abs().max() > 0)
+
+
 @pytest.mark.parametrize("C1,C2", [(64, 0), (64, 64)])
 def test_rw_conv3x3_groupnorm_from_producer_accumulators(C1, C2):
     B, H, W = 3, 32, 64
