@@ -482,6 +482,23 @@ int ds_launch_ode_stage(const OdeArgs& a, hipStream_t st, int* nblk = nullptr);
 int ds_launch_ode_norm_final(const double* part, int nblk, long n, double* out, hipStream_t st);
 int ds_launch_ode_cast(const float* x, double* y, long n, hipStream_t st);   // y = (double) x
 int ds_launch_ode_round(const double* y, float* x, long n, hipStream_t st);  // x = (float) y
+// The same pass with one step controller per utterance of a zero-padded batch (ode.hip, ode_stage_each_kernel): a.h, a.t,
+// a.tt, a.t_next and a.part's layout are replaced by device tables [B]; a.t_next_out[b] = tnext[b] where tnext != null.
+//   active[b] == 0: utterance b is skipped (nothing of it is read or written);
+//   samples t >= lens[b] are never read; kout, xo and yo are written as exact zeros there;
+//   mode 3: the partial sums of utterance b go to part[b][2 blk + q] (rows of 2 DS_ODE_MAX_BLOCKS), in the summation tree
+//   ds_launch_ode_stage + ds_launch_ode_norm_final build for B = 1, T = lens[b] — whatever B, b and the padded T are.
+struct OdeEachArgs {
+  OdeArgs a;
+  const double* h; const float* tnext; const int* active; const int* lens;
+};
+int ds_launch_ode_stage_each(const OdeEachArgs& e, hipStream_t st);
+// norms[b][q] = sqrt(sum_blk part[b][2 blk + q]) / sqrt(S lens[b]) for the active utterances (the others keep theirs)
+int ds_launch_ode_norm_final_each(const double* part, const int* lens, const int* active, int B, int S, double* norms,
+                                  hipStream_t st);
+// the step accepted (active[b] and norms[b][0] < 1): y[b] <- ynew[b], k0[b] <- kns[b]; every other utterance untouched
+int ds_launch_ode_commit_each(double* y, const double* ynew, float* k0, const float* kns, const double* norms,
+                              const int* active, int B, int S, long T, hipStream_t st);
 
 // time embedding: y[b][o] = sum_k act_in(x[b][k]) * W[o][k] + bias[o]   (fp32)
 int ds_launch_linear(const float* x, const float* W, const float* bias, float* y, int B, int K, int O, int silu_in,

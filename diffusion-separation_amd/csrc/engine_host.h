@@ -326,6 +326,7 @@ struct diffsep_engine {
   char* ode_buf = nullptr;
   size_t ode_cap = 0;
   PinnedStage ode_pin;  // readback of the norms
+  PinnedStage ode_tab_pin;  // diffsep_ode_sample_each: staging of the per-utterance tables of one step attempt
 };
 
 // One launch (or launch sequence) `body` on st, bracketed by two events when the engine is inside a profile_begin .. profile_end

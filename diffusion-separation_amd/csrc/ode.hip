@@ -264,6 +264,267 @@ int ds_launch_ode_round(const double* y, float* x, long n, hipStream_t st) {
   return 0;
 }
 
+// ------------------------------------------------------------------ one step controller per utterance
+// The passes above on a zero-padded batch of utterances that are B independent ODE systems (diffsep_ode_sample_each): the
+// step size, the times, whether the utterance still integrates and its length come from device tables [B].  What utterance
+// b computes — every stage input, and the summation tree of its two norms — is what ode_stage_kernel +
+// ode_norm_final_kernel compute for it alone (B = 1, T = lens[b]): a thread item is 4 consecutive samples x all sources
+// when lens[b] % 4 == 0 and one sample otherwise, nb = min(cdiv(items, 256), DS_ODE_MAX_BLOCKS) blocks of the row's grid
+// stride over the items with a stride of nb * 256, and the partials are reduced in the same order.  None of that depends
+// on B, b or the padded T; rows that are not 16-byte aligned (T % 4 != 0) keep the item shape and load by element.
+template <int V, bool VEC> __device__ inline void ldfe(const float* p, float* v) {
+  if constexpr (VEC) {
+    ldf<4>(p, v);
+  } else {
+#pragma unroll
+    for (int i = 0; i < V; ++i) v[i] = p[i];
+  }
+}
+template <int V, bool VEC> __device__ inline void stfe(float* p, const float* v) {
+  if constexpr (VEC) {
+    stf<4>(p, v);
+  } else {
+#pragma unroll
+    for (int i = 0; i < V; ++i) p[i] = v[i];
+  }
+}
+template <int V, bool VEC> __device__ inline void ldde(const double* p, double* v) {
+  if constexpr (VEC) {
+    ldd<4>(p, v);
+  } else {
+#pragma unroll
+    for (int i = 0; i < V; ++i) v[i] = p[i];
+  }
+}
+template <int V, bool VEC> __device__ inline void stde(double* p, const double* v) {
+  if constexpr (VEC) {
+    std_<4>(p, v);
+  } else {
+#pragma unroll
+    for (int i = 0; i < V; ++i) p[i] = v[i];
+  }
+}
+
+// the items of utterance b that block blockIdx.x of its nb blocks owns: the loop body of ode_stage_kernel, operation for
+// operation, with the utterance's own t and h
+template <int V, bool VEC>
+__device__ inline void ode_each_items(const OdeEachArgs& e, int b, long len, long nb, double& q0, double& q1) {
+  const OdeArgs& a = e.a;
+  const int S = a.S;
+  const long T = a.T, items = len / V;
+  const double h = a.mode ? e.h[b] : 0.0;
+  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += nb * 256) {
+    const long t0 = it * V;
+    float kd[DS_MAX_SRC][V];
+    if (a.kout) {
+      float xv[DS_MAX_SRC][V];
+#pragma unroll
+      for (int s = 0; s < DS_MAX_SRC; ++s)
+        if (s < S) ldfe<V, VEC>(a.x + ((long)b * S + s) * T + t0, xv[s]);
+      const float g0 = sde_g_of_t(a.s, a.tt[b]);
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        float xs[DS_MAX_SRC], f[DS_MAX_SRC];
+#pragma unroll
+        for (int s = 0; s < DS_MAX_SRC; ++s) xs[s] = s < S ? xv[s][v] : 0.f;
+        sde_mix_drift(a.s, xs, f, S);
+#pragma unroll
+        for (int s = 0; s < DS_MAX_SRC; ++s)
+          if (s < S) kd[s][v] = f[s];
+      }
+#pragma unroll
+      for (int s = 0; s < DS_MAX_SRC; ++s) {
+        if (s >= S) continue;
+        const long o = ((long)b * S + s) * T + t0;
+        float sc[V];
+        ldfe<V, VEC>(a.score + o, sc);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const float g = a.smix ? g0 * a.smix[(long)b * T + t0 + v] : g0;
+          kd[s][v] = kd[s][v] - g * g * sc[v] * 0.5f;
+        }
+        stfe<V, VEC>(a.kout + o, kd[s]);
+      }
+    }
+    if (a.mode == 0) continue;
+#pragma unroll
+    for (int s = 0; s < DS_MAX_SRC; ++s) {
+      if (s >= S) continue;
+      const long o = ((long)b * S + s) * T + t0;
+      double yv[V], acc[V];
+      ldde<V, VEC>(a.y + o, yv);
+#pragma unroll
+      for (int v = 0; v < V; ++v) acc[v] = 0.0;
+      for (int j = 0; j < a.nk; ++j) {
+        float kv[V];
+        if (j == a.kidx) {
+#pragma unroll
+          for (int v = 0; v < V; ++v) kv[v] = kd[s][v];
+        } else {
+          ldfe<V, VEC>(a.k[j] + o, kv);
+        }
+        const double cj = a.c[j];
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[v] = acc[v] + cj * (double)kv[v];
+      }
+      if (a.mode == 1) {
+        float xo[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) xo[v] = (float)(yv[v] + acc[v] * h);
+        stfe<V, VEC>(a.xo + o, xo);
+      } else if (a.mode == 2) {
+        double yn[V];
+        float xo[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          yn[v] = yv[v] + h * acc[v];
+          xo[v] = (float)yn[v];
+        }
+        stde<V, VEC>(a.yo + o, yn);
+        if (a.xo) stfe<V, VEC>(a.xo + o, xo);
+      } else {
+        double yn[V];
+        if (a.ynew) ldde<V, VEC>(a.ynew + o, yn);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const double m = a.ynew ? fmax(fabs(yv[v]), fabs(yn[v])) : fabs(yv[v]);
+          const double scale = a.atol + m * a.rtol;
+          const double d = (acc[v] * h) / scale;
+          const double dy = yv[v] / scale;
+          q0 = q0 + d * d;
+          q1 = q1 + dy * dy;
+        }
+      }
+    }
+  }
+}
+
+// blocks of an utterance's row of the grid that its summation tree needs: min(cdiv(items, 256), DS_ODE_MAX_BLOCKS)
+__device__ inline long ode_each_blocks(long len) {
+  const long items = len % 4 == 0 ? len / 4 : len;
+  const long nb = (items + 255) / 256;
+  return nb < DS_ODE_MAX_BLOCKS ? nb : DS_ODE_MAX_BLOCKS;
+}
+
+// grid (min(cdiv(T, 256), DS_ODE_MAX_BLOCKS), B): row b of the grid is utterance b; vec: T % 4 == 0 and every tensor 16-byte aligned
+__global__ __launch_bounds__(256) void ode_stage_each_kernel(OdeEachArgs e, int vec) {
+  __shared__ double sh[2][4];
+  const OdeArgs& a = e.a;
+  const int b = blockIdx.y;
+  if (!e.active[b]) return;
+  const int S = a.S;
+  const long T = a.T, len = e.lens[b];
+  if (len < 1 || len > T) return;  // (the drivers check the lengths on the host; a bad table entry touches nothing)
+  if (e.tnext && blockIdx.x == 0 && threadIdx.x == 0) a.t_next_out[b] = e.tnext[b];
+  const long nb = ode_each_blocks(len);
+  double q0 = 0.0, q1 = 0.0;
+  if (blockIdx.x < nb) {
+    if (len % 4 != 0) ode_each_items<1, false>(e, b, len, nb, q0, q1);
+    else if (vec) ode_each_items<4, true>(e, b, len, nb, q0, q1);
+    else ode_each_items<4, false>(e, b, len, nb, q0, q1);
+  }
+  // the zero tail of what this pass writes (every block of the row)
+  const long tail = T - len;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < tail * S; i += (long)gridDim.x * 256) {
+    const int s = (int)(i / tail);
+    const long o = ((long)b * S + s) * T + len + (i - (long)s * tail);
+    if (a.kout) a.kout[o] = 0.f;
+    if ((a.mode == 1 || a.mode == 2) && a.xo) a.xo[o] = 0.f;
+    if (a.mode == 2) a.yo[o] = 0.0;
+  }
+  if (a.mode != 3 || blockIdx.x >= nb) return;
+  q0 = wave_sum_d(q0);
+  q1 = wave_sum_d(q1);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) { sh[0][w] = q0; sh[1][w] = q1; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r0 = 0.0, r1 = 0.0;
+    for (int i = 0; i < 4; ++i) { r0 = r0 + sh[0][i]; r1 = r1 + sh[1][i]; }
+    double* part = a.part + (long)b * 2 * DS_ODE_MAX_BLOCKS;
+    part[2 * blockIdx.x] = r0;
+    part[2 * blockIdx.x + 1] = r1;
+  }
+}
+
+// grid (B): ode_norm_final_kernel on the slab of utterance b with its own block count and n = S lens[b]
+__global__ __launch_bounds__(256) void ode_norm_final_each_kernel(const double* __restrict__ part_all,
+                                                                  const int* __restrict__ lens,
+                                                                  const int* __restrict__ active, int S,
+                                                                  double* __restrict__ norms) {
+  __shared__ double sh[2][4];
+  const int b = blockIdx.x;
+  if (!active[b]) return;
+  const long len = lens[b];
+  if (len < 1) return;
+  const int nblk = (int)ode_each_blocks(len);
+  const double* part = part_all + (long)b * 2 * DS_ODE_MAX_BLOCKS;
+  double r[2] = {0.0, 0.0};
+  for (int i = threadIdx.x; i < nblk; i += 256) { r[0] = r[0] + part[2 * i]; r[1] = r[1] + part[2 * i + 1]; }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int q = 0; q < 2; ++q) {
+    const double v = wave_sum_d(r[q]);
+    if (lane == 0) sh[q][w] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    double s = 0.0;
+    for (int i = 0; i < 4; ++i) s = s + sh[threadIdx.x][i];
+    norms[2 * b + threadIdx.x] = sqrt(s) / sqrt((double)((long)S * len));
+  }
+}
+
+// grid (x, B): the accepted utterances take their step (whole rows: the tails of y_new and K[ns] are zero like those of y, K[0])
+__global__ __launch_bounds__(256) void ode_commit_each_kernel(double* __restrict__ y, const double* __restrict__ ynew,
+                                                              float* __restrict__ k0, const float* __restrict__ kns,
+                                                              const double* __restrict__ norms,
+                                                              const int* __restrict__ active, long n) {
+  const int b = blockIdx.y;
+  if (!active[b] || !(norms[2 * b] < 1.0)) return;
+  const long o = (long)b * n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    y[o + i] = ynew[o + i];
+    k0[o + i] = kns[o + i];
+  }
+}
+
+int ds_launch_ode_stage_each(const OdeEachArgs& e, hipStream_t st) {
+  const OdeArgs& a = e.a;
+  DS_CHECK(a.S >= 1 && a.S <= DS_MAX_SRC && a.B >= 1 && a.B <= 65535 && a.T >= 1 && a.T <= 0x7fffffffL, "ode each: bad shape");
+  DS_CHECK(a.nk >= 0 && a.nk <= DS_ODE_MAX_K && a.kidx < a.nk && (a.kidx < 0 || a.kout), "ode each: bad stage combination");
+  DS_CHECK(a.mode >= 0 && a.mode <= 3, "ode each: bad mode");
+  DS_CHECK(e.active && e.lens && (a.mode == 0 || e.h), "ode each: the tables h, active and lengths are needed");
+  DS_CHECK(!a.kout || (a.x && a.score && a.tt), "ode each: the drift needs x, t [B] and the score");
+  DS_CHECK(a.mode == 0 || a.y, "ode each: the stage combination needs y");
+  DS_CHECK(a.mode != 1 || a.xo, "ode each: stage mode needs x_out");
+  DS_CHECK(a.mode != 2 || a.yo, "ode each: y_new mode needs y_new_out");
+  DS_CHECK(a.mode != 3 || a.part, "ode each: error mode needs the partial-sum slabs");
+  DS_CHECK(!e.tnext || a.t_next_out, "ode each: t_next needs its output");
+  for (int j = 0; j < a.nk; ++j) DS_CHECK(j == a.kidx || a.k[j], "ode each: null stage derivative");
+  bool vec = a.T % 4 == 0;
+  const void* ps[] = {a.x, a.score, a.kout, a.y, a.ynew, a.yo, a.xo};
+  for (const void* p : ps) vec = vec && al16(p);
+  for (int j = 0; j < a.nk; ++j) vec = vec && al16(a.k[j]);
+  const int nb = (int)std::min<long>(cdiv(a.T, 256), DS_ODE_MAX_BLOCKS);
+  hipLaunchKernelGGL(ode_stage_each_kernel, dim3(nb, a.B), dim3(256), 0, st, e, vec ? 1 : 0);
+  DS_LAUNCH_CHECK();
+  return 0;
+}
+int ds_launch_ode_norm_final_each(const double* part, const int* lens, const int* active, int B, int S, double* norms,
+                                  hipStream_t st) {
+  hipLaunchKernelGGL(ode_norm_final_each_kernel, dim3(B), dim3(256), 0, st, part, lens, active, S, norms);
+  DS_LAUNCH_CHECK();
+  return 0;
+}
+int ds_launch_ode_commit_each(double* y, const double* ynew, float* k0, const float* kns, const double* norms,
+                              const int* active, int B, int S, long T, hipStream_t st) {
+  const long n = (long)S * T;
+  const int nb = (int)std::min<long>(cdiv(n, 256), 1024);
+  hipLaunchKernelGGL(ode_commit_each_kernel, dim3(nb, B), dim3(256), 0, st, y, ynew, k0, kns, norms, active, n);
+  DS_LAUNCH_CHECK();
+  return 0;
+}
+
 // ------------------------------------------------------------------ C-ABI: tableau + unit entry points
 extern "C" int32_t diffsep_ode_tableau(int32_t method, double* A, double* B, double* C, double* E, int32_t* n_stages,
                                        int32_t* error_order) {
@@ -322,4 +583,45 @@ extern "C" int32_t diffsep_ode_error_norm(const diffsep_sde_config* sde, const f
   int nb = 0;
   if (ds_launch_ode_stage(a, (hipStream_t)stream, &nb)) return 1;
   return ds_launch_ode_norm_final(a.part, nb, (long)B * S * T, norms_out, (hipStream_t)stream);
+}
+
+// the per-utterance passes (h, active, lengths: device tables [B]); see ds_launch_ode_stage_each
+static int unit_each(OdeEachArgs& e, const double* h, const int32_t* active, const int32_t* lengths, const char* who) {
+  DS_CHECK(h && active && lengths, std::string(who) + ": null table (h, active, lengths are device arrays [B])");
+  e.h = h; e.active = active; e.lens = lengths; e.tnext = nullptr;
+  return 0;
+}
+
+extern "C" int32_t diffsep_ode_stage_update_each(const diffsep_sde_config* sde, const float* x, const float* t,
+                                                 const float* score, const float* sigma_mix, const double* y,
+                                                 float* const* K, const double* coef, int32_t n_k, int32_t k_out,
+                                                 const double* h, const int32_t* active, const int32_t* lengths,
+                                                 float* x_out, double* y_new_out, int32_t B, int32_t S, int64_t T,
+                                                 void* stream) {
+  OdeEachArgs e;
+  if (unit_args(e.a, sde, x, t, score, sigma_mix, y, K, coef, n_k, k_out, 0.0, B, S, T)) return 1;
+  if (unit_each(e, h, active, lengths, "ode_stage_update_each")) return 1;
+  DS_CHECK(k_out < 0 || t, "ode_stage_update_each: null t");
+  e.a.mode = n_k == 0 ? 0 : (y_new_out ? 2 : 1);
+  e.a.xo = x_out; e.a.yo = y_new_out;
+  return ds_launch_ode_stage_each(e, (hipStream_t)stream);
+}
+
+extern "C" int32_t diffsep_ode_error_norm_each(const diffsep_sde_config* sde, const float* x, const float* t,
+                                               const float* score, const float* sigma_mix, const double* y,
+                                               const double* y_new, float* const* K, const double* coef, int32_t n_k,
+                                               int32_t k_out, const double* h, const int32_t* active,
+                                               const int32_t* lengths, double rtol, double atol, double* norms_out,
+                                               int32_t B, int32_t S, int64_t T, void* workspace,
+                                               int64_t workspace_bytes, void* stream) {
+  OdeEachArgs e;
+  if (unit_args(e.a, sde, x, t, score, sigma_mix, y, K, coef, n_k, k_out, 0.0, B, S, T)) return 1;
+  if (unit_each(e, h, active, lengths, "ode_error_norm_each")) return 1;
+  DS_CHECK(k_out < 0 || t, "ode_error_norm_each: null t");
+  DS_CHECK(norms_out && workspace && B >= 1 && workspace_bytes >= (int64_t)B * DIFFSEP_ODE_WORKSPACE_BYTES && n_k >= 1,
+           "ode_error_norm_each: bad argument (workspace >= B * DIFFSEP_ODE_WORKSPACE_BYTES)");
+  e.a.mode = 3;
+  e.a.ynew = y_new; e.a.rtol = rtol; e.a.atol = atol; e.a.part = (double*)workspace;
+  if (ds_launch_ode_stage_each(e, (hipStream_t)stream)) return 1;
+  return ds_launch_ode_norm_final_each(e.a.part, lengths, active, B, S, norms_out, (hipStream_t)stream);
 }

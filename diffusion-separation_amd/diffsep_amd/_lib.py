@@ -50,6 +50,10 @@ class OdeConfig(C.Structure):  # diffsep_ode_config
                 ("N", C.c_int32)]
 
 
+class OdeExt(C.Structure):  # diffsep_ode_ext
+    _fields_ = [("lengths_host", C.POINTER(C.c_int64)), ("seeds_host", C.POINTER(C.c_uint64))]
+
+
 class OdeInfo(C.Structure):  # diffsep_ode_info
     _fields_ = [("nfev", C.c_int32), ("n_accepted", C.c_int32), ("n_rejected", C.c_int32), ("status", C.c_int32),
                 ("t_final", C.c_double)]
@@ -102,11 +106,17 @@ _SIGS = {
                                   _L, _P, _U64, _P, C.POINTER(_I), _P]),
     "diffsep_ode_sample": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(OdeConfig), _P, _P, _P, _U64, _P, _I, _L,
                                 C.POINTER(OdeInfo), _P]),
+    "diffsep_ode_sample_each": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(OdeConfig), C.POINTER(OdeExt), _P, _P, _P, _U64, _P,
+                                     _I, _L, C.POINTER(OdeInfo), C.POINTER(_I), _P]),
     "diffsep_ode_tableau": (_I, [_I, _P, _P, _P, _P, C.POINTER(_I), C.POINTER(_I)]),
     "diffsep_ode_stage_update": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_double, _P, _P, _I,
                                       _I, _L, _P]),
     "diffsep_ode_error_norm": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_double,
                                     C.c_double, C.c_double, _P, _I, _I, _L, _P, _L, _P]),
+    "diffsep_ode_stage_update_each": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P,
+                                           _I, _I, _L, _P]),
+    "diffsep_ode_error_norm_each": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P,
+                                         C.c_double, C.c_double, _P, _I, _I, _L, _P, _L, _P]),
     "diffsep_engine_set_graph": (_I, [_P, _I]),
     "diffsep_set_option": (_I, [C.c_char_p, _L]),
     "diffsep_engine_set_option": (_I, [_P, C.c_char_p, _L]),

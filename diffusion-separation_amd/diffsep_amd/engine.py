@@ -297,3 +297,47 @@ class Engine:
                                              _stream_ptr(self.device)), self._L)
         return out, dict(nfev=info.nfev, n_accepted=info.n_accepted, n_rejected=info.n_rejected, status=info.status,
                          t_final=info.t_final)
+
+    def ode_sample_each(self, mix_norm, sde, lengths=None, seeds=None, method="RK45", rtol=1e-5, atol=1e-5, eps=3e-2,
+                        first_step=None, max_step=None, max_nfe=0, denoise=True, N=30, x_init=None, noise=None, seed=0):
+        """The probability-flow ODE sampler with one step controller per utterance (diffsep_ode_sample_each): the batch
+        is B independent systems solved in lock step, all sharing every network evaluation.  lengths [B]: a zero-padded
+        batch of utterances that share one padded frame count; seeds [B]: per-utterance seeds of the prior draw.  Where the
+        fp32 network evaluation does not depend on the batch row b inside lengths[b] is bit-for-bit
+        ode_sample on that utterance alone with its seed.  Returns
+        (out [B,S,T], [info dict per utterance], evals_run = network evaluations actually run = max nfev)."""
+        if method not in _lib.ODE_METHODS:
+            raise NotImplementedError(f"ODE method '{method}': only RK45 and RK23 run on the engine")
+        mix_norm = self._f32(mix_norm)
+        B, one, T = mix_norm.shape
+        assert one == 1
+        sc = _lib.SdeConfig(sde.get("kind", _lib.SDE_MIX), sde["ndim"], sde["d_lambda"], sde["sigma_min"],
+                            sde["sigma_max"], sde.get("avg_len", 0))
+        oc = _lib.OdeConfig(float(rtol), float(atol), float(eps), float(first_step or 0.0),
+                            float(max_step) if max_step is not None else 0.0, _lib.ODE_METHODS[method], int(max_nfe or 0),
+                            int(bool(denoise)), int(N))
+        for name, v in (("x_init", x_init), ("noise", noise)):
+            if v is not None:
+                assert tuple(v.shape) == (B, self.S, T), f"{name} must be [B,S,T]"
+        x_init = self._f32(x_init) if x_init is not None else None
+        noise = self._f32(noise) if noise is not None else None
+        ext, keep = _lib.OdeExt(), []
+        if lengths is not None:
+            la = np.ascontiguousarray(lengths, dtype=np.int64)
+            assert la.shape == (B,), "lengths must be [B]"
+            ext.lengths_host = la.ctypes.data_as(C.POINTER(C.c_int64))
+            keep.append(la)
+        if seeds is not None:
+            sa = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
+            assert sa.shape == (B,), "seeds must be [B]"
+            ext.seeds_host = sa.ctypes.data_as(C.POINTER(C.c_uint64))
+            keep.append(sa)
+        out = torch.empty((B, self.S, T), dtype=torch.float32, device=mix_norm.device)
+        infos = (_lib.OdeInfo * B)()
+        evals = C.c_int32()
+        with torch.cuda.device(self.device):
+            check(self._L.diffsep_ode_sample_each(self._h, C.byref(sc), C.byref(oc), C.byref(ext), _ptr(mix_norm),
+                                                  _ptr(x_init), _ptr(noise), int(seed) % (1 << 64), _ptr(out), B, T, infos,
+                                                  C.byref(evals), _stream_ptr(self.device)), self._L)
+        return out, [dict(nfev=i.nfev, n_accepted=i.n_accepted, n_rejected=i.n_rejected, status=i.status,
+                          t_final=i.t_final) for i in infos], int(evals.value)

@@ -33,6 +33,13 @@ the batch is zero-padded on the right to its longest member, the engine keeps ev
 not depend on which batch, stream or rank it was separated in (bit-for-bit with --dtype f32; to the rounding of the
 GroupNorm sums of the weight-stationary bf16 convolution otherwise).
 
+--sampler ode [--rtol --atol --max-nfe] separates with the probability-flow ODE sampler instead (adaptive RK45 on the
+device, one step controller per utterance: sdes.get_ode_sampler with lengths / seeds, diffsep_ode_sample_each).  The
+batches and seeds are the same; an utterance's `nfe` is its own solver's count (solve_ivp's nfev), whatever the others of
+its batch needed, each record carries its `ode_status` (0 reached eps, -1 step too small, 1 --max-nfe reached) and the
+summary counts them (`ode_status_counts`) and names the `sampler`.  An ODE call blocks the host on one readback per step
+attempt, so --streams adds nothing to it.
+
 --streams K such calls are in flight on K engines / K HIP streams.  What that takes (hardware queues, engines before
 streams, workspace reserve, per-utterance seeds and normalisation, pinned uploads, the launch / collect ring, the overflow
 re-run) is inflight.py's, shared with separate.py.  Here: main() sets the run up, a SplitRun holds one split's state and
@@ -198,6 +205,13 @@ def build_parser():
     ap.add_argument("--batch", type=int, default=16,
                     help="utterances per engine call: those with the same padded spectrogram width share a call "
                          "(zero-padded to the longest; --batch 1 = the reference's one-utterance loop)")
+    ap.add_argument("--sampler", default="pc", choices=["pc", "ode"],
+                    help="pc (default): the reference's predictor-corrector sampler; ode: the probability-flow ODE (adaptive "
+                         "RK45), one step controller per utterance of a batch")
+    ap.add_argument("--rtol", type=float, default=1e-5, help="--sampler ode: relative tolerance (reference default)")
+    ap.add_argument("--atol", type=float, default=1e-5, help="--sampler ode: absolute tolerance (reference default)")
+    ap.add_argument("--max-nfe", type=int, default=0,
+                    help="--sampler ode: no step attempt of an utterance starts beyond this many network evaluations (0: unbounded)")
     ap.add_argument("--streams", type=int, default=4,
                     help="engine calls (batches) in flight per GPU: K engines on K HIP streams; the records do not "
                          "depend on K.  'runtime' of an utterance is its batch's latency / batch size.")
@@ -257,6 +271,8 @@ def main(argv=None):
         output_dir = args.output_dir / ("mix" if args.tag is None else args.tag)
     else:
         tag_inf = f"N-{N}_snr-{snr}_corrstep-{cs}_denoise-{args.denoise}_schedule-{args.schedule}"
+        if args.sampler == "ode":
+            tag_inf += f"_sampler-ode_rtol-{args.rtol}_atol-{args.atol}"
         if args.tag is not None:
             output_dir = args.output_dir / f"{args.tag}_{tag_inf}"
         elif args.ckpt is not None and not args.synthetic_weights:
@@ -324,6 +340,7 @@ class SplitRun:
     stoi_jobs: list = field(default_factory=list)  # (record, future of the per-source STOI list)
     fallbacks: list = field(default_factory=list)  # batches repeated on the split-precision engine after non-finite f16 samples
     ahead: dict = field(default_factory=dict)  # batch number -> future of its host_stage()
+    ode_reruns: dict = field(default_factory=dict)  # first utterance of a repeated ODE batch -> the repeat's per-utterance infos
 
     def __post_init__(self):
         a = self.args
@@ -362,6 +379,10 @@ class SplitRun:
         return (mix, *inflight.normalize_padded(self.models[w], lens, mix, tgt), lens)
 
     def sampler_for(self, model, group, lens, mix_n):
+        if self.args.sampler == "ode":  # one step controller per utterance; sampler.info: the utterances' own counts
+            a = self.args
+            return model.get_ode_sampler(mix_n, N=self.sampler_kw["N"], denoise=a.denoise, rtol=a.rtol, atol=a.atol,
+                                         max_nfe=a.max_nfe, lengths=lens, seeds=[self.seeds[i] for i in group])
         return model.get_pc_sampler("reverse_diffusion", "ald2", mix_n, **self.sampler_kw, denoise=self.args.denoise,
                                     intermediate=False, schedule=self.args.schedule, lengths=lens,
                                     seeds=[self.seeds[i] for i in group], check_finite=False)
@@ -400,7 +421,11 @@ class SplitRun:
 
     def reissue(self, fb, b):
         self.fallbacks.append(list(b.group))
-        return self.sampler_for(fb, b.group, b.lens, b.mix_n)()
+        sampler = self.sampler_for(fb, b.group, b.lens, b.mix_n)
+        out = sampler()
+        if self.args.sampler == "ode":
+            self.ode_reruns[b.group[0]] = sampler.info
+        return out
 
     def collect(self, w, b):
         """batch b, whose sampler has drained from worker w's stream, into records (+ STOI jobs, saved samples)"""
@@ -409,6 +434,9 @@ class SplitRun:
             est, nfe, *_ = inflight.finite_or_rerun(self.models[w], stream, (est, nfe), lambda fb: self.reissue(fb, b),
                                                     what=f"utterances {group[:3]}...")
         runtime = 0.0 if b.t0 is None else (time.perf_counter() - b.t0) / len(group)
+        ode = None  # --sampler ode: the utterances' own solver counts
+        if not self.no_proc and a.sampler == "ode":
+            ode = self.ode_reruns.pop(group[0], None) or b.sampler.info
         with torch.cuda.stream(stream):
             mets = compute_metrics(est, tgt_n, self.n_src)
         need_host = needs_host_waveforms(a, group)
@@ -425,8 +453,10 @@ class SplitRun:
             with torch.cuda.stream(stream):
                 sloss = b.sloss.cpu().tolist()
         for k, i in enumerate(group):
-            rec = {"batch_idx": i, **mets[k], "pesq": None, "stoi": None, "nfe": int(nfe), "runtime": runtime,
-                   "len_s": lens[k] / self.fs}
+            rec = {"batch_idx": i, **mets[k], "pesq": None, "stoi": None, "nfe": int(nfe if ode is None else ode[k]["nfev"]),
+                   "runtime": runtime, "len_s": lens[k] / self.fs}
+            if ode is not None:
+                rec["ode_status"] = int(ode[k]["status"])
             if sloss is not None:
                 rec["score_loss"] = float(sloss[k])
             self.records.append(rec)
@@ -448,16 +478,19 @@ class SplitRun:
         flat = sorted([r for part in allrec for r in part], key=lambda r: r["batch_idx"])
         with open(self.output_dir / f"{self.split}.json", "w") as f:
             json.dump(flat, f, indent=2)
-        summary = datasets.summarize([{k: v for k, v in r.items() if k not in ("batch_idx", "perm")} for r in flat])
+        summary = datasets.summarize([{k: v for k, v in r.items() if k not in ("batch_idx", "perm", "ode_status")} for r in flat])
         tot_rt = sum(r["runtime"] for r in flat)
         summary.update({"rtf": tot_rt / max(sum(r["len_s"] for r in flat), 1e-9), "world_size": self.world,
                         "streams": len(self.streams), "batch": a.batch, "engine_calls_rank0": len(self.batches),
                         "dtype": model.dtype if model is not None else None,
+                        "sampler": None if model is None else a.sampler,
                         "utt_per_s_rank0": len(self.mine) / max(wall, 1e-9), "split_fallback_batches_rank0": len(self.fallbacks),
                         # PESQ is ITU-T P.862 reference C code behind the third-party `pesq` package: not restated here
                         # (DESIGN.md section 7); STOI / ESTOI is diffsep_amd.metrics.stoi (published algorithm, restated)
                         "not_computed": ["pesq"] + (["stoi"] if a.no_stoi else []),
                         "stoi_on": a.stoi_on, "stoi_extended": not a.stoi_no_extended, "pesq_mode": a.pesq_mode})
+        if model is not None and a.sampler == "ode":
+            summary["ode_status_counts"] = {str(c): sum(1 for r in flat if r.get("ode_status") == c) for c in (0, -1, 1)}
         with open(self.output_dir / f"{self.split}_summary.json", "w") as f:
             json.dump(summary, f, indent=2)
         print(json.dumps(summary))

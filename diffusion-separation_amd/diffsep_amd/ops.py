@@ -678,3 +678,47 @@ def ode_error_norm(sde, K, coef, h, y, rtol, atol, y_new=None, k_out=-1, x=None,
                                        float(rtol), float(atol), _ptr(out), B, S, T, _ptr(ws), ws.numel(),
                                        _stream_ptr()))
     return out
+
+
+def _ode_tables(h, active, lengths, B, dev):
+    """the per-utterance device tables of the *_each passes: h float64 [B], active int32 [B], lengths int32 [B]"""
+    tabs = (torch.as_tensor(h, dtype=torch.float64).to(dev).contiguous(),
+            torch.as_tensor(active, dtype=torch.int32).to(dev).contiguous(),
+            torch.as_tensor(lengths, dtype=torch.int32).to(dev).contiguous())
+    assert all(v.shape == (B,) for v in tabs), "h, active and lengths must be [B]"
+    return tabs
+
+
+def ode_stage_update_each(sde, K, coef, h, active, lengths, y, k_out=-1, x=None, t=None, score=None, sigma_mix=None,
+                          x_out=None, y_new_out=None):
+    """diffsep_ode_stage_update_each: ode_stage_update with a step size h[b] per utterance; utterances with active[b] == 0
+    are skipped, samples t >= lengths[b] are never read and written as exact zeros."""
+    B, S, T = K[0].shape
+    c = np.ascontiguousarray(coef, dtype=np.float64)
+    assert len(c) <= len(K) and k_out < len(K) and all(k.shape == (B, S, T) and k.dtype == torch.float32 for k in K)
+    hd, ad, ld = _ode_tables(h, active, lengths, B, K[0].device)
+    sc = _sde(sde)
+    check(lib().diffsep_ode_stage_update_each(C.byref(sc), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y),
+                                              _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), _ptr(hd),
+                                              _ptr(ad), _ptr(ld), _ptr(x_out), _ptr(y_new_out), B, S, T, _stream_ptr()))
+    return x_out, y_new_out
+
+
+def ode_error_norm_each(sde, K, coef, h, active, lengths, y, rtol, atol, y_new=None, k_out=-1, x=None, t=None, score=None,
+                        sigma_mix=None, out=None):
+    """diffsep_ode_error_norm_each: float64 [B,2] device tensor, row b = the two norms of ode_error_norm over utterance
+    b's lengths[b] samples alone (rows of inactive utterances keep the value of `out`, zeros when it is not given)."""
+    B, S, T = K[0].shape
+    c = np.ascontiguousarray(coef, dtype=np.float64)
+    assert len(c) <= len(K) and k_out < len(K) and all(k.shape == (B, S, T) and k.dtype == torch.float32 for k in K)
+    hd, ad, ld = _ode_tables(h, active, lengths, B, K[0].device)
+    if out is None:
+        out = torch.zeros(B, 2, dtype=torch.float64, device=K[0].device)
+    assert out.shape == (B, 2) and out.dtype == torch.float64 and out.is_contiguous()
+    ws = torch.empty(B * ODE_WORKSPACE_BYTES, dtype=torch.uint8, device=K[0].device)
+    sc = _sde(sde)
+    check(lib().diffsep_ode_error_norm_each(C.byref(sc), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y),
+                                            _ptr(y_new), _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out),
+                                            _ptr(hd), _ptr(ad), _ptr(ld), float(rtol), float(atol), _ptr(out), B, S, T,
+                                            _ptr(ws), ws.numel(), _stream_ptr()))
+    return out

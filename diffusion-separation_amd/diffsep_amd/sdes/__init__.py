@@ -133,7 +133,7 @@ def get_pc_scheduled_sampler(predictor_name, corrector_name, sde, score_fn, y, d
                          lengths=kwargs.get("lengths"), seeds=kwargs.get("seeds"))
 
 
-_ODE_KWARGS = ("first_step", "max_step", "max_nfe", "seed", "noise")
+_ODE_KWARGS = ("first_step", "max_step", "max_nfe", "seed", "noise", "per_utterance", "lengths", "seeds")
 
 
 def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e-5, atol=1e-5, method="RK45", eps=3e-2,
@@ -149,13 +149,21 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
 
     method: "RK45" / "RK23" (other solve_ivp methods raise NotImplementedError); device: accepted and ignored.
     **kwargs: solve_ivp's first_step / max_step, and the extensions max_nfe (no step attempt starts that would take the
-    evaluation count above it), seed (device RNG seed of the prior draw; default: drawn from torch's generator) and
-    noise ([B,S,T] draws of the prior).  Anything else raises TypeError.
+    evaluation count above it), seed (device RNG seed of the prior draw; default: drawn from torch's generator),
+    noise ([B,S,T] draws of the prior) and per_utterance / lengths / seeds (below).  Anything else raises TypeError.
 
     Cost: every network evaluation runs on the score function's engine; on a dtype="hybrid" model all of them run on its
     split-precision engine.  A 16-bit (f16 / bf16) model runs as it is, and that is costly: the score's rounding noise
     (~3e-3 relative per evaluation) enters the embedded error estimate, which can shrink the step far below what the
     fp32 drift needs at tight tolerances — bound the work with max_nfe.
+
+    per_utterance=True (extension; implied by lengths= or seeds=) runs Engine.ode_sample_each instead: every utterance of
+    the batch is its own ODE system with its own step controller, all sharing each network evaluation.  lengths [B]: y is
+    a zero-padded batch of utterances that share one padded frame count; seeds [B]: per-utterance seeds of the prior draw.
+    On an fp32 engine utterance b then comes out bit for bit as a B = 1 sampler on it alone with seed seeds[b], wherever
+    the network evaluation itself does not depend on the batch.  The
+    sampler returns (x, evals_run), the network evaluations actually run (the largest nfev), and ode_sampler.info is
+    the list of the utterances' info dicts.
 
     The returned ode_sampler(z=None) -> (x, nfe): z [B,S,T] is used as x_T when given (the reference documents z as the
     latent code and ignores it); nfe is solve_ivp's nfev (the denoise evaluation is not counted).  After a call,
@@ -174,10 +182,22 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
         raise ValueError("get_ode_sampler: score_fn has no engine (an engine-backed DiffSepModel / ScoreModelNCSNpp is "
                          "needed; the ODE sampler has no host fallback)")
     seed, noise_ = kwargs.get("seed"), kwargs.get("noise")
+    lengths, seeds = kwargs.get("lengths"), kwargs.get("seeds")
+    each = bool(kwargs.get("per_utterance", False)) or lengths is not None or seeds is not None
 
     def ode_sampler(z=None, **_):
         with torch.no_grad():
             s_ = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+            if each:
+                x, infos, evals = eng.ode_sample_each(y, sde.engine_config(), lengths=lengths, seeds=seeds, method=method,
+                                                      rtol=rtol, atol=atol, eps=eps, first_step=kwargs.get("first_step"),
+                                                      max_step=kwargs.get("max_step"), max_nfe=kwargs.get("max_nfe") or 0,
+                                                      denoise=denoise, N=sde.N, x_init=z,
+                                                      noise=noise_ if z is None else None, seed=s_)
+                ode_sampler.info = infos
+                if inverse_scaler is not None:
+                    x = inverse_scaler(x)
+                return x, evals
             x, info = eng.ode_sample(y, sde.engine_config(), method=method, rtol=rtol, atol=atol, eps=eps,
                                      first_step=kwargs.get("first_step"), max_step=kwargs.get("max_step"),
                                      max_nfe=kwargs.get("max_nfe") or 0, denoise=denoise, N=sde.N, x_init=z,

@@ -203,7 +203,7 @@ int32_t diffsep_pc_sample_ex(diffsep_engine* e, const diffsep_sde_config* sde, c
  *              the PC sampler's prior with the same seed); otherwise the caller's x_T [B,S,T] (the reference's `z`);
  *   info     : may be NULL.  nfev is scipy's solution.nfev (the denoise evaluation is not counted).
  * Buffers: y, y_new, 7 K and a partial-sum slab, allocated at the first call (diffsep_engine_device_bytes grows then;
- * the workspace of the PC sampler does not change).  No mixed-length batches, no tail engine. */
+ * the workspace of the PC sampler does not change).  No mixed-length batches (diffsep_ode_sample_each), no tail engine. */
 typedef struct {
   double rtol, atol;   /* solve_ivp tolerances (reference default 1e-5 / 1e-5) */
   double eps;          /* t_bound: integrate from 1 down to eps (3e-2) */
@@ -223,6 +223,37 @@ typedef struct {
 int32_t diffsep_ode_sample(diffsep_engine* e, const diffsep_sde_config* sde, const diffsep_ode_config* ode,
                            const float* mix_norm, const float* x_init, const float* noise, uint64_t seed, float* out,
                            int32_t B, int64_t T, diffsep_ode_info* info, void* stream);
+/* The same sampler with ONE STEP CONTROLLER PER UTTERANCE (no counterpart in the reference, whose evaluate.py:348-376 runs
+ * sdes.get_ode_sampler (sdes/__init__.py:193-278) on one utterance at a time, where "the batch is one system" and "every
+ * utterance is its own system" are the same thing).  The batch [B,S,T] is B independent ODE systems solved in lock step:
+ * utterance b keeps its own t, h, error norm, accept / reject decisions and counts, exactly as diffsep_ode_sample computes
+ * them for it alone, and all utterances share every network evaluation (one step attempt = n_stages evaluations of the whole
+ * batch with a per-utterance time).  An utterance that has reached eps (or failed, or hit max_nfe) is frozen: its rows ride
+ * through the remaining evaluations, its state is not touched.  Given the same network evaluations, row b of `out` inside
+ * its length is bit-for-bit what diffsep_ode_sample returns for that utterance alone (B = 1, T = lengths[b], the same
+ * seed), whatever batch, position or padded width it rides in: the norms are summed in the B = 1 order of an utterance of
+ * that length.  So it is wherever the fp32 engine's evaluation does not depend on the batch (the reach of
+ * diffsep_sampler_ext.lengths_host's guarantee; DESIGN.md section 5b has the measurement); the 16-bit engines are not
+ * bit-independent of the batch, so there the decisions may differ too.
+ *   ext (may be NULL, both fields optional):
+ *     lengths_host [B] : as in diffsep_sampler_ext — within [1, T], all with the padded frame count of T; the mixture's tail
+ *                        is masked, the state's tail stays exactly zero and enters no norm (n = S * lengths[b]);
+ *     seeds_host [B]   : per-utterance Philox seeds of the prior draw (noise == NULL and x_init == NULL); without it
+ *                        utterance b uses seed + b * 0x9E3779B97F4A7C15, as the PC sampler does;
+ *   x_init / noise     : as in diffsep_ode_sample, their tails zeroed;
+ *   infos [B]          : may be NULL; the counts utterance b would have had alone;
+ *   evals_run          : may be NULL; network evaluations of the batch actually run = max_b infos[b].nfev (the denoise
+ *                        evaluation is not counted).
+ * One pinned readback of 2 B norms per step attempt; the call blocks on it.  Buffers as diffsep_ode_sample, plus one
+ * partial-sum slab per utterance and the per-attempt tables. */
+typedef struct {
+  const int64_t* lengths_host;
+  const uint64_t* seeds_host;
+} diffsep_ode_ext;
+int32_t diffsep_ode_sample_each(diffsep_engine* e, const diffsep_sde_config* sde, const diffsep_ode_config* ode,
+                                const diffsep_ode_ext* ext, const float* mix_norm, const float* x_init,
+                                const float* noise, uint64_t seed, float* out, int32_t B, int64_t T,
+                                diffsep_ode_info* infos, int32_t* evals_run, void* stream);
 /* Butcher tableau of RK45 / RK23 exactly as scipy's rk.py holds it (sdes/__init__.py:193-278 -> solve_ivp): A [ns][ns]
  * row-major, B [ns], C [ns], E [ns+1]; every pointer may be NULL (host memory, no GPU needed). */
 int32_t diffsep_ode_tableau(int32_t method, double* A, double* B, double* C, double* E, int32_t* n_stages,
@@ -245,6 +276,25 @@ int32_t diffsep_ode_error_norm(const diffsep_sde_config* sde, const float* x, co
                                const double* coef, int32_t n_k, int32_t k_out, double h, double rtol, double atol,
                                double* norms_out, int32_t B, int32_t S, int64_t T, void* workspace,
                                int64_t workspace_bytes, void* stream);
+
+/* The two passes with per-utterance tables, as diffsep_ode_sample_each launches them (sdes/__init__.py:193-278 per
+ * utterance).  h [B] (fp64), active [B] and lengths [B] (int32) are DEVICE arrays; everything else as above.
+ *   active[b] == 0 : nothing of utterance b is read or written (its norms keep their value);
+ *   t >= lengths[b]: never read; K[k_out], x_out and y_new_out are written as exact zeros there;
+ *   norms_out [B][2]: the two norms of utterance b over its S * lengths[b] values, summed in the order
+ *                     diffsep_ode_error_norm uses for B = 1, T = lengths[b] (whatever B, b and T are);
+ *   workspace      : >= B * DIFFSEP_ODE_WORKSPACE_BYTES. */
+int32_t diffsep_ode_stage_update_each(const diffsep_sde_config* sde, const float* x, const float* t, const float* score,
+                                      const float* sigma_mix, const double* y, float* const* K, const double* coef,
+                                      int32_t n_k, int32_t k_out, const double* h, const int32_t* active,
+                                      const int32_t* lengths, float* x_out, double* y_new_out, int32_t B, int32_t S,
+                                      int64_t T, void* stream);
+int32_t diffsep_ode_error_norm_each(const diffsep_sde_config* sde, const float* x, const float* t, const float* score,
+                                    const float* sigma_mix, const double* y, const double* y_new, float* const* K,
+                                    const double* coef, int32_t n_k, int32_t k_out, const double* h,
+                                    const int32_t* active, const int32_t* lengths, double rtol, double atol,
+                                    double* norms_out, int32_t B, int32_t S, int64_t T, void* workspace,
+                                    int64_t workspace_bytes, void* stream);
 
 /* Use hipGraph replay of the per-NFE launch sequence inside diffsep_pc_sample (default 1). */
 int32_t diffsep_engine_set_graph(diffsep_engine* e, int32_t enable);

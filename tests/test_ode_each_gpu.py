@@ -1,0 +1,308 @@
+"""The probability-flow ODE sampler with one step controller per utterance on the MI355X (diffsep_ode_sample_each,
+Engine.ode_sample_each, sdes.get_ode_sampler(lengths= / seeds= / per_utterance=)): its two passes against numpy float64,
+and every utterance of a zero-padded batch against its own B = 1 solve by the whole-batch entry (diffsep_ode_sample),
+bit for bit on the fp32 engine — whatever batch, position or padded width it rides in.  nf = 16, S = 2, synthetic
+weights of seed 7; rtol = atol = 1e-3 unless said otherwise."""
+import json
+
+import numpy as np
+import pytest
+import torch
+
+from diffsep_amd import _lib, ops, synth, wavio
+from diffsep_amd import evaluate as eval_cli
+from diffsep_amd import separate as sep_cli
+from diffsep_amd.engine import Engine, pack_state_dict, param_table
+from diffsep_amd.pl_model import DiffSepModel, default_config
+
+pytestmark = pytest.mark.gpu
+torch.set_grad_enabled(False)
+
+NF, S = 16, 2
+MIX = dict(kind=_lib.SDE_MIX, ndim=2, d_lambda=2.0, sigma_min=0.05, sigma_max=0.5)
+PRIOR = dict(kind=_lib.SDE_PRIORMIX, ndim=2, d_lambda=2.0, sigma_min=0.05, sigma_max=0.5, avg_len=510)
+SDES = {"mix": MIX, "priormix": PRIOR}
+LENS = [7000, 6500, 6017, 6999]  # 58, 54, 51, 58 frames: one padded width (64) for all
+SEEDS = [101, 202, 303, 404]
+TOL = dict(rtol=1e-3, atol=1e-3)
+_cache = {}
+
+
+def engine(dtype=_lib.F32):
+    if ("eng", dtype) not in _cache:
+        cfg = _lib.model_config(nf=NF, num_sources=S, dtype=dtype)
+        sd = synth.synth_state_dict([(n, s) for n, s, _ in param_table(cfg)], 7)
+        _cache["eng", dtype] = Engine(cfg, pack_state_dict(cfg, sd))
+    return _cache["eng", dtype]
+
+
+def utt(u):
+    """utterance u of the set above alone: its normalised mixture [1,1,LENS[u]]"""
+    if ("utt", u) not in _cache:
+        mix = torch.from_numpy(synth.synth_mixture(u, T=LENS[u])[0])[None].cuda()
+        _cache["utt", u] = ops.normalize_batch(mix)[0].contiguous()
+    return _cache["utt", u]
+
+
+def padded(us, T=None):
+    """the utterances `us` as one right-zero-padded batch [B,1,T]"""
+    T = T or max(LENS[u] for u in us)
+    mixn = torch.zeros(len(us), 1, T, device="cuda")
+    for b, u in enumerate(us):
+        mixn[b, :, :LENS[u]] = utt(u)[0]
+    return mixn
+
+
+def solo(kind, u, **kw):
+    """utterance u through the whole-batch entry as a batch of one: (out [1,S,L], info); computed once per setting"""
+    key = ("solo", kind, u, tuple(sorted(kw.items())))
+    if key not in _cache:
+        _cache[key] = engine().ode_sample(utt(u), SDES[kind], seed=SEEDS[u], **{**TOL, **kw})
+    return _cache[key]
+
+
+def check_rows(out, infos, kind, us, **kw):
+    T = out.shape[-1]
+    for b, u in enumerate(us):
+        one, info = solo(kind, u, **kw)
+        L = LENS[u]
+        assert torch.equal(out[b, :, :L], one[0]), (kind, b, u)
+        assert infos[b] == info, (kind, b, u, infos[b], info)
+        assert L == T or float(out[b, :, L:].abs().max()) == 0.0
+
+
+# ---------------------------------------------------------------- 1. the two passes against numpy float64
+def test_passes_match_numpy_float64_per_utterance():
+    B, T = 3, 7000
+    lens, h, active = [7000, 6500, 6017], [-0.0123, -0.004, -0.02], [1, 0, 1]
+    g = torch.Generator().manual_seed(3)
+    K = [torch.randn(B, S, T, generator=g).cuda() for _ in range(7)]
+    y = torch.randn(B, S, T, generator=g, dtype=torch.float64).cuda()
+    y2 = y + 1e-3 * torch.randn(B, S, T, generator=g, dtype=torch.float64).cuda()
+    A, Bt, C, E, ns, _ = _lib.ode_tableau("RK45")
+    Kn = [k.cpu().double().numpy() for k in K]
+    yn, y2n = y.cpu().numpy(), y2.cpu().numpy()
+    hn = np.asarray(h)[:, None, None]
+    SENT = 7.5
+
+    def comb(c, n):
+        acc = np.zeros_like(yn)
+        for j in range(n):
+            acc = acc + c[j] * Kn[j]
+        return acc
+
+    def check(got, want):
+        got = got.cpu().numpy()
+        for b in range(B):
+            if not active[b]:
+                assert np.all(got[b] == SENT), b  # a frozen utterance: nothing written
+                continue
+            assert np.array_equal(got[b, :, :lens[b]], want[b, :, :lens[b]]), b
+            assert np.all(got[b, :, lens[b]:] == 0), b
+
+    for s in range(1, ns):  # stage inputs fp32(y + (sum_j a_sj K_j) h[b])
+        xo = torch.full((B, S, T), SENT, device="cuda")
+        ops.ode_stage_update_each(MIX, K, A[s, :s], h, active, lens, y, x_out=xo)
+        check(xo, (yn + comb(A[s], s) * hn).astype(np.float32))
+    yo = torch.full((B, S, T), SENT, dtype=torch.float64, device="cuda")
+    xo = torch.full((B, S, T), SENT, device="cuda")
+    ops.ode_stage_update_each(MIX, K, Bt, h, active, lens, y, x_out=xo, y_new_out=yo)
+    want = yn + hn * comb(Bt, ns)
+    check(yo, want)
+    check(xo, want.astype(np.float32))
+
+    def norms(K_, y_, y2_):
+        out = torch.full((B, 2), SENT, dtype=torch.float64, device="cuda")
+        return ops.ode_error_norm_each(MIX, K_, E, h, active, lens, y_, 1e-5, 1e-5, y_new=y2_, out=out).cpu().numpy()
+
+    nrm = norms(K, y, y2)
+    acc = comb(E, ns + 1)
+    for b in range(B):
+        if not active[b]:
+            assert np.all(nrm[b] == SENT)
+            continue
+        L = lens[b]
+        sc = 1e-5 + np.maximum(np.abs(yn[b, :, :L]), np.abs(y2n[b, :, :L])) * 1e-5
+        e0 = np.linalg.norm(acc[b, :, :L] * h[b] / sc) / np.sqrt(S * L)
+        e1 = np.linalg.norm(yn[b, :, :L] / sc) / np.sqrt(S * L)
+        print(f"utterance {b}: norms {nrm[b]}, numpy {e0} {e1}")
+        assert abs(nrm[b, 0] - e0) <= 1e-12 * e0 and abs(nrm[b, 1] - e1) <= 1e-12 * e1
+    # what lies beyond an utterance's length enters no norm: NaN there, the same bits out
+    def dirty(v):
+        v = v.clone()
+        for b in range(B):
+            v[b, :, lens[b]:] = float("nan")
+        return v
+    assert np.array_equal(norms([dirty(k) for k in K], dirty(y), dirty(y2)), nrm)
+
+    # the fused drift: inside the lengths the whole-batch pass's K, bit for bit; zero beyond
+    x = torch.randn(B, S, T, generator=g).cuda()
+    score = torch.randn(B, S, T, generator=g).cuda()
+    t = torch.tensor([0.9, 0.5, 0.1], device="cuda")
+    Kw = [torch.zeros(B, S, T, device="cuda") for _ in range(2)]
+    ops.ode_stage_update(MIX, Kw, [0.5, 0.25], -0.01, y, k_out=1, x=x, t=t, score=score, x_out=torch.empty_like(x))
+    Ke = [torch.zeros(B, S, T, device="cuda"), torch.full((B, S, T), SENT, device="cuda")]
+    ops.ode_stage_update_each(MIX, Ke, [0.5, 0.25], h, active, lens, y, k_out=1, x=x, t=t, score=score,
+                              x_out=torch.empty_like(x))
+    check(Ke[1], Kw[1].cpu().numpy())
+
+
+# ---------------------------------------------------------------- 2. each utterance equals its solo solve
+def test_solo_attempt_counts_differ():
+    # the precondition of the tests below, on the whole-batch entry: the four utterances need different numbers of step
+    # attempts, so that some are frozen while others still integrate
+    for kind in SDES:
+        n = [solo(kind, u)[1]["n_accepted"] + solo(kind, u)[1]["n_rejected"] for u in range(4)]
+        print(kind, [solo(kind, u)[1] for u in range(4)])
+        assert len(set(n)) > 1, (kind, n)
+
+
+@pytest.mark.parametrize("kind", ["mix", "priormix"])
+def test_each_utterance_equals_its_solo_solve_bit_for_bit(kind):
+    us = [0, 1, 2, 3]
+    out, infos, evals = engine().ode_sample_each(padded(us), SDES[kind], lengths=[LENS[u] for u in us],
+                                                 seeds=[SEEDS[u] for u in us], **TOL)
+    print(kind, infos, evals)
+    check_rows(out, infos, kind, us)
+    assert evals == max(i["nfev"] for i in infos)
+    assert all(i["status"] == 0 for i in infos)
+
+
+# ---------------------------------------------------------------- 3. position, batch size, padded width
+def test_result_is_independent_of_position_batch_size_and_padded_width():
+    eng = engine()
+    rows = []
+    for us in ([1], [3, 2, 1], [1, 0]):  # alone (T = 6500); T = 6999: unaligned rows, 4-sample items; row 0 of T = 7000
+        out, infos, _ = eng.ode_sample_each(padded(us), MIX, lengths=[LENS[u] for u in us], seeds=[SEEDS[u] for u in us],
+                                            **TOL)
+        b = us.index(1)
+        rows.append((out[b, :, :LENS[1]].clone(), infos[b]))
+    for r, i in rows[1:]:
+        assert torch.equal(r, rows[0][0]) and i == rows[0][1]
+    assert torch.equal(rows[0][0], solo("mix", 1)[0][0]) and rows[0][1] == solo("mix", 1)[1]
+
+
+# ---------------------------------------------------------------- 4. RK23
+def test_rk23():
+    us = [0, 2]
+    out, infos, evals = engine().ode_sample_each(padded(us), MIX, lengths=[LENS[u] for u in us],
+                                                 seeds=[SEEDS[u] for u in us], method="RK23", **TOL)
+    check_rows(out, infos, "mix", us, method="RK23")
+    assert evals == max(i["nfev"] for i in infos)
+
+
+# ---------------------------------------------------------------- 5. max_nfe
+def test_max_nfe_freezes_one_utterance_and_stops_the_other():
+    nfev = [solo("mix", u)[1]["nfev"] for u in range(4)]
+    lo, hi = int(np.argmin(nfev)), int(np.argmax(nfev))
+    assert nfev[lo] < nfev[hi]
+    m = nfev[lo] + 1  # the shorter solve ends within it, the longer one does not
+    us = [lo, hi]
+    out, infos, evals = engine().ode_sample_each(padded(us), MIX, lengths=[LENS[u] for u in us],
+                                                 seeds=[SEEDS[u] for u in us], max_nfe=m, **TOL)
+    print(infos, evals)
+    assert [i["status"] for i in infos] == [0, 1]
+    assert infos[0]["nfev"] == nfev[lo] and infos[1]["nfev"] <= m
+    check_rows(out, infos, "mix", us, max_nfe=m)
+    # the other order: the finished utterance frozen in row 1 while row 0 goes on
+    m2 = nfev[hi] - 1
+    us = [hi, lo]
+    out, infos, _ = engine().ode_sample_each(padded(us), MIX, lengths=[LENS[u] for u in us],
+                                             seeds=[SEEDS[u] for u in us], max_nfe=m2, **TOL)
+    assert [i["status"] for i in infos] == [1, 0]
+    check_rows(out, infos, "mix", us, max_nfe=m2)
+
+
+# ---------------------------------------------------------------- 6. first_step
+def test_first_step_skips_the_initial_step_evaluation():
+    us = [0, 2]
+    out, infos, evals = engine().ode_sample_each(padded(us), MIX, lengths=[LENS[u] for u in us],
+                                                 seeds=[SEEDS[u] for u in us], first_step=0.01, **TOL)
+    check_rows(out, infos, "mix", us, first_step=0.01)
+    assert all((i["nfev"] - 1) % 6 == 0 for i in infos) and evals == max(i["nfev"] for i in infos)
+
+
+# ---------------------------------------------------------------- 7. argument errors
+def test_argument_errors():
+    eng = engine()
+    mixn = padded([0, 1])
+    z = torch.zeros(2, S, 7000, device="cuda")
+    with pytest.raises(_lib.DiffsepError):  # longer than the batch
+        eng.ode_sample_each(mixn, MIX, lengths=[7000, 9000], **TOL)
+    with pytest.raises(_lib.DiffsepError) as ei:  # a length with another padded frame count
+        eng.ode_sample_each(torch.zeros(2, 1, 9000, device="cuda"), MIX, lengths=[9000, 3000], **TOL)
+    assert "padded frame count" in str(ei.value)
+    with pytest.raises(_lib.DiffsepError):
+        eng.ode_sample_each(mixn, MIX, x_init=z, noise=z, **TOL)
+    with pytest.raises(_lib.DiffsepError):
+        eng.ode_sample_each(mixn, MIX, noise=z, seeds=[1, 2], **TOL)
+
+
+# ---------------------------------------------------------------- 8. API
+def test_get_ode_sampler_per_utterance_and_default_path():
+    model = DiffSepModel(default_config(nf=16), dtype="f32", device="cuda")
+    us = [0, 2]
+    mixn, lens, seeds = padded(us), [LENS[u] for u in us], [SEEDS[u] for u in us]
+    sampler = model.get_ode_sampler(mixn, lengths=lens, seeds=seeds, **TOL)
+    x, evals = sampler()
+    want, infos, evals2 = model.engine().ode_sample_each(mixn, model.sde.engine_config(), lengths=lens, seeds=seeds,
+                                                         eps=model.t_eps, N=model.sde.N, **TOL)
+    assert torch.equal(x, want) and sampler.info == infos and evals == evals2 == max(i["nfev"] for i in infos)
+    # per_utterance alone: equal lengths, the seeds derived from `seed`; row 0 draws what a B = 1 sampler of that seed draws
+    full = torch.cat([utt(0), utt(0).flip(-1)]).contiguous()
+    xa, _ = model.get_ode_sampler(full, per_utterance=True, seed=5, **TOL)()
+    xb, _ = model.get_ode_sampler(full[:1].contiguous(), seed=5, **TOL)()
+    assert torch.equal(xa[:1], xb)
+    # without the new kwargs: the whole-batch entry, as before
+    sampler = model.get_ode_sampler(full, seed=5, **TOL)
+    xc, nfe = sampler()
+    xd, info = model.engine().ode_sample(full, model.sde.engine_config(), eps=model.t_eps, N=model.sde.N, seed=5, **TOL)
+    assert torch.equal(xc, xd) and sampler.info == info and nfe == info["nfev"]
+
+
+# ---------------------------------------------------------------- a 16-bit engine: bounded work, nothing bit-exact asked
+def test_f16_engine_is_bounded_by_max_nfe():
+    us = [0, 1]
+    out, infos, evals = engine(_lib.F16).ode_sample_each(padded(us), MIX, lengths=[LENS[u] for u in us],
+                                                         seeds=[SEEDS[u] for u in us], max_nfe=60)
+    print(f"f16 at rtol = atol = 1e-5, max_nfe 60: {infos}, {evals} evaluations")
+    assert torch.isfinite(out).all() and all(i["nfev"] <= 60 for i in infos) and evals <= 60
+
+
+# ---------------------------------------------------------------- 9. separate --sampler ode --batch K
+def test_separate_cli_batched_files_equal_one_file_per_call(tmp_path):
+    ind = tmp_path / "in"
+    ind.mkdir()
+    for i, L in enumerate([7000, 6500, 6017]):
+        wavio.save(ind / f"utt{i}.wav", torch.from_numpy(synth.synth_mixture(i, T=L)[0]), 8000)
+    common = ["--synthetic-weights", "16", "--dtype", "f32", "--sampler", "ode", "--rtol", "1e-3", "--atol", "1e-3",
+              "--seed", "11"]
+    sep_cli.main([str(ind), str(tmp_path / "b3"), "--batch", "3"] + common)
+    sep_cli.main([str(ind), str(tmp_path / "b1"), "--batch", "1"] + common)
+    for i, L in enumerate([7000, 6500, 6017]):
+        for k in range(2):
+            a, sra = wavio.load(tmp_path / "b3" / f"s{k}" / f"utt{i}.wav")
+            b, srb = wavio.load(tmp_path / "b1" / f"s{k}" / f"utt{i}.wav")
+            assert sra == srb == 8000 and a.shape == b.shape == (1, L)
+            assert torch.isfinite(a).all() and a.numpy().tobytes() == b.numpy().tobytes(), (i, k)
+    with pytest.raises(SystemExit):  # the ODE driver blocks on its readback: no second stream
+        sep_cli.main([str(ind), str(tmp_path / "s2"), "--batch", "3", "--streams", "2"] + common)
+
+
+# ---------------------------------------------------------------- 10. evaluate --sampler ode
+def test_evaluate_cli_records_every_utterances_own_nfe(tmp_path):
+    common = ["--synthetic", "3", "--samples", "4000", "--synthetic-weights", "16", "--dtype", "f32", "--flat-output",
+              "--streams", "1", "--save-n", "0", "--no-stoi"]
+    eval_cli.main(common + ["--sampler", "ode", "--rtol", "1e-3", "--atol", "1e-3", "--max-nfe", "20", "-o", str(tmp_path / "ode")])
+    rec = json.load(open(tmp_path / "ode" / "test.json"))
+    summ = json.load(open(tmp_path / "ode" / "test_summary.json"))
+    assert [r["batch_idx"] for r in rec] == [0, 1, 2]
+    assert all(2 < r["nfe"] <= 20 and r["ode_status"] in (0, 1) and np.isfinite(r["si_sdr"]).all() for r in rec)
+    assert summ["sampler"] == "ode" and summ["number"] == 3
+    assert summ["ode_status_counts"] == {str(c): sum(r["ode_status"] == c for r in rec) for c in (0, -1, 1)}
+    eval_cli.main(common + ["-N", "2", "-o", str(tmp_path / "pc")])
+    rec_pc = json.load(open(tmp_path / "pc" / "test.json"))
+    summ_pc = json.load(open(tmp_path / "pc" / "test_summary.json"))
+    assert all(set(r) == {"batch_idx", "si_sdr", "si_sir", "si_sar", "perm", "pesq", "stoi", "nfe", "runtime", "len_s"}
+               and r["nfe"] == 4 for r in rec_pc)
+    assert summ_pc["sampler"] == "pc" and "ode_status_counts" not in summ_pc

@@ -1,13 +1,19 @@
 """Cost of the probability-flow ODE sampler (Engine.ode_sample, sdes.get_ode_sampler) on one GPU.
 
     python tools/ode_bench.py [--nf 64] [--B 16] [--T 32000] [--rtol 1e-5] [--atol 1e-5] [--max-nfe 600]
-                              [--dtypes f32,split,f16] [--reps 2]
+                              [--dtypes f32,split,f16] [--reps 2] [--each]
 
 Synthetic weights, synthetic mixtures, MixSDE.  Per engine dtype: nfev / accepted / rejected / status of the solve, the
 wall time of one batch (median of --reps timed calls after one warm-up call), and the share of that time spent outside
 the network evaluations.  That share is estimated as 1 - (nfev + denoise) * t_nfe / wall, with t_nfe the time of one
 graph-replayed evaluation of the same (B, T) plan measured through a PC sampler run without corrector (N evaluations +
 N light update kernels).  Prints one JSON line per dtype.
+
+--each: the per-utterance sampler instead (Engine.ode_sample_each: one step controller per utterance, all sharing every
+network evaluation).  Per dtype: the wall time of one ode_sample_each call on the batch (after one warm-up call) against
+the SUM of the wall times of B calls of ode_sample on the utterances one by one (B = 1, the same seeds, after one warm-up
+call of that plan), the evaluations the batch call ran (evals_run = the largest nfev), the utterances' nfev range and
+whether every row of the batch call equals its B = 1 result bit for bit (expected on f32 only).
 """
 import argparse
 import json
@@ -35,6 +41,30 @@ def timed(fn):
     return r, time.perf_counter() - t0
 
 
+def bench_each(eng, mix_norm, args, name):
+    B = mix_norm.shape[0]
+    seeds = [1000 + 7 * b for b in range(B)]
+    kw = dict(rtol=args.rtol, atol=args.atol, max_nfe=args.max_nfe)
+    each = lambda: eng.ode_sample_each(mix_norm, MIX, seeds=seeds, **kw)  # noqa
+    each()
+    (out, infos, evals), wall_each = timed(each)
+    one = [mix_norm[b:b + 1].contiguous() for b in range(B)]
+    eng.ode_sample(one[0], MIX, seed=seeds[0], **kw)
+    wall_solo, equal, solo_nfev = 0.0, True, []
+    for b in range(B):
+        (x, info), w = timed(lambda: eng.ode_sample(one[b], MIX, seed=seeds[b], **kw))
+        wall_solo += w
+        solo_nfev.append(info["nfev"])
+        equal = equal and bool(torch.equal(x[0], out[b])) and info == infos[b]
+    nfev = [i["nfev"] for i in infos]
+    print(json.dumps(dict(mode="each", dtype=name, nf=args.nf, B=B, T=args.T, rtol=args.rtol, atol=args.atol,
+                          max_nfe=args.max_nfe, evals_run=evals, nfev_min=min(nfev), nfev_max=max(nfev),
+                          statuses=sorted({i["status"] for i in infos}), solo_nfev_sum=sum(solo_nfev),
+                          finite=bool(torch.isfinite(out).all()), wall_each_ms=round(wall_each * 1e3, 1),
+                          wall_solo_sum_ms=round(wall_solo * 1e3, 1), speedup=round(wall_solo / wall_each, 2),
+                          rows_equal_solo=equal)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nf", type=int, default=64)
@@ -46,6 +76,7 @@ def main():
     ap.add_argument("--dtypes", default="f32,split,f16")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--pc-steps", type=int, default=30)
+    ap.add_argument("--each", action="store_true", help="one ode_sample_each call against the sum of B calls at B = 1")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
     mix = torch.from_numpy(synth.synth_batch(args.B, T=args.T)[0]).cuda()
@@ -56,6 +87,12 @@ def main():
         if sd is None:
             sd = synth.synth_state_dict([(n, s) for n, s, _ in param_table(cfg)], 7)
         eng = Engine(cfg, pack_state_dict(cfg, sd))
+        if args.each:
+            bench_each(eng, mix_norm, args, name)
+            eng.close()
+            del eng
+            torch.cuda.empty_cache()
+            continue
         # one evaluation of this plan, graph-replayed: PC sampler without corrector
         eng.pc_sample(mix_norm, MIX, N=args.pc_steps, corrector="none", seed=1)
         _, t_pc = timed(lambda: eng.pc_sample(mix_norm, MIX, N=args.pc_steps, corrector="none", seed=1))
