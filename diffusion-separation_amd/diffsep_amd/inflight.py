@@ -54,6 +54,29 @@ def utterance_seeds(n, seed):
     return torch.randint(0, 2 ** 62, (max(n, 1),), generator=torch.Generator().manual_seed(seed)).tolist()
 
 
+WINDOW_SEED_STRIDE = 0x9E3779B97F4A7C15  # the stride get_pc_sampler(minibatch=) advances an explicit seed by
+
+
+def window_seeds(seed, K):
+    """Device RNG seeds of the K windows of one long file (DiffSepModel.separate_long, separate --chunk): window 0 has the
+    file's seed, window k (seed + WINDOW_SEED_STRIDE k) mod 2^64 — what is computed for a window depends neither on how
+    the windows are batched nor on the streams they run on."""
+    return [(int(seed) + WINDOW_SEED_STRIDE * k) % (1 << 64) for k in range(K)]
+
+
+def plan_windows(lengths, window, overlap, plan):
+    """The windows of all files in file-major order: -> (items, item_lengths, starts), items[n] = (file index, window
+    index), item_lengths[n] = its samples (min(file length, window)), starts[i] = plan(lengths[i], window, overlap), the
+    window starts of file i (ops.longform_plan).  The items are what plan_batches groups in place of files."""
+    items, item_lengths, starts = [], [], []
+    for i, T in enumerate(lengths):
+        st = plan(T, window, overlap)
+        starts.append(st)
+        items += [(i, k) for k in range(len(st))]
+        item_lengths += [min(T, window)] * len(st)
+    return items, item_lengths, starts
+
+
 def setup_workers(model, K, own_stream=True):
     """-> (K models, K streams).  One engine (weights repacked on the device + workspace) per stream over ONE set of
     parameters: the model, then replica()s; in the throughput mode when several batches are in flight

@@ -524,6 +524,41 @@ def gram(ref, est):
     return out
 
 
+def longform_plan(T, Tw, Tv):
+    """Window starts of a T-sample file cut into windows of Tw samples with a nominal overlap of Tv (diffsep_longform_plan:
+    host arithmetic, no device needed; raises for a request it refuses: T < 1, Tv < 1 or 3 Tv > Tw).  T <= Tw: [0]."""
+    l = lib()
+    K = l.diffsep_longform_plan(int(T), int(Tw), int(Tv), None, 0)
+    check(0 if K >= 1 else 1, l)
+    starts = (C.c_int64 * K)()
+    check(0 if l.diffsep_longform_plan(int(T), int(Tw), int(Tv), starts, K) == K else 1, l)
+    return list(starts)
+
+
+def longform_stitch(win, T, Tv, want_gram=False, out=None):
+    """diffsep_longform_stitch: win [K,S,Tw] float32 device tensor, the K windows of longform_plan(T, Tw, Tv) -> (out [S,T]
+    float32, perm [K,S] int32[, gram [K-1,S,S] float64]): windows aligned by the source permutation of least squared distance
+    over each overlap (perm[k][i] = the row of window k that is output source i), cross-faded over the seams.  Asynchronous on
+    the current stream, no readback.  out: a dense float32 [S,T] tensor to write into (every element is written)."""
+    if win.dim() != 3 or win.dtype != torch.float32 or not win.is_cuda:
+        raise ValueError("longform_stitch: win must be a float32 [K,S,Tw] device tensor")
+    win = win.contiguous()
+    K, S, Tw = win.shape
+    l = lib()
+    nbytes = l.diffsep_longform_workspace_bytes(K, S)
+    check(0 if nbytes >= 0 else 1, l)
+    if out is None:
+        out = torch.empty((S, int(T)), dtype=torch.float32, device=win.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (S, int(T)) or out.device != win.device:
+        raise ValueError("longform_stitch: out must be a dense float32 [S,T] tensor on win's device")
+    perm = torch.empty((K, S), dtype=torch.int32, device=win.device)
+    gram_ = torch.empty((max(K - 1, 0), S, S), dtype=torch.float64, device=win.device) if want_gram else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=win.device)
+    check(l.diffsep_longform_stitch(_ptr(win), K, S, Tw, int(T), int(Tv), _ptr(out), _ptr(perm),
+                                    _ptr(gram_) if (want_gram and K > 1) else None, _ptr(ws), nbytes, _stream_ptr()), l)
+    return (out, perm, gram_) if want_gram else (out, perm)
+
+
 def _dev_i32(v, device):
     """host list / array or tensor -> contiguous int32 device tensor (host values through pinned memory on the current
     stream: a pageable copy would stall every other stream's work)"""

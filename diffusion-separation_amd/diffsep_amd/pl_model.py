@@ -317,6 +317,41 @@ class DiffSepModel:
         est, *others = self.get_pc_sampler("reverse_diffusion", "ald2", mix_n, **skw)()
         return self.denormalize_batch(est, mean, std)
 
+    def separate_long(self, mix, window, overlap, batch=16, seed=None, **sampler_kwargs):
+        """A recording of any length as windows of the shape the engine is fast at (extension): mix
+        [1,T] / [1,1,T] on the device is cut into the K windows of ops.longform_plan(T, window, overlap) (samples), up to
+        `batch` windows share an engine call, and ops.longform_stitch aligns their source orders over the overlaps and
+        cross-fades them on the device.  Every window is handled exactly as a file is (separate.separate_on_device): normalised
+        over its own samples, sampled by the fused PC sampler with lengths= / seeds=, rescaled against its own stretch of the
+        mixture.  Window k's device RNG seed is inflight.window_seeds(seed, K)[k]; seed None: one draw of torch's generator.
+        T <= window: one window, the file through that same call.  Returns [1,S,T]; self.longform_info = {"starts", "perm"
+        (device int32 [K,S]: output source i is row perm[k][i] of window k), "seeds", "K"}."""
+        from . import inflight
+        from .separate import separate_on_device
+        if mix.dim() == 2:
+            mix = mix[None]
+        if mix.dim() != 3 or tuple(mix.shape[:2]) != (1, 1) or not mix.is_cuda:
+            raise ValueError("separate_long: mix must be a [1,T] or [1,1,T] device tensor (one single-channel recording)")
+        T = int(mix.shape[-1])
+        starts = ops.longform_plan(T, window, overlap)
+        K, L = len(starts), min(T, int(window))
+        seeds = inflight.window_seeds(int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else seed, K)
+        batch = max(1, int(batch))
+        parts = []
+        for k0 in range(0, K, batch):
+            ks = range(k0, min(K, k0 + batch))
+            mb = torch.stack([mix[0, :, starts[k]:starts[k] + L] for k in ks])
+            parts.append(separate_on_device(mb, self, sampler_kwargs, mix.device, lengths=[L] * len(ks),
+                                            seeds=[seeds[k] for k in ks], check_finite=True))
+        win = torch.cat(parts) if len(parts) > 1 else parts[0]
+        if K == 1:
+            out, perm = win, torch.arange(win.shape[1], dtype=torch.int32, device=win.device)[None]
+        else:
+            out, perm = ops.longform_stitch(win, T, overlap)
+            out = out[None]
+        self.longform_info = {"starts": starts, "perm": perm, "seeds": seeds, "K": K}
+        return out
+
     # ---- denoising score-matching loss, forward values (pl_model.py:166-247, 327-424) --------------------------
     FORWARD_ONLY = ("the score-matching loss is implemented forward-only (diffsep_score_loss): backward passes, optimiser, EMA "
                     "update, gradient clipping and compute_score_loss_with_pit (train_source_order 'pit', init_hack 6) are "

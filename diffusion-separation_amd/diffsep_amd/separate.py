@@ -11,7 +11,11 @@ hybrid), --batch B: files whose padded spectrogram width is equal share one engi
 each file's tail kept at zero by the engine: the docstring of evaluate.py has the details), --streams K engine calls
 in flight on K engines / HIP streams (planning, worker set-up, workspace reserve, the launch / collect ring and the
 overflow re-run are inflight.py's, shared with evaluate), and --seed (file i of the sorted folder then gets the i-th
-draw of that generator as its device RNG seed: the written files do not depend on --batch or --streams).  --sampler ode [--rtol --atol --max-nfe] runs the
+draw of that generator as its device RNG seed: the written files do not depend on --batch or --streams), and --chunk SECONDS [--overlap SECONDS]: a file longer than the chunk is
+cut into windows of that length (ops.longform_plan; the overlap defaults to an eighth of the chunk), the windows of all files are
+what --batch groups and --streams keeps in flight, and a file is stitched on the device (ops.longform_stitch: source orders
+aligned over the overlaps, seams cross-faded) and written when its last window has been collected; a file
+no longer than the chunk is handled as without --chunk.  --sampler ode [--rtol --atol --max-nfe] runs the
 probability-flow ODE sampler (sdes.get_ode_sampler, adaptive RK45 on the device) instead of the PC sampler.  With
 --batch 1 a file is one engine call; with --batch K > 1 the files of a batch (the same plan as the PC path) share every
 network evaluation while each keeps its own step controller (diffsep_ode_sample_each), so with --dtype f32 the written
@@ -112,6 +116,89 @@ def separate(mix, model, sampler_kwargs, device):
     return separate_on_device(mix, model, sampler_kwargs, device, check_finite=True).cpu()
 
 
+def chunk_samples(args, fs):
+    """(window, overlap) of --chunk / --overlap in samples at the model's rate, or SystemExit for a refused request"""
+    window = int(round(args.chunk * fs))
+    overlap = int(round((args.chunk / 8 if args.overlap is None else args.overlap) * fs))
+    if window < 3:
+        raise SystemExit(f"--chunk {args.chunk}: a window of {window} samples is too short")
+    if overlap < 1:
+        raise SystemExit(f"--overlap: an overlap of {overlap} samples is too short (at least one sample)")
+    if 3 * overlap > window:
+        raise SystemExit(f"--overlap {overlap / fs:g} s is more than a third of --chunk {args.chunk:g} s: the seams of "
+                         "neighbouring windows would intersect")
+    return window, overlap
+
+
+def separate_chunked(args, files, lengths, seeds, models, streams, kw, model_sr):
+    """--chunk: the windows of all files (file-major) are the items of the batches in flight; window results stay on the device
+    until their file's last one has been collected, then the file is stitched there and written."""
+    window, overlap = chunk_samples(args, model_sr)
+    eng = models[0].score_model.engine()
+    items, item_lengths, starts = inflight.plan_windows(lengths, window, overlap, ops.longform_plan)
+    if seeds is None:  # one draw of torch's generator per file, as a file without --seed gets one per engine call
+        seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in files]
+    wseeds = [inflight.window_seeds(seeds[i], len(starts[i])) for i in range(len(files))]
+    batches = inflight.plan_batches(range(len(items)), item_lengths, eng.padded_frames, max(1, args.batch))
+    inflight.reserve_largest(models, batches, item_lengths)
+    wavs, done = {}, {}  # per file: (samples, rate) while windows of it are still to be launched; collected windows by index
+
+    def load(i):
+        if i not in wavs:
+            wav, sr = wavio.load(files[i])
+            if sr != model_sr:  # the reference only warns (separate.py:151-155, quirk Q9)
+                print(f"Warning: {files[i].stem}: this model expects {model_sr} Hz, but the file is {sr} Hz.")
+            wavs[i] = (wav[:1], sr, len(starts[i]))
+        wav, sr, left = wavs[i]
+        wavs[i] = (wav, sr, left - 1)
+        if left == 1:
+            del wavs[i]
+        return wav, sr
+
+    def launch(w, j, group):
+        parts, srs = [], []
+        for n in group:
+            i, k = items[n]
+            wav, sr = load(i)
+            seg = wav[:, starts[i][k]:starts[i][k] + item_lengths[n]]
+            parts.append((seg, seg))
+            srs.append(sr)
+        mix, _, lens = datasets.pad_batch(parts, side="right",
+                                          to=eng.bucket_length(eng.padded_frames(max(item_lengths[n] for n in group))))
+        sds = [wseeds[items[n][0]][items[n][1]] for n in group]
+        mix_d = inflight.upload(mix, args.device)
+        sep = separate_on_device(mix_d, models[w], kw, args.device, lengths=lens, seeds=sds)
+        return group, lens, srs, sep, mix_d, sds
+
+    def collect(w, item):
+        group, lens, srs, sep, mix_d, sds = item
+        sep = inflight.finite_or_rerun(
+            models[w], streams[w], (sep,),
+            lambda fb: (separate_on_device(mix_d, fb, kw, args.device, lengths=lens, seeds=sds),),
+            what=str([f"{files[items[n][0]].name}[{items[n][1]}]" for n in group]))[0]
+        for b, n in enumerate(group):
+            i, k = items[n]
+            got = done.setdefault(i, {})
+            got[k] = sep[b, :, :lens[b]]
+            if len(got) < len(starts[i]):
+                continue
+            # every window of file i has been collected, i.e. its stream has drained: stitch on this worker's stream
+            with torch.cuda.stream(streams[w]):
+                if len(got) == 1:
+                    out = got[0]
+                else:
+                    out, _ = ops.longform_stitch(torch.stack([got[q] for q in range(len(got))]), lengths[i], overlap)
+                out = out.cpu()
+            del done[i]
+            for q in range(out.shape[0]):
+                d = args.output_dir / f"s{q}"
+                d.mkdir(parents=True, exist_ok=True)
+                wavio.save(d / f"{files[i].stem}.wav", out[q:q + 1], srs[b], bits=32)
+
+    inflight.Ring(streams, launch, collect).run(batches)
+    print(f"separated {len(files)} files into {args.output_dir} ({len(items)} windows of up to {window} samples)")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Separate all the wav files in a specified folder")
     ap.add_argument("input_dir", type=Path)
@@ -137,7 +224,21 @@ def main(argv=None):
     ap.add_argument("--atol", type=float, default=1e-5, help="--sampler ode: absolute tolerance (reference default)")
     ap.add_argument("--max-nfe", type=int, default=0,
                     help="--sampler ode: no step attempt starts beyond this many network evaluations (0: unbounded)")
+    ap.add_argument("--chunk", type=float, default=None, metavar="SECONDS",
+                    help="cut files longer than this into windows of this length (4 = the shape the engine is tuned for), "
+                         "separate the windows as the items of --batch / --streams and stitch them on the device")
+    ap.add_argument("--overlap", type=float, default=None, metavar="SECONDS",
+                    help="with --chunk: overlap of neighbouring windows (default: an eighth of the chunk; at most a third)")
     args = ap.parse_args(argv)
+    if args.chunk is None and args.overlap is not None:
+        raise SystemExit("--overlap goes with --chunk")
+    if args.chunk is not None and args.sampler == "ode":
+        raise SystemExit("--chunk runs the predictor-corrector sampler: --sampler ode --chunk is not supported")
+    if args.chunk is not None and args.chunk <= 0:
+        raise SystemExit("--chunk must be positive")
+    if args.overlap is not None and not 0 < 3 * args.overlap <= args.chunk:
+        raise SystemExit(f"--overlap {args.overlap:g} s must be positive and at most a third of --chunk {args.chunk:g} s: the "
+                         "seams of neighbouring windows would intersect")
     if args.sampler == "ode" and args.streams > 1:
         raise SystemExit("--sampler ode blocks on a readback per step attempt: --streams must be 1 (use --batch)")
     K = max(1, args.streams)
@@ -193,6 +294,8 @@ def main(argv=None):
                 wavio.save(d / f"{f.stem}.wav", sep[0, k:k + 1], sr, bits=32)
         print(f"separated {len(files)} files into {args.output_dir} (probability-flow ODE)")
         return
+    if args.chunk is not None:
+        return separate_chunked(args, files, lengths, seeds, models, streams, kw, model_sr)
     eng = model.score_model.engine()
     batches = inflight.plan_batches(range(len(files)), lengths, eng.padded_frames, max(1, args.batch))
     inflight.reserve_largest(models, batches, lengths)

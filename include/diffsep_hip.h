@@ -627,6 +627,37 @@ int32_t diffsep_stoi(const float* ref, const float* est, double* out, int32_t B,
                      const int32_t* lengths, const int32_t* perm, int32_t fs, int32_t extended, void* workspace,
                      int64_t workspace_bytes, void* stream);
 
+/* Long recordings: a file of T samples as K windows of Tw samples with a nominal overlap of Tv, stitched on the device.
+ * The plan (host arithmetic only, no device needed): refused (-1 and a message) unless T >= 1, Tv >= 1 and 3 Tv <= Tw.
+ * T <= Tw: K = 1, starts = {0}, the one window is the file itself (T samples).  Otherwise hop = Tw - Tv,
+ * K = 1 + ceil((T - Tw) / hop), starts[k] = k hop for k < K - 1 and starts[K - 1] = T - Tw: the last window is shifted back to
+ * end at T, so every window is full length.  Windows k and k + 1 overlap on [starts[k + 1], starts[k] + Tw): Tv samples, more
+ * for the last pair only.  Their seam is the n = min(Tv, overlap) samples from starts[k + 1] + (overlap - n) / 2 on; seams
+ * never intersect, and a sample outside every seam belongs to exactly one window (the one between its neighbouring seams).
+ * diffsep_longform_plan returns K and fills starts_out when it is non-NULL (cap < K is refused).  diffsep_longform_locate
+ * says where sample t comes from, by the arithmetic the blend kernel uses: window *k alone (*n = 0), or offset *j of the
+ * *n-sample seam of windows *k and *k + 1.
+ * diffsep_longform_stitch — win [K][S][Tw] -> out [S][T], asynchronous on `stream`, no host readback, three launches; K must be
+ * the plan's K (K = 1: the first T samples of the one window's rows).  Sources come out of a separator in arbitrary order per
+ * window, so windows are aligned before they are cross-faded:
+ *   cross-Gram  C_k[i][j] = sum over the overlap of win[k][i] win[k + 1][j]: products exact in float64, float64 sums in a fixed
+ *               order (no atomics: the result does not depend on the stream, on co-resident work or on repetition);
+ *               gram_out [K - 1][S][S] (nullable) receives them;
+ *   permutation r_k = the permutation maximising sum_i C_k[i][r(i)] (= least squared distance over the overlap), candidates in
+ *               lexicographic order with a strict >: a tie, an all-silent overlap included, keeps the earliest (the identity);
+ *               g_0 = identity, g_{k+1}[i] = r_k[g_k[i]]; perm_out [K][S] = g: output source i is row g_k[i] of window k;
+ *   blend       every out[i][t] written exactly once (no pre-zeroing): the owning window's sample, or inside a seam
+ *               a + (b - a) r, r = (j + 0.5f) / n, each operation rounded to float32 on its own — where the two windows
+ *               agree bit for bit the output is that value bit for bit.
+ * S in 1..3.  Refusals (S, K, a refused plan, a workspace below diffsep_longform_workspace_bytes(K, S), null pointers) return
+ * non-zero with a message and write nothing.  Alignment sees the overlap only: a source silent through a whole overlap leaves
+ * that pair's decision to the tie rule or to noise. */
+int32_t diffsep_longform_plan(int64_t T, int64_t Tw, int64_t Tv, int64_t* starts_out, int32_t cap);
+int32_t diffsep_longform_locate(int64_t T, int64_t Tw, int64_t Tv, int64_t t, int32_t* k_out, int64_t* j_out, int64_t* n_out);
+int64_t diffsep_longform_workspace_bytes(int32_t K, int32_t S);
+int32_t diffsep_longform_stitch(const float* win, int32_t K, int32_t S, int64_t Tw, int64_t T, int64_t Tv, float* out,
+                                int32_t* perm_out, double* gram_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- the denoising score-matching loss (forward values only): DiffSepModel.sample_prior (pl_model.py:179-247),
  * compute_score_loss (:411-424), compute_score_loss_init_hack_pit (:370-405), compute_score_loss_with_pit_allthetime
  * (:327-368).  With true_mix = mix / S, mean = (A + exp(-lambda t) Pn) x0 and L the marginal std (times sigma_mix for
