@@ -452,11 +452,8 @@ int ds_launch_convert(const void* src, void* dst, long n, int sd, int dd, hipStr
 int ds_launch_fill(float* p, float v, long n, hipStream_t st);
 
 // ------------------------------------------------------------------ probability-flow ODE (ode.hip)
-#define DS_ODE_MAX_K 7        // Runge-Kutta stage derivatives held at once (RK45: 6 stages + FSAL)
+#include "ode_host.h"  // DS_ODE_MAX_K, ds_ode_tableau, and the host-only step controller (OdePlan, OdeCtl)
 #define DS_ODE_MAX_BLOCKS 1024  // grid cap of the ODE passes = rows of the per-block partial-sum slab
-// Butcher tableau of scipy.integrate's RK45 (method 0, Dormand-Prince) / RK23 (method 1, Bogacki-Shampine): A [ns][ns]
-// row-major, B [ns], C [ns], E [ns + 1]; any output may be null.  Returns -1 for an unknown method.
-int ds_ode_tableau(int method, double* A, double* B, double* C, double* E, int* n_stages, int* error_order);
 // One pass over the state [B][S][T] (ode.hip, ode_stage_kernel):
 //   kout != null:  kout = x's probability-flow drift  f(x, t) - 0.5 g(t)^2 [sigma_mix^2] score   (the K of this stage)
 //   acc = sum_{j < nk} c[j] k[j]   (k[kidx] is the drift just computed, taken from registers)

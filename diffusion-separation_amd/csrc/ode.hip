@@ -4,8 +4,11 @@
 // The solver state y / y_new is fp64 (scipy holds its state in float64), the stage derivatives K_j are fp32 (they are the
 // network's float32 drift, which is what scipy stores after its float64 round trip), and a stage input is
 // fp32(y + (sum_j a_j K_j) h) formed in fp64: the very numbers scipy's rk_step hands the reference's ode_func.
-// One thread = V consecutive time indices of one utterance x all sources (the drift couples the sources through
-// their mean); loads are float4 / 2 x double2 when the rows allow it (V = 4), grid-stride over a capped grid.
+// One thread item = V consecutive time indices of one utterance x all sources (the drift couples the sources through
+// their mean): ode_item is what every pass computes for it, with float4 / 2 x double2 accesses when the rows allow it.
+// Two kernels walk the items — the whole batch as one system (ode_stage_kernel) and one system per utterance of a
+// zero-padded batch (ode_stage_each_kernel) — and share the item body, the block-partials tail and the final tree, so
+// that what an utterance computes is the same code whichever entry it came through.
 // Contraction is off in this file: every sum and product rounds on its own, like numpy's, so that the stage inputs
 // can be reproduced bit for bit in float64 on the host (tests/test_ode_gpu.py).
 #include <string.h>
@@ -17,172 +20,139 @@
 
 #pragma clang fp contract(off)
 
-// ------------------------------------------------------------------ tableaux (scipy/integrate/_ivp/rk.py, scipy 1.15)
-int ds_ode_tableau(int method, double* A, double* B, double* C, double* E, int* n_stages, int* error_order) {
-  if (method == DIFFSEP_ODE_RK45) {  // Dormand-Prince 5(4)
-    static const double a[6][6] = {
-        {0, 0, 0, 0, 0, 0},
-        {1.0 / 5, 0, 0, 0, 0, 0},
-        {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
-        {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
-        {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
-        {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0}};
-    static const double b[6] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
-    static const double c[6] = {0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1};
-    static const double e[7] = {-71.0 / 57600, 0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
-    if (A) memcpy(A, a, sizeof(a));
-    if (B) memcpy(B, b, sizeof(b));
-    if (C) memcpy(C, c, sizeof(c));
-    if (E) memcpy(E, e, sizeof(e));
-    if (n_stages) *n_stages = 6;
-    if (error_order) *error_order = 4;
-    return 0;
-  }
-  if (method == DIFFSEP_ODE_RK23) {  // Bogacki-Shampine 3(2)
-    static const double a[3][3] = {{0, 0, 0}, {1.0 / 2, 0, 0}, {0, 3.0 / 4, 0}};
-    static const double b[3] = {2.0 / 9, 1.0 / 3, 4.0 / 9};
-    static const double c[3] = {0, 1.0 / 2, 3.0 / 4};
-    static const double e[4] = {5.0 / 72, -1.0 / 12, -1.0 / 9, 1.0 / 8};
-    if (A) memcpy(A, a, sizeof(a));
-    if (B) memcpy(B, b, sizeof(b));
-    if (C) memcpy(C, c, sizeof(c));
-    if (E) memcpy(E, e, sizeof(e));
-    if (n_stages) *n_stages = 3;
-    if (error_order) *error_order = 2;
-    return 0;
-  }
-  return -1;
-}
-
-// ------------------------------------------------------------------ vector loads / stores
-template <int V> __device__ inline void ldf(const float* p, float* v) {
-  if constexpr (V == 4) {
+// ------------------------------------------------------------------ loads / stores of V consecutive elements (VEC: V = 4, 16-byte aligned)
+template <int V, bool VEC> __device__ inline void ldf(const float* p, float* v) {
+  if constexpr (VEC) {
     const float4 q = *reinterpret_cast<const float4*>(p);
     v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
   } else {
-    v[0] = p[0];
+#pragma unroll
+    for (int i = 0; i < V; ++i) v[i] = p[i];
   }
 }
-template <int V> __device__ inline void stf(float* p, const float* v) {
-  if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  else p[0] = v[0];
+template <int V, bool VEC> __device__ inline void stf(float* p, const float* v) {
+  if constexpr (VEC) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < V; ++i) p[i] = v[i];
+  }
 }
-template <int V> __device__ inline void ldd(const double* p, double* v) {
-  if constexpr (V == 4) {
+template <int V, bool VEC> __device__ inline void ldd(const double* p, double* v) {
+  if constexpr (VEC) {
     const double2 q0 = reinterpret_cast<const double2*>(p)[0], q1 = reinterpret_cast<const double2*>(p)[1];
     v[0] = q0.x; v[1] = q0.y; v[2] = q1.x; v[3] = q1.y;
   } else {
-    v[0] = p[0];
+#pragma unroll
+    for (int i = 0; i < V; ++i) v[i] = p[i];
   }
 }
-template <int V> __device__ inline void std_(double* p, const double* v) {
-  if constexpr (V == 4) {
+template <int V, bool VEC> __device__ inline void std_(double* p, const double* v) {
+  if constexpr (VEC) {
     reinterpret_cast<double2*>(p)[0] = make_double2(v[0], v[1]);
     reinterpret_cast<double2*>(p)[1] = make_double2(v[2], v[3]);
   } else {
-    p[0] = v[0];
+#pragma unroll
+    for (int i = 0; i < V; ++i) p[i] = v[i];
   }
 }
 
 // ------------------------------------------------------------------ the fused pass (see OdeArgs in common.h)
-template <int V>
-__global__ __launch_bounds__(256) void ode_stage_kernel(OdeArgs a) {
-  __shared__ double sh[2][4];
+// One item: samples t0 .. t0 + V of utterance b, all sources; the drift at time t_eval, the combination with step size h.
+// Mode 3 adds the item's squares to q0, q1.
+template <int V, bool VEC>
+__device__ inline void ode_item(const OdeArgs& a, int b, long t0, float t_eval, double h, double& q0, double& q1) {
   const int S = a.S;
-  const long T = a.T, TV = T / V;
-  const long items = (long)a.B * TV;
-  if (a.t_next_out && blockIdx.x == 0)
-    for (int i = threadIdx.x; i < a.B; i += 256) a.t_next_out[i] = a.t_next;
-  double q0 = 0.0, q1 = 0.0;
-  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
-    const int b = (int)(it / TV);
-    const long t0 = (it - (long)b * TV) * V;
-    float kd[DS_MAX_SRC][V];
-    if (a.kout) {
-      // the drift of sde_coeff_kernel (f, g through the same helpers), then rev_f = f - g g score 0.5 in the operation
-      // order of sde_reverse_kernel (RSDE.sde with probability_flow = True, sdes/sdes.py:130-160)
-      float xv[DS_MAX_SRC][V];
+  const long T = a.T;
+  float kd[DS_MAX_SRC][V];
+  if (a.kout) {
+    // the drift of sde_coeff_kernel (f, g through the same helpers), then rev_f = f - g g score 0.5 in the operation
+    // order of sde_reverse_kernel (RSDE.sde with probability_flow = True, sdes/sdes.py:130-160)
+    float xv[DS_MAX_SRC][V];
+#pragma unroll
+    for (int s = 0; s < DS_MAX_SRC; ++s)
+      if (s < S) ldf<V, VEC>(a.x + ((long)b * S + s) * T + t0, xv[s]);
+    const float g0 = sde_g_of_t(a.s, t_eval);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      float xs[DS_MAX_SRC], f[DS_MAX_SRC];
+#pragma unroll
+      for (int s = 0; s < DS_MAX_SRC; ++s) xs[s] = s < S ? xv[s][v] : 0.f;
+      sde_mix_drift(a.s, xs, f, S);
 #pragma unroll
       for (int s = 0; s < DS_MAX_SRC; ++s)
-        if (s < S) ldf<V>(a.x + ((long)b * S + s) * T + t0, xv[s]);
-      const float g0 = sde_g_of_t(a.s, a.tt ? a.tt[b] : a.t);
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        float xs[DS_MAX_SRC], f[DS_MAX_SRC];
-#pragma unroll
-        for (int s = 0; s < DS_MAX_SRC; ++s) xs[s] = s < S ? xv[s][v] : 0.f;
-        sde_mix_drift(a.s, xs, f, S);
-#pragma unroll
-        for (int s = 0; s < DS_MAX_SRC; ++s)
-          if (s < S) kd[s][v] = f[s];
-      }
-#pragma unroll
-      for (int s = 0; s < DS_MAX_SRC; ++s) {
-        if (s >= S) continue;
-        const long o = ((long)b * S + s) * T + t0;
-        float sc[V];
-        ldf<V>(a.score + o, sc);
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          const float g = a.smix ? g0 * a.smix[(long)b * T + t0 + v] : g0;
-          kd[s][v] = kd[s][v] - g * g * sc[v] * 0.5f;
-        }
-        stf<V>(a.kout + o, kd[s]);
-      }
+        if (s < S) kd[s][v] = f[s];
     }
-    if (a.mode == 0) continue;
 #pragma unroll
     for (int s = 0; s < DS_MAX_SRC; ++s) {
       if (s >= S) continue;
       const long o = ((long)b * S + s) * T + t0;
-      double yv[V], acc[V];
-      ldd<V>(a.y + o, yv);
+      float sc[V];
+      ldf<V, VEC>(a.score + o, sc);
 #pragma unroll
-      for (int v = 0; v < V; ++v) acc[v] = 0.0;
-      for (int j = 0; j < a.nk; ++j) {
-        float kv[V];
-        if (j == a.kidx) {
-#pragma unroll
-          for (int v = 0; v < V; ++v) kv[v] = kd[s][v];
-        } else {
-          ldf<V>(a.k[j] + o, kv);
-        }
-        const double cj = a.c[j];
-#pragma unroll
-        for (int v = 0; v < V; ++v) acc[v] = acc[v] + cj * (double)kv[v];
+      for (int v = 0; v < V; ++v) {
+        const float g = a.smix ? g0 * a.smix[(long)b * T + t0 + v] : g0;
+        kd[s][v] = kd[s][v] - g * g * sc[v] * 0.5f;
       }
-      if (a.mode == 1) {  // rk_step: fun(t + c h, y + dot(K[:s].T, a[:s]) * h)
-        float xo[V];
+      stf<V, VEC>(a.kout + o, kd[s]);
+    }
+  }
+  if (a.mode == 0) return;
 #pragma unroll
-        for (int v = 0; v < V; ++v) xo[v] = (float)(yv[v] + acc[v] * a.h);
-        stf<V>(a.xo + o, xo);
-      } else if (a.mode == 2) {  // rk_step: y_new = y + h * dot(K[:-1].T, B)
-        double yn[V];
-        float xo[V];
+  for (int s = 0; s < DS_MAX_SRC; ++s) {
+    if (s >= S) continue;
+    const long o = ((long)b * S + s) * T + t0;
+    double yv[V], acc[V];
+    ldd<V, VEC>(a.y + o, yv);
 #pragma unroll
-        for (int v = 0; v < V; ++v) {
-          yn[v] = yv[v] + a.h * acc[v];
-          xo[v] = (float)yn[v];
-        }
-        std_<V>(a.yo + o, yn);
-        if (a.xo) stf<V>(a.xo + o, xo);
-      } else {  // _estimate_error_norm: norm(dot(K.T, E) * h / (atol + max(|y|, |y_new|) rtol))
-        double yn[V];
-        if (a.ynew) ldd<V>(a.ynew + o, yn);
+    for (int v = 0; v < V; ++v) acc[v] = 0.0;
+    for (int j = 0; j < a.nk; ++j) {
+      float kv[V];
+      if (j == a.kidx) {
 #pragma unroll
-        for (int v = 0; v < V; ++v) {
-          const double m = a.ynew ? fmax(fabs(yv[v]), fabs(yn[v])) : fabs(yv[v]);
-          const double scale = a.atol + m * a.rtol;
-          const double d = (acc[v] * a.h) / scale;
-          const double dy = yv[v] / scale;
-          q0 = q0 + d * d;
-          q1 = q1 + dy * dy;
-        }
+        for (int v = 0; v < V; ++v) kv[v] = kd[s][v];
+      } else {
+        ldf<V, VEC>(a.k[j] + o, kv);
+      }
+      const double cj = a.c[j];
+#pragma unroll
+      for (int v = 0; v < V; ++v) acc[v] = acc[v] + cj * (double)kv[v];
+    }
+    if (a.mode == 1) {  // rk_step: fun(t + c h, y + dot(K[:s].T, a[:s]) * h)
+      float xo[V];
+#pragma unroll
+      for (int v = 0; v < V; ++v) xo[v] = (float)(yv[v] + acc[v] * h);
+      stf<V, VEC>(a.xo + o, xo);
+    } else if (a.mode == 2) {  // rk_step: y_new = y + h * dot(K[:-1].T, B)
+      double yn[V];
+      float xo[V];
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        yn[v] = yv[v] + h * acc[v];
+        xo[v] = (float)yn[v];
+      }
+      std_<V, VEC>(a.yo + o, yn);
+      if (a.xo) stf<V, VEC>(a.xo + o, xo);
+    } else {  // _estimate_error_norm: norm(dot(K.T, E) * h / (atol + max(|y|, |y_new|) rtol))
+      double yn[V];
+      if (a.ynew) ldd<V, VEC>(a.ynew + o, yn);
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        const double m = a.ynew ? fmax(fabs(yv[v]), fabs(yn[v])) : fabs(yv[v]);
+        const double scale = a.atol + m * a.rtol;
+        const double d = (acc[v] * h) / scale;
+        const double dy = yv[v] / scale;
+        q0 = q0 + d * d;
+        q1 = q1 + dy * dy;
       }
     }
   }
-  if (a.mode != 3) return;
-  // per-block partials, fixed order (no float atomics): wave butterfly, then the 4 waves in order
+}
+
+// per-block partials of a mode-3 pass, fixed order (no float atomics): wave butterfly, then the 4 waves in order, then
+// part[2 blk + q].  Every thread of the block calls it.
+__device__ inline void ode_block_partials(double q0, double q1, double* part) {
+  __shared__ double sh[2][4];
   q0 = wave_sum_d(q0);
   q1 = wave_sum_d(q1);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -191,13 +161,14 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(OdeArgs a) {
   if (threadIdx.x == 0) {
     double r0 = 0.0, r1 = 0.0;
     for (int i = 0; i < 4; ++i) { r0 = r0 + sh[0][i]; r1 = r1 + sh[1][i]; }
-    a.part[2 * blockIdx.x] = r0;
-    a.part[2 * blockIdx.x + 1] = r1;
+    part[2 * blockIdx.x] = r0;
+    part[2 * blockIdx.x + 1] = r1;
   }
 }
 
-__global__ __launch_bounds__(256) void ode_norm_final_kernel(const double* __restrict__ part, int nblk, long n,
-                                                             double* __restrict__ out) {
+// the final tree of one block over nblk partials: strided sums, wave sums, the 4 waves in order;
+// out[q] = sqrt(sum) / sqrt(n)   (common.norm: ||x||_2 / sqrt(x.size))
+__device__ inline void ode_norm_tree(const double* __restrict__ part, int nblk, long n, double* __restrict__ out) {
   __shared__ double sh[2][4];
   double r[2] = {0.0, 0.0};
   for (int i = threadIdx.x; i < nblk; i += 256) { r[0] = r[0] + part[2 * i]; r[1] = r[1] + part[2 * i + 1]; }
@@ -210,8 +181,28 @@ __global__ __launch_bounds__(256) void ode_norm_final_kernel(const double* __res
   if (threadIdx.x < 2) {
     double s = 0.0;
     for (int i = 0; i < 4; ++i) s = s + sh[threadIdx.x][i];
-    out[threadIdx.x] = sqrt(s) / sqrt((double)n);  // common.norm: ||x||_2 / sqrt(x.size)
+    out[threadIdx.x] = sqrt(s) / sqrt((double)n);
   }
+}
+
+// the whole batch as one system: items of all utterances in one sequence, grid-stride over a capped grid
+template <int V>
+__global__ __launch_bounds__(256) void ode_stage_kernel(OdeArgs a) {
+  const long TV = a.T / V;
+  const long items = (long)a.B * TV;
+  if (a.t_next_out && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < a.B; i += 256) a.t_next_out[i] = a.t_next;
+  double q0 = 0.0, q1 = 0.0;
+  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
+    const int b = (int)(it / TV);
+    ode_item<V, V == 4>(a, b, (it - (long)b * TV) * V, a.tt ? a.tt[b] : a.t, a.h, q0, q1);
+  }
+  if (a.mode == 3) ode_block_partials(q0, q1, a.part);
+}
+
+__global__ __launch_bounds__(256) void ode_norm_final_kernel(const double* __restrict__ part, int nblk, long n,
+                                                             double* __restrict__ out) {
+  ode_norm_tree(part, nblk, n, out);
 }
 
 __global__ __launch_bounds__(256) void ode_cast_kernel(const float* __restrict__ x, double* __restrict__ y, long n) {
@@ -222,23 +213,33 @@ __global__ __launch_bounds__(256) void ode_round_kernel(const double* __restrict
 }
 
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-int ds_launch_ode_stage(const OdeArgs& a, hipStream_t st, int* nblk) {
-  DS_CHECK(a.S >= 1 && a.S <= DS_MAX_SRC && a.B >= 1 && a.T >= 1, "ode: bad shape");
-  DS_CHECK(a.nk >= 0 && a.nk <= DS_ODE_MAX_K && a.kidx < a.nk && (a.kidx < 0 || a.kout), "ode: bad stage combination");
-  DS_CHECK(a.mode >= 0 && a.mode <= 3, "ode: bad mode");
-  DS_CHECK(!a.kout || (a.x && a.score && (a.tt || a.t > 0.f)), "ode: the drift needs x, t and the score");
-  DS_CHECK(a.mode == 0 || a.y, "ode: the stage combination needs y");
-  DS_CHECK(a.mode != 1 || a.xo, "ode: stage mode needs x_out");
-  DS_CHECK(a.mode != 2 || a.yo, "ode: y_new mode needs y_new_out");
-  DS_CHECK(a.mode != 3 || a.part, "ode: error mode needs the partial-sum slab");
-  for (int j = 0; j < a.nk; ++j) DS_CHECK(j == a.kidx || a.k[j], "ode: null stage derivative");
+// float4 / double2 accesses: rows of a multiple of 4 samples and every tensor 16-byte aligned
+static bool ode_vec(const OdeArgs& a) {
   bool vec = a.T % 4 == 0;
   const void* ps[] = {a.x, a.score, a.kout, a.y, a.ynew, a.yo, a.xo};
   for (const void* p : ps) vec = vec && al16(p);
   for (int j = 0; j < a.nk; ++j) vec = vec && al16(a.k[j]);
-  const int V = vec ? 4 : 1;
-  const long items = (long)a.B * (a.T / V);
+  return vec;
+}
+// what both stage launches ask of their arguments (`who`: "ode" / "ode each" in the message)
+static int ode_check(const OdeArgs& a, const char* who) {
+  const std::string w(who);
+  DS_CHECK(a.S >= 1 && a.S <= DS_MAX_SRC && a.B >= 1 && a.T >= 1, w + ": bad shape");
+  DS_CHECK(a.nk >= 0 && a.nk <= DS_ODE_MAX_K && a.kidx < a.nk && (a.kidx < 0 || a.kout), w + ": bad stage combination");
+  DS_CHECK(a.mode >= 0 && a.mode <= 3, w + ": bad mode");
+  DS_CHECK(!a.kout || (a.x && a.score && (a.tt || a.t > 0.f)), w + ": the drift needs x, t and the score");
+  DS_CHECK(a.mode == 0 || a.y, w + ": the stage combination needs y");
+  DS_CHECK(a.mode != 1 || a.xo, w + ": stage mode needs x_out");
+  DS_CHECK(a.mode != 2 || a.yo, w + ": y_new mode needs y_new_out");
+  DS_CHECK(a.mode != 3 || a.part, w + ": error mode needs the partial-sum slab");
+  for (int j = 0; j < a.nk; ++j) DS_CHECK(j == a.kidx || a.k[j], w + ": null stage derivative");
+  return 0;
+}
+
+int ds_launch_ode_stage(const OdeArgs& a, hipStream_t st, int* nblk) {
+  if (ode_check(a, "ode")) return 1;
+  const bool vec = ode_vec(a);
+  const long items = (long)a.B * (a.T / (vec ? 4 : 1));
   const int nb = (int)std::min<long>(cdiv(items, 256), DS_ODE_MAX_BLOCKS);
   if (vec) hipLaunchKernelGGL(ode_stage_kernel<4>, dim3(nb), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(ode_stage_kernel<1>, dim3(nb), dim3(256), 0, st, a);
@@ -265,138 +266,22 @@ int ds_launch_ode_round(const double* y, float* x, long n, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------ one step controller per utterance
-// The passes above on a zero-padded batch of utterances that are B independent ODE systems (diffsep_ode_sample_each): the
+// The same pass on a zero-padded batch of utterances that are B independent ODE systems (diffsep_ode_sample_each): the
 // step size, the times, whether the utterance still integrates and its length come from device tables [B].  What utterance
 // b computes — every stage input, and the summation tree of its two norms — is what ode_stage_kernel +
 // ode_norm_final_kernel compute for it alone (B = 1, T = lens[b]): a thread item is 4 consecutive samples x all sources
 // when lens[b] % 4 == 0 and one sample otherwise, nb = min(cdiv(items, 256), DS_ODE_MAX_BLOCKS) blocks of the row's grid
 // stride over the items with a stride of nb * 256, and the partials are reduced in the same order.  None of that depends
 // on B, b or the padded T; rows that are not 16-byte aligned (T % 4 != 0) keep the item shape and load by element.
-template <int V, bool VEC> __device__ inline void ldfe(const float* p, float* v) {
-  if constexpr (VEC) {
-    ldf<4>(p, v);
-  } else {
-#pragma unroll
-    for (int i = 0; i < V; ++i) v[i] = p[i];
-  }
-}
-template <int V, bool VEC> __device__ inline void stfe(float* p, const float* v) {
-  if constexpr (VEC) {
-    stf<4>(p, v);
-  } else {
-#pragma unroll
-    for (int i = 0; i < V; ++i) p[i] = v[i];
-  }
-}
-template <int V, bool VEC> __device__ inline void ldde(const double* p, double* v) {
-  if constexpr (VEC) {
-    ldd<4>(p, v);
-  } else {
-#pragma unroll
-    for (int i = 0; i < V; ++i) v[i] = p[i];
-  }
-}
-template <int V, bool VEC> __device__ inline void stde(double* p, const double* v) {
-  if constexpr (VEC) {
-    std_<4>(p, v);
-  } else {
-#pragma unroll
-    for (int i = 0; i < V; ++i) p[i] = v[i];
-  }
-}
 
-// the items of utterance b that block blockIdx.x of its nb blocks owns: the loop body of ode_stage_kernel, operation for
-// operation, with the utterance's own t and h
+// the items of utterance b that block blockIdx.x of its nb blocks owns, with the utterance's own t and h
 template <int V, bool VEC>
 __device__ inline void ode_each_items(const OdeEachArgs& e, int b, long len, long nb, double& q0, double& q1) {
   const OdeArgs& a = e.a;
-  const int S = a.S;
-  const long T = a.T, items = len / V;
+  const float t_eval = a.kout ? a.tt[b] : 0.f;
   const double h = a.mode ? e.h[b] : 0.0;
-  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += nb * 256) {
-    const long t0 = it * V;
-    float kd[DS_MAX_SRC][V];
-    if (a.kout) {
-      float xv[DS_MAX_SRC][V];
-#pragma unroll
-      for (int s = 0; s < DS_MAX_SRC; ++s)
-        if (s < S) ldfe<V, VEC>(a.x + ((long)b * S + s) * T + t0, xv[s]);
-      const float g0 = sde_g_of_t(a.s, a.tt[b]);
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        float xs[DS_MAX_SRC], f[DS_MAX_SRC];
-#pragma unroll
-        for (int s = 0; s < DS_MAX_SRC; ++s) xs[s] = s < S ? xv[s][v] : 0.f;
-        sde_mix_drift(a.s, xs, f, S);
-#pragma unroll
-        for (int s = 0; s < DS_MAX_SRC; ++s)
-          if (s < S) kd[s][v] = f[s];
-      }
-#pragma unroll
-      for (int s = 0; s < DS_MAX_SRC; ++s) {
-        if (s >= S) continue;
-        const long o = ((long)b * S + s) * T + t0;
-        float sc[V];
-        ldfe<V, VEC>(a.score + o, sc);
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          const float g = a.smix ? g0 * a.smix[(long)b * T + t0 + v] : g0;
-          kd[s][v] = kd[s][v] - g * g * sc[v] * 0.5f;
-        }
-        stfe<V, VEC>(a.kout + o, kd[s]);
-      }
-    }
-    if (a.mode == 0) continue;
-#pragma unroll
-    for (int s = 0; s < DS_MAX_SRC; ++s) {
-      if (s >= S) continue;
-      const long o = ((long)b * S + s) * T + t0;
-      double yv[V], acc[V];
-      ldde<V, VEC>(a.y + o, yv);
-#pragma unroll
-      for (int v = 0; v < V; ++v) acc[v] = 0.0;
-      for (int j = 0; j < a.nk; ++j) {
-        float kv[V];
-        if (j == a.kidx) {
-#pragma unroll
-          for (int v = 0; v < V; ++v) kv[v] = kd[s][v];
-        } else {
-          ldfe<V, VEC>(a.k[j] + o, kv);
-        }
-        const double cj = a.c[j];
-#pragma unroll
-        for (int v = 0; v < V; ++v) acc[v] = acc[v] + cj * (double)kv[v];
-      }
-      if (a.mode == 1) {
-        float xo[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) xo[v] = (float)(yv[v] + acc[v] * h);
-        stfe<V, VEC>(a.xo + o, xo);
-      } else if (a.mode == 2) {
-        double yn[V];
-        float xo[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          yn[v] = yv[v] + h * acc[v];
-          xo[v] = (float)yn[v];
-        }
-        stde<V, VEC>(a.yo + o, yn);
-        if (a.xo) stfe<V, VEC>(a.xo + o, xo);
-      } else {
-        double yn[V];
-        if (a.ynew) ldde<V, VEC>(a.ynew + o, yn);
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          const double m = a.ynew ? fmax(fabs(yv[v]), fabs(yn[v])) : fabs(yv[v]);
-          const double scale = a.atol + m * a.rtol;
-          const double d = (acc[v] * h) / scale;
-          const double dy = yv[v] / scale;
-          q0 = q0 + d * d;
-          q1 = q1 + dy * dy;
-        }
-      }
-    }
-  }
+  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < len / V; it += nb * 256)
+    ode_item<V, VEC>(a, b, it * V, t_eval, h, q0, q1);
 }
 
 // blocks of an utterance's row of the grid that its summation tree needs: min(cdiv(items, 256), DS_ODE_MAX_BLOCKS)
@@ -406,9 +291,8 @@ __device__ inline long ode_each_blocks(long len) {
   return nb < DS_ODE_MAX_BLOCKS ? nb : DS_ODE_MAX_BLOCKS;
 }
 
-// grid (min(cdiv(T, 256), DS_ODE_MAX_BLOCKS), B): row b of the grid is utterance b; vec: T % 4 == 0 and every tensor 16-byte aligned
+// grid (min(cdiv(T, 256), DS_ODE_MAX_BLOCKS), B): row b of the grid is utterance b; vec: ode_vec of the padded batch
 __global__ __launch_bounds__(256) void ode_stage_each_kernel(OdeEachArgs e, int vec) {
-  __shared__ double sh[2][4];
   const OdeArgs& a = e.a;
   const int b = blockIdx.y;
   if (!e.active[b]) return;
@@ -432,46 +316,19 @@ __global__ __launch_bounds__(256) void ode_stage_each_kernel(OdeEachArgs e, int 
     if ((a.mode == 1 || a.mode == 2) && a.xo) a.xo[o] = 0.f;
     if (a.mode == 2) a.yo[o] = 0.0;
   }
-  if (a.mode != 3 || blockIdx.x >= nb) return;
-  q0 = wave_sum_d(q0);
-  q1 = wave_sum_d(q1);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { sh[0][w] = q0; sh[1][w] = q1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r0 = 0.0, r1 = 0.0;
-    for (int i = 0; i < 4; ++i) { r0 = r0 + sh[0][i]; r1 = r1 + sh[1][i]; }
-    double* part = a.part + (long)b * 2 * DS_ODE_MAX_BLOCKS;
-    part[2 * blockIdx.x] = r0;
-    part[2 * blockIdx.x + 1] = r1;
-  }
+  if (a.mode == 3 && blockIdx.x < nb) ode_block_partials(q0, q1, a.part + (long)b * 2 * DS_ODE_MAX_BLOCKS);
 }
 
-// grid (B): ode_norm_final_kernel on the slab of utterance b with its own block count and n = S lens[b]
+// grid (B): the final tree on the slab of utterance b with its own block count and n = S lens[b]
 __global__ __launch_bounds__(256) void ode_norm_final_each_kernel(const double* __restrict__ part_all,
                                                                   const int* __restrict__ lens,
                                                                   const int* __restrict__ active, int S,
                                                                   double* __restrict__ norms) {
-  __shared__ double sh[2][4];
   const int b = blockIdx.x;
   if (!active[b]) return;
   const long len = lens[b];
   if (len < 1) return;
-  const int nblk = (int)ode_each_blocks(len);
-  const double* part = part_all + (long)b * 2 * DS_ODE_MAX_BLOCKS;
-  double r[2] = {0.0, 0.0};
-  for (int i = threadIdx.x; i < nblk; i += 256) { r[0] = r[0] + part[2 * i]; r[1] = r[1] + part[2 * i + 1]; }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int q = 0; q < 2; ++q) {
-    const double v = wave_sum_d(r[q]);
-    if (lane == 0) sh[q][w] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    double s = 0.0;
-    for (int i = 0; i < 4; ++i) s = s + sh[threadIdx.x][i];
-    norms[2 * b + threadIdx.x] = sqrt(s) / sqrt((double)((long)S * len));
-  }
+  ode_norm_tree(part_all + (long)b * 2 * DS_ODE_MAX_BLOCKS, (int)ode_each_blocks(len), (long)S * len, norms + 2 * b);
 }
 
 // grid (x, B): the accepted utterances take their step (whole rows: the tails of y_new and K[ns] are zero like those of y, K[0])
@@ -490,23 +347,13 @@ __global__ __launch_bounds__(256) void ode_commit_each_kernel(double* __restrict
 
 int ds_launch_ode_stage_each(const OdeEachArgs& e, hipStream_t st) {
   const OdeArgs& a = e.a;
-  DS_CHECK(a.S >= 1 && a.S <= DS_MAX_SRC && a.B >= 1 && a.B <= 65535 && a.T >= 1 && a.T <= 0x7fffffffL, "ode each: bad shape");
-  DS_CHECK(a.nk >= 0 && a.nk <= DS_ODE_MAX_K && a.kidx < a.nk && (a.kidx < 0 || a.kout), "ode each: bad stage combination");
-  DS_CHECK(a.mode >= 0 && a.mode <= 3, "ode each: bad mode");
+  if (ode_check(a, "ode each")) return 1;
+  DS_CHECK(a.B <= 65535 && a.T <= 0x7fffffffL, "ode each: bad shape");
   DS_CHECK(e.active && e.lens && (a.mode == 0 || e.h), "ode each: the tables h, active and lengths are needed");
-  DS_CHECK(!a.kout || (a.x && a.score && a.tt), "ode each: the drift needs x, t [B] and the score");
-  DS_CHECK(a.mode == 0 || a.y, "ode each: the stage combination needs y");
-  DS_CHECK(a.mode != 1 || a.xo, "ode each: stage mode needs x_out");
-  DS_CHECK(a.mode != 2 || a.yo, "ode each: y_new mode needs y_new_out");
-  DS_CHECK(a.mode != 3 || a.part, "ode each: error mode needs the partial-sum slabs");
+  DS_CHECK(!a.kout || a.tt, "ode each: the drift needs x, t [B] and the score");
   DS_CHECK(!e.tnext || a.t_next_out, "ode each: t_next needs its output");
-  for (int j = 0; j < a.nk; ++j) DS_CHECK(j == a.kidx || a.k[j], "ode each: null stage derivative");
-  bool vec = a.T % 4 == 0;
-  const void* ps[] = {a.x, a.score, a.kout, a.y, a.ynew, a.yo, a.xo};
-  for (const void* p : ps) vec = vec && al16(p);
-  for (int j = 0; j < a.nk; ++j) vec = vec && al16(a.k[j]);
   const int nb = (int)std::min<long>(cdiv(a.T, 256), DS_ODE_MAX_BLOCKS);
-  hipLaunchKernelGGL(ode_stage_each_kernel, dim3(nb, a.B), dim3(256), 0, st, e, vec ? 1 : 0);
+  hipLaunchKernelGGL(ode_stage_each_kernel, dim3(nb, a.B), dim3(256), 0, st, e, ode_vec(a) ? 1 : 0);
   DS_LAUNCH_CHECK();
   return 0;
 }

@@ -1,0 +1,156 @@
+// ode_host.h — the host side of the probability-flow ODE sampler that needs no GPU: scipy's Butcher tableaux, what a solve
+// derives from its diffsep_ode_config (OdePlan) and the adaptive step controller (OdeCtl), ported from scipy 1.15
+// (integrate/_ivp/rk.py RungeKutta._step_impl, common.py select_initial_step / validate_tol, base.py OdeSolver.step, ivp.py
+// solve_ivp's loop).  diffsep_ode_sample drives one OdeCtl, diffsep_ode_sample_each one per utterance (sampler.hip);
+// tests/ode_ctl_main.cpp drives one on a small float64 system against scipy itself.  Plain C++17, no HIP.
+#pragma once
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+
+#include "../../include/diffsep_hip.h"
+
+#define DS_ODE_MAX_K 7  // Runge-Kutta stage derivatives held at once (RK45: 6 stages + FSAL)
+
+// Butcher tableau of scipy.integrate's RK45 (method 0, Dormand-Prince) / RK23 (method 1, Bogacki-Shampine), as rk.py holds
+// it: A [ns][ns] row-major, B [ns], C [ns], E [ns + 1]; any output may be null.  Returns -1 for an unknown method.
+inline int ds_ode_tableau(int method, double* A, double* B, double* C, double* E, int* n_stages, int* error_order) {
+  if (method == DIFFSEP_ODE_RK45) {  // Dormand-Prince 5(4)
+    static const double a[6][6] = {
+        {0, 0, 0, 0, 0, 0},
+        {1.0 / 5, 0, 0, 0, 0, 0},
+        {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
+        {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
+        {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
+        {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0}};
+    static const double b[6] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
+    static const double c[6] = {0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1};
+    static const double e[7] = {-71.0 / 57600, 0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
+    if (A) memcpy(A, a, sizeof(a));
+    if (B) memcpy(B, b, sizeof(b));
+    if (C) memcpy(C, c, sizeof(c));
+    if (E) memcpy(E, e, sizeof(e));
+    if (n_stages) *n_stages = 6;
+    if (error_order) *error_order = 4;
+    return 0;
+  }
+  if (method == DIFFSEP_ODE_RK23) {  // Bogacki-Shampine 3(2)
+    static const double a[3][3] = {{0, 0, 0}, {1.0 / 2, 0, 0}, {0, 3.0 / 4, 0}};
+    static const double b[3] = {2.0 / 9, 1.0 / 3, 4.0 / 9};
+    static const double c[3] = {0, 1.0 / 2, 3.0 / 4};
+    static const double e[4] = {5.0 / 72, -1.0 / 12, -1.0 / 9, 1.0 / 8};
+    if (A) memcpy(A, a, sizeof(a));
+    if (B) memcpy(B, b, sizeof(b));
+    if (C) memcpy(C, c, sizeof(c));
+    if (E) memcpy(E, e, sizeof(e));
+    if (n_stages) *n_stages = 3;
+    if (error_order) *error_order = 2;
+    return 0;
+  }
+  return -1;
+}
+
+// What a solve derives from its diffsep_ode_config: the tableau (row s of A at A + s * DS_ODE_MAX_K), the tolerances as
+// scipy uses them and the integration interval sde.T = 1 -> eps.
+struct OdePlan {
+  double A[DS_ODE_MAX_K * DS_ODE_MAX_K], B[DS_ODE_MAX_K], C[DS_ODE_MAX_K], E[DS_ODE_MAX_K + 1];
+  int ns, eorder;
+  double rtol, atol, max_step, eps;
+  double t0, t_bound, dir, interval, err_exp;
+  double first_step;  // <= 0: select_initial_step
+  int max_nfe;        // 0: unbounded
+};
+
+// Fill and validate the plan (`who`: the entry point's name in the message); returns the message, empty when all is well.
+inline std::string ode_plan_fill(OdePlan& p, const diffsep_ode_config& oc, const char* who) {
+  const std::string w(who);
+  memset(&p, 0, sizeof(p));
+  double A0[6 * 6];
+  if (ds_ode_tableau(oc.method, A0, p.B, p.C, p.E, &p.ns, &p.eorder) != 0)
+    return w + ": method must be DIFFSEP_ODE_RK45 or DIFFSEP_ODE_RK23 (DOP853 / Radau / BDF / LSODA are not implemented)";
+  for (int i = 0; i < p.ns; ++i)
+    for (int j = 0; j < p.ns; ++j) p.A[i * DS_ODE_MAX_K + j] = A0[i * p.ns + j];
+  if (!(oc.eps > 0.0 && oc.eps < 1.0)) return w + ": eps must be in (0, 1)";
+  if (!(oc.atol >= 0.0 && oc.rtol >= 0.0)) return w + ": tolerances must be non-negative";
+  if (!(oc.N >= 1 || !oc.denoise)) return w + ": the denoise step needs N >= 1";
+  if (!(oc.max_nfe >= 0)) return w + ": max_nfe must be >= 0";
+  // common.validate_tol: rtol below 100 machine epsilons is raised to it (scipy warns)
+  p.rtol = std::max(oc.rtol, 100 * 2.220446049250313e-16);
+  p.atol = oc.atol;
+  p.max_step = (oc.max_step > 0.0) ? oc.max_step : INFINITY;
+  p.eps = oc.eps;
+  p.t0 = 1.0;  // sde.T = 1
+  p.t_bound = oc.eps;
+  p.dir = -1.0;
+  p.interval = fabs(p.t_bound - p.t0);
+  p.err_exp = -1.0 / (p.eorder + 1);
+  p.first_step = oc.first_step;
+  p.max_nfe = oc.max_nfe;
+  if (!(oc.first_step <= 0.0 || oc.first_step <= p.interval))
+    return w + ": first_step exceeds the interval (scipy: `first_step` exceeds bounds)";
+  return std::string();
+}
+
+// One system's step controller.  The caller evaluates the right-hand side and the RMS norms; every decision is taken here:
+//   while (c.begin_attempt(p)) { rk_step from c.t with c.h (stage s at c.stage_time(p, s)); c.end_attempt(p, error norm); }
+struct OdeCtl {
+  double t = 1.0, h_abs = 0.0, h = 0.0, t_new = 0.0, min_step = 0.0;
+  int nfev = 0, n_acc = 0, n_rej = 0, status = 2;  // status 2: integrating; 0: reached t_bound; -1: step too small; 1: max_nfe
+  bool new_step = true, rejected = false;
+
+  // common.select_initial_step: h0 from d0 = norm(y0 / scale) and d1 = norm(f0 / scale) ...
+  static double initial_h0(const OdePlan& p, double d0, double d1) {
+    const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+    return std::min(h0, p.interval);
+  }
+  // ... and the first h_abs from d1, h0 and norm((f1 - f0) / scale), f1 = f(t0 + h0 dir, y0 + h0 dir f0)
+  void initial_step(const OdePlan& p, double d1, double norm_f1_f0, double h0) {
+    const double d2 = norm_f1_f0 / h0;
+    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0 * 1e-3)
+                                                   : pow(0.01 / std::max(d1, d2), 1.0 / (p.eorder + 1));
+    h_abs = std::min(std::min(100 * h0, h1), std::min(p.interval, p.max_step));
+  }
+  // OdeSolver.step / _step_impl up to rk_step: false when the system attempts no (further) step — it had ended, or ends
+  // here with status -1 or 1; otherwise h and t_new of this attempt are set.  (min_step is fixed when a step begins; the
+  // two exits are tested before every attempt of it.)
+  bool begin_attempt(const OdePlan& p) {
+    if (status != 2) return false;
+    if (new_step) {
+      min_step = 10 * fabs(nextafter(t, p.dir * INFINITY) - t);
+      if (h_abs > p.max_step) h_abs = p.max_step;
+      else if (h_abs < min_step) h_abs = min_step;
+      rejected = false;
+      new_step = false;
+    }
+    if (h_abs < min_step) { status = -1; return false; }
+    if (p.max_nfe > 0 && nfev + p.ns > p.max_nfe) { status = 1; return false; }
+    h = h_abs * p.dir;
+    t_new = t + h;
+    if (p.dir * (t_new - p.t_bound) > 0) t_new = p.t_bound;
+    h = t_new - t;
+    h_abs = fabs(h);
+    return true;
+  }
+  // the time of stage s of the attempt (s = ns: the FSAL evaluation at t + h)
+  double stage_time(const OdePlan& p, int s) const { return s < p.ns ? t + p.C[s] * h : t + h; }
+  // _step_impl after rk_step, with the attempt's error norm: true when the step is accepted (t advanced; status 0 at t_bound)
+  bool end_attempt(const OdePlan& p, double err) {
+    nfev += p.ns;
+    if (err < 1) {
+      double factor = err == 0 ? 10.0 : std::min(10.0, 0.9 * pow(err, p.err_exp));
+      if (rejected) factor = std::min(1.0, factor);
+      h_abs *= factor;
+      t = t_new;
+      ++n_acc;
+      new_step = true;
+      if (p.dir * (t - p.t_bound) >= 0) status = 0;
+      return true;
+    }
+    h_abs *= std::max(0.2, 0.9 * pow(err, p.err_exp));
+    rejected = true;
+    ++n_rej;
+    return false;
+  }
+};

@@ -203,44 +203,24 @@ extern "C" int32_t diffsep_pc_sample(diffsep_engine* e, const diffsep_sde_config
 
 // ------------------------------------------------------------------ probability-flow ODE sampler
 // sdes.get_ode_sampler(...)() (reference sdes/__init__.py:193-278): scipy.integrate.solve_ivp(RK45 | RK23) on the
-// probability-flow ODE, the controller ported from scipy 1.15 (integrate/_ivp/rk.py RungeKutta._step_impl, common.py
-// select_initial_step / norm, base.py OdeSolver.step, ivp.py solve_ivp's loop) and run on the host; every stage is one
-// graph-replayed network evaluation (run_nfe) + one fused pass (ode.hip), every step attempt one pinned readback of its
-// error norm.
-extern "C" int32_t diffsep_ode_sample(diffsep_engine* e, const diffsep_sde_config* sde, const diffsep_ode_config* oc,
-                                      const float* mix_norm, const float* x_init, const float* noise, uint64_t seed,
-                                      float* out, int32_t B, int64_t T, diffsep_ode_info* info, void* stream) {
-  DS_CHECK(e && sde && oc && mix_norm && out, "ode_sample: null argument");
-  if (check_sde(e, sde, "ode_sample")) return 1;
-  DS_CHECK(B >= 1 && T >= 1, "ode_sample: empty batch");
-  DS_CHECK(!(x_init && noise), "ode_sample: x_init and noise are alternatives");
-  double Ab[DS_ODE_MAX_K * DS_ODE_MAX_K], Bb[DS_ODE_MAX_K], Cb[DS_ODE_MAX_K], Eb[DS_ODE_MAX_K + 1];
-  int ns = 0, eorder = 0;
-  DS_CHECK(ds_ode_tableau(oc->method, nullptr, nullptr, nullptr, nullptr, &ns, &eorder) == 0,
-           "ode_sample: method must be DIFFSEP_ODE_RK45 or DIFFSEP_ODE_RK23 (DOP853 / Radau / BDF / LSODA are not implemented)");
-  {
-    double A0[6 * 6];
-    ds_ode_tableau(oc->method, A0, Bb, Cb, Eb, nullptr, nullptr);
-    for (int i = 0; i < ns; ++i) for (int j = 0; j < ns; ++j) Ab[i * DS_ODE_MAX_K + j] = A0[i * ns + j];
-  }
-  const double eps = oc->eps;
-  DS_CHECK(eps > 0.0 && eps < 1.0, "ode_sample: eps must be in (0, 1)");
-  DS_CHECK(oc->atol >= 0.0 && oc->rtol >= 0.0, "ode_sample: tolerances must be non-negative");
-  DS_CHECK(oc->N >= 1 || !oc->denoise, "ode_sample: the denoise step needs N >= 1");
-  DS_CHECK(oc->max_nfe >= 0, "ode_sample: max_nfe must be >= 0");
-  // common.validate_tol: rtol below 100 machine epsilons is raised to it (scipy warns)
-  const double rtol = std::max(oc->rtol, 100 * 2.220446049250313e-16), atol = oc->atol;
-  const double max_step = (oc->max_step > 0.0) ? oc->max_step : INFINITY;
-  const double t0 = 1.0, t_bound = eps, dir = -1.0, interval = std::fabs(t_bound - t0);  // sde.T = 1
-  DS_CHECK(oc->first_step <= 0.0 || oc->first_step <= interval, "ode_sample: first_step exceeds the interval (scipy: `first_step` exceeds bounds)");
+// probability-flow ODE.  scipy's controller runs on the host (ode_host.h: OdePlan, OdeCtl — one copy for both entries
+// below); every stage is one graph-replayed network evaluation (run_nfe) + one fused pass (ode.hip), every step attempt one
+// pinned readback of its error norm.
+namespace {
+// the solver's device state, carved from the engine's ODE buffer: y, y_new, K[], then per system (the whole batch, or each
+// utterance) a partial-sum slab and two norms, then the entry's upload tables
+struct OdeWork {
+  double *y, *ynew;
+  float* K[DS_ODE_MAX_K];
+  double *part, *dnorm;
+  char* tab;
+};
+}  // namespace
 
-  StreamScope sc_(e, stream);
-  hipStream_t st = sc_.st;
-  const int S = e->cfg.num_sources;
-  if (ensure_plan(e, B, T, st)) return 1;
-  const size_t nst = (size_t)B * S * T;
+static int ode_workspace(diffsep_engine* e, size_t nst, int n_sys, size_t tab_bytes, OdeWork& w) {
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t need = 2 * al(nst * 8) + DS_ODE_MAX_K * al(nst * 4) + al(2 * DS_ODE_MAX_BLOCKS * 8) + 256;
+  const size_t part_bytes = al((size_t)n_sys * 2 * DS_ODE_MAX_BLOCKS * 8), norm_bytes = al((size_t)n_sys * 16);
+  const size_t need = 2 * al(nst * 8) + DS_ODE_MAX_K * al(nst * 4) + part_bytes + norm_bytes + al(tab_bytes);
   if (need > e->ode_cap) {
     if (e->ode_buf) {
       DS_HIP(hipDeviceSynchronize());
@@ -251,15 +231,87 @@ extern "C" int32_t diffsep_ode_sample(diffsep_engine* e, const diffsep_sde_confi
     DS_HIP(hipMalloc((void**)&e->ode_buf, need));
     e->ode_cap = need;
   }
+  char* p = e->ode_buf;
+  w.y = (double*)p; p += al(nst * 8);
+  w.ynew = (double*)p; p += al(nst * 8);
+  for (int j = 0; j < DS_ODE_MAX_K; ++j) { w.K[j] = (float*)p; p += al(nst * 4); }
+  w.part = (double*)p; p += part_bytes;
+  w.dnorm = (double*)p; p += norm_bytes;
+  w.tab = p;
+  return 0;
+}
+
+// The fused pass after a network evaluation: K[kout] = drift (kout >= 0), then the combination `mode` of K[0..nk) with
+// coefficients c, written for the next evaluation (mode 3: the error scale from max(|y|, |y_new|), or from |y| alone in
+// select_initial_step).  The times and the step size are the caller's: scalars for the whole batch, tables per utterance.
+static OdeArgs ode_pass_args(const diffsep_engine* e, const OdeArgs& base, const OdeWork& w, int kout, int mode, int nk,
+                             const double* c, bool scale_ynew = true) {
+  OdeArgs a = base;
+  a.kout = kout >= 0 ? w.K[kout] : nullptr;
+  a.kidx = (kout >= 0 && kout < nk) ? kout : -1;
+  a.nk = nk;
+  for (int j = 0; j < nk; ++j) { a.k[j] = w.K[j]; a.c[j] = c[j]; }
+  a.mode = mode; a.y = w.y;
+  if (mode == 1) a.xo = e->st_x;
+  if (mode == 2) { a.yo = w.ynew; a.xo = e->st_x; }
+  if (mode == 3 && scale_ynew) a.ynew = w.ynew;
+  if (mode == 1 || mode == 2) a.t_next_out = e->st_t;
+  return a;
+}
+static OdeArgs ode_base_args(const diffsep_engine* e, const SdeP& sp, const float* smix, const OdePlan& plan,
+                             const OdeWork& w, int B, int S, long T) {
+  OdeArgs base;
+  memset(&base, 0, sizeof(base));
+  base.s = sp; base.x = e->st_x; base.score = e->st_score; base.smix = smix;
+  base.rtol = plan.rtol; base.atol = plan.atol; base.part = w.part; base.B = B; base.S = S; base.T = T;
+  base.kidx = -1;
+  return base;
+}
+static diffsep_engine::ProfRec ode_pass_rec(const char* name, size_t nst, int nk, int mode, int B, long T, int S) {
+  return hbm_rec(name, 4.0 * nst * (2 + nk) + 8.0 * nst * (mode >= 2 ? 2 : 1), B, 1, (int)T, S);
+}
+
+// solution.y[:, -1] (the last accepted state) -> float32; optional denoise: x_mean of one reverse_diffusion step at eps
+// without noise (reference denoise_update_fn; dt = 1/N, quirk Q1).  lens: the tails of a zero-padded batch stay zero.
+static int ode_finish(diffsep_engine* e, const SdeP& sp, const diffsep_ode_config* oc, const float* smix, const double* y,
+                      float* out, int B, int S, long T, const int* lens, hipStream_t st) {
+  const size_t nst = (size_t)B * S * T;
+  if (ds_launch_ode_round(y, e->st_x, (long)nst, st)) return 1;
+  if (oc->denoise) {
+    if (ds_launch_fill(e->st_t, (float)oc->eps, B, st)) return 1;
+    if (run_nfe(e, B, T, st)) return 1;
+    if (ds_launch_sde_predictor(sp, oc->N, e->st_x, e->st_t, e->st_score, nullptr, e->st_xm, out, B, S, T, smix, 0, st, lens))
+      return 1;
+  } else {
+    DS_HIP(hipMemcpyAsync(out, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
+  }
+  return 0;
+}
+static void ode_info(const OdeCtl& c, diffsep_ode_info* info) {
+  info->nfev = c.nfev; info->n_accepted = c.n_acc; info->n_rejected = c.n_rej; info->status = c.status; info->t_final = c.t;
+}
+
+extern "C" int32_t diffsep_ode_sample(diffsep_engine* e, const diffsep_sde_config* sde, const diffsep_ode_config* oc,
+                                      const float* mix_norm, const float* x_init, const float* noise, uint64_t seed,
+                                      float* out, int32_t B, int64_t T, diffsep_ode_info* info, void* stream) {
+  DS_CHECK(e && sde && oc && mix_norm && out, "ode_sample: null argument");
+  if (check_sde(e, sde, "ode_sample")) return 1;
+  DS_CHECK(B >= 1 && T >= 1, "ode_sample: empty batch");
+  DS_CHECK(!(x_init && noise), "ode_sample: x_init and noise are alternatives");
+  OdePlan plan;
+  const std::string bad = ode_plan_fill(plan, *oc, "ode_sample");
+  DS_CHECK(bad.empty(), bad);
+  const int ns = plan.ns;
+
+  StreamScope sc_(e, stream);
+  hipStream_t st = sc_.st;
+  const int S = e->cfg.num_sources;
+  if (ensure_plan(e, B, T, st)) return 1;
+  const size_t nst = (size_t)B * S * T;
+  OdeWork w;
+  if (ode_workspace(e, nst, 1, 0, w)) return 1;
   double* pin;  // pinned readback of the two norms
   if (e->ode_pin.acquire(2, &pin)) return 1;
-  char* p = e->ode_buf;
-  double* y = (double*)p; p += al(nst * 8);
-  double* ynew = (double*)p; p += al(nst * 8);
-  float* K[DS_ODE_MAX_K];
-  for (int j = 0; j < DS_ODE_MAX_K; ++j) { K[j] = (float*)p; p += al(nst * 4); }
-  double* part = (double*)p; p += al(2 * DS_ODE_MAX_BLOCKS * 8);
-  double* dnorm = (double*)p;
   const SdeP sp = to_sdep(sde);
 
   // x_T -> st_x (and y = x_T in fp64)
@@ -276,167 +328,88 @@ extern "C" int32_t diffsep_ode_sample(diffsep_engine* e, const diffsep_sde_confi
     }
     if (ds_launch_sde_prior(sp, e->st_mix, z, e->st_x, B, S, T, smix, st)) return 1;
   }
-  if (ds_launch_ode_cast(e->st_x, y, (long)nst, st)) return 1;
+  if (ds_launch_ode_cast(e->st_x, w.y, (long)nst, st)) return 1;
 
-  OdeArgs base;
-  memset(&base, 0, sizeof(base));
-  base.s = sp; base.x = e->st_x; base.score = e->st_score; base.smix = smix;
-  base.rtol = rtol; base.atol = atol; base.part = part; base.B = B; base.S = S; base.T = T;
-  base.kidx = -1;
-  // the fused pass after the network evaluation at (float) t_eval: K[kout] = drift, then the combination `mode` of
-  // K[0..nk) with coefficients c, written for the next evaluation at (float) t_next (mode 3: the error scale from
-  // max(|y|, |y_new|), or from |y| alone in select_initial_step)
+  const OdeArgs base = ode_base_args(e, sp, smix, plan, w, B, S, T);
+  // one pass after the evaluation at (float) t_eval, written for the next evaluation at (float) t_next; name: its profile
+  // record (null: none)
   auto pass = [&](int kout, double t_eval, int mode, int nk, const double* c, double h, double t_next, int* nblk,
-                  bool scale_ynew = true) -> int {
-    OdeArgs a = base;
-    a.kout = kout >= 0 ? K[kout] : nullptr;
-    a.t = (float)t_eval;
-    a.kidx = (kout >= 0 && kout < nk) ? kout : -1;
-    a.nk = nk;
-    for (int j = 0; j < nk; ++j) { a.k[j] = K[j]; a.c[j] = c[j]; }
-    a.h = h; a.mode = mode; a.y = y;
-    if (mode == 1) a.xo = e->st_x;
-    if (mode == 2) { a.yo = ynew; a.xo = e->st_x; }
-    if (mode == 3 && scale_ynew) a.ynew = ynew;
-    if (mode == 1 || mode == 2) { a.t_next_out = e->st_t; a.t_next = (float)t_next; }
-    return prof_launch(e, st, hbm_rec("ode_stage (fused drift + RK stage)", 4.0 * nst * (2 + nk) + 8.0 * nst * (mode >= 2 ? 2 : 1), B, 1, (int)T, S),
-                       [&]() { return ds_launch_ode_stage(a, st, nblk); });
+                  bool scale_ynew = true, const char* name = "ode_stage (fused drift + RK stage)") -> int {
+    OdeArgs a = ode_pass_args(e, base, w, kout, mode, nk, c, scale_ynew);
+    a.t = (float)t_eval; a.h = h; a.t_next = (float)t_next;
+    if (!name) return ds_launch_ode_stage(a, st, nblk);
+    const diffsep_engine::ProfRec rec = kout < 0 ? hbm_rec(name, 16.0 * nst, B, 1, (int)T, S) : ode_pass_rec(name, nst, nk, mode, B, T, S);
+    return prof_launch(e, st, rec, [&]() { return ds_launch_ode_stage(a, st, nblk); });
   };
   // the two norms of the last mode-3 pass -> host (stream-ordered pinned readback, waited on by its event)
   auto read_norms = [&](int nblk, double* n0, double* n1) -> int {
-    if (ds_launch_ode_norm_final(part, nblk, (long)nst, dnorm, st)) return 1;
-    DS_HIP(hipMemcpyAsync(pin, dnorm, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (ds_launch_ode_norm_final(w.part, nblk, (long)nst, w.dnorm, st)) return 1;
+    DS_HIP(hipMemcpyAsync(pin, w.dnorm, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     if (e->ode_pin.record(st) || e->ode_pin.wait()) return 1;
     *n0 = pin[0];
     if (n1) *n1 = pin[1];
     return 0;
   };
 
-  int nfev = 0, n_acc = 0, n_rej = 0, status = 2;
-  double t = t0;
-  if (ds_launch_fill(e->st_t, (float)t, B, st)) return 1;
+  OdeCtl c;
+  c.t = plan.t0;
+  if (ds_launch_fill(e->st_t, (float)c.t, B, st)) return 1;
   if (run_nfe(e, B, T, st)) return 1;
-  ++nfev;
-  double h_abs;
+  ++c.nfev;
   const double one = 1.0;
-  if (oc->first_step <= 0.0) {  // common.select_initial_step
+  int nb = 0;
+  if (plan.first_step <= 0.0) {  // common.select_initial_step
     const double pm[2] = {-1.0, 1.0};
-    int nb = 0;
     double d0, d1, d2;
-    if (pass(0, t, 3, 1, &one, 1.0, 0.0, &nb, false)) return 1;  // K0 = f0; norm(f0 / scale), norm(y0 / scale)
+    if (pass(0, c.t, 3, 1, &one, 1.0, 0.0, &nb, false)) return 1;  // K0 = f0; norm(f0 / scale), norm(y0 / scale)
     if (read_norms(nb, &d1, &d0)) return 1;
-    double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-    h0 = std::min(h0, interval);
-    OdeArgs a = base;  // y1 = y0 + h0 * direction * f0
-    a.nk = 1; a.k[0] = K[0]; a.c[0] = 1.0; a.h = h0 * dir; a.mode = 1; a.y = y; a.xo = e->st_x;
-    a.t_next_out = e->st_t; a.t_next = (float)(t0 + h0 * dir);
-    if (ds_launch_ode_stage(a, st)) return 1;
+    const double h0 = OdeCtl::initial_h0(plan, d0, d1), t1 = plan.t0 + h0 * plan.dir;
+    if (pass(-1, 0.0, 1, 1, &one, h0 * plan.dir, t1, nullptr, true, nullptr)) return 1;  // y1 = y0 + h0 * direction * f0
     if (run_nfe(e, B, T, st)) return 1;
-    ++nfev;
-    if (pass(1, t0 + h0 * dir, 3, 2, pm, 1.0, 0.0, &nb, false)) return 1;  // norm((f1 - f0) / scale)
+    ++c.nfev;
+    if (pass(1, t1, 3, 2, pm, 1.0, 0.0, &nb, false)) return 1;  // norm((f1 - f0) / scale)
     if (read_norms(nb, &d2, nullptr)) return 1;
-    d2 = d2 / h0;
-    const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0 * 1e-3)
-                                                   : std::pow(0.01 / std::max(d1, d2), 1.0 / (eorder + 1));
-    h_abs = std::min(std::min(100 * h0, h1), std::min(interval, max_step));
+    c.initial_step(plan, d1, d2, h0);
   } else {
-    if (pass(0, t, 0, 0, nullptr, 0.0, 0.0, nullptr)) return 1;  // K0 = f0
-    h_abs = oc->first_step;
+    if (pass(0, c.t, 0, 0, nullptr, 0.0, 0.0, nullptr)) return 1;  // K0 = f0
+    c.h_abs = plan.first_step;
   }
 
-  const double err_exp = -1.0 / (eorder + 1);
-  for (;;) {  // solve_ivp: while status is None: solver.step()
-    const double min_step = 10 * std::fabs(std::nextafter(t, dir * INFINITY) - t);
-    if (h_abs > max_step) h_abs = max_step;
-    else if (h_abs < min_step) h_abs = min_step;
-    bool accepted = false, rejected = false;
-    double t_new = t;
-    while (!accepted) {
-      if (h_abs < min_step) { status = -1; break; }
-      if (oc->max_nfe > 0 && nfev + ns > oc->max_nfe) { status = 1; break; }
-      double h = h_abs * dir;
-      t_new = t + h;
-      if (dir * (t_new - t_bound) > 0) t_new = t_bound;
-      h = t_new - t;
-      h_abs = std::fabs(h);
-      // rk_step: stage s input fp32(y + dot(K[:s].T, A[s,:s]) h) at t + C[s] h; y_new; f_new = f(t + h, y_new)
-      {
-        OdeArgs a = base;
-        a.nk = 1; a.k[0] = K[0]; a.c[0] = Ab[1 * DS_ODE_MAX_K]; a.h = h; a.mode = 1; a.y = y; a.xo = e->st_x;
-        a.t_next_out = e->st_t; a.t_next = (float)(t + Cb[1] * h);
-        if (prof_launch(e, st, hbm_rec("ode_stage (RK stage input)", 16.0 * nst, B, 1, (int)T, S),
-                        [&]() { return ds_launch_ode_stage(a, st); }))
-          return 1;
-      }
-      int nb = 0;
-      for (int s = 1; s <= ns; ++s) {
-        if (run_nfe(e, B, T, st)) return 1;
-        ++nfev;
-        const double ts = s < ns ? t + Cb[s] * h : t + h;
-        if (s < ns - 1) {
-          if (pass(s, ts, 1, s + 1, Ab + (s + 1) * DS_ODE_MAX_K, h, t + Cb[s + 1] * h, nullptr)) return 1;
-        } else if (s == ns - 1) {
-          if (pass(s, ts, 2, ns, Bb, h, t + h, nullptr)) return 1;
-        } else {
-          if (pass(s, ts, 3, ns + 1, Eb, h, 0.0, &nb)) return 1;
-        }
-      }
-      double err;
-      if (read_norms(nb, &err, nullptr)) return 1;
-      if (err < 1) {
-        double factor = err == 0 ? 10.0 : std::min(10.0, 0.9 * std::pow(err, err_exp));
-        if (rejected) factor = std::min(1.0, factor);
-        h_abs *= factor;
-        accepted = true;
+  while (c.begin_attempt(plan)) {  // solve_ivp: while status is None: solver.step(), one attempt of a step per trip
+    // rk_step: stage s input fp32(y + dot(K[:s].T, A[s,:s]) h) at t + C[s] h; y_new; f_new = f(t + h, y_new)
+    if (pass(-1, 0.0, 1, 1, plan.A + 1 * DS_ODE_MAX_K, c.h, c.stage_time(plan, 1), nullptr, true, "ode_stage (RK stage input)"))
+      return 1;
+    for (int s = 1; s <= ns; ++s) {
+      if (run_nfe(e, B, T, st)) return 1;
+      const double ts = c.stage_time(plan, s);
+      if (s < ns - 1) {
+        if (pass(s, ts, 1, s + 1, plan.A + (s + 1) * DS_ODE_MAX_K, c.h, c.stage_time(plan, s + 1), nullptr)) return 1;
+      } else if (s == ns - 1) {
+        if (pass(s, ts, 2, ns, plan.B, c.h, c.stage_time(plan, ns), nullptr)) return 1;
       } else {
-        h_abs *= std::max(0.2, 0.9 * std::pow(err, err_exp));
-        rejected = true;
-        ++n_rej;
+        if (pass(s, ts, 3, ns + 1, plan.E, c.h, 0.0, &nb)) return 1;
       }
     }
-    if (!accepted) break;
-    std::swap(y, ynew);  // y <- y_new, f <- f_new: pointer swaps, no copies
-    std::swap(K[0], K[ns]);
-    base.y = y;
-    t = t_new;
-    ++n_acc;
-    if (dir * (t - t_bound) >= 0) { status = 0; break; }
+    double err;
+    if (read_norms(nb, &err, nullptr)) return 1;
+    if (c.end_attempt(plan, err)) {  // y <- y_new, f <- f_new: pointer swaps, no copies
+      std::swap(w.y, w.ynew);
+      std::swap(w.K[0], w.K[ns]);
+    }
   }
 
-  // solution.y[:, -1] (the last accepted state) -> float32; optional denoise: x_mean of one reverse_diffusion step at
-  // eps without noise (reference denoise_update_fn; dt = 1/N, quirk Q1)
-  if (ds_launch_ode_round(y, e->st_x, (long)nst, st)) return 1;
-  if (oc->denoise) {
-    if (ds_launch_fill(e->st_t, (float)eps, B, st)) return 1;
-    if (run_nfe(e, B, T, st)) return 1;
-    if (ds_launch_sde_predictor(sp, oc->N, e->st_x, e->st_t, e->st_score, nullptr, e->st_xm, out, B, S, T, smix, 0, st))
-      return 1;
-  } else {
-    DS_HIP(hipMemcpyAsync(out, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
-  }
-  if (info) {
-    info->nfev = nfev; info->n_accepted = n_acc; info->n_rejected = n_rej; info->status = status; info->t_final = t;
-  }
+  if (ode_finish(e, sp, oc, smix, w.y, out, B, S, T, nullptr, st)) return 1;
+  if (info) ode_info(c, info);
   return 0;
 }
 
 // ------------------------------------------------------------------ ... with one step controller per utterance
-// B copies of the controller above in lock step on a zero-padded batch: utterance b has its own t, h, error norm,
-// accept / reject decisions and counts — the host arithmetic of diffsep_ode_sample, per utterance — and all utterances
-// share every network evaluation.  One step attempt = one upload of its tables (h, active, the evaluation times of its
-// stages: a row per pass, so that no pass waits for the host), n_stages evaluations of the whole batch, and one pinned
-// readback of the 2 B norms.  The device takes the accepted steps itself (ode_commit_each_kernel: norm < 1, the host's
-// own test on the same number).  An utterance whose status is set is frozen: its rows ride through the network, its
-// state is not touched.
-namespace {
-struct OdeCtl {  // one utterance's controller (the locals of diffsep_ode_sample)
-  double t, h_abs, h = 0.0, t_new = 0.0;
-  int nfev = 0, n_acc = 0, n_rej = 0, status = 2;  // 2: integrating
-  bool new_step = true, rejected = false;
-  double min_step = 0.0;
-};
-}  // namespace
-
+// B controllers in lock step on a zero-padded batch: utterance b has its own OdeCtl — its own t, h, error norm, accept /
+// reject decisions and counts, the same code as diffsep_ode_sample's one — and all utterances share every network
+// evaluation.  One step attempt = one upload of its tables (h, active, the evaluation times of its stages: a row per pass,
+// so that no pass waits for the host), n_stages evaluations of the whole batch, and one pinned readback of the 2 B norms.
+// The device takes the accepted steps itself (ode_commit_each_kernel: norm < 1, the host's own test on the same number).
+// An utterance whose status is set is frozen: its rows ride through the network, its state is not touched.
 extern "C" int32_t diffsep_ode_sample_each(diffsep_engine* e, const diffsep_sde_config* sde, const diffsep_ode_config* oc,
                                            const diffsep_ode_ext* ext, const float* mix_norm, const float* x_init,
                                            const float* noise, uint64_t seed, float* out, int32_t B, int64_t T,
@@ -456,61 +429,28 @@ extern "C" int32_t diffsep_ode_sample_each(diffsep_engine* e, const diffsep_sde_
                "ode_sample_each: every utterance of a mixed-length batch must have the padded frame count of T");
     }
   }
-  double Ab[DS_ODE_MAX_K * DS_ODE_MAX_K], Bb[DS_ODE_MAX_K], Cb[DS_ODE_MAX_K], Eb[DS_ODE_MAX_K + 1];
-  int ns = 0, eorder = 0;
-  DS_CHECK(ds_ode_tableau(oc->method, nullptr, nullptr, nullptr, nullptr, &ns, &eorder) == 0,
-           "ode_sample_each: method must be DIFFSEP_ODE_RK45 or DIFFSEP_ODE_RK23 (DOP853 / Radau / BDF / LSODA are not implemented)");
-  {
-    double A0[6 * 6];
-    ds_ode_tableau(oc->method, A0, Bb, Cb, Eb, nullptr, nullptr);
-    for (int i = 0; i < ns; ++i) for (int j = 0; j < ns; ++j) Ab[i * DS_ODE_MAX_K + j] = A0[i * ns + j];
-  }
-  const double eps = oc->eps;
-  DS_CHECK(eps > 0.0 && eps < 1.0, "ode_sample_each: eps must be in (0, 1)");
-  DS_CHECK(oc->atol >= 0.0 && oc->rtol >= 0.0, "ode_sample_each: tolerances must be non-negative");
-  DS_CHECK(oc->N >= 1 || !oc->denoise, "ode_sample_each: the denoise step needs N >= 1");
-  DS_CHECK(oc->max_nfe >= 0, "ode_sample_each: max_nfe must be >= 0");
-  const double rtol = std::max(oc->rtol, 100 * 2.220446049250313e-16), atol = oc->atol;
-  const double max_step = (oc->max_step > 0.0) ? oc->max_step : INFINITY;
-  const double t0 = 1.0, t_bound = eps, dir = -1.0, interval = std::fabs(t_bound - t0);
-  DS_CHECK(oc->first_step <= 0.0 || oc->first_step <= interval, "ode_sample_each: first_step exceeds the interval (scipy: `first_step` exceeds bounds)");
+  OdePlan plan;
+  const std::string bad = ode_plan_fill(plan, *oc, "ode_sample_each");
+  DS_CHECK(bad.empty(), bad);
+  const int ns = plan.ns;
 
   StreamScope sc_(e, stream);
   hipStream_t st = sc_.st;
   const int S = e->cfg.num_sources;
   if (ensure_plan(e, B, T, st)) return 1;
   const size_t nst = (size_t)B * S * T;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   // device tables of one attempt: h [B] | ones [B] (fp64) | active [B] (int) | evaluation times [DS_ODE_MAX_K + 1][B] (fp32)
   const int n_trows = DS_ODE_MAX_K + 1;
   const size_t off_ones = (size_t)B * 8, off_act = (size_t)B * 16, off_tt = (size_t)B * 20;
   const size_t tab_bytes = (size_t)B * (20 + 4 * n_trows);
-  const size_t need = 2 * al(nst * 8) + DS_ODE_MAX_K * al(nst * 4) + al((size_t)B * 2 * DS_ODE_MAX_BLOCKS * 8) +
-                      al((size_t)B * 16) + al(tab_bytes);
-  if (need > e->ode_cap) {
-    if (e->ode_buf) {
-      DS_HIP(hipDeviceSynchronize());
-      DS_HIP(hipFree(e->ode_buf));
-    }
-    e->ode_buf = nullptr;
-    e->ode_cap = 0;
-    DS_HIP(hipMalloc((void**)&e->ode_buf, need));
-    e->ode_cap = need;
-  }
+  OdeWork w;
+  if (ode_workspace(e, nst, B, tab_bytes, w)) return 1;
   double* pin;  // pinned readback of the 2 B norms
   if (e->ode_pin.acquire((size_t)2 * B, &pin)) return 1;
-  char* p = e->ode_buf;
-  double* y = (double*)p; p += al(nst * 8);
-  double* ynew = (double*)p; p += al(nst * 8);
-  float* K[DS_ODE_MAX_K];
-  for (int j = 0; j < DS_ODE_MAX_K; ++j) { K[j] = (float*)p; p += al(nst * 4); }
-  double* part = (double*)p; p += al((size_t)B * 2 * DS_ODE_MAX_BLOCKS * 8);
-  double* dnorm = (double*)p; p += al((size_t)B * 16);
-  char* tab = p;
-  const double* d_h = (const double*)tab;
-  const double* d_ones = (const double*)(tab + off_ones);
-  const int* d_act = (const int*)(tab + off_act);
-  const float* d_tt = (const float*)(tab + off_tt);
+  const double* d_h = (const double*)w.tab;
+  const double* d_ones = (const double*)(w.tab + off_ones);
+  const int* d_act = (const int*)(w.tab + off_act);
+  const float* d_tt = (const float*)(w.tab + off_tt);
   const SdeP sp = to_sdep(sde);
 
   // mixture, lengths and seeds -> device; x_T -> st_x with a zero tail (and y = x_T in fp64)
@@ -543,12 +483,11 @@ extern "C" int32_t diffsep_ode_sample_each(diffsep_engine* e, const diffsep_sde_
     }
     if (ds_launch_sde_prior(sp, e->st_mix, z, e->st_x, B, S, T, smix, st, lens)) return 1;
   }
-  if (ds_launch_ode_cast(e->st_x, y, (long)nst, st)) return 1;
-
+  if (ds_launch_ode_cast(e->st_x, w.y, (long)nst, st)) return 1;
   std::vector<OdeCtl> u(B);
   std::vector<int> act(B, 1);
   std::vector<double> hv(B, 1.0);
-  std::vector<float> ttv((size_t)n_trows * B, (float)t0);
+  std::vector<float> ttv((size_t)n_trows * B, (float)plan.t0);
   // this attempt's tables -> device (the staging buffer is free again once the previous upload has gone through)
   auto upload = [&]() -> int {
     char* tp;
@@ -558,61 +497,49 @@ extern "C" int32_t diffsep_ode_sample_each(diffsep_engine* e, const diffsep_sde_
     int* pa = reinterpret_cast<int*>(tp + off_act);
     for (int b = 0; b < B; ++b) { ph[b] = hv[b]; po[b] = 1.0; pa[b] = act[b]; }
     memcpy(tp + off_tt, ttv.data(), ttv.size() * 4);
-    DS_HIP(hipMemcpyAsync(tab, tp, tab_bytes, hipMemcpyHostToDevice, st));
+    DS_HIP(hipMemcpyAsync(w.tab, tp, tab_bytes, hipMemcpyHostToDevice, st));
     return e->ode_tab_pin.record(st);
   };
 
-  OdeEachArgs base;
-  memset(&base, 0, sizeof(base));
-  base.a.s = sp; base.a.x = e->st_x; base.a.score = e->st_score; base.a.smix = smix;
-  base.a.rtol = rtol; base.a.atol = atol; base.a.part = part; base.a.B = B; base.a.S = S; base.a.T = T;
-  base.a.kidx = -1; base.a.y = y;
-  base.active = d_act; base.lens = lens;
-  // the fused pass after the network evaluation at the times of table row `row` (kout >= 0: K[kout] = drift), the
-  // combination `mode` of K[0..nk) with the step sizes of `htab`, written for the next evaluation at row + 1
+  const OdeArgs base = ode_base_args(e, sp, smix, plan, w, B, S, T);
+  // one pass after the evaluation at the times of table row `row`, with the step sizes of `htab`, written for the next
+  // evaluation at row + 1
   auto pass = [&](int kout, int row, int mode, int nk, const double* c, const double* htab, bool scale_ynew = true) -> int {
-    OdeEachArgs a = base;
-    a.a.kout = kout >= 0 ? K[kout] : nullptr;
+    OdeEachArgs a;
+    a.a = ode_pass_args(e, base, w, kout, mode, nk, c, scale_ynew);
     a.a.tt = d_tt + (size_t)row * B;
-    a.a.kidx = (kout >= 0 && kout < nk) ? kout : -1;
-    a.a.nk = nk;
-    for (int j = 0; j < nk; ++j) { a.a.k[j] = K[j]; a.a.c[j] = c[j]; }
-    a.a.mode = mode; a.h = htab;
-    if (mode == 1) a.a.xo = e->st_x;
-    if (mode == 2) { a.a.yo = ynew; a.a.xo = e->st_x; }
-    if (mode == 3 && scale_ynew) a.a.ynew = ynew;
-    if (mode == 1 || mode == 2) { a.a.t_next_out = e->st_t; a.tnext = d_tt + (size_t)(row + 1) * B; }
-    return prof_launch(e, st, hbm_rec("ode_stage_each (fused drift + RK stage)", 4.0 * nst * (2 + nk) + 8.0 * nst * (mode >= 2 ? 2 : 1), B, 1, (int)T, S),
+    a.h = htab; a.active = d_act; a.lens = lens;
+    a.tnext = a.a.t_next_out ? d_tt + (size_t)(row + 1) * B : nullptr;
+    return prof_launch(e, st, ode_pass_rec("ode_stage_each (fused drift + RK stage)", nst, nk, mode, B, T, S),
                        [&]() { return ds_launch_ode_stage_each(a, st); });
   };
   // the norms of the last mode-3 pass -> host; commit: the device takes the accepted steps before the host knows of them
   auto read_norms = [&](bool commit) -> int {
-    if (ds_launch_ode_norm_final_each(part, lens, d_act, B, S, dnorm, st)) return 1;
-    if (commit && ds_launch_ode_commit_each(y, ynew, K[0], K[ns], dnorm, d_act, B, S, T, st)) return 1;
-    DS_HIP(hipMemcpyAsync(pin, dnorm, (size_t)2 * B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (ds_launch_ode_norm_final_each(w.part, lens, d_act, B, S, w.dnorm, st)) return 1;
+    if (commit && ds_launch_ode_commit_each(w.y, w.ynew, w.K[0], w.K[ns], w.dnorm, d_act, B, S, T, st)) return 1;
+    DS_HIP(hipMemcpyAsync(pin, w.dnorm, (size_t)2 * B * sizeof(double), hipMemcpyDeviceToHost, st));
     if (e->ode_pin.record(st) || e->ode_pin.wait()) return 1;
     return 0;
   };
 
   int evals = 0;
-  for (int b = 0; b < B; ++b) u[b].t = t0;
-  if (ds_launch_fill(e->st_t, (float)t0, B, st)) return 1;
+  for (int b = 0; b < B; ++b) u[b].t = plan.t0;
+  if (ds_launch_fill(e->st_t, (float)plan.t0, B, st)) return 1;
   if (upload()) return 1;  // everyone active, row 0 = t0
   if (run_nfe(e, B, T, st)) return 1;
   ++evals;
   for (int b = 0; b < B; ++b) ++u[b].nfev;
   const double one = 1.0;
-  if (oc->first_step <= 0.0) {  // common.select_initial_step, per utterance
+  if (plan.first_step <= 0.0) {  // common.select_initial_step, per utterance
     const double pm[2] = {-1.0, 1.0};
-    std::vector<double> d0(B), d1(B), h0(B);
+    std::vector<double> d1(B), h0(B);
     if (pass(0, 0, 3, 1, &one, d_ones, false)) return 1;  // K0 = f0; norm(f0 / scale), norm(y0 / scale)
     if (read_norms(false)) return 1;
     for (int b = 0; b < B; ++b) {
-      d1[b] = pin[2 * b]; d0[b] = pin[2 * b + 1];
-      h0[b] = (d0[b] < 1e-5 || d1[b] < 1e-5) ? 1e-6 : 0.01 * d0[b] / d1[b];
-      h0[b] = std::min(h0[b], interval);
-      hv[b] = h0[b] * dir;
-      ttv[(size_t)1 * B + b] = (float)(t0 + h0[b] * dir);
+      d1[b] = pin[2 * b];
+      h0[b] = OdeCtl::initial_h0(plan, pin[2 * b + 1], d1[b]);
+      hv[b] = h0[b] * plan.dir;
+      ttv[(size_t)1 * B + b] = (float)(plan.t0 + h0[b] * plan.dir);
     }
     if (upload()) return 1;
     if (pass(-1, 0, 1, 1, &one, d_h)) return 1;  // y1 = y0 + h0 * direction * f0
@@ -622,97 +549,46 @@ extern "C" int32_t diffsep_ode_sample_each(diffsep_engine* e, const diffsep_sde_
     if (read_norms(false)) return 1;
     for (int b = 0; b < B; ++b) {
       ++u[b].nfev;
-      const double d2 = pin[2 * b] / h0[b];
-      const double h1 = (d1[b] <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0[b] * 1e-3)
-                                                        : std::pow(0.01 / std::max(d1[b], d2), 1.0 / (eorder + 1));
-      u[b].h_abs = std::min(std::min(100 * h0[b], h1), std::min(interval, max_step));
+      u[b].initial_step(plan, d1[b], pin[2 * b], h0[b]);
     }
   } else {
     if (pass(0, 0, 0, 0, nullptr, nullptr)) return 1;  // K0 = f0
-    for (int b = 0; b < B; ++b) u[b].h_abs = oc->first_step;
+    for (int b = 0; b < B; ++b) u[b].h_abs = plan.first_step;
   }
 
-  const double err_exp = -1.0 / (eorder + 1);
   for (;;) {  // one step attempt of every utterance that still integrates
     int n_active = 0;
     for (int b = 0; b < B; ++b) {
       OdeCtl& c = u[b];
-      act[b] = 0;
-      if (c.status != 2) continue;
-      if (c.new_step) {  // solve_ivp: solver.step()
-        c.min_step = 10 * std::fabs(std::nextafter(c.t, dir * INFINITY) - c.t);
-        if (c.h_abs > max_step) c.h_abs = max_step;
-        else if (c.h_abs < c.min_step) c.h_abs = c.min_step;
-        c.rejected = false;
-        c.new_step = false;
-      }
-      if (c.h_abs < c.min_step) { c.status = -1; continue; }
-      if (oc->max_nfe > 0 && c.nfev + ns > oc->max_nfe) { c.status = 1; continue; }
-      double h = c.h_abs * dir;
-      c.t_new = c.t + h;
-      if (dir * (c.t_new - t_bound) > 0) c.t_new = t_bound;
-      h = c.t_new - c.t;
-      c.h_abs = std::fabs(h);
-      c.h = h;
-      hv[b] = h;
-      for (int s = 1; s < ns; ++s) ttv[(size_t)s * B + b] = (float)(c.t + Cb[s] * h);
-      ttv[(size_t)ns * B + b] = (float)(c.t + h);
-      act[b] = 1;
+      act[b] = c.begin_attempt(plan) ? 1 : 0;
+      if (!act[b]) continue;
+      hv[b] = c.h;
+      for (int s = 1; s <= ns; ++s) ttv[(size_t)s * B + b] = (float)c.stage_time(plan, s);
       ++n_active;
     }
     if (!n_active) break;
     if (upload()) return 1;
     // rk_step: stage s input fp32(y + dot(K[:s].T, A[s,:s]) h) at t + C[s] h; y_new; f_new = f(t + h, y_new)
-    if (pass(-1, 0, 1, 1, Ab + 1 * DS_ODE_MAX_K, d_h)) return 1;
+    if (pass(-1, 0, 1, 1, plan.A + 1 * DS_ODE_MAX_K, d_h)) return 1;
     for (int s = 1; s <= ns; ++s) {
       if (run_nfe(e, B, T, st)) return 1;
       ++evals;
       if (s < ns - 1) {
-        if (pass(s, s, 1, s + 1, Ab + (s + 1) * DS_ODE_MAX_K, d_h)) return 1;
+        if (pass(s, s, 1, s + 1, plan.A + (s + 1) * DS_ODE_MAX_K, d_h)) return 1;
       } else if (s == ns - 1) {
-        if (pass(s, s, 2, ns, Bb, d_h)) return 1;
+        if (pass(s, s, 2, ns, plan.B, d_h)) return 1;
       } else {
-        if (pass(s, s, 3, ns + 1, Eb, d_h)) return 1;
+        if (pass(s, s, 3, ns + 1, plan.E, d_h)) return 1;
       }
     }
     if (read_norms(true)) return 1;
-    for (int b = 0; b < B; ++b) {
-      if (!act[b]) continue;
-      OdeCtl& c = u[b];
-      c.nfev += ns;
-      const double err = pin[2 * b];
-      if (err < 1) {
-        double factor = err == 0 ? 10.0 : std::min(10.0, 0.9 * std::pow(err, err_exp));
-        if (c.rejected) factor = std::min(1.0, factor);
-        c.h_abs *= factor;
-        c.t = c.t_new;  // (y <- y_new, f <- f_new: taken on the device)
-        ++c.n_acc;
-        c.new_step = true;
-        if (dir * (c.t - t_bound) >= 0) c.status = 0;
-      } else {
-        c.h_abs *= std::max(0.2, 0.9 * std::pow(err, err_exp));
-        c.rejected = true;
-        ++c.n_rej;
-      }
-    }
+    for (int b = 0; b < B; ++b)
+      if (act[b]) u[b].end_attempt(plan, pin[2 * b]);  // (y <- y_new, f <- f_new: taken on the device)
   }
 
-  // the last accepted states -> float32; optional denoise as in diffsep_ode_sample, the tails staying zero
-  if (ds_launch_ode_round(y, e->st_x, (long)nst, st)) return 1;
-  if (oc->denoise) {
-    if (ds_launch_fill(e->st_t, (float)eps, B, st)) return 1;
-    if (run_nfe(e, B, T, st)) return 1;
-    if (ds_launch_sde_predictor(sp, oc->N, e->st_x, e->st_t, e->st_score, nullptr, e->st_xm, out, B, S, T, smix, 0, st,
-                                lengths ? lens : nullptr))
-      return 1;
-  } else {
-    DS_HIP(hipMemcpyAsync(out, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
-  }
+  if (ode_finish(e, sp, oc, smix, w.y, out, B, S, T, lengths ? lens : nullptr, st)) return 1;
   if (infos)
-    for (int b = 0; b < B; ++b) {
-      infos[b].nfev = u[b].nfev; infos[b].n_accepted = u[b].n_acc; infos[b].n_rejected = u[b].n_rej;
-      infos[b].status = u[b].status; infos[b].t_final = u[b].t;
-    }
+    for (int b = 0; b < B; ++b) ode_info(u[b], &infos[b]);
   if (evals_run) *evals_run = evals;
   return 0;
 }

@@ -263,17 +263,8 @@ class Engine:
                                              _stream_ptr(self.device)), self._L)
         return out, int(nfe.value)
 
-    def ode_sample(self, mix_norm, sde, method="RK45", rtol=1e-5, atol=1e-5, eps=3e-2, first_step=None, max_step=None,
-                   max_nfe=0, denoise=True, N=30, x_init=None, noise=None, seed=0, lengths=None, tail=None):
-        """The probability-flow ODE sampler (sdes.get_ode_sampler(...)(), diffsep_ode_sample): scipy's RK45 / RK23
-        controller on the device-resident state, the whole batch as one system.  x_init [B,S,T]: start from this x_T (the
-        reference's z); else the prior sample from noise [B,S,T] or from the device RNG keyed by seed.  Returns
-        (out [B,S,T], info dict: nfev, n_accepted, n_rejected, status 0 / -1 / 1, t_final)."""
-        if lengths is not None:
-            raise _lib.DiffsepError("ode_sample: the whole batch is one ODE system with one step size; mixed-length "
-                                    "batches are not supported (run the utterances one by one)")
-        if tail is not None:
-            raise _lib.DiffsepError("ode_sample: every evaluation runs on one engine; there is no tail engine")
+    def _ode_setup(self, mix_norm, sde, method, rtol, atol, eps, first_step, max_step, max_nfe, denoise, N, x_init, noise):
+        """what both ODE entries make of their arguments: (mix_norm, SdeConfig, OdeConfig, x_init, noise, out)"""
         if method not in _lib.ODE_METHODS:
             raise NotImplementedError(f"ODE method '{method}': only RK45 and RK23 run on the engine")
         mix_norm = self._f32(mix_norm)
@@ -290,6 +281,22 @@ class Engine:
         x_init = self._f32(x_init) if x_init is not None else None
         noise = self._f32(noise) if noise is not None else None
         out = torch.empty((B, self.S, T), dtype=torch.float32, device=mix_norm.device)
+        return mix_norm, sc, oc, x_init, noise, out
+
+    def ode_sample(self, mix_norm, sde, method="RK45", rtol=1e-5, atol=1e-5, eps=3e-2, first_step=None, max_step=None,
+                   max_nfe=0, denoise=True, N=30, x_init=None, noise=None, seed=0, lengths=None, tail=None):
+        """The probability-flow ODE sampler (sdes.get_ode_sampler(...)(), diffsep_ode_sample): scipy's RK45 / RK23
+        controller on the device-resident state, the whole batch as one system.  x_init [B,S,T]: start from this x_T (the
+        reference's z); else the prior sample from noise [B,S,T] or from the device RNG keyed by seed.  Returns
+        (out [B,S,T], info dict: nfev, n_accepted, n_rejected, status 0 / -1 / 1, t_final)."""
+        if lengths is not None:
+            raise _lib.DiffsepError("ode_sample: the whole batch is one ODE system with one step size; mixed-length "
+                                    "batches are not supported (run the utterances one by one)")
+        if tail is not None:
+            raise _lib.DiffsepError("ode_sample: every evaluation runs on one engine; there is no tail engine")
+        mix_norm, sc, oc, x_init, noise, out = self._ode_setup(mix_norm, sde, method, rtol, atol, eps, first_step, max_step,
+                                                               max_nfe, denoise, N, x_init, noise)
+        B, _, T = mix_norm.shape
         info = _lib.OdeInfo()
         with torch.cuda.device(self.device):
             check(self._L.diffsep_ode_sample(self._h, C.byref(sc), C.byref(oc), _ptr(mix_norm), _ptr(x_init), _ptr(noise),
@@ -306,21 +313,9 @@ class Engine:
         fp32 network evaluation does not depend on the batch row b inside lengths[b] is bit-for-bit
         ode_sample on that utterance alone with its seed.  Returns
         (out [B,S,T], [info dict per utterance], evals_run = network evaluations actually run = max nfev)."""
-        if method not in _lib.ODE_METHODS:
-            raise NotImplementedError(f"ODE method '{method}': only RK45 and RK23 run on the engine")
-        mix_norm = self._f32(mix_norm)
-        B, one, T = mix_norm.shape
-        assert one == 1
-        sc = _lib.SdeConfig(sde.get("kind", _lib.SDE_MIX), sde["ndim"], sde["d_lambda"], sde["sigma_min"],
-                            sde["sigma_max"], sde.get("avg_len", 0))
-        oc = _lib.OdeConfig(float(rtol), float(atol), float(eps), float(first_step or 0.0),
-                            float(max_step) if max_step is not None else 0.0, _lib.ODE_METHODS[method], int(max_nfe or 0),
-                            int(bool(denoise)), int(N))
-        for name, v in (("x_init", x_init), ("noise", noise)):
-            if v is not None:
-                assert tuple(v.shape) == (B, self.S, T), f"{name} must be [B,S,T]"
-        x_init = self._f32(x_init) if x_init is not None else None
-        noise = self._f32(noise) if noise is not None else None
+        mix_norm, sc, oc, x_init, noise, out = self._ode_setup(mix_norm, sde, method, rtol, atol, eps, first_step, max_step,
+                                                               max_nfe, denoise, N, x_init, noise)
+        B, _, T = mix_norm.shape
         ext, keep = _lib.OdeExt(), []
         if lengths is not None:
             la = np.ascontiguousarray(lengths, dtype=np.int64)
@@ -332,7 +327,6 @@ class Engine:
             assert sa.shape == (B,), "seeds must be [B]"
             ext.seeds_host = sa.ctypes.data_as(C.POINTER(C.c_uint64))
             keep.append(sa)
-        out = torch.empty((B, self.S, T), dtype=torch.float32, device=mix_norm.device)
         infos = (_lib.OdeInfo * B)()
         evals = C.c_int32()
         with torch.cuda.device(self.device):

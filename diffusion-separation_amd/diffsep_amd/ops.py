@@ -680,6 +680,14 @@ def score_loss(engine, sde, mix_norm, target, t, beta=None, z=None, seed=0, leng
     return (out, best, arg, x_t, score) if debug else (out, best, arg)
 
 
+def _ode_unit(K, coef, k_out):
+    """the unit wrappers' view of a stage list: (B, S, T, coefficients as a float64 array); K: float32 [B,S,T] tensors"""
+    B, S, T = K[0].shape
+    c = np.ascontiguousarray(coef, dtype=np.float64)
+    assert len(c) <= len(K) and k_out < len(K) and all(k.shape == (B, S, T) and k.dtype == torch.float32 for k in K)
+    return B, S, T, c
+
+
 def _ode_ptrs(K):
     return (C.c_void_p * max(1, len(K)))(*[k.data_ptr() for k in K])
 
@@ -689,9 +697,7 @@ def ode_stage_update(sde, K, coef, h, y, k_out=-1, x=None, t=None, score=None, s
     """diffsep_ode_stage_update: K[k_out] = probability-flow drift of (x, t, score) (k_out >= 0), then with
     acc = sum_j coef[j] K[j]: x_out = fp32(y + acc h), or (y_new_out given) y_new_out = y + h acc and x_out = fp32 of it.
     K: list of float32 [B,S,T] tensors (written in place at k_out); y float64 [B,S,T]."""
-    B, S, T = K[0].shape
-    c = np.ascontiguousarray(coef, dtype=np.float64)
-    assert len(c) <= len(K) and k_out < len(K) and all(k.shape == (B, S, T) and k.dtype == torch.float32 for k in K)
+    B, S, T, c = _ode_unit(K, coef, k_out)
     sc = _sde(sde)
     check(lib().diffsep_ode_stage_update(C.byref(sc), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y),
                                          _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), float(h),
@@ -702,9 +708,7 @@ def ode_stage_update(sde, K, coef, h, y, k_out=-1, x=None, t=None, score=None, s
 def ode_error_norm(sde, K, coef, h, y, rtol, atol, y_new=None, k_out=-1, x=None, t=None, score=None, sigma_mix=None):
     """diffsep_ode_error_norm: float64 [2] device tensor (||acc h / sc||_rms, ||y / sc||_rms), sc = atol + max(|y|,
     |y_new|) rtol; with k_out >= 0 the drift K[k_out] is produced in the same pass."""
-    B, S, T = K[0].shape
-    c = np.ascontiguousarray(coef, dtype=np.float64)
-    assert len(c) <= len(K) and k_out < len(K) and all(k.shape == (B, S, T) and k.dtype == torch.float32 for k in K)
+    B, S, T, c = _ode_unit(K, coef, k_out)
     out = torch.empty(2, dtype=torch.float64, device=K[0].device)
     ws = torch.empty(ODE_WORKSPACE_BYTES, dtype=torch.uint8, device=K[0].device)
     sc = _sde(sde)
@@ -728,9 +732,7 @@ def ode_stage_update_each(sde, K, coef, h, active, lengths, y, k_out=-1, x=None,
                           x_out=None, y_new_out=None):
     """diffsep_ode_stage_update_each: ode_stage_update with a step size h[b] per utterance; utterances with active[b] == 0
     are skipped, samples t >= lengths[b] are never read and written as exact zeros."""
-    B, S, T = K[0].shape
-    c = np.ascontiguousarray(coef, dtype=np.float64)
-    assert len(c) <= len(K) and k_out < len(K) and all(k.shape == (B, S, T) and k.dtype == torch.float32 for k in K)
+    B, S, T, c = _ode_unit(K, coef, k_out)
     hd, ad, ld = _ode_tables(h, active, lengths, B, K[0].device)
     sc = _sde(sde)
     check(lib().diffsep_ode_stage_update_each(C.byref(sc), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y),
@@ -743,9 +745,7 @@ def ode_error_norm_each(sde, K, coef, h, active, lengths, y, rtol, atol, y_new=N
                         sigma_mix=None, out=None):
     """diffsep_ode_error_norm_each: float64 [B,2] device tensor, row b = the two norms of ode_error_norm over utterance
     b's lengths[b] samples alone (rows of inactive utterances keep the value of `out`, zeros when it is not given)."""
-    B, S, T = K[0].shape
-    c = np.ascontiguousarray(coef, dtype=np.float64)
-    assert len(c) <= len(K) and k_out < len(K) and all(k.shape == (B, S, T) and k.dtype == torch.float32 for k in K)
+    B, S, T, c = _ode_unit(K, coef, k_out)
     hd, ad, ld = _ode_tables(h, active, lengths, B, K[0].device)
     if out is None:
         out = torch.zeros(B, 2, dtype=torch.float64, device=K[0].device)

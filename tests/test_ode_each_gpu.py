@@ -147,6 +147,59 @@ def test_passes_match_numpy_float64_per_utterance():
     check(Ke[1], Kw[1].cpu().numpy())
 
 
+@pytest.mark.parametrize("T", [1049605, 1049604], ids=["unaligned_rows", "aligned_rows"])
+def test_passes_beyond_the_capped_grid_per_utterance(T):
+    # both utterances have more than DS_ODE_MAX_BLOCKS x 256 = 262144 thread items (262401 of four samples; 262401 of one):
+    # their rows of the grid are capped and stride a second time, with a stride that is not the whole-batch kernel's
+    B, lens, h, active = 2, [1049604, 262401], [-0.0123, -0.004], [1, 1]
+    g = torch.Generator(device="cuda").manual_seed(5)
+    K = [torch.randn(B, S, T, generator=g, device="cuda") for _ in range(7)]
+    y = torch.randn(B, S, T, generator=g, dtype=torch.float64, device="cuda")
+    y2 = y + 1e-3 * torch.randn(B, S, T, generator=g, dtype=torch.float64, device="cuda")
+    A, Bt, C, E, ns, _ = _lib.ode_tableau("RK45")
+    Kn = [k.cpu().double().numpy() for k in K]
+    yn, y2n = y.cpu().numpy(), y2.cpu().numpy()
+    hn = np.asarray(h)[:, None, None]
+    SENT = 7.5
+
+    def comb(c, n):
+        acc = np.zeros_like(yn)
+        for j in range(n):
+            acc = acc + c[j] * Kn[j]
+        return acc
+
+    def check(got, want):
+        got = got.cpu().numpy()
+        for b in range(B):
+            assert np.array_equal(got[b, :, :lens[b]], want[b, :, :lens[b]]), b
+            assert np.all(got[b, :, lens[b]:] == 0), b  # the tail: exact zeros
+
+    for s in range(1, ns):
+        xo = torch.full((B, S, T), SENT, device="cuda")
+        ops.ode_stage_update_each(MIX, K, A[s, :s], h, active, lens, y, x_out=xo)
+        check(xo, (yn + comb(A[s], s) * hn).astype(np.float32))
+    yo = torch.full((B, S, T), SENT, dtype=torch.float64, device="cuda")
+    xo = torch.full((B, S, T), SENT, device="cuda")
+    ops.ode_stage_update_each(MIX, K, Bt, h, active, lens, y, x_out=xo, y_new_out=yo)
+    want = yn + hn * comb(Bt, ns)
+    check(yo, want)
+    check(xo, want.astype(np.float32))
+
+    nrm = ops.ode_error_norm_each(MIX, K, E, h, active, lens, y, 1e-5, 1e-5, y_new=y2).cpu().numpy()
+    acc = comb(E, ns + 1)
+    for b in range(B):
+        L = lens[b]
+        sc = 1e-5 + np.maximum(np.abs(yn[b, :, :L]), np.abs(y2n[b, :, :L])) * 1e-5
+        e0 = np.linalg.norm(acc[b, :, :L] * h[b] / sc) / np.sqrt(S * L)
+        e1 = np.linalg.norm(yn[b, :, :L] / sc) / np.sqrt(S * L)
+        # the utterance alone through the whole-batch pass, [1, S, L] contiguous: the summation tree of common.h, so the same bits
+        cut = lambda v: v[b:b + 1, :, :L].contiguous()
+        alone = ops.ode_error_norm(MIX, [cut(k) for k in K], E, h[b], cut(y), 1e-5, 1e-5, y_new=cut(y2)).cpu().numpy()
+        print(f"T = {T}, utterance {b}: norms {nrm[b]}, alone {alone}, numpy {e0} {e1}")
+        assert abs(nrm[b, 0] - e0) <= 1e-12 * e0 and abs(nrm[b, 1] - e1) <= 1e-12 * e1
+        assert np.array_equal(nrm[b], alone), b
+
+
 # ---------------------------------------------------------------- 2. each utterance equals its solo solve
 def test_solo_attempt_counts_differ():
     # the precondition of the tests below, on the whole-batch entry: the four utterances need different numbers of step

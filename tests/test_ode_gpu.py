@@ -86,6 +86,41 @@ def test_stage_and_error_passes_match_numpy_float64():
             assert all(torch.equal(a, b) for a, b in zip(first, again))  # repeated runs: the same bits
 
 
+@pytest.mark.parametrize("T_", [262401, 1049604], ids=["one_sample_items", "four_sample_items"])
+def test_passes_beyond_the_capped_grid_match_numpy_float64(T_):
+    # more than DS_ODE_MAX_BLOCKS x 256 = 262144 thread items in one system (262401 of one sample; 262401 of four): the grid
+    # is capped and the grid-stride loop takes a second trip, which no other test does
+    g = torch.Generator(device="cuda").manual_seed(5)
+    K = [torch.randn(1, S, T_, generator=g, device="cuda") for _ in range(7)]
+    y = torch.randn(1, S, T_, generator=g, dtype=torch.float64, device="cuda")
+    y2 = y + 1e-3 * torch.randn(1, S, T_, generator=g, dtype=torch.float64, device="cuda")
+    A, Bt, C, E, ns, _ = _lib.ode_tableau("RK45")
+    h = -0.0123456789
+    Kn = [k.cpu().double().numpy() for k in K]
+    yn, y2n = y.cpu().numpy(), y2.cpu().numpy()
+
+    def comb(c, n):
+        acc = np.zeros_like(yn)
+        for j in range(n):
+            acc = acc + c[j] * Kn[j]
+        return acc
+
+    for s in range(1, ns):
+        xo = torch.empty(1, S, T_, device="cuda")
+        ops.ode_stage_update(MIX, K, A[s, :s], h, y, x_out=xo)
+        assert np.array_equal(xo.cpu().numpy(), (yn + comb(A[s], s) * h).astype(np.float32)), s
+    yo, xo = torch.empty_like(y), torch.empty(1, S, T_, device="cuda")
+    ops.ode_stage_update(MIX, K, Bt, h, y, x_out=xo, y_new_out=yo)
+    want = yn + h * comb(Bt, ns)
+    assert np.array_equal(yo.cpu().numpy(), want) and np.array_equal(xo.cpu().numpy(), want.astype(np.float32))
+    nrm = ops.ode_error_norm(MIX, K, E, h, y, 1e-5, 1e-5, y_new=y2).cpu().numpy()
+    sc = 1e-5 + np.maximum(np.abs(yn), np.abs(y2n)) * 1e-5
+    e0 = np.linalg.norm(comb(E, ns + 1) * h / sc) / np.sqrt(yn.size)
+    e1 = np.linalg.norm(yn / sc) / np.sqrt(yn.size)
+    print(f"T = {T_}: norms {nrm}, numpy {e0} {e1}")
+    assert abs(nrm[0] - e0) <= 1e-12 * e0 and abs(nrm[1] - e1) <= 1e-12 * e1
+
+
 @pytest.mark.parametrize("sde", [MIX, PRIOR], ids=["mix", "priormix"])
 def test_fused_drift_is_the_unit_drift_bit_for_bit(sde):
     eng, _ = engine()
