@@ -177,6 +177,8 @@ _SIGS = {
     "diffsep_gram": (_I, [_P, _P, _P, _I, _I, _L, _P]),
     "diffsep_stoi_workspace_bytes": (_L, [_I, _I, _L, _I]),
     "diffsep_stoi": (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _I, _I, _P, _L, _P]),
+    "diffsep_composite_workspace_bytes": (_L, [_I, _I, _L, _I]),
+    "diffsep_composite": (_I, [_P, _P, _P, _P, _L, _I, _I, _L, _P, _P, _I, _P, _L, _P]),
     "diffsep_longform_plan": (_I, [_L, _L, _L, C.POINTER(_L), _I]),
     "diffsep_longform_locate": (_I, [_L, _L, _L, _L, C.POINTER(_I), C.POINTER(_L), C.POINTER(_L)]),
     "diffsep_longform_workspace_bytes": (_L, [_I, _I]),

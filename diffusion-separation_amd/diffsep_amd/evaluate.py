@@ -16,7 +16,10 @@ Output tree (evaluate.py:306-323,436-443): `<output_dir>/<exp>_<ckpt>_<tag_inf>/
 the targets) for the first --save-n utterances (default: all).  Not produced: `fig/` (matplotlib spectrogram plots of the
 intermediate states) and the PESQ field (ITU-T P.862 C code, third-party `pesq`; null, named under `not_computed`).  STOI /
 ESTOI is computed on loader threads (diffsep_amd.metrics.stoi, `--stoi-on host`, the default) or on the GPU
-(diffsep_amd.metrics.stoi_batch, `--stoi-on device`: no waveform leaves the device unless it is saved).
+(diffsep_amd.metrics.stoi_batch, `--stoi-on device`: no waveform leaves the device unless it is saved).  --composite (off by
+default; without it records and summaries are what they were) adds the signal measures of the reference's evaluate_covl.py to
+every record: per-source llr, wss, segsnr from the GPU (diffsep_amd.metrics.composite_batch) and csig / cbak / covl as null
+(they need PESQ: diffsep_amd.evaluate_covl takes it from a file).
 
 Utterances are sharded over ranks in contiguous ranges (evaluate_mp.py:495-503); each rank separates its
 share, records {batch_idx, si_sdr, si_sir, si_sar, pesq, stoi, nfe, runtime, len_s} per utterance (evaluate.py:394-405;
@@ -193,6 +196,10 @@ def build_parser():
     ap.add_argument("--stoi-on", choices=["host", "device"], default="host",
                     help="where STOI / ESTOI is computed: host = numpy on the loader threads (needs the waveforms on the host); "
                          "device = the HIP kernels of diffsep_stoi on the worker's stream (B x S numbers cross PCIe)")
+    ap.add_argument("--composite", action="store_true",
+                    help="also record the signal measures of the composite enhancement scores (evaluate_covl.py): per-source "
+                         "llr, wss, segsnr from the HIP kernels of diffsep_composite on the worker's stream, and csig / cbak / covl "
+                         "as null (they need PESQ: python -m diffsep_amd.evaluate_covl --pesq-json).  8 or 16 kHz models only")
     ap.add_argument("--score-loss", type=int, default=0, metavar="K",
                     help="also record every utterance's denoising score-matching loss (the reference's val/score_loss): the mean "
                          "of K plain losses at times linspace(t_eps, 1, K) with device noise keyed by the utterance's seed, one "
@@ -263,6 +270,8 @@ def main(argv=None):
     models, streams = inflight.setup_workers(model, max(1, args.streams))  # (__no_proc__: no models, streams only)
     fs_model = cfg_get(model.config, "model.fs", 8000) if model is not None else None
     N, cs, snr = inflight.sampler_settings(model.config, args) if model is not None else (None, None, None)
+    if args.composite and fs_model is not None and int(fs_model) not in metrics.COMPOSITE_RATES:
+        ap.error(f"--composite: the model's sample rate {fs_model} is not one of {metrics.COMPOSITE_RATES}")
 
     # ---- the output folder (evaluate.py:257-262,306-323)
     if args.flat_output:
@@ -306,6 +315,8 @@ def main(argv=None):
             args_split = argparse.Namespace(**{**vars(args), "split": split})
             fs = fs_model if fs_model is not None else 8000
             n, get, lengths = load_dataset(args_split, fs)
+        if args.composite and int(fs) not in metrics.COMPOSITE_RATES:
+            ap.error(f"--composite: the sample rate {fs} of {split} is not one of {metrics.COMPOSITE_RATES}")
         run_split(SplitRun(**common, split=split, fs=fs, n=n, get=get, lengths=lengths))
     loader.shutdown()
     if world > 1:
@@ -445,6 +456,10 @@ class SplitRun:
             with torch.cuda.stream(stream):
                 stoi_dev = metrics.stoi_batch(tgt_n, est, self.fs, extended=not a.stoi_no_extended, lengths=lens,
                                               perm=[m["perm"] for m in mets])
+        comp_dev = None
+        if a.composite:  # LLR / WSS / segmental SNR of every source against its permuted estimate: 4 B S numbers cross PCIe
+            with torch.cuda.stream(stream):
+                comp_dev = metrics.composite_batch(tgt_n, est, self.fs, lengths=lens, perm=[m["perm"] for m in mets])
         if need_host:
             with torch.cuda.stream(stream):
                 est_h, tgt_h, mix_h = est.cpu(), tgt_n.cpu(), b.mix_n.cpu()
@@ -464,6 +479,10 @@ class SplitRun:
             k_src = len(perm) if self.n_src is None else self.n_src
             if stoi_dev is not None:
                 rec["stoi"] = [float(v) for v in stoi_dev[k, :k_src]]
+            if comp_dev is not None:
+                for q, name in enumerate(("llr", "wss", "segsnr")):
+                    rec[name] = [float(v) for v in comp_dev[k, :k_src, q]]
+                rec.update({"csig": None, "cbak": None, "covl": None})  # (they need PESQ)
             if need_host:
                 est_k = est_h[k, perm, :lens[k]]  # "fix the permutation" (evaluate.py:392): estimates in the targets' order
                 if not a.no_stoi and a.stoi_on == "host":
@@ -487,7 +506,7 @@ class SplitRun:
                         "utt_per_s_rank0": len(self.mine) / max(wall, 1e-9), "split_fallback_batches_rank0": len(self.fallbacks),
                         # PESQ is ITU-T P.862 reference C code behind the third-party `pesq` package: not restated here
                         # (DESIGN.md section 7); STOI / ESTOI is diffsep_amd.metrics.stoi (published algorithm, restated)
-                        "not_computed": ["pesq"] + (["stoi"] if a.no_stoi else []),
+                        "not_computed": ["pesq"] + (["stoi"] if a.no_stoi else []) + (["csig", "cbak", "covl"] if a.composite else []),
                         "stoi_on": a.stoi_on, "stoi_extended": not a.stoi_no_extended, "pesq_mode": a.pesq_mode})
         if model is not None and a.sampler == "ode":
             summary["ode_status_counts"] = {str(c): sum(1 for r in flat if r.get("ode_status") == c) for c in (0, -1, 1)}

@@ -192,6 +192,194 @@ def stoi_batch(ref, est, fs, extended=True, lengths=None, perm=None):
     return h.numpy().copy()
 
 
+# ---------------------------------------------------------------------------------------------------------------- composite
+# The reference scores enhancement with evaluate_covl.py: Hu & Loizou's composite measures CSIG / CBAK / COVL, three linear
+# formulas over the log-likelihood ratio (LLR), the weighted spectral slope (WSS), the segmental SNR and PESQ.  What follows
+# restates its llr (:358-408, lpcoeff :62-95), wss (:155-355), SSNR (:106-152) and the aggregation of eval_composite (:18-54)
+# in vectorised float64 numpy.  Not reproduced: the float32 casts of the autocorrelation, the LPC vector and the quadratic forms
+# in lpcoeff / llr, and SSNR's in-place float32 mean removal and rescaling (rounding noise only; tests/golden records it).
+_COMP_CENT = np.array([50.0, 120, 190, 260, 330, 400, 470, 540, 617.372, 703.378, 798.717, 904.128, 1020.38, 1148.30, 1288.72,
+                       1442.54, 1610.70, 1794.16, 1993.93, 2211.08, 2446.71, 2701.97, 2978.04, 3276.17, 3597.63])
+_COMP_BW = np.array([70.0, 70, 70, 70, 70, 70, 70, 77.3724, 86.0056, 95.3398, 105.411, 116.256, 127.914, 140.423, 153.823,
+                     168.154, 183.457, 199.776, 217.153, 235.631, 255.255, 276.072, 298.126, 321.465, 346.136])
+COMPOSITE_RATES = (8000, 16000)
+_COMP_CACHE = {}
+
+
+def composite_params(fs):
+    """(win, skip, n_fft, LPC order, window [win], critical-band filters [25, n_fft / 2]) of a supported sample rate"""
+    fs = int(fs)
+    if fs not in COMPOSITE_RATES:
+        raise ValueError(f"composite: unsupported sample rate {fs} (supported: 8000, 16000)")
+    if fs not in _COMP_CACHE:
+        win = int(round(30 * fs / 1000.0))
+        skip = win // 4
+        n_fft = int(2 ** np.ceil(np.log(2 * win) / np.log(2)))
+        half = n_fft // 2
+        window = 0.5 * (1 - np.cos(2 * np.pi * (np.linspace(1, win, win) / (win + 1))))
+        max_freq = fs / 2
+        min_factor = np.exp(-30.0 / (2 * 2.303))
+        filt = np.zeros((25, half))
+        j = np.arange(half)
+        for i in range(25):
+            f0 = (_COMP_CENT[i] / max_freq) * half
+            bw = (_COMP_BW[i] / max_freq) * half
+            norm_factor = np.log(_COMP_BW[0]) - np.log(_COMP_BW[i])
+            row = np.exp(-11 * (((j - np.floor(f0)) / bw) ** 2) + norm_factor)
+            filt[i] = row * (row > min_factor)
+        _COMP_CACHE[fs] = (win, skip, n_fft, 10 if fs < 10000 else 16, window, filt)
+    return _COMP_CACHE[fs]
+
+
+def composite_num_frames(length, fs):
+    """int(len / skip - win / skip) of the reference, in integers"""
+    win, skip = composite_params(fs)[:2]
+    return max(0, (int(length) - win) // skip)
+
+
+def composite_trim_count(n):
+    """int(round(n * 0.95)): Python's round of the double product, half to even"""
+    return int(round(n * 0.95))
+
+
+def _comp_frames(x, fs):
+    win, skip, _, _, window, _ = composite_params(fs)
+    n = composite_num_frames(len(x), fs)
+    idx = (np.arange(n) * skip)[:, None] + np.arange(win)[None, :]
+    return x[idx] * window[None, :] if n else np.zeros((0, win))
+
+
+def composite_band_db(x, fs):
+    """[frames, 25] critical-band energies in dB (floor 1e-10) of the windowed frames of x"""
+    _, _, n_fft, _, _, filt = composite_params(fs)
+    fr = _comp_frames(np.asarray(x, dtype=np.float64).reshape(-1), fs)
+    spec = np.abs(np.fft.fft(fr, n_fft, axis=1)[:, : n_fft // 2]) ** 2
+    return 10 * np.log10(np.maximum(spec @ filt.T, 1e-10))
+
+
+def _comp_peaks(db, slope):
+    """the reference's nearest-peak search (:292-315) on every frame at once: [frames, 24] peak levels"""
+    n, nb = slope.shape
+    rows = np.arange(n)
+    out = np.zeros_like(slope)
+    for i in range(nb):
+        up = slope[:, i] > 0
+        r = np.full(n, i)  # to the right while the slope stays > 0
+        while True:
+            go = up & (r < nb) & (slope[rows, np.minimum(r, nb - 1)] > 0)
+            if not go.any():
+                break
+            r = r + go
+        l = np.full(n, i)  # to the left while it stays <= 0
+        while True:
+            go = ~up & (l >= 0) & (slope[rows, np.maximum(l, 0)] <= 0)
+            if not go.any():
+                break
+            l = l - go
+        out[:, i] = np.where(up, db[rows, np.maximum(r - 1, 0)], db[rows, np.minimum(l + 1, nb)])
+    return out
+
+
+def _comp_wss(dbx, dby):
+    sx, sy = np.diff(dbx, axis=1), np.diff(dby, axis=1)
+    w = 0.0
+    for db, slope in ((dbx, sx), (dby, sy)):
+        peak = _comp_peaks(db, slope)
+        wmax = 20 / (20 + db.max(axis=1, keepdims=True) - db[:, :-1])
+        wloc = 1 / (1 + peak - db[:, :-1])
+        w = w + wmax * wloc
+    w = w / 2
+    return np.sum(w * (sx - sy) ** 2, axis=1) / np.sum(w, axis=1)
+
+
+def _comp_lpc(fr, P):
+    """autocorrelation lags 0 .. P and Levinson-Durbin in the reference's operation order (:62-90), every frame at once
+    -> (R [frames, P + 1], lp [frames, P + 1] = [1, -a])"""
+    n, win = fr.shape
+    R = np.stack([np.sum(fr[:, : win - k] * fr[:, k:], axis=1) for k in range(P + 1)], axis=1)
+    a = np.ones((n, P))
+    E = R[:, 0].copy()
+    for i in range(P):
+        sum_term = np.sum(a[:, :i] * R[:, i:0:-1], axis=1) if i else 0.0
+        rc = (R[:, i + 1] - sum_term) / np.maximum(1e-15, E)
+        if i:
+            a[:, :i] = a[:, :i] - rc[:, None] * a[:, :i][:, ::-1]
+        a[:, i] = rc
+        E = (1 - rc * rc) * E
+    return R, np.concatenate([np.ones((n, 1)), -a], axis=1)
+
+
+def _comp_llr(frx, fry, P):
+    Rx, ax = _comp_lpc(frx, P)
+    _, ay = _comp_lpc(fry, P)
+    k = np.abs(np.arange(P + 1)[:, None] - np.arange(P + 1)[None, :])
+    toep = Rx[:, k]  # [frames, P + 1, P + 1]
+    num = np.maximum(1e-10, np.einsum("ni,nij,nj->n", ay, toep, ay))
+    den = np.maximum(1e-10, np.einsum("ni,nij,nj->n", ax, toep, ax))
+    return np.log(num / den)
+
+
+def _comp_segsnr(x, y, fs):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x = x - x.mean()
+        y = y - y.mean()
+        y = y * (np.max(np.abs(x)) / np.max(np.abs(y)))
+        fx, fy = _comp_frames(x, fs), _comp_frames(y, fs)
+        snr = 10 * np.log10(np.sum(fx ** 2, axis=1) / (np.sum((fx - fy) ** 2, axis=1) + 1e-10) + 1e-10)
+    return np.minimum(np.maximum(snr, -10), 35)
+
+
+def _comp_trimmed_mean(v, m):
+    return float(np.cumsum(np.sort(v)[:m])[-1] / m) if m else float("nan")  # summed in ascending order
+
+
+def composite(ref, est, fs=16000):
+    """The signal measures behind CSIG / CBAK / COVL for one pair of 1-D arrays of one length (evaluate_covl.py, float64): ->
+    dict(llr = mean of the int(round(0.95 n)) smallest frame LLRs, wss = the same of the frame WSS values, segsnr = mean
+    segmental SNR, n_frames, llr_frames, wss_frames, segsnr_frames).  No frame (len < win + skip): NaN, like the reference's
+    mean of an empty list.  The arguments are not modified (the reference's SSNR removes their means in place)."""
+    x = np.asarray(ref, dtype=np.float64).reshape(-1)
+    y = np.asarray(est, dtype=np.float64).reshape(-1)
+    if x.shape != y.shape:
+        raise ValueError("composite: ref and est must have the same length")
+    P = composite_params(fs)[3]
+    n = composite_num_frames(len(x), fs)
+    if n == 0:
+        z = np.zeros(0)
+        return dict(llr=float("nan"), wss=float("nan"), segsnr=float("nan"), n_frames=0, llr_frames=z, wss_frames=z.copy(),
+                    segsnr_frames=z.copy())
+    with np.errstate(divide="ignore", invalid="ignore"):
+        llr = _comp_llr(_comp_frames(x, fs), _comp_frames(y, fs), P)
+        wss = _comp_wss(composite_band_db(x, fs), composite_band_db(y, fs))
+    seg = _comp_segsnr(x, y, fs)
+    m = composite_trim_count(n)
+    return dict(llr=_comp_trimmed_mean(llr, m), wss=_comp_trimmed_mean(wss, m), segsnr=float(np.cumsum(seg)[-1] / n), n_frames=n,
+                llr_frames=llr, wss_frames=wss, segsnr_frames=seg)
+
+
+def composite_batch(ref, est, fs=16000, lengths=None, perm=None):
+    """composite() of every source of a zero-padded batch, computed on the device (ops.composite, csrc/composite.hip): ref, est
+    [B,S,T] device tensors -> [B,S,4] float64 numpy array {llr, wss, segsnr, n_frames}; estimate row perm[b][i] (default i)
+    against reference row i over the first lengths[b] (default T) samples.  One pinned, non-blocking readback of 4 B S numbers
+    on the current stream."""
+    d = ops.composite(ref, est, fs=fs, lengths=lengths, perm=perm)
+    h = torch.empty(d.shape, dtype=d.dtype, pin_memory=True)
+    h.copy_(d, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return h.numpy().copy()
+
+
+def eval_composite(llr, wss, segsnr, pesq):
+    """CSIG / CBAK / COVL from the three signal measures and a PESQ score (evaluate_covl.py:47-59: Hu & Loizou's linear
+    formulas, each trimmed to [1, 5]).  pesq=None (PESQ is third-party code this package does not restate): three Nones."""
+    if pesq is None:
+        return {"csig": None, "cbak": None, "covl": None}
+    trim = lambda v: min(max(v, 1), 5)
+    return {"csig": trim(3.093 - 1.029 * llr + 0.603 * pesq - 0.009 * wss),
+            "cbak": trim(1.634 + 0.478 * pesq - 0.007 * wss + 0.063 * segsnr),
+            "covl": trim(1.594 + 0.805 * pesq - 0.512 * llr - 0.007 * wss)}
+
+
 def si_sdr_loss(est, ref, zero_mean=True, clamp_db=30.0, sign_flip=True):
     """SISDRLoss(zero_mean, clamp_db, sign_flip), mean-reduced (reference models/losses.py:8-37 over
     fast_bss_eval.si_sdr_pit_loss): the SI-SDR of the best source permutation from the Gram matrices above, averaged over

@@ -597,6 +597,42 @@ def stoi(ref, est, fs, extended=True, lengths=None, perm=None):
     return out
 
 
+def composite_workspace_bytes(B, S, T, fs):
+    """bytes of workspace diffsep_composite needs (host arithmetic; raises for a sample rate or shape it refuses)"""
+    n = lib().diffsep_composite_workspace_bytes(int(B), int(S), int(T), int(fs))
+    check(0 if n >= 0 else 1)
+    return int(n)
+
+
+def composite(ref, est, fs=16000, lengths=None, perm=None, frames=False):
+    """LLR / WSS / segmental SNR (the ingredients of CSIG / CBAK / COVL) of every source of a zero-padded batch on the device:
+    ref, est [B,S,T] float32 device tensors -> float64 [B,S,4] device tensor {llr_mean, wss_dist, segsnr, n_frames}; estimate
+    row perm[b][i] (default i) against reference row i over the first lengths[b] (default T) samples.  frames=True: also the
+    per-frame values, float64 [B,S,3,F] {llr, wss, segsnr} in frame order with F = the frame count of T (NaN beyond a row's
+    own count).  The algorithm of metrics.composite in float64 (csrc/composite.hip); asynchronous on the current stream."""
+    if ref.shape != est.shape or ref.dim() != 3:
+        raise ValueError("composite: ref and est must be [B,S,T] tensors of one shape")
+    B, S, T = ref.shape
+    ref, est = ref.float().contiguous(), est.float().contiguous()
+    nbytes = composite_workspace_bytes(B, S, T, fs)
+    ln = None if lengths is None else _dev_i32(lengths, ref.device)
+    pm = None if perm is None else _dev_i32(perm, ref.device)
+    if ln is not None and ln.numel() != B:
+        raise ValueError("composite: lengths must have B entries")
+    if pm is not None and tuple(pm.shape) != (B, S):
+        raise ValueError("composite: perm must be [B,S]")
+    out = torch.empty((B, S, 4), dtype=torch.float64, device=ref.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=ref.device)
+    fr, cap = None, 0
+    if frames:
+        win = int(round(30 * int(fs) / 1000))
+        cap = max(1, (T - win) // (win // 4))
+        fr = torch.full((B, S, 3, cap), float("nan"), dtype=torch.float64, device=ref.device)
+    check(lib().diffsep_composite(_ptr(ref), _ptr(est), _ptr(out), _ptr(fr), cap, B, S, T, _ptr(ln), _ptr(pm), int(fs),
+                                  _ptr(ws), nbytes, _stream_ptr()))
+    return (out, fr) if frames else out
+
+
 PIT_MODES = {None: 0, "none": 0, "true_mix": 1, "init_hack_pit": 1, "mean0": 2, "allthetime": 2}
 
 

@@ -627,6 +627,31 @@ int32_t diffsep_stoi(const float* ref, const float* est, double* out, int32_t B,
                      const int32_t* lengths, const int32_t* perm, int32_t fs, int32_t extended, void* workspace,
                      int64_t workspace_bytes, void* stream);
 
+/* Ingredients of the Hu & Loizou composite measures CSIG / CBAK / COVL for every source of a zero-padded batch
+ * (evaluate_covl.py:18-54 eval_composite; :358-408 llr with :62-95 lpcoeff; :155-355 wss; :106-152 SSNR): the log-likelihood
+ * ratio, the weighted spectral slope and the segmental SNR.  ref, est [B,S,T] float32; estimate row perm[b][i] (NULL: i) is
+ * scored against reference row i over the first lengths[b] (NULL: T) samples, in float64 from the samples on.  fs = 16000
+ * (30 ms frames of 480 samples, 1024-point spectrum, LPC order 16) or 8000 (240, 512, 10); frames start every win / 4
+ * samples, n = max(0, (len - win) div (win / 4)) of them, under the window 0.5 (1 - cos(2 pi j / (win + 1))), j = 1..win.
+ *   LLR  per frame: log of the ratio of the two LPC residual energies on the reference's autocorrelation (Levinson-Durbin
+ *        with the max(1e-15, E) guard, both quadratic forms floored at 1e-10); the reference's float32 casts are NOT
+ *        reproduced;
+ *   WSS  per frame: 25 Gaussian critical bands on the power spectrum, dB with a 1e-10 floor, 24 slopes, Klatt's weights
+ *        from the nearest peak (Kmax 20, Klocmax 1), sum W dslope^2 / sum W;
+ *   segSNR per frame: 10 log10(E_ref / (E_diff + 1e-10) + 1e-10) clamped to [-10, 35] after removing each signal's mean
+ *        and scaling the estimate by max|ref| / max|est| (LLR and WSS see the original samples).
+ * out [B][S][4] float64 = { mean of the m = round-half-even(0.95 n) smallest frame LLRs, the same of the frame WSS, mean
+ * segSNR over all frames, n }; n = 0: NaN, NaN, NaN, 0.  frames_out (nullable) [B][S][3][frames_cap] = per-frame { llr, wss,
+ * segsnr } in frame order, entries beyond n untouched; frames_cap >= the frame count of T when given.  lengths, perm: device
+ * int32.  Row (b, i) does not depend on the rest of the batch or on the stream (fixed-order reductions, no atomics);
+ * asynchronous on stream, no host readback.  S in 1..3.  A refusal returns non-zero with a message and writes nothing.
+ * Caller-owned workspace of diffsep_composite_workspace_bytes(B, S, T, fs) bytes (host arithmetic only; -1 and an error
+ * message for a bad shape or rate, or for more frames per row than the on-device ranking takes: 65536). */
+int64_t diffsep_composite_workspace_bytes(int32_t B, int32_t S, int64_t T, int32_t fs);
+int32_t diffsep_composite(const float* ref, const float* est, double* out, double* frames_out, int64_t frames_cap,
+                          int32_t B, int32_t S, int64_t T, const int32_t* lengths, const int32_t* perm, int32_t fs,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Long recordings: a file of T samples as K windows of Tw samples with a nominal overlap of Tv, stitched on the device.
  * The plan (host arithmetic only, no device needed): refused (-1 and a message) unless T >= 1, Tv >= 1 and 3 Tv <= Tw.
  * T <= Tw: K = 1, starts = {0}, the one window is the file itself (T samples).  Otherwise hop = Tw - Tv,
