@@ -234,6 +234,7 @@ struct ConvArgs {
 #define DS_OPT_NO_RW128 2u    // ... for its 128-cout variants only
 #define DS_OPT_RW_SMALL 4u    // register-weight kernel also for launches with fewer tiles than CUs (unit tests of small shapes)
 #define DS_OPT_NO_RW_RES 8u   // residual launches stay on the weight-stationary kernel
+#define DS_OPT_NO_RW_HELPER 131072u  // the 64 -> 64 GroupNorm launches of the register-weight kernel in its 4-wave form: no helper waves (A/B, tests)
 #define DS_OPT_NO_ATTN_FUSED 64u  // attention blocks as the 11 separate launches of rounds 1 - 3 (A/B)
 #define DS_OPT_NO_SPLIT256 128u   // cat(128, 128) -> 128 blocks as ONE launch per convolution on the generic tile (A/B)
 #define DS_OPT_NO_STFT_FUSED 256u // (process default only) STFT / iSTFT as the launch sequences of rounds 1 - 4 instead of the fused kernels (A/B)
@@ -283,6 +284,7 @@ inline bool ds_rw_frag_shape(int taps, int Cin, int Cout) {  // the weight shape
 }
 bool ds_conv_rw_supported(const ConvArgs& a);  // conv3x3_rw.hip: register-resident weights, 64 / 128 -> 64 and 128 -> 128, 16-bit, >= 32-row images
 int ds_launch_conv_rw(const ConvArgs& a, hipStream_t st);
+int ds_launch_conv_rw4(const ConvArgs& a, hipStream_t st);  // conv3x3_rw4.hip: the helper-form instantiations in their 4-wave form (DS_OPT_NO_RW_HELPER)
 // the weight shapes conv3x3_sw.hip streams (fragment-major copies of 3x3 weights and folded 1x1 skips)
 // (Cout 64 too: ds_conv_sw_supported takes e.g. the 192 -> 64 layer of the 128-row level, which is no register-weight shape; until
 // round 6 those copies existed only because the split kernel's shape test below happened to cover them)

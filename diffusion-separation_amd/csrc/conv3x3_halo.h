@@ -136,13 +136,13 @@ inline int halo_blocks_wanted(const ConvArgs& a, int ncb) {
 // argument: the statics are per instantiation), launch, check, and the name "family<targs>" for ds_last_conv_kernel()
 template <auto KERN, typename K>
 int halo_launch(K k, const ConvArgs& a, int tile_h, int g, int ncb, int lds, hipStream_t st, const char* family,
-                std::initializer_list<int> targs) {
+                std::initializer_list<int> targs, int threads = NT) {
   const int tiles = halo_tiles(a, tile_h);
   k.G = g < 1 ? 1 : (g > tiles ? tiles : g);
   k.tiles_x = a.W / TW;
   k.tiles_per_img = tiles;
   DS_FUNC_LDS_ONCE(KERN, lds);
-  hipLaunchKernelGGL(KERN, dim3(a.B * ncb * k.G), dim3(NT), lds, st, k);
+  hipLaunchKernelGGL(KERN, dim3(a.B * ncb * k.G), dim3(threads), lds, st, k);
   DS_LAUNCH_CHECK();
   static char name[64] = {0};
   if (!name[0]) {

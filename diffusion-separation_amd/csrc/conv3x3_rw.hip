@@ -34,14 +34,23 @@
 //     wait for every earlier store: vmcnt retires in order);
 //   * each phase runs in two halves of the wave's rows: the epilogue of one half (bias + temb bias, 1/sqrt(2),
 //     statistics for the next GroupNorm, packing, v_permlane32_swap / v_permlane16_swap into 64-byte row pieces,
-//     buffer_store_b128 — all in the accumulator layout, no LDS) runs under the MFMAs of the other half.
+//     buffer_store_b128 — all in the accumulator layout, no LDS) runs under the MFMAs of the other half;
+//   * the 64 -> 64 GroupNorm + SiLU instantiations (0 .. 3 skip chunks) run in the HELPER form: 8 waves, two per SIMD with 256
+//     registers each.  Waves 0 - 3 keep the MFMAs, the fragment reads and the epilogue (20 weight fragments in registers, the
+//     rest read from LDS one k-step ahead); waves 4 - 7 do the staging alone.  The block barrier is the only synchronisation,
+//     the same count in both roles.  Same tiles, K order, activation sequence and statistics mapping: the same bits as the
+//     4-wave form, which conv3x3_rw4.hip keeps behind engine option no_rw_helper.
 //
 // What bounds it: the issue slots of the single in-order wave (<= 5 instructions fit under a
 // 32-cycle MFMA, the GroupNorm variant has ~9).  K order (chunk, tap, 16-channel block) as in conv_mfma.hip / conv3x3_ws.hip.
 #include <stdlib.h>
 
-#ifdef RW_TIMING  // profiling build only: per-phase cycle totals of wave 0 (diffsep_rw_debug_read)
+#ifdef RW_TIMING  // profiling build only: per-phase cycle totals of wave 0 (diffsep_rw_debug_read; conv3x3_rw4.hip: diffsep_rw4_debug_read)
+#ifdef RW_FOUR_WAVE_TU
+#define HALO_TIMING rw4
+#else
 #define HALO_TIMING rw
+#endif
 #endif
 #include "conv3x3_halo.h"
 
@@ -81,9 +90,25 @@ struct RwK {
 #endif
 constexpr int rw_lds_ksteps(int nch, int rpw, int nsk, int ncg) { return ncg == 4 ? nch * KSC - 64 + nsk * NKB : (nch == 2 ? RW_NWL2 : 0); }
 
+// The HELPER form (64 -> 64 with GroupNorm + SiLU, 0 .. 3 skip chunks): a block of 8 waves, two per SIMD with 256 registers
+// each.  Waves 0 - 3 (the matrix role) keep MFMAs, fragment reads and the epilogue; waves 4 - 7 (the helper role) do the
+// staging alone: loads, GroupNorm affine + SiLU, LDS writes.  The matrix wave's file holds RW_HELPER_WREGS weight fragments
+// beside accumulators, pixel fragments, statistics and bias; the rest are read from LDS one k-step ahead (NWL).
+// -DRW_NO_HELPER: the 4-wave form for every instantiation (the A/B).
+#ifndef RW_HELPER_WREGS
+#define RW_HELPER_WREGS 20
+#endif
+constexpr bool rw_helper_form(int nch, int mode, int ncg) {
+#ifdef RW_NO_HELPER
+  return false;
+#else
+  return nch == 1 && mode == 2 && ncg == 2;
+#endif
+}
+
 // NCG: cout groups of 32 (2: 64 couts, the block's 4 waves = 2 cout groups x 2 pixel groups; 4: 128 couts, 4 cout
 // groups on ONE pixel group — the same staging and epilogue work per wave for twice the MFMAs)
-template <int NCH, int RPW, int NSK, int NCG>
+template <int NCH, int RPW, int NSK, int NCG, bool HLP = false>
 struct RwGeom {
   static constexpr int CO = 32 * NCG, PGN = 4 / NCG;
   static constexpr int TH = PGN * RPW, HH_ = TH + 2, HP = HH_ * HW_;
@@ -99,7 +124,7 @@ struct RwGeom {
   static_assert((NI + NB) * (NT / PPL) >= HP + NB * (NT / PPL) - NBP, "dummy pixels of the last border pass fit the slot");
   static constexpr int NPH = NCH + NSK;                   // phases (chunks) per tile
   static constexpr int NKS = NCH * KSC + NSK * NKB;       // k-steps = weight fragments per wave
-  static constexpr int NWL = rw_lds_ksteps(NCH, RPW, NSK, NCG), NWR = NKS - NWL;  // fragments in LDS / in registers
+  static constexpr int NWL = HLP ? NKS - RW_HELPER_WREGS : rw_lds_ksteps(NCH, RPW, NSK, NCG), NWR = NKS - NWL;  // fragments in LDS / in registers
   static constexpr int LDS_WL = NWL * NCG * 64 * 16;      // [k-step][cout group][lane] x 16 B
   static constexpr int WL_STEP = NCG * 64 * 16;
   static constexpr int OFF_TAB = 2 * LDS_A, OFF_WL = OFF_TAB + ((LDS_TAB + 15) & ~15), OFF_DESC = OFF_WL + LDS_WL;
@@ -113,16 +138,28 @@ struct RwGeom {
 
 // NCH: 64-channel chunks of the 3x3 input (1: 64 channels, 2: 128 = one or two sources); RPW: pixel rows per wave
 // (tile = 2 RPW x 32); NSK: 64-channel chunks of the folded 1x1 skip (0, 1, 2); MODE: 0 raw input, 2 GroupNorm + SiLU
+// The helper form (8 waves, above) is a compile-time property of the instantiation.  Its 4-wave form (engine option
+// no_rw_helper) is this same text compiled a second time with -DRW_NO_HELPER in conv3x3_rw4.hip: a function boundary around the
+// body moves the registers of every instantiation (profiles/rw_helper_ab.txt, section 1).
 template <int NCH, int RPW, int NSK, int MODE, int NCG>
-__global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
-  using G = RwGeom<NCH, RPW, NSK, NCG>;
+__global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_helper_form(NCH, MODE, NCG) ? 2 : 1) void conv3x3_rw_kernel(RwK p) {
+  constexpr bool HLP = rw_helper_form(NCH, MODE, NCG);
+  using G = RwGeom<NCH, RPW, NSK, NCG, HLP>;
   constexpr int CO = G::CO, PGN = G::PGN;
   constexpr int TH = G::TH, HP = G::HP, LDS_A = G::LDS_A, NL = G::NL, NPH = G::NPH, NKS = G::NKS, CIN = G::CIN, NWR = G::NWR;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* sA = smem;
   float* sTab = reinterpret_cast<float*>(smem + G::OFF_TAB);
   int* sDesc = reinterpret_cast<int*>(smem + G::OFF_DESC);
-  const int tid = threadIdx.x;
+  // helper form: thread 256 + t of the helper role owns the staging pieces thread t owns in the 4-wave form, and thread t of
+  // the matrix role its cout group, pixel group and statistics: both roles see the same tid in [0, NT)
+  const int tid = HLP ? (int)(threadIdx.x & (NT - 1)) : (int)threadIdx.x;
+  const bool helper = HLP && __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8) != 0;  // (wave-uniform)
+  // Synchronisation of the two roles is the block barrier alone: each role executes the same, statically known number of
+  // barriers — BAR_PRO in the prologue, BAR_PH per phase, BAR_TAIL in the tail when the launch has statistics (uniform)
+  constexpr int BAR_PRO_M = 1, BAR_PH_M = 1, BAR_TAIL_M = 2;  // matrix role: tables + LDS fragments | chunk in the ring | reduce
+  constexpr int BAR_PRO_H = 1, BAR_PH_H = 1, BAR_TAIL_H = 2;  // helper role: tables before the activation | chunk written | reduce
+  static_assert(BAR_PRO_M == BAR_PRO_H && BAR_PH_M == BAR_PH_H && BAR_TAIL_M == BAR_TAIL_H, "both roles meet at every barrier");
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l32 = lane & 31, h = lane >> 5;
   const int cg = wave % NCG, pg = wave / NCG;
@@ -140,7 +177,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
   float t_gam = 1.f, t_bet = 0.f, t_sc = 1.f, t_sh = 0.f, t_bias = 0.f;
 #pragma unroll
   for (int j = 0; j < CPG_MAX; ++j) { t_s[j] = 0; t_q[j] = 0; }
-  if (tid < CIN) {
+  if (!helper && tid < CIN) {
     const int c = tid;
     if (p.gn_acc1) {  // statistics straight from the producers' channel-sum accumulators
       const int C1 = p.C1, C2 = CIN - C1;
@@ -161,7 +198,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
       t_sh = p.gn_shift[(long)b * CIN + c];
     }
   }
-  if (tid < CO) t_bias = (p.bias ? p.bias[tid] : 0.f) + (p.bias_b ? p.bias_b[(long)b * p.bias_b_ld + tid] : 0.f);
+  if (!helper && tid < CO) t_bias = (p.bias ? p.bias[tid] : 0.f) + (p.bias_b ? p.bias_b[(long)b * p.bias_b_ld + tid] : 0.f);
   auto build_tables = [&]() __attribute__((always_inline)) {
     if (tid < CIN) {
       float sc = t_sc, sh = t_sh;
@@ -455,6 +492,183 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
     unit_s2(P1_, P2_, g1, g2, sl, u, rel);
   };
 
+  // ---- the helper role (waves 4 - 7 of the helper form), whole: the staging of the 4-wave form — same pieces, same unit()
+  // stages, same ring slots — as a plain loop per phase.  Without skip chunks (second block below): between two phase barriers it
+  // waits for the chunk after the one in the ring (in flight since the phase before), activates it, writes it to the other slot
+  // and re-issues every piece's registers as the load of the chunk after that.  Barriers of either block: BAR_PRO_H, BAR_PH_H
+  // per phase, BAR_TAIL_H; the role returns behind them.
+  // With skip chunks (NSK > 0) a tile's phases are NSK short ones (a skip chunk: 16 MFMAs per wave) and a long one (the 3x3
+  // chunk: 144).  Staged one phase ahead, the 3x3 chunk's whole activation would fall into the last short phase, and the
+  // matrix role would wait for it.  So the helper keeps TWO register sets: ps[] carries the raw skip chunks (tile pixels only,
+  // written as they are), pa[] the 3x3 chunk of the NEXT tile — loaded in the last short phase (as the registers of this
+  // tile's 3x3 chunk are written out), activated IN PLACE during the long phase, written in the next tile's last short phase.
+  if constexpr (HLP && NSK > 0) {
+    if (helper) {
+      using C0 = std::integral_constant<int, 0>;  // the 3x3 chunk
+      u32x4_t ps[NI];
+      auto issue_skip = [&](auto C_, const TileG& g, int k) __attribute__((always_inline)) {  // issue_one of a skip chunk's tile pixel, into ps[]
+        constexpr int CB = (decltype(C_)::value - NCH) * KC;
+        const bool second = CB >= p.sC1;  // (wave-uniform)
+        const unsigned ld2 = (unsigned)(second ? p.ldsx2 : p.ldsx) * 2u;
+        const unsigned co2 = (unsigned)((second ? CB - p.sC1 : CB) * 2) + (unsigned)slot * 16u;
+        ps[k] = ld16v(second ? rs2 : rs1, __umul24((unsigned)(g.pix0 + k * p.W + ixp), ld2) + co2, 0);
+      };
+      auto put_skip = [&](int sl, int k) __attribute__((always_inline)) {
+        *reinterpret_cast<u32x4_t*>(sA + sl * LDS_A + ldi0 + k * HW_ * AROW) = ps[k];
+      };
+      // the three stages of unit(), the result back into pa[] instead of the ring
+      auto act_inplace = [&](int u) __attribute__((always_inline)) {
+        unit_s01(C0{}, u, -1);
+        unit_s01(C0{}, -1, u);
+        const int k = u >> 2, d = u & 3, q = u % 3;
+        if constexpr (ACT_PK) {
+          unsigned v;
+          asm volatile("v_pk_mul_f16 %0, %1, %2" : "=v"(v) : "v"(uzp[q]), "v"(urp[q]));
+          so[d] = v;
+        } else {
+          so[d] = pack_h2(uz[q][0] * ut[q][0], uz[q][1] * ut[q][1]);
+        }
+        if (d == 3) pa[k] = so;
+      };
+      // an activated piece into the ring (zero padding stays zero), its registers re-issued as the next tile's piece
+      auto put_conv = [&](const TileG& g1, const TileG& g2, int sl, int k, int rel) __attribute__((always_inline)) {
+        so = pa[k];
+        if (k >= NI) {
+          const bool ok = piece_ok(C0{}, g1, k);
+          so.x = ok ? so.x : 0u;
+          so.y = ok ? so.y : 0u;
+          so.z = ok ? so.z : 0u;
+          so.w = ok ? so.w : 0u;
+        }
+        *reinterpret_cast<u32x4_t*>(sA + sl * LDS_A + (k < NI ? ldi0 + k * HW_ * AROW : dstb[k < NI ? 0 : k - NI])) = so;
+        issue_one(C0{}, g2, k, rel);
+      };
+      TileG hc = tile_geom(0);
+      TileG hnc = tile_geom(1);
+      int hrel[NB];
+#pragma unroll
+      for (int k = 0; k < NB; ++k) hrel[k] = sDesc[k * NT + tid];  // (the thread's own entries: no barrier)
+#pragma unroll
+      for (int k = 0; k < NI; ++k) issue_skip(std::integral_constant<int, NCH>{}, hc, k);
+#pragma unroll
+      for (int k = 0; k < NL; ++k) issue_one(C0{}, hc, k, k < NI ? 0 : hrel[k < NI ? 0 : k - NI]);
+      sync_lds();  // BAR_PRO_H: the matrix role's tables
+      RT_MARK(0)
+#pragma unroll
+      for (int k = 0; k < NI; ++k) {  // the first phase's chunk; ps[] goes on to the next skip chunk
+        put_skip(0, k);
+        if constexpr (NSK > 1) issue_skip(std::integral_constant<int, NCH + 1>{}, hc, k);
+        else issue_skip(std::integral_constant<int, NCH>{}, hnc, k);
+      }
+      act_tab(0);  // (one 3x3 chunk: its scale / shift stay in registers for the whole launch)
+#pragma unroll
+      for (int u = 0; u < NL * 4; ++u) act_inplace(u);
+      RT_MARK(1)
+      int hph = 0;
+      int hy2 = (t0 + 2) / p.tiles_x, hx2 = (t0 + 2) - hy2 * p.tiles_x;
+      for (int i = 0; i < nt; ++i) {
+        const TileG hn = hnc, hnn = geom_at(hy2, hx2, i + 2 < nt);
+        auto stage_phase = [&](auto self, auto P_) __attribute__((always_inline)) {
+          constexpr int P = decltype(P_)::value;
+          sync_lds();  // BAR_PH_H: the matrix role has read the slot written now; the chunk staged last phase is visible to it
+          RT_MARK(2)
+          const int sl = (hph & 1) ^ 1;
+          if constexpr (P == NSK - 1) {  // the next phase is this tile's long one: its 3x3 chunk, activated a tile ago
+#pragma unroll
+            for (int k = 0; k < NL; ++k) put_conv(hc, hn, sl, k, k < NI ? 0 : hrel[k < NI ? 0 : k - NI]);
+          } else {
+            // the next phase's skip chunk SW (of the next tile after the long phase), then ps[] goes on to the skip chunk after it
+            constexpr int SW = (P + 1) % NPH;
+            constexpr bool NEXT = P == NSK, WRAP = SW + 1 >= NSK;
+            constexpr int SN = WRAP ? 0 : SW + 1;
+            const TileG& gsn = NEXT ? (WRAP ? hnn : hn) : (WRAP ? hn : hc);
+#pragma unroll
+            for (int k = 0; k < NI; ++k) {
+              put_skip(sl, k);
+              issue_skip(std::integral_constant<int, NCH + SN>{}, gsn, k);
+            }
+            if constexpr (P == NSK) {  // the long phase: the next tile's 3x3 chunk, in flight since the phase before
+#pragma unroll
+              for (int u = 0; u < NL * 4; ++u) act_inplace(u);
+            }
+          }
+          ++hph;
+          RT_MARK(3)
+          if constexpr (P + 1 < NPH) self(self, std::integral_constant<int, P + 1>{});
+        };
+        stage_phase(stage_phase, std::integral_constant<int, 0>{});
+        hc = hn;
+        hnc = hnn;
+        if (++hx2 == p.tiles_x) { hx2 = 0; ++hy2; }
+      }
+      if (p.stats != nullptr) {  // BAR_TAIL_H: the matrix role's statistics reduce reuses the ring
+        __syncthreads();
+        __syncthreads();
+      }
+#ifdef RW_TIMING  // the helper role's marks: counters 8 .. 11 (wave 4; the matrix role's are 0 .. 7 of wave 0)
+      if (threadIdx.x == NT) {
+        for (int q = 0; q < 4; ++q) atomicAdd(&HALO_DBG[8 + q], (unsigned long long)rt_acc[q]);
+      }
+#endif
+      return;
+    }
+  }
+  if constexpr (HLP && NSK == 0) {
+    if (helper) {
+      constexpr int HC0 = G::chunk_of(0), HC1 = G::chunk_of(1 % NPH);
+      TileG hc = tile_geom(0);
+      const TileG h1st = NPH > 1 ? hc : tile_geom(1);
+#pragma unroll
+      for (int k = 0; k < NL; ++k) issue_one(std::integral_constant<int, HC0>{}, hc, k, k < NI ? 0 : sDesc[(k < NI ? 0 : k - NI) * NT + tid]);
+      int hrel[NB];
+#pragma unroll
+      for (int k = 0; k < NB; ++k) hrel[k] = sDesc[k * NT + tid];  // (the thread's own entries: no barrier)
+      sync_lds();  // BAR_PRO_H: the matrix role's tables
+      RT_MARK(0)   // (profiling build, wave 4: 0 = up to the tables, 1 = first chunk, 2 = waiting at phase barriers, 3 = staging)
+      act_tab(HC0);
+#pragma unroll
+      for (int u = 0; u < NL * 4; ++u)
+        unit(std::integral_constant<int, HC0>{}, std::integral_constant<int, HC1>{}, hc, h1st, 0, u, (u >> 2) < NI ? 0 : hrel[(u >> 2) < NI ? 0 : (u >> 2) - NI]);
+      RT_MARK(1)
+      int hph = 0;
+      TileG hnc = tile_geom(1);
+      int hy2 = (t0 + 2) / p.tiles_x, hx2 = (t0 + 2) - hy2 * p.tiles_x;
+      for (int i = 0; i < nt; ++i) {
+        const TileG hn = hnc, hnn = geom_at(hy2, hx2, i + 2 < nt);
+        auto stage_phase = [&](auto self, auto P_) __attribute__((always_inline)) {
+          constexpr int P = decltype(P_)::value;
+          constexpr int C1 = G::chunk_of((P + 1) % NPH), C2 = G::chunk_of((P + 2) % NPH);
+          sync_lds();  // BAR_PH_H: the matrix role has read the slot written now; the chunk staged last phase is visible to it
+          RT_MARK(2)
+          const int sl = (hph & 1) ^ 1;
+          const TileG& g1 = (P + 1) / NPH == 0 ? hc : hn;
+          const TileG& g2 = (P + 2) / NPH == 0 ? hc : ((P + 2) / NPH == 1 ? hn : hnn);
+          if constexpr (C1 < NCH) act_tab(C1);
+#pragma unroll
+          for (int u = 0; u < NL * 4; ++u)
+            unit(std::integral_constant<int, C1>{}, std::integral_constant<int, C2>{}, g1, g2, sl, u, (u >> 2) < NI ? 0 : hrel[(u >> 2) < NI ? 0 : (u >> 2) - NI]);
+          ++hph;
+          RT_MARK(3)
+          if constexpr (P + 1 < NPH) self(self, std::integral_constant<int, P + 1>{});
+        };
+        stage_phase(stage_phase, std::integral_constant<int, 0>{});
+        hc = hn;
+        hnc = hnn;
+        if (++hx2 == p.tiles_x) { hx2 = 0; ++hy2; }
+      }
+      if (p.stats != nullptr) {  // BAR_TAIL_H: the matrix role's statistics reduce reuses the ring
+        __syncthreads();
+        __syncthreads();
+      }
+#ifdef RW_TIMING  // the helper role's marks: counters 8 .. 11 (wave 4; the matrix role's are 0 .. 7 of wave 0)
+      if (threadIdx.x == NT) {
+        for (int q = 0; q < 4; ++q) atomicAdd(&HALO_DBG[8 + q], (unsigned long long)rt_acc[q]);
+      }
+#endif
+      return;
+    }
+  }
+
   f32x16 acc[RPW];
 #pragma unroll
   for (int r = 0; r < RPW; ++r)
@@ -593,7 +807,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
       for (int r = 0; r < RH; ++r) asm volatile("s_nop 11" : "+v"(acc[ER0 + r]));
     }
 #endif
-    if constexpr (HF == 0 && C1 < NCH) act_tab(C1);
+    if constexpr (!HLP && HF == 0 && C1 < NCH) act_tab(C1);  // (helper form: the staging is the helper role's, stage_phase)
     // K order inside a 3x3 chunk: (kx, 16-channel block) groups outside, ky inside.  The RH rows of this half use the
     // pixel fragments of input rows R0 .. R0 + RH + 1 at the group's (kx, block): each is read ONCE per group and serves up
     // to three k-steps (ky) — RH + 2 fragment reads per 3 RH MFMAs instead of 3 RH, and one wait per group.  (A skip
@@ -629,7 +843,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
           rels[par][u >> 2] = REL_REGS ? relreg[(u >> 2) - NI] : sDesc[((u >> 2) - NI) * NT + tid];
       }
     };
-    fetch_rels(0, 0);  // (the first k-step's operands: the one exposed round trip of the half)
+    if constexpr (!HLP) fetch_rels(0, 0);  // (the first k-step's operands: the one exposed round trip of the half)
 
     // ---- lumps.  (An inline-asm instruction that reads a register written by one of the two instructions in front of it
     // gets a wait state from the compiler, which cannot see whether the producer was a transcendental: the orders below
@@ -737,7 +951,9 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
 
 #pragma unroll
     for (int ks = 0; ks < NK; ++ks) {
-      if (ks + 1 < NK) fetch_rels(ks + 1, (ks + 1) & 1);
+      if constexpr (!HLP) {
+        if (ks + 1 < NK) fetch_rels(ks + 1, (ks + 1) & 1);
+      }
       const int wi = W0 + widx(ks), win = W0 + widx(ks + 1 < NK ? ks + 1 : ks);
       if (win >= NWR && ks + 1 < NK) wln = *reinterpret_cast<const u32x4_t*>(sWl + (win - NWR) * G::WL_STEP);
       const u32x4_t wk = wi < NWR ? wf[wi < NWR ? wi : 0] : wl;
@@ -750,7 +966,9 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
         // and feeds the MFMA from there; accumulators, pixel fragments and everything the VALU touches live in the
         // architectural half.  What the compiler does not know about an asm MFMA: the 12 wait states between its result and
         // a VALU read — the guard at the start of every half.
-        if (wi < NWR) {
+        // (helper form: no accumulator half at two waves per SIMD — the wave's 256 registers are all architectural, and the
+        // register-resident fragments feed the MFMA from there like the LDS-resident ones)
+        if (!HLP && wi < NWR) {
           if (P == 0 && ks == 0) asm volatile(DS_MFMA_H32_ASM " %0, %1, %2, 0" : "=v"(acc[R0 + r]) : "a"(wk), "v"(RW_FRAG(ks, r)) RW_DEP);
           else asm volatile(DS_MFMA_H32_ASM " %0, %1, %2, %0" : "+v"(acc[R0 + r]) : "a"(wk), "v"(RW_FRAG(ks, r)) RW_DEP);
         } else {  // LDS-resident fragment: straight from the ds_read's VGPRs (no VALU copy in front of the MFMA)
@@ -763,8 +981,10 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
           if (q < RFN && g + 1 < NG) rf[(g + 1) & 1][q] = ldg(g + 1, q);
         }
         const int gh = ks * RH + r, gp = HF * NGH + gh;
+        if constexpr (!HLP) {
 #pragma unroll
-        for (int L = lub(gp); L < lub(gp + 1); ++L) unit_lump(L, ks & 1);
+          for (int L = lub(gp); L < lub(gp + 1); ++L) unit_lump(L, ks & 1);
+        }
 #ifndef RW_ABL_NOEPI
         if constexpr (EPI) {
 #pragma unroll
@@ -784,13 +1004,16 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
   {
     // the first chunk's loads go out ahead of the weights (loads return in order: the tile can be staged while the
     // weight fragments are still streaming in; the MFMAs then wait for them fragment by fragment)
+    // (helper form, here the matrix role: weights, tables and the bias registers; the chunks are the helper role's)
+    if constexpr (!HLP) {
 #pragma unroll
-    for (int k = 0; k < NL; ++k) issue_one(std::integral_constant<int, CH0>{}, gc, k, k < NI ? 0 : sDesc[(k < NI ? 0 : k - NI) * NT + tid]);
+      for (int k = 0; k < NL; ++k) issue_one(std::integral_constant<int, CH0>{}, gc, k, k < NI ? 0 : sDesc[(k < NI ? 0 : k - NI) * NT + tid]);
+    }
     load_weights();
     build_tables();
-    sync_lds();  // tables (and the LDS-resident weight fragments) visible
+    sync_lds();  // tables (and the LDS-resident weight fragments) visible (BAR_PRO_M)
     RT_MARK(7)
-    if constexpr (REL_REGS) {
+    if constexpr (REL_REGS && !HLP) {
 #pragma unroll
       for (int k = 0; k < NB; ++k) relreg[k] = sDesc[k * NT + tid];
     }
@@ -801,12 +1024,14 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_rw_kernel(RwK p) {
         breg[j][1] = *reinterpret_cast<const float4*>(sTab + 2 * CIN + cg * 32 + 8 * (2 * j + 1) + 4 * h);
       }
     }
-    act_tab(CH0);
-    // (staging the first chunk re-issues every piece as the second one)
+    if constexpr (!HLP) {
+      act_tab(CH0);
+      // (staging the first chunk re-issues every piece as the second one)
 #pragma unroll
-    for (int u = 0; u < NL * 4; ++u)
-      unit(std::integral_constant<int, CH0>{}, std::integral_constant<int, CH1>{}, gc, g1st, 0, u,
-           (u >> 2) < NI ? 0 : sDesc[((u >> 2) < NI ? 0 : (u >> 2) - NI) * NT + tid]);
+      for (int u = 0; u < NL * 4; ++u)
+        unit(std::integral_constant<int, CH0>{}, std::integral_constant<int, CH1>{}, gc, g1st, 0, u,
+             (u >> 2) < NI ? 0 : sDesc[((u >> 2) < NI ? 0 : (u >> 2) - NI) * NT + tid]);
+    }
   }
   RT_MARK(0)
   TileG gp = tile_geom(nt);  // "previous tile" of the first one: no tile (its stores fall outside every tensor)
@@ -894,10 +1119,11 @@ int rw_blocks_per_image(const ConvArgs& a, int tiles) {
 
 template <int NCH, int RPW, int NSK, int MODE, int NCG>
 int rw_launch(const RwK& k, const ConvArgs& a, hipStream_t st) {
-  using G = RwGeom<NCH, RPW, NSK, NCG>;
+  constexpr bool HLP = rw_helper_form(NCH, MODE, NCG);
+  using G = RwGeom<NCH, RPW, NSK, NCG, HLP>;
   static_assert(G::TH <= HALO_TH_MAX, "halo_addressing_ok covers the tile");
   return halo_launch<conv3x3_rw_kernel<NCH, RPW, NSK, MODE, NCG>>(k, a, G::TH, rw_blocks_per_image(a, halo_tiles(a, G::TH)), 1, G::LDS_TOTAL, st,
-                                                                 "conv3x3_rw_kernel", {NCH, RPW, NSK, MODE, NCG});
+                                                                 "conv3x3_rw_kernel", {NCH, RPW, NSK, MODE, NCG}, HLP ? 2 * NT : NT);
 }
 
 // The instantiated set, written ONCE: (Cout, 64-channel chunks of the 3x3 input, of the folded skip / residual, mode).  The shape
@@ -905,10 +1131,14 @@ int rw_launch(const RwK& k, const ConvArgs& a, hipStream_t st) {
 // (192 skip channels = the cat(64, 128) block of the 128^2 up path: 36 + 12 fragments fill 192 of the 256 weight registers; a
 // residual is one chunk) or 128 without (no layer of the network has both; the register file would not hold it either).  128 couts
 // = 4 cout groups: the skip / residual fragments live in LDS; every such layer normalises its input.
+#ifdef RW_FOUR_WAVE_TU  // conv3x3_rw4.hip: the instantiations that have a helper form, in their 4-wave form
+#define RW_SHAPES(X) X(64, 1, 0, 2) X(64, 1, 1, 2) X(64, 1, 2, 2) X(64, 1, 3, 2)
+#else
 #define RW_SHAPES(X)                                                                        \
   X(64, 1, 0, 0) X(64, 1, 1, 0) X(64, 1, 2, 0) X(64, 1, 3, 0) X(64, 2, 0, 0)                \
   X(64, 1, 0, 2) X(64, 1, 1, 2) X(64, 1, 2, 2) X(64, 1, 3, 2) X(64, 2, 0, 2)                \
   X(128, 2, 0, 0) X(128, 2, 0, 2) X(128, 2, 1, 2) X(128, 2, 2, 2)
+#endif
 #define RW_IS(CO_, NCH_, NSK_, MODE_) cout == CO_ && nch == NCH_ && nsk == NSK_ && mode == MODE_
 bool rw_shape(int cout, int nch, int nsk, int mode) {
 #define RW_CASE(CO_, NCH_, NSK_, MODE_) if (RW_IS(CO_, NCH_, NSK_, MODE_)) return true;
@@ -929,6 +1159,9 @@ int rw_dispatch(const RwK& k, const ConvArgs& a, int cout, int nch, int nsk, int
 // The layers this kernel can take: 16-bit 3x3, 64 couts from 64 or 128 input channels or 128 from 128 (one tensor or the in-place
 // concat of two), input raw or GroupNorm + SiLU, optional folded 1x1 skip on 64 / 128 (/ 192) raw channels or a residual, whole
 // tiles.  Which of them it is given (tile counts against compute units, the A/B switches): ds_conv_plan.
+#ifdef RW_FOUR_WAVE_TU
+#define ds_launch_conv_rw ds_launch_conv_rw4  // (this translation unit defines the 4-wave entry only)
+#else
 bool ds_conv_rw_supported(const ConvArgs& a) {
   const int CO = a.Cout;
   if (!(a.dtype == DS_BF16 && a.taps == 9 && a.Cin % KC == 0 && a.w_bs == 0 && (a.w_chunked == 0 || a.w_chunked == 32) &&
@@ -947,8 +1180,14 @@ bool ds_conv_rw_supported(const ConvArgs& a) {
   }
   return rw_shape(CO, a.Cin / KC, nsk, (a.gn_scale || a.gn_acc1) ? 2 : 0);
 }
+#endif
 
 int ds_launch_conv_rw(const ConvArgs& a, hipStream_t st) {
+#ifndef RW_FOUR_WAVE_TU
+  // option no_rw_helper: same tiles, same blocks, same kernel name — the 4-wave form of the same instantiation
+  if ((a.opts & DS_OPT_NO_RW_HELPER) && rw_helper_form(a.Cin / KC, ((a.gn_scale || a.gn_acc1) && a.gn_act) ? 2 : 0, a.Cout / 32))
+    return ds_launch_conv_rw4(a, st);
+#endif
   RwK k;
   halo_fill_common(k, a);
   k.w = reinterpret_cast<const bf16_t*>(a.w); k.w_chunked = a.w_chunked;

@@ -26,6 +26,7 @@ static const struct { const char* name; const char* env; unsigned bit; } kOpts[]
     {"no_rw128", "DIFFSEP_NO_RW128", DS_OPT_NO_RW128},
     {"rw_small", "DIFFSEP_RW_SMALL", DS_OPT_RW_SMALL},
     {"no_rw_res", "DIFFSEP_NO_RW_RES", DS_OPT_NO_RW_RES},
+    {"no_rw_helper", nullptr, DS_OPT_NO_RW_HELPER},
     {"no_wfrag", nullptr, DS_OPT_NO_WFRAG},
     {"no_attn_fused", nullptr, DS_OPT_NO_ATTN_FUSED},
     {"no_stft_fused", "DIFFSEP_NO_STFT_FUSED", DS_OPT_NO_STFT_FUSED},

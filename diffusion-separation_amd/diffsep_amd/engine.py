@@ -112,7 +112,8 @@ class Engine:
     def set_option(self, name, value):
         """diffsep_engine_set_option.  Kernel-dispatch switches (0 / 1; A/B and test aids, the defaults are what ships; the
         table of DESIGN.md section 7b says which route each one closes): "no_rw", "no_rw128", "no_rw_res", "rw_small",
-        "no_sw", "no_sw_rw", "no_sw_rows4", "sw_rows4", "no_sws", "no_wfrag", "no_attn_fused", "no_split256"; launch
+        "no_sw", "no_sw_rw", "no_sw_rows4", "sw_rows4", "no_sws", "no_wfrag", "no_attn_fused", "no_split256";
+        "no_rw_helper" (the 64 -> 64 GroupNorm launches of the register-weight kernel without helper waves: same bits); launch
         geometry of the register-weight kernel: "rw_half", "rw_quarter", "rw_big_half" ("no_stft_fused" is a process
         default only: diffsep_set_option).  Others: "graph_cache" (captured graphs kept, LRU), "ablate" (measurement aid),
         "track_tensors", "dbg_alloc".  Synchronises the device, drops the captured graphs."""
