@@ -169,13 +169,8 @@ template <> __device__ inline float silu_t<float>(float v) { return v / (1.0f + 
 // bf16 mode: v_exp_f32 + v_rcp_f32 (1 ulp) instead of the 11-instruction IEEE division
 template <> __device__ inline float silu_t<bf16_t>(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
-// wave64 butterfly reductions (no LDS)
+// wave64 butterfly reductions (no LDS); the float64 ones and the fixed-order block reductions on them: reduce_device.h
 __device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ inline double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;

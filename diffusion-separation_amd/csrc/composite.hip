@@ -18,15 +18,15 @@
 //                       nearest-peak search, Klatt weights -> WSS
 //   comp_final_kernel   per pair: rank of every frame's LLR and WSS (ties by frame index) -> sorted lists, the sequential
 //                       ascending sum of the m = rint(0.95 n) smallest, the sequential sum of the segmental SNRs
-// Every reduction has a fixed order that depends on the pair's own length only (no atomics): row (b, i) of a batch equals the
-// B = 1 call bit for bit, on any stream.
+// Every reduction has a fixed order that depends on the pair's own length only (reduce_device.h; no atomics): row (b, i) of a
+// batch equals the B = 1 call bit for bit, on any stream.  Pair addressing, workspace carving, the table cache and the boundary
+// checks are those of every measure on pairs: pair_metrics.h.
 #include <cmath>
-#include <map>
-#include <mutex>
-#include <vector>
 
 #include "../../include/diffsep_hip.h"
 #include "common.h"
+#include "pair_metrics.h"
+#include "reduce_device.h"
 
 namespace {
 
@@ -65,12 +65,11 @@ int comp_layout(int B, int S, int64_t T, const CompRate& r, CompLayout* l) {
   l->fmax = comp_frames(T, r);
   if (l->fmax > kMaxFrames) return 2;
   l->fcap = l->fmax > 0 ? l->fmax : 1;
-  auto up = [](int64_t v) { return (v + 255) / 256 * 256; };
-  int64_t o = 0;
-  l->off_stats = o;  o += up(l->P * 4 * 8);
-  l->off_fr = o;     o += up(l->P * 3 * l->fcap * 8);
-  l->off_sorted = o; o += up(l->P * 2 * l->fcap * 8);
-  l->total = o;
+  DsCarver ws;
+  l->off_stats = ws.take(l->P * 4 * 8);
+  l->off_fr = ws.take(l->P * 3 * l->fcap * 8);
+  l->off_sorted = ws.take(l->P * 2 * l->fcap * 8);
+  l->total = ws.total;
   return 0;
 }
 
@@ -111,22 +110,12 @@ void comp_filters(const CompRate& r, std::vector<double>* w, CompBands* bp) {
 // [25][nb] at kTabFilt
 constexpr int kTabWin = 0, kTabCos = kMaxWin, kTabSin = kMaxWin + kMaxFft, kTabFilt = kMaxWin + 2 * kMaxFft;
 
-int comp_table(const CompRate& r, const double** out, CompBands* bp) {
-  struct Entry { double* dev; CompBands bands; };
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, Entry> cache;
-  int dev = 0;
-  DS_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> g(mu);
-  auto key = std::make_pair(dev, r.fs);
-  auto it = cache.find(key);
-  if (it != cache.end()) { *out = it->second.dev; *bp = it->second.bands; return 0; }
+void comp_build_table(const CompRate& r, std::vector<double>& t, CompBands* bands) {
   const double pi = 3.14159265358979323846;
   std::vector<double> filt;
-  Entry e;
-  comp_filters(r, &filt, &e.bands);
-  const int nb = e.bands.nb, half = r.nfft / 2;
-  std::vector<double> t((size_t)kTabFilt + (size_t)kCrit * nb, 0.0);
+  comp_filters(r, &filt, bands);
+  const int nb = bands->nb, half = r.nfft / 2;
+  t.assign((size_t)kTabFilt + (size_t)kCrit * nb, 0.0);
   for (int j = 0; j < r.win; ++j) t[kTabWin + j] = 0.5 * (1.0 - std::cos(2.0 * pi * ((double)(j + 1) / (r.win + 1))));
   for (int j = 0; j < r.nfft; ++j) {
     t[kTabCos + j] = std::cos(2.0 * pi * j / r.nfft);
@@ -134,46 +123,10 @@ int comp_table(const CompRate& r, const double** out, CompBands* bp) {
   }
   for (int i = 0; i < kCrit; ++i)
     for (int j = 0; j < nb; ++j) t[(size_t)kTabFilt + (size_t)i * nb + j] = filt[(size_t)i * half + j];
-  DS_HIP(hipMalloc(&e.dev, t.size() * sizeof(double)));
-  DS_HIP(hipMemcpy(e.dev, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
-  cache[key] = e;
-  *out = e.dev;
-  *bp = e.bands;
-  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
-__device__ inline int comp_len(const int* lengths, int b, long T) {
-  long n = lengths ? (long)lengths[b] : T;
-  return (int)(n < 0 ? 0 : (n > T ? T : n));
-}
 __device__ inline int comp_nframes(int len, int win, int skip) { return len > win ? (len - win) / skip : 0; }
-__device__ inline const float* comp_row(const float* ref, const float* est, const int* perm, int pair, int sig, int S, long T) {
-  const int b = pair / S;
-  int row = pair % S;
-  if (sig == 1 && perm) {
-    row = perm[pair];
-    row = row < 0 ? 0 : (row >= S ? S - 1 : row);
-  }
-  return (sig == 0 ? ref : est) + ((long)b * S + row) * T;
-}
-
-// fixed-order sum / maximum over a 256-thread block: butterfly inside each wave, then the 4 wave results in order
-__device__ inline double comp_block_sum(double v, double* sh4) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh4[0] + sh4[1]) + sh4[2]) + sh4[3];
-}
-__device__ inline double comp_block_max(double v, double* sh4) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmax(fmax(sh4[0], sh4[1]), fmax(sh4[2], sh4[3]));
-}
 
 // stats[pair][sig] = mean of the row over its len samples, stats[pair][2 + sig] = max |x - mean|.  grid (2, P), 256 threads
 __global__ __launch_bounds__(256) void comp_stats_kernel(const float* __restrict__ ref, const float* __restrict__ est,
@@ -181,14 +134,14 @@ __global__ __launch_bounds__(256) void comp_stats_kernel(const float* __restrict
                                                          double* __restrict__ stats, int S, long T) {
   __shared__ double sh4[4];
   const int pair = blockIdx.y, sig = blockIdx.x;
-  const int len = comp_len(lengths, pair / S, T);
-  const float* x = comp_row(ref, est, perm, pair, sig, S, T);
+  const int len = ds_pair_len(lengths, pair / S, T);
+  const float* x = ds_pair_row(ref, est, perm, pair, sig, S, T);
   double part = 0.0;
   for (int j = threadIdx.x; j < len; j += 256) part += (double)x[j];
-  const double mean = comp_block_sum(part, sh4) / (double)len;  // len = 0: NaN, and no frame reads it
+  const double mean = ds_block_sum_d<4>(part, sh4) / (double)len;  // len = 0: NaN, and no frame reads it
   double mx = 0.0;
   for (int j = threadIdx.x; j < len; j += 256) mx = fmax(mx, fabs((double)x[j] - mean));
-  mx = comp_block_max(mx, sh4);
+  mx = ds_block_max_d<4>(mx, sh4);
   if (threadIdx.x == 0) {
     stats[(long)pair * 4 + sig] = mean;
     stats[(long)pair * 4 + 2 + sig] = mx;
@@ -250,10 +203,10 @@ __global__ __launch_bounds__(256) void comp_frame_kernel(const float* __restrict
   __shared__ double edb[2][kCrit], slope[2][kCrit - 1], peak[2][kCrit - 1];
   __shared__ double sh4[4];
   const int pair = blockIdx.y, f = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int len = comp_len(lengths, pair / S, T);
+  const int len = ds_pair_len(lengths, pair / S, T);
   if (f >= comp_nframes(len, p.win, p.skip)) return;
-  const float* x0 = comp_row(ref, est, perm, pair, 0, S, T) + (long)f * p.skip;  // f skip + win <= len: inside the row
-  const float* x1 = comp_row(ref, est, perm, pair, 1, S, T) + (long)f * p.skip;
+  const float* x0 = ds_pair_row(ref, est, perm, pair, 0, S, T) + (long)f * p.skip;  // f skip + win <= len: inside the row
+  const float* x1 = ds_pair_row(ref, est, perm, pair, 1, S, T) + (long)f * p.skip;
   const double mean0 = stats[(long)pair * 4], mean1 = stats[(long)pair * 4 + 1];
   const double scale = stats[(long)pair * 4 + 2] / stats[(long)pair * 4 + 3];
   double e_sig = 0.0, e_noise = 0.0;
@@ -269,8 +222,8 @@ __global__ __launch_bounds__(256) void comp_frame_kernel(const float* __restrict
     twc[j] = tab[kTabCos + j];
     tws[j] = tab[kTabSin + j];
   }
-  e_sig = comp_block_sum(e_sig, sh4);
-  e_noise = comp_block_sum(e_noise, sh4);  // (its barriers also publish xw and the twiddles)
+  e_sig = ds_block_sum_d<4>(e_sig, sh4);
+  e_noise = ds_block_sum_d<4>(e_noise, sh4);  // (its barriers also publish xw and the twiddles)
   double segsnr = 10.0 * log10(e_sig / (e_noise + 1e-10) + 1e-10);
   segsnr = fmin(fmax(segsnr, -10.0), 35.0);
 
@@ -355,7 +308,7 @@ __global__ __launch_bounds__(256) void comp_final_kernel(const double* __restric
   __shared__ double tile[2][256];
   __shared__ double res[3];
   const int pair = blockIdx.x, t = threadIdx.x;
-  const int n = comp_nframes(comp_len(lengths, pair / S, T), win, skip);
+  const int n = comp_nframes(ds_pair_len(lengths, pair / S, T), win, skip);
   double* o = out + (long)pair * 4;
   if (n == 0) {
     if (t < 3) o[t] = __longlong_as_double(0x7ff8000000000000LL);
@@ -441,21 +394,17 @@ extern "C" int32_t diffsep_composite(const float* ref, const float* est, double*
                                      void* workspace, int64_t workspace_bytes, void* stream) {
   CompRate r;
   CompLayout l;
-  DS_CHECK(ref && est && out && workspace, "composite: null pointer");
   DS_CHECK(comp_rate(fs, &r), "composite: unsupported sample rate " + std::to_string(fs) + " (16000 or 8000)");
   const int rc = comp_layout(B, S, T, r, &l);
   DS_CHECK(rc != 1, "composite: bad shape " + comp_shape(B, S, T));
   DS_CHECK(rc != 2, "composite: more than " + std::to_string(kMaxFrames) + " frames per row (" + comp_shape(B, S, T) + ")");
-  DS_CHECK(l.P <= 65535, "composite: more than 65535 (utterance, source) pairs in one call");
   DS_CHECK(!frames_out || frames_cap >= l.fmax, "composite: frames_cap " + std::to_string(frames_cap) + " < " +
                                                     std::to_string(l.fmax) + " frames of T");
-  DS_CHECK(workspace_bytes >= l.total, "composite: workspace too small (" + std::to_string(workspace_bytes) + " < " +
-                                           std::to_string(l.total) + " bytes)");
-  DS_CHECK(((uintptr_t)workspace & 7) == 0, "composite: workspace must be 8-byte aligned");
+  if (ds_pair_check("composite", ref, est, out, workspace, workspace_bytes, l.P, l.total)) return 1;
   hipStream_t st = (hipStream_t)stream;
   const double* tab = nullptr;
   CompFrameP fp;
-  if (comp_table(r, &tab, &fp.bands)) return 1;
+  if (ds_device_table({r.fs, 0}, [&](std::vector<double>& t, CompBands& b) { comp_build_table(r, t, &b); }, &tab, &fp.bands)) return 1;
   DS_CHECK(fp.bands.nb >= 1 && fp.bands.nb <= r.nfft / 2, "composite: filter bank outside the half spectrum");
   fp.win = r.win; fp.skip = r.skip; fp.nfft = r.nfft; fp.P = r.P;
   char* ws = (char*)workspace;

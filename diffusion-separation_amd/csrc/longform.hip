@@ -9,7 +9,7 @@
 // A separator emits its sources in an arbitrary order per window, so the stitch aligns before it cross-fades.  Three launches,
 // asynchronous, no readback; the kernels recompute the plan from (T, Tw, Tv, K), no table is uploaded:
 //   lf_gram_kernel   per pair k and block: partial sums of C_k[i][j] = sum over the overlap of win[k][i] win[k + 1][j]; every
-//                    product of two floats is exact in float64, the sums are float64 in a fixed order (no atomics)
+//                    product of two floats is exact in float64, the sums are float64 in the fixed order of reduce_device.h
 //   lf_perm_kernel   one block: finishes the sums (block partials in order), then one thread walks the pairs: r_k = the
 //                    permutation of largest sum_i C_k[i][r(i)] (lexicographic order, strict >: a tie keeps the earliest, the
 //                    identity among them), g_0 = identity, g_{k+1}[i] = r_k[g_k[i]]; perm_out[k] = g_k
@@ -19,6 +19,7 @@
 
 #include "../../include/diffsep_hip.h"
 #include "common.h"
+#include "reduce_device.h"  // the fixed-order fp64 block totals of the cross-Gram partials
 
 namespace {
 
@@ -70,10 +71,10 @@ __device__ inline int lf_perm_entry(int S, int p, int i) {  // entry i of the p-
 }
 
 // part[pair][blk][S][S]: block blk of pair sums its contiguous share of the overlap, thread t the samples t, t + 256, ... of it,
-// then the 64 lanes of a wave (butterfly), then the 4 waves in order.  grid ((K - 1) kLfBlocks), 256 threads
+// then the block totals in the fixed order of reduce_device.h.  grid ((K - 1) kLfBlocks), 256 threads
 template <int S>
 __global__ __launch_bounds__(256) void lf_gram_kernel(const float* __restrict__ win, double* __restrict__ part, LfPlan p) {
-  __shared__ double sh[4][S * S];
+  __shared__ double sh[S * S][4];
   const int pair = blockIdx.x / kLfBlocks, blk = blockIdx.x % kLfBlocks;
   const long ov = lf_overlap(p, pair);
   const long share = (ov + kLfBlocks - 1) / kLfBlocks;
@@ -96,15 +97,8 @@ __global__ __launch_bounds__(256) void lf_gram_kernel(const float* __restrict__ 
 #pragma unroll
       for (int q = 0; q < S; ++q) acc[i * S + q] += av[i] * bv[q];
   }
-#pragma unroll
-  for (int e = 0; e < S * S; ++e) {
-    const double v = wave_sum_d(acc[e]);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][e] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < S * S)
-    part[((long)pair * kLfBlocks + blk) * (S * S) + threadIdx.x] =
-        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+  const double r = ds_block_totals_d<4, S * S>(acc, S * S, sh);
+  if (threadIdx.x < S * S) part[((long)pair * kLfBlocks + blk) * (S * S) + threadIdx.x] = r;
 }
 
 // cmat[pair][S][S] (and gram_out) = the block partials summed in order; then thread 0 chains the permutations.  grid (1), 256 threads

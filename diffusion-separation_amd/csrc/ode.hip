@@ -7,8 +7,8 @@
 // One thread item = V consecutive time indices of one utterance x all sources (the drift couples the sources through
 // their mean): ode_item is what every pass computes for it, with float4 / 2 x double2 accesses when the rows allow it.
 // Two kernels walk the items — the whole batch as one system (ode_stage_kernel) and one system per utterance of a
-// zero-padded batch (ode_stage_each_kernel) — and share the item body, the block-partials tail and the final tree, so
-// that what an utterance computes is the same code whichever entry it came through.
+// zero-padded batch (ode_stage_each_kernel) — and share the item body, the block-partials tail and the final tree (both
+// in the fixed order of reduce_device.h), so that what an utterance computes is the same code whichever entry it came through.
 // Contraction is off in this file: every sum and product rounds on its own, like numpy's, so that the stage inputs
 // can be reproduced bit for bit in float64 on the host (tests/test_ode_gpu.py).
 #include <string.h>
@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "reduce_device.h"  // the fixed-order fp64 block totals of the error norms
 #include "../../include/diffsep_hip.h"
 
 #pragma clang fp contract(off)
@@ -149,40 +150,23 @@ __device__ inline void ode_item(const OdeArgs& a, int b, long t0, float t_eval, 
   }
 }
 
-// per-block partials of a mode-3 pass, fixed order (no float atomics): wave butterfly, then the 4 waves in order, then
-// part[2 blk + q].  Every thread of the block calls it.
+// per-block partials of a mode-3 pass in the fixed order of reduce_device.h (no float atomics) -> part[2 blk + q].
+// Every thread of the block calls it.
 __device__ inline void ode_block_partials(double q0, double q1, double* part) {
   __shared__ double sh[2][4];
-  q0 = wave_sum_d(q0);
-  q1 = wave_sum_d(q1);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { sh[0][w] = q0; sh[1][w] = q1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r0 = 0.0, r1 = 0.0;
-    for (int i = 0; i < 4; ++i) { r0 = r0 + sh[0][i]; r1 = r1 + sh[1][i]; }
-    part[2 * blockIdx.x] = r0;
-    part[2 * blockIdx.x + 1] = r1;
-  }
+  const double q[2] = {q0, q1};
+  const double r = ds_block_totals_d<4, 2>(q, 2, sh);
+  if (threadIdx.x < 2) part[2 * blockIdx.x + threadIdx.x] = r;
 }
 
-// the final tree of one block over nblk partials: strided sums, wave sums, the 4 waves in order;
+// the final tree of one block over nblk partials: strided sums, then the block total in the same order;
 // out[q] = sqrt(sum) / sqrt(n)   (common.norm: ||x||_2 / sqrt(x.size))
 __device__ inline void ode_norm_tree(const double* __restrict__ part, int nblk, long n, double* __restrict__ out) {
   __shared__ double sh[2][4];
   double r[2] = {0.0, 0.0};
   for (int i = threadIdx.x; i < nblk; i += 256) { r[0] = r[0] + part[2 * i]; r[1] = r[1] + part[2 * i + 1]; }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int q = 0; q < 2; ++q) {
-    const double v = wave_sum_d(r[q]);
-    if (lane == 0) sh[q][w] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    double s = 0.0;
-    for (int i = 0; i < 4; ++i) s = s + sh[threadIdx.x][i];
-    out[threadIdx.x] = sqrt(s) / sqrt((double)n);
-  }
+  const double s = ds_block_totals_d<4, 2>(r, 2, sh);
+  if (threadIdx.x < 2) out[threadIdx.x] = sqrt(s) / sqrt((double)n);
 }
 
 // the whole batch as one system: items of all utterances in one sequence, grid-stride over a capped grid

@@ -9,6 +9,7 @@
 // One thread owns all S sources of 4 consecutive samples, whatever the alignment (128-bit accesses when T % 4 == 0 and the
 // pointers allow, scalar otherwise): the order of every sum depends on the sample index alone.
 #include "engine_host.h"
+#include "reduce_device.h"  // the fixed-order fp64 block totals of the loss partials and the finishing pass
 
 // per-sample arithmetic is plain fp32 in the order written: the float64 restatement of the tests (tests/score_loss_cases.py)
 // follows it operation by operation, which a fused multiply-add here and not there would break
@@ -235,20 +236,9 @@ __global__ __launch_bounds__(256) void score_loss_partial_kernel(LossArgs a) {
       }
     }
   }
-  // per-block partials in a fixed order (no float atomics): wave butterfly, then the 4 waves in order
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int p = 0; p < SL_MAX_P; ++p) {
-    if (p >= a.P) break;
-    const double v = wave_sum_d(acc[p]);
-    if (lane == 0) sh[p][w] = v;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < a.P) {
-    double r = 0.0;
-    for (int i = 0; i < 4; ++i) r = r + sh[threadIdx.x][i];
-    a.part[((long)b * gridDim.x + blockIdx.x) * SL_MAX_P + threadIdx.x] = r;
-  }
+  // per-block partials in the fixed order of reduce_device.h (no float atomics)
+  const double r = ds_block_totals_d<4, SL_MAX_P>(acc, a.P, sh);
+  if ((int)threadIdx.x < a.P) a.part[((long)b * gridDim.x + blockIdx.x) * SL_MAX_P + threadIdx.x] = r;
 }
 
 // one finishing block per utterance: partials in a fixed order, the mean, the best permutation (first minimum)
@@ -259,17 +249,14 @@ __global__ __launch_bounds__(256) void score_loss_final_kernel(const double* __r
   __shared__ double sh[SL_MAX_P][4];
   __shared__ double tot[SL_MAX_P];
   const int b = blockIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int p = 0; p < P; ++p) {
-    double r = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) r = r + part[((long)b * nblk + i) * SL_MAX_P + p];
-    r = wave_sum_d(r);
-    if (lane == 0) sh[p][w] = r;
+  double r[SL_MAX_P] = {};
+#pragma unroll
+  for (int p = 0; p < SL_MAX_P; ++p) {
+    if (p >= P) break;
+    for (int i = threadIdx.x; i < nblk; i += 256) r[p] = r[p] + part[((long)b * nblk + i) * SL_MAX_P + p];
   }
-  __syncthreads();
+  double s = ds_block_totals_d<4, SL_MAX_P>(r, P, sh);
   if ((int)threadIdx.x < P) {
-    double s = 0.0;
-    for (int i = 0; i < 4; ++i) s = s + sh[threadIdx.x][i];
     const long len = lens ? max(0L, min((long)lens[b], T)) : T;  // (as the partial pass clamps; an empty row scores 0)
     s = len > 0 ? s / ((double)S * (double)len) : 0.0;
     tot[threadIdx.x] = s;

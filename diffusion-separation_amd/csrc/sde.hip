@@ -7,6 +7,7 @@
 //   L   = sqrt(ev1) A + sqrt(ev2) P                                                      sdes.py:315-320
 //   g(t)= smin r^t sqrt(2 ln r);  G = g sqrt(dt), dt = 1/N (quirk Q1)                     sdes.py:275-284, 93-107
 #include "common.h"
+#include "reduce_device.h"  // the fixed-order fp64 block sums of the Langevin norms, normalize, scale_output and the Gram matrices
 
 // (mix_eig: the eigenvalues ev1, ev2 of the perturbation covariance, common.h)
 // PriorMixSDE._std_sigma_mix  sdes.py:477-489: 0.5 * sqrt(clamp(avg_pool1d(mix^2, k, stride 1, pad k/2), 1e-4)),
@@ -322,19 +323,9 @@ __global__ __launch_bounds__(1024) void batch_norm2_kernel(const float* __restri
     a += u * u;
     c += v * v;
   }
-  a = wave_sum_d(a);
-  c = wave_sum_d(c);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) sh[w] = a;
-  __syncthreads();
-  double ta = 0.0;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) ta += sh[i];
-  __syncthreads();
-  if (lane == 0) sh[w] = c;
-  __syncthreads();
-  double tc = 0.0;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) tc += sh[i];
-  if (threadIdx.x == 0) { out[2 * b] = sqrt(ta); out[2 * b + 1] = sqrt(tc); }
+  a = ds_block_sum_d<16>(a, sh);
+  c = ds_block_sum_d<16>(c, sh);
+  if (threadIdx.x == 0) { out[2 * b] = sqrt(a); out[2 * b + 1] = sqrt(c); }
 }
 __global__ void langevin_step_kernel(const double* __restrict__ norms, int B, float snr, float* __restrict__ step) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -370,19 +361,6 @@ int ds_launch_langevin(float snr, const float* x, const float* score, const floa
   return 0;
 }
 
-// ------------------------------------------------------------------ block reductions (fp64)
-__device__ inline double block_sum_d(double v, double* sh) {
-  v = wave_sum_d(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[w] = v;
-  __syncthreads();
-  double r = 0.0;
-  const int nw = (blockDim.x + 63) >> 6;
-  for (int i = 0; i < nw; ++i) r += sh[i];
-  return r;
-}
-
 // normalize_batch  pl_model.py:81-88: (mix - mean) / clamp(std_unbiased, 1e-5) over (chan=1, time)
 __global__ __launch_bounds__(1024) void normalize_kernel(const float* __restrict__ mix, float* __restrict__ out,
                                                          float* __restrict__ mean_o, float* __restrict__ std_o,
@@ -392,13 +370,13 @@ __global__ __launch_bounds__(1024) void normalize_kernel(const float* __restrict
   const float* m = mix + (long)b * T;
   double s = 0.0;
   for (long i = threadIdx.x; i < T; i += blockDim.x) s += (double)m[i];
-  const double mean = block_sum_d(s, sh) / (double)T;
+  const double mean = ds_block_sum_d<16>(s, sh) / (double)T;
   double q = 0.0;
   for (long i = threadIdx.x; i < T; i += blockDim.x) {
     const double d = (double)m[i] - mean;
     q += d * d;
   }
-  const double var = block_sum_d(q, sh) / (double)(T > 1 ? T - 1 : 1);
+  const double var = ds_block_sum_d<16>(q, sh) / (double)(T > 1 ? T - 1 : 1);
   float sd = (float)sqrt(var);
   if (sd < 1e-5f) sd = 1e-5f;
   const float mu = (float)mean;
@@ -427,8 +405,8 @@ __global__ __launch_bounds__(1024) void scale_output_kernel(const float* __restr
     num += (double)m[i] * v;
     den += v * v + 1e-10;
   }
-  num = block_sum_d(num, sh);
-  den = block_sum_d(den, sh);
+  num = ds_block_sum_d<16>(num, sh);
+  den = ds_block_sum_d<16>(den, sh);
   const float alpha = (float)(num / den);
   for (long i = threadIdx.x; i < T; i += blockDim.x) x[i] = alpha * x[i];
 }
@@ -464,19 +442,11 @@ __global__ __launch_bounds__(1024) void gram_kernel(const float* __restrict__ re
         acc[(2 * DS_MAX_SRC + a) * DS_MAX_SRC + c] += e[a] * e[c];
       }
   }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int m = 0; m < 3; ++m)
     for (int a = 0; a < S; ++a)
       for (int c = 0; c < S; ++c) {
-        double v = wave_sum_d(acc[(m * DS_MAX_SRC + a) * DS_MAX_SRC + c]);
-        __syncthreads();
-        if (lane == 0) sh[w] = v;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-          double t = 0.0;
-          for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-          out[(((long)b * 3 + m) * S + a) * S + c] = t;
-        }
+        const double t = ds_block_sum_d<16>(acc[(m * DS_MAX_SRC + a) * DS_MAX_SRC + c], sh);
+        if (threadIdx.x == 0) out[(((long)b * 3 + m) * S + a) * S + c] = t;
       }
 }
 int ds_launch_gram(const float* ref, const float* est, double* out, int B, int S, long T, hipStream_t st) {

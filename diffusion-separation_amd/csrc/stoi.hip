@@ -20,15 +20,15 @@
 //                         give exactly zero bands), power summed over the bins of each band, sqrt
 //   stoi_segment_kernel   per 30-frame segment: the ESTOI / STOI term
 //   stoi_final_kernel     per pair: sum over segments in a fixed order, the 1e-5 sentinel below 30 frames
-// Every reduction has a fixed order that depends on the pair's own length only (no floating-point atomics): row (b, i) of a
-// batch equals the B = 1 call bit for bit, on any stream.
+// Every reduction has a fixed order that depends on the pair's own length only (reduce_device.h; no floating-point atomics):
+// row (b, i) of a batch equals the B = 1 call bit for bit, on any stream.  Pair addressing, workspace carving, the table cache
+// and the boundary checks are those of every measure on pairs: pair_metrics.h.
 #include <cmath>
-#include <map>
-#include <mutex>
-#include <vector>
 
 #include "../../include/diffsep_hip.h"
 #include "common.h"
+#include "pair_metrics.h"
+#include "reduce_device.h"
 
 namespace {
 
@@ -83,15 +83,14 @@ bool stoi_layout(int B, int S, int64_t T, const Ratio& r, StoiLayout* l) {
   if (l->nmax >= ((int64_t)1 << 31) - 4096) return false;
   l->fmax = stoi_frames(l->nmax);
   const int64_t fm = l->fmax > 0 ? l->fmax : 1;
-  auto up = [](int64_t v) { return (v + 255) / 256 * 256; };
-  int64_t o = 0;
-  l->off_xr = o;     o += up(l->P * 2 * l->nmax * 8);
-  l->off_energy = o; o += up(l->P * fm * 8);
-  l->off_kidx = o;   o += up(l->P * fm * 4);
-  l->off_nkeep = o;  o += up(l->P * 4);
-  l->off_bands = o;  o += up(l->P * 2 * fm * kBands * 8);
-  l->off_seg = o;    o += up(l->P * fm * 8);
-  l->total = o;
+  DsCarver ws;
+  l->off_xr = ws.take(l->P * 2 * l->nmax * 8);
+  l->off_energy = ws.take(l->P * fm * 8);
+  l->off_kidx = ws.take(l->P * fm * 4);
+  l->off_nkeep = ws.take(l->P * 4);
+  l->off_bands = ws.take(l->P * 2 * fm * kBands * 8);
+  l->off_seg = ws.take(l->P * fm * 8);
+  l->total = ws.total;
   return true;
 }
 
@@ -99,17 +98,9 @@ bool stoi_layout(int B, int S, int64_t T, const Ratio& r, StoiLayout* l) {
 // device doubles: hann[256] | cos(2 pi j / 512), j < 256 | -sin(2 pi j / 512), j < 256 | taps h[2 L + 1] (scaled by p)
 constexpr int kTabHann = 0, kTabCos = 256, kTabSin = 512, kTabTaps = 768;
 
-int stoi_table(const Ratio& r, const double** out) {
-  static std::mutex mu;
-  static std::map<std::pair<int, std::pair<int, int>>, double*> cache;
-  int dev = 0;
-  DS_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> g(mu);
-  auto key = std::make_pair(dev, std::make_pair(r.p, r.q));
-  auto it = cache.find(key);
-  if (it != cache.end()) { *out = it->second; return 0; }
+void stoi_build_table(const Ratio& r, std::vector<double>& t) {
   const double pi = 3.14159265358979323846;
-  std::vector<double> t(kTabTaps + 2 * r.L + 1);
+  t.assign(kTabTaps + 2 * r.L + 1, 0.0);
   for (int k = 0; k < kNw; ++k) t[kTabHann + k] = 0.5 * (1.0 - std::cos(2.0 * pi * (k + 1) / (kNw + 1)));  // Matlab hanning(256)
   for (int j = 0; j < kNfft / 2; ++j) {
     t[kTabCos + j] = std::cos(2.0 * pi * j / kNfft);
@@ -130,32 +121,13 @@ int stoi_table(const Ratio& r, const double** out) {
   } else {
     t[kTabTaps] = 1.0;
   }
-  double* d = nullptr;
-  DS_HIP(hipMalloc(&d, t.size() * sizeof(double)));
-  DS_HIP(hipMemcpy(d, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
-  cache[key] = d;
-  *out = d;
-  return 0;
 }
 
 struct StoiBandsP { int lo[kBands], hi[kBands]; };
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
-__device__ inline int stoi_len(const int* lengths, int b, long T) {
-  long n = lengths ? (long)lengths[b] : T;
-  return (int)(n < 0 ? 0 : (n > T ? T : n));
-}
 __device__ inline long stoi_nout(int len, int p, int q) { return ((long)len * p + q - 1) / q; }
 __device__ inline int stoi_nframes(long n) { return n > kNw ? (int)((n - kNw + kHop - 1) / kHop) : 0; }
-
-// fixed-order sum over a 256-thread block: butterfly inside each wave, then the 4 wave totals in order
-__device__ inline double stoi_block_sum(double v, double* sh4) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh4[0] + sh4[1]) + sh4[2]) + sh4[3];
-}
 
 // y[m] = sum_j h[m q + L - p j] x[j]: the zero-stuffed direct form, centred, n_out = ceil(len p / q).
 // grid (ceil(nmax / 256), 2, P); xr [P][2][nmax]
@@ -163,16 +135,11 @@ __global__ __launch_bounds__(256) void stoi_resample_kernel(const float* __restr
                                                             const int* __restrict__ lengths, const int* __restrict__ perm,
                                                             const double* __restrict__ taps, double* __restrict__ xr, int S,
                                                             long T, long nmax, int p, int q, int L) {
-  const int pair = blockIdx.z, sig = blockIdx.y, b = pair / S, i = pair % S;
-  const int len = stoi_len(lengths, b, T);
+  const int pair = blockIdx.z, sig = blockIdx.y;
+  const int len = ds_pair_len(lengths, pair / S, T);
   const long m = (long)blockIdx.x * 256 + threadIdx.x;
   if (m >= stoi_nout(len, p, q)) return;
-  int row = i;
-  if (sig == 1 && perm) {
-    row = perm[pair];
-    row = row < 0 ? 0 : (row >= S ? S - 1 : row);
-  }
-  const float* x = (sig == 0 ? ref : est) + ((long)b * S + row) * T;
+  const float* x = ds_pair_row(ref, est, perm, pair, sig, S, T);
   const long c = m * q + L, a = c - 2 * (long)L;
   long jlo = a > 0 ? (a + p - 1) / p : 0, jhi = c / p;
   if (jhi > len - 1) jhi = len - 1;
@@ -187,10 +154,10 @@ __global__ __launch_bounds__(256) void stoi_energy_kernel(const double* __restri
                                                           long T, long nmax, long fcap, int p, int q) {
   __shared__ double sh4[4];
   const int pair = blockIdx.y, f = blockIdx.x;
-  const int nfr = stoi_nframes(stoi_nout(stoi_len(lengths, pair / S, T), p, q));
+  const int nfr = stoi_nframes(stoi_nout(ds_pair_len(lengths, pair / S, T), p, q));
   if (f >= nfr) return;
   const double v = tab[kTabHann + threadIdx.x] * xr[(long)pair * 2 * nmax + (long)f * kHop + threadIdx.x];
-  const double s = stoi_block_sum(v * v, sh4);
+  const double s = ds_block_sum_d<4>(v * v, sh4);
   if (threadIdx.x == 0) energy[(long)pair * fcap + f] = 20.0 * log10(sqrt(s) + kEps);
 }
 
@@ -201,7 +168,7 @@ __global__ __launch_bounds__(256) void stoi_keep_kernel(const double* __restrict
   __shared__ double shmax[256];
   __shared__ int shcnt[256];
   const int pair = blockIdx.x, t = threadIdx.x;
-  const int nfr = stoi_nframes(stoi_nout(stoi_len(lengths, pair / S, T), p, q));
+  const int nfr = stoi_nframes(stoi_nout(ds_pair_len(lengths, pair / S, T), p, q));
   const double* e = energy + (long)pair * fcap;
   const int chunk = (nfr + 255) / 256, f0 = t * chunk, f1 = min(nfr, f0 + chunk);
   double mx = -1e300;
@@ -370,7 +337,7 @@ __global__ __launch_bounds__(256) void stoi_final_kernel(const double* __restric
   const int nseg = M - kSeg + 1;
   double part = 0.0;
   for (int g = threadIdx.x; g < nseg; g += 256) part += segval[(long)pair * fcap + g];
-  const double s = stoi_block_sum(part, sh4);
+  const double s = ds_block_sum_d<4>(part, sh4);
   if (threadIdx.x == 0) out[pair] = extended ? s / nseg : s / ((double)nseg * kBands);
 }
 
@@ -396,15 +363,13 @@ extern "C" int32_t diffsep_stoi(const float* ref, const float* est, double* out,
                                 int64_t workspace_bytes, void* stream) {
   Ratio r;
   StoiLayout l;
-  DS_CHECK(ref && est && out && workspace, "stoi: null pointer");
   DS_CHECK(stoi_ratio(fs, &r), "stoi: unsupported sample rate " + std::to_string(fs));
   DS_CHECK(stoi_layout(B, S, T, r, &l), "stoi: bad shape B=" + std::to_string(B) + " S=" + std::to_string(S) + " T=" + std::to_string(T));
-  DS_CHECK(l.P <= 65535, "stoi: more than 65535 (utterance, source) pairs in one call");
-  DS_CHECK(workspace_bytes >= l.total, "stoi: workspace too small (" + std::to_string(workspace_bytes) + " < " + std::to_string(l.total) + " bytes)");
-  DS_CHECK(((uintptr_t)workspace & 7) == 0, "stoi: workspace must be 8-byte aligned");
+  if (ds_pair_check("stoi", ref, est, out, workspace, workspace_bytes, l.P, l.total)) return 1;
   hipStream_t st = (hipStream_t)stream;
   const double* tab = nullptr;
-  if (stoi_table(r, &tab)) return 1;
+  DsNoExtra none;
+  if (ds_device_table({r.p, r.q}, [&](std::vector<double>& t, DsNoExtra&) { stoi_build_table(r, t); }, &tab, &none)) return 1;
   char* ws = (char*)workspace;
   double* xr = (double*)(ws + l.off_xr);
   double* energy = (double*)(ws + l.off_energy);

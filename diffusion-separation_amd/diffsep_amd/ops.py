@@ -545,8 +545,7 @@ def longform_stitch(win, T, Tv, want_gram=False, out=None):
     win = win.contiguous()
     K, S, Tw = win.shape
     l = lib()
-    nbytes = l.diffsep_longform_workspace_bytes(K, S)
-    check(0 if nbytes >= 0 else 1, l)
+    nbytes = _workspace_bytes(l.diffsep_longform_workspace_bytes, K, S)
     if out is None:
         out = torch.empty((S, int(T)), dtype=torch.float32, device=win.device)
     elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (S, int(T)) or out.device != win.device:
@@ -568,28 +567,40 @@ def _dev_i32(v, device):
     return h.pin_memory().to(device, non_blocking=True)
 
 
-def stoi_workspace_bytes(B, S, T, fs):
-    """bytes of workspace diffsep_stoi needs (host arithmetic; raises for a sample rate or shape it refuses)"""
-    n = lib().diffsep_stoi_workspace_bytes(int(B), int(S), int(T), int(fs))
+def _workspace_bytes(fn, *shape):
+    """what a *_workspace_bytes entry of the library answers for the shape, or the error it raises"""
+    n = fn(*(int(v) for v in shape))
     check(0 if n >= 0 else 1)
     return int(n)
+
+
+def _pair_call(name, ref, est, lengths, perm):
+    """a [B,S,T] pair call (estimate row perm[b][i] against reference row i over lengths[b] samples) validated:
+    -> (ref, est, B, S, T, lengths_dev, perm_dev), float32 contiguous / int32 device tensors or None"""
+    if ref.shape != est.shape or ref.dim() != 3:
+        raise ValueError(f"{name}: ref and est must be [B,S,T] tensors of one shape")
+    B, S, T = ref.shape
+    ref, est = ref.float().contiguous(), est.float().contiguous()
+    ln = None if lengths is None else _dev_i32(lengths, ref.device)
+    pm = None if perm is None else _dev_i32(perm, ref.device)
+    if ln is not None and ln.numel() != B:
+        raise ValueError(f"{name}: lengths must have B entries")
+    if pm is not None and tuple(pm.shape) != (B, S):
+        raise ValueError(f"{name}: perm must be [B,S]")
+    return ref, est, B, S, T, ln, pm
+
+
+def stoi_workspace_bytes(B, S, T, fs):
+    """bytes of workspace diffsep_stoi needs (host arithmetic; raises for a sample rate or shape it refuses)"""
+    return _workspace_bytes(lib().diffsep_stoi_workspace_bytes, B, S, T, fs)
 
 
 def stoi(ref, est, fs, extended=True, lengths=None, perm=None):
     """STOI (extended: ESTOI) of every source of a zero-padded batch on the device: ref, est [B,S,T] float32 device tensors ->
     float64 [B,S] device tensor; estimate row perm[b][i] (default i) against reference row i over the first lengths[b]
     (default T) samples.  The algorithm of metrics.stoi in float64 (csrc/stoi.hip); asynchronous on the current stream."""
-    if ref.shape != est.shape or ref.dim() != 3:
-        raise ValueError("stoi: ref and est must be [B,S,T] tensors of one shape")
-    B, S, T = ref.shape
-    ref, est = ref.float().contiguous(), est.float().contiguous()
+    ref, est, B, S, T, ln, pm = _pair_call("stoi", ref, est, lengths, perm)
     nbytes = stoi_workspace_bytes(B, S, T, fs)
-    ln = None if lengths is None else _dev_i32(lengths, ref.device)
-    pm = None if perm is None else _dev_i32(perm, ref.device)
-    if ln is not None and ln.numel() != B:
-        raise ValueError("stoi: lengths must have B entries")
-    if pm is not None and tuple(pm.shape) != (B, S):
-        raise ValueError("stoi: perm must be [B,S]")
     out = torch.empty((B, S), dtype=torch.float64, device=ref.device)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=ref.device)
     check(lib().diffsep_stoi(_ptr(ref), _ptr(est), _ptr(out), B, S, T, _ptr(ln), _ptr(pm), int(fs), int(bool(extended)),
@@ -599,9 +610,7 @@ def stoi(ref, est, fs, extended=True, lengths=None, perm=None):
 
 def composite_workspace_bytes(B, S, T, fs):
     """bytes of workspace diffsep_composite needs (host arithmetic; raises for a sample rate or shape it refuses)"""
-    n = lib().diffsep_composite_workspace_bytes(int(B), int(S), int(T), int(fs))
-    check(0 if n >= 0 else 1)
-    return int(n)
+    return _workspace_bytes(lib().diffsep_composite_workspace_bytes, B, S, T, fs)
 
 
 def composite(ref, est, fs=16000, lengths=None, perm=None, frames=False):
@@ -610,23 +619,14 @@ def composite(ref, est, fs=16000, lengths=None, perm=None, frames=False):
     row perm[b][i] (default i) against reference row i over the first lengths[b] (default T) samples.  frames=True: also the
     per-frame values, float64 [B,S,3,F] {llr, wss, segsnr} in frame order with F = the frame count of T (NaN beyond a row's
     own count).  The algorithm of metrics.composite in float64 (csrc/composite.hip); asynchronous on the current stream."""
-    if ref.shape != est.shape or ref.dim() != 3:
-        raise ValueError("composite: ref and est must be [B,S,T] tensors of one shape")
-    B, S, T = ref.shape
-    ref, est = ref.float().contiguous(), est.float().contiguous()
+    ref, est, B, S, T, ln, pm = _pair_call("composite", ref, est, lengths, perm)
     nbytes = composite_workspace_bytes(B, S, T, fs)
-    ln = None if lengths is None else _dev_i32(lengths, ref.device)
-    pm = None if perm is None else _dev_i32(perm, ref.device)
-    if ln is not None and ln.numel() != B:
-        raise ValueError("composite: lengths must have B entries")
-    if pm is not None and tuple(pm.shape) != (B, S):
-        raise ValueError("composite: perm must be [B,S]")
     out = torch.empty((B, S, 4), dtype=torch.float64, device=ref.device)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=ref.device)
     fr, cap = None, 0
     if frames:
-        win = int(round(30 * int(fs) / 1000))
-        cap = max(1, (T - win) // (win // 4))
+        from . import metrics  # (metrics imports this module: resolved at the call, no cycle)
+        cap = max(1, metrics.composite_num_frames(T, fs))
         fr = torch.full((B, S, 3, cap), float("nan"), dtype=torch.float64, device=ref.device)
     check(lib().diffsep_composite(_ptr(ref), _ptr(est), _ptr(out), _ptr(fr), cap, B, S, T, _ptr(ln), _ptr(pm), int(fs),
                                   _ptr(ws), nbytes, _stream_ptr()))
@@ -660,9 +660,7 @@ def sde_perturb(sde, x0, mix, t, z=None, sigma_mix=None, beta=None, redefine_z=F
 
 def score_loss_workspace_bytes(B, S, T):
     """bytes of workspace the loss entries need (host arithmetic; raises for a shape they refuse)"""
-    n = lib().diffsep_score_loss_workspace_bytes(int(B), int(S), int(T))
-    check(0 if n >= 0 else 1)
-    return int(n)
+    return _workspace_bytes(lib().diffsep_score_loss_workspace_bytes, B, S, T)
 
 
 def score_loss_reduce(sde, score, z, t, x0=None, mix=None, sigma_mix=None, lengths=None, pit=None, want_coef=False):
