@@ -15,6 +15,8 @@ F16 = 3        # Python-side only: dtype code 1 (16-bit storage) of the half-pre
 SDE_MIX, SDE_PRIORMIX = 0, 1
 PRED_REVERSE_DIFFUSION, PRED_EULER_MARUYAMA, PRED_NONE = 0, 1, 2
 CORR_ALD2, CORR_NONE, CORR_ALD, CORR_LANGEVIN = 0, 1, 2, 3
+PREDICTORS = {"reverse_diffusion": PRED_REVERSE_DIFFUSION, "euler_maruyama": PRED_EULER_MARUYAMA, "none": PRED_NONE}
+CORRECTORS = {"ald2": CORR_ALD2, "none": CORR_NONE, "ald": CORR_ALD, "langevin": CORR_LANGEVIN}
 
 
 class ModelConfig(C.Structure):
@@ -78,6 +80,33 @@ class ProfRecord(C.Structure):  # diffsep_prof_record
 
 class DiffsepError(RuntimeError):
     pass
+
+
+# ---- marshalling shared by engine.py and ops.py: what a C argument is made of, each once
+def _stream_ptr(device=None):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def sde_config(d):
+    """dict(kind, ndim, d_lambda, sigma_min, sigma_max[, avg_len]) -> SdeConfig"""
+    return SdeConfig(d.get("kind", SDE_MIX), d["ndim"], d["d_lambda"], d["sigma_min"], d["sigma_max"], d.get("avg_len", 0))
+
+
+def host_array(values, dtype, n, what):
+    """(contiguous numpy array [n] of dtype, its typed pointer) for a `*_host` argument; the caller keeps the array alive"""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(values, dtype=dtype))
+    assert a.shape == (n,), f"{what} must be [B]"
+    return a, a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+
+
+def ode_info_dict(info):
+    return dict(nfev=info.nfev, n_accepted=info.n_accepted, n_rejected=info.n_rejected, status=info.status, t_final=info.t_final)
 
 
 _lib = None
@@ -224,6 +253,11 @@ def check(rc, l=None):
         raise DiffsepError((l or lib()).diffsep_last_error().decode("utf-8", "replace"))
 
 
+def call(L, name, *args):
+    """L.<name>(*args), then check() against L itself: the error text always comes from the library that was called"""
+    check(getattr(L, name)(*args), L)
+
+
 def half_kind(dtype_code):
     """storage variant of a dtype code: F16 lives in the half-precision build, everything else in the default one"""
     return "f16" if dtype_code == F16 else "bf16"
@@ -247,9 +281,8 @@ def ode_tableau(method="RK45"):
     l = lib()
     code = ODE_METHODS[method]
     ns, eo = C.c_int32(), C.c_int32()
-    check(l.diffsep_ode_tableau(code, None, None, None, None, C.byref(ns), C.byref(eo)), l)
+    call(l, "diffsep_ode_tableau", code, None, None, None, None, C.byref(ns), C.byref(eo))
     n = ns.value
     A, B, Cc, E = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros(n + 1)
-    check(l.diffsep_ode_tableau(code, A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
-                                Cc.ctypes.data_as(C.c_void_p), E.ctypes.data_as(C.c_void_p), None, None), l)
+    call(l, "diffsep_ode_tableau", code, *(a.ctypes.data_as(C.c_void_p) for a in (A, B, Cc, E)), None, None)
     return A, B, Cc, E, n, eo.value

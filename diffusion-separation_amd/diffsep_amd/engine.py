@@ -9,15 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import F32, BF16, F16, check, lib
-
-
-def _stream_ptr(device=None):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+from ._lib import F32, BF16, F16, _ptr, _stream_ptr, call, check, lib
 
 
 def _c_cfg(cfg):
@@ -43,7 +35,7 @@ def param_table(cfg):
     ndim = C.c_int32()
     off = C.c_int64()
     for i in range(n):
-        check(l.diffsep_param_info(C.byref(cfg), i, name, 256, shape, C.byref(ndim), C.byref(off)))
+        call(l, "diffsep_param_info", C.byref(cfg), i, name, 256, shape, C.byref(ndim), C.byref(off))
         out.append((name.value.decode(), tuple(int(shape[k]) for k in range(ndim.value)), int(off.value)))
     return out
 
@@ -84,8 +76,7 @@ class Engine:
         blob = np.ascontiguousarray(weights_blob, dtype=np.float32)
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
-            check(self._L.diffsep_engine_create(C.byref(cfg), blob.ctypes.data_as(C.c_void_p), blob.size,
-                                                C.byref(self._h)), self._L)
+            call(self._L, "diffsep_engine_create", C.byref(cfg), blob.ctypes.data_as(C.c_void_p), blob.size, C.byref(self._h))
         self.S = cfg.num_sources
 
     def close(self):
@@ -107,7 +98,7 @@ class Engine:
         return int(self._L.diffsep_engine_device_bytes(self._h))
 
     def set_graph(self, enable):
-        check(self._L.diffsep_engine_set_graph(self._h, int(bool(enable))), self._L)
+        call(self._L, "diffsep_engine_set_graph", self._h, int(bool(enable)))
 
     def set_option(self, name, value):
         """diffsep_engine_set_option.  Kernel-dispatch switches (0 / 1; A/B and test aids, the defaults are what ships; the
@@ -117,7 +108,7 @@ class Engine:
         geometry of the register-weight kernel: "rw_half", "rw_quarter", "rw_big_half" ("no_stft_fused" is a process
         default only: diffsep_set_option).  Others: "graph_cache" (captured graphs kept, LRU), "ablate" (measurement aid),
         "track_tensors", "dbg_alloc".  Synchronises the device, drops the captured graphs."""
-        check(self._L.diffsep_engine_set_option(self._h, str(name).encode(), int(value)), self._L)
+        call(self._L, "diffsep_engine_set_option", self._h, str(name).encode(), int(value))
 
     def get_option(self, name):
         return int(self._L.diffsep_engine_get_option(self._h, str(name).encode()))
@@ -127,7 +118,7 @@ class Engine:
                     "conv3x3_sw_streamed", "conv3x3_sws_split")
 
     def profile_begin(self):
-        check(self._L.diffsep_engine_profile_begin(self._h), self._L)
+        call(self._L, "diffsep_engine_profile_begin", self._h)
 
     def profile_end(self):
         """{class: (algorithmic flops, milliseconds, launches, algorithmic bytes)} of the MFMA kernels since
@@ -135,17 +126,16 @@ class Engine:
         nc = len(self.CONV_CLASSES)
         fl, ms, n, by = (C.c_double * nc)(), (C.c_double * nc)(), (C.c_int64 * nc)(), (C.c_double * nc)()
         nw = C.c_int32(0)
-        check(self._L.diffsep_engine_profile_end_n(self._h, nc, fl, ms, n, by, C.byref(nw)), self._L)
+        call(self._L, "diffsep_engine_profile_end_n", self._h, nc, fl, ms, n, by, C.byref(nw))
         return {k: (fl[i], ms[i], int(n[i]), by[i]) for i, k in enumerate(self.CONV_CLASSES[:nw.value])}
 
     def profile_records(self):
         """The launches of the last profile_begin .. profile_end span, one dict per launch: kernel instantiation (real
         template arguments), shape, algorithmic flops / bytes, milliseconds."""
-        from ._lib import ProfRecord
         n = C.c_int32(0)
-        check(self._L.diffsep_engine_profile_records(self._h, None, 0, C.byref(n)), self._L)
-        buf = (ProfRecord * max(1, n.value))()
-        check(self._L.diffsep_engine_profile_records(self._h, buf, n.value, C.byref(n)), self._L)
+        call(self._L, "diffsep_engine_profile_records", self._h, None, 0, C.byref(n))
+        buf = (_lib.ProfRecord * max(1, n.value))()
+        call(self._L, "diffsep_engine_profile_records", self._h, buf, n.value, C.byref(n))
         return [dict(kernel=r.kernel.decode(), B=r.B, H=r.H, W=r.W, Cin=r.Cin, Cout=r.Cout, taps=r.taps,
                      skip_cin=r.skip_cin, has_res=bool(r.has_res), cls=r.cls, flops=r.flops, bytes=r.bytes, ms=r.ms)
                 for r in buf[:n.value]]
@@ -170,29 +160,29 @@ class Engine:
         assert S == self.S and mix.shape == (B, 1, T) and t.shape == (B,)
         out = torch.empty_like(xt)
         with torch.cuda.device(self.device):
-            check(self._L.diffsep_score_forward(self._h, _ptr(xt), _ptr(t), _ptr(mix), _ptr(out), B, T,
-                                              _stream_ptr(self.device)), self._L)
+            call(self._L, "diffsep_score_forward", self._h, _ptr(xt), _ptr(t), _ptr(mix), _ptr(out), B, T,
+                 _stream_ptr(self.device))
         return out
 
     def reserve(self, B, T):
         """Size the workspace for batches of up to B x T samples now (later, smaller plans never reallocate)."""
         with torch.cuda.device(self.device):
-            check(self._L.diffsep_engine_reserve(self._h, int(B), int(T), _stream_ptr(self.device)), self._L)
+            call(self._L, "diffsep_engine_reserve", self._h, int(B), int(T), _stream_ptr(self.device))
 
     def debug_absmax(self):
         """[(max finite |value|, non-finite count, rows H, channels C)] of every activation tensor of the last eager forward
         (set_option("track_tensors", 1) first; score() is an eager forward).  Debug / test aid."""
         n = C.c_int32(0)
-        check(self._L.diffsep_engine_debug_absmax(self._h, None, 0, C.byref(n)), self._L)
+        call(self._L, "diffsep_engine_debug_absmax", self._h, None, 0, C.byref(n))
         buf = (C.c_double * (4 * max(1, n.value)))()
-        check(self._L.diffsep_engine_debug_absmax(self._h, buf, n.value, C.byref(n)), self._L)
+        call(self._L, "diffsep_engine_debug_absmax", self._h, buf, n.value, C.byref(n))
         return [(buf[4 * i], int(buf[4 * i + 1]), int(buf[4 * i + 2]), int(buf[4 * i + 3])) for i in range(n.value)]
 
     def debug_arena(self):
         """(uint8 view of the workspace arena, offset of the forward region): every intermediate tensor of the last
         forward, in launch order.  Debug / test aid."""
         base, nb, fb = C.c_void_p(), C.c_int64(), C.c_int64()
-        check(self._L.diffsep_engine_debug_arena(self._h, C.byref(base), C.byref(nb), C.byref(fb)), self._L)
+        call(self._L, "diffsep_engine_debug_arena", self._h, C.byref(base), C.byref(nb), C.byref(fb))
 
         class _Raw:
             __cuda_array_interface__ = {"shape": (nb.value,), "typestr": "|u1", "data": (base.value, False), "version": 2}
@@ -205,8 +195,8 @@ class Engine:
         cout = ((2 * self.S + 7) // 8) * 8
         y = torch.zeros((B, H, W, cout), dtype=x_nhwc.dtype, device=x_nhwc.device)
         with torch.cuda.device(self.device):
-            check(self._L.diffsep_backbone_forward(self._h, _ptr(x_nhwc.contiguous()), _ptr(t), _ptr(y), B, W,
-                                                 _stream_ptr(self.device)), self._L)
+            call(self._L, "diffsep_backbone_forward", self._h, _ptr(x_nhwc.contiguous()), _ptr(t), _ptr(y), B, W,
+                 _stream_ptr(self.device))
         return y
 
     def pc_sample(self, mix_norm, sde, N=30, corrector_steps=1, snr=0.5, eps=0.03, denoise=True,
@@ -221,13 +211,9 @@ class Engine:
         mix_norm = self._f32(mix_norm)
         B, one, T = mix_norm.shape
         assert one == 1
-        sc = _lib.SdeConfig(sde.get("kind", _lib.SDE_MIX), sde["ndim"], sde["d_lambda"], sde["sigma_min"],
-                            sde["sigma_max"], sde.get("avg_len", 0))
-        pred = {"reverse_diffusion": _lib.PRED_REVERSE_DIFFUSION, "euler_maruyama": _lib.PRED_EULER_MARUYAMA,
-                "none": _lib.PRED_NONE}[predictor]
-        corr = {"ald2": _lib.CORR_ALD2, "none": _lib.CORR_NONE, "ald": _lib.CORR_ALD,
-                "langevin": _lib.CORR_LANGEVIN}[corrector]
-        sm = _lib.SamplerConfig(N, corrector_steps, snr, eps, int(bool(denoise)), pred, corr)
+        sc = _lib.sde_config(sde)
+        sm = _lib.SamplerConfig(N, corrector_steps, snr, eps, int(bool(denoise)), _lib.PREDICTORS[predictor],
+                                _lib.CORRECTORS[corrector])
         out = torch.empty((B, self.S, T), dtype=torch.float32, device=mix_norm.device)
         if noise is not None:
             noise = self._f32(noise)
@@ -239,29 +225,22 @@ class Engine:
             ts = np.ascontiguousarray(timesteps, dtype=np.float32)
             assert ts.size >= N
         nfe = C.c_int32()
-        ext, keep = None, []
+        ext = None  # (la / sa below: the host arrays its pointers refer to, alive until this method returns)
         if lengths is not None or seeds is not None or (tail is not None and (tail_steps > 0 or head_steps > 0)):
             ext = _lib.SamplerExt()
             if lengths is not None:
-                la = np.ascontiguousarray(lengths, dtype=np.int64)
-                assert la.shape == (B,), "lengths must be [B]"
-                ext.lengths_host = la.ctypes.data_as(C.POINTER(C.c_int64))
-                keep.append(la)
+                la, ext.lengths_host = _lib.host_array(lengths, np.int64, B, "lengths")
             if seeds is not None:
-                sa = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
-                assert sa.shape == (B,), "seeds must be [B]"
-                ext.seeds_host = sa.ctypes.data_as(C.POINTER(C.c_uint64))
-                keep.append(sa)
+                sa, ext.seeds_host = _lib.host_array(seeds, np.uint64, B, "seeds")
             if tail is not None and (tail_steps > 0 or head_steps > 0):
                 if tail.kind != self.kind:  # an engine handle means something to the library that created it only
                     raise _lib.DiffsepError(f"the other engine was created by the '{tail.kind}' build of the library, this one "
                                             f"by the '{self.kind}' build: create it with Engine(..., lib_kind='{self.kind}')")
                 ext.tail_engine, ext.tail_steps, ext.head_steps = tail._h, int(tail_steps), int(head_steps)
         with torch.cuda.device(self.device):
-            check(self._L.diffsep_pc_sample_ex(self._h, C.byref(sc), C.byref(sm), C.byref(ext) if ext is not None else None,
-                                             _ptr(mix_norm), _ptr(out), B, T, _ptr(noise), seed,
-                                             ts.ctypes.data_as(C.c_void_p) if ts is not None else None, C.byref(nfe),
-                                             _stream_ptr(self.device)), self._L)
+            call(self._L, "diffsep_pc_sample_ex", self._h, C.byref(sc), C.byref(sm), C.byref(ext) if ext is not None else None,
+                 _ptr(mix_norm), _ptr(out), B, T, _ptr(noise), seed, ts.ctypes.data_as(C.c_void_p) if ts is not None else None,
+                 C.byref(nfe), _stream_ptr(self.device))
         return out, int(nfe.value)
 
     def _ode_setup(self, mix_norm, sde, method, rtol, atol, eps, first_step, max_step, max_nfe, denoise, N, x_init, noise):
@@ -271,8 +250,7 @@ class Engine:
         mix_norm = self._f32(mix_norm)
         B, one, T = mix_norm.shape
         assert one == 1
-        sc = _lib.SdeConfig(sde.get("kind", _lib.SDE_MIX), sde["ndim"], sde["d_lambda"], sde["sigma_min"],
-                            sde["sigma_max"], sde.get("avg_len", 0))
+        sc = _lib.sde_config(sde)
         oc = _lib.OdeConfig(float(rtol), float(atol), float(eps), float(first_step or 0.0),
                             float(max_step) if max_step is not None else 0.0, _lib.ODE_METHODS[method], int(max_nfe or 0),
                             int(bool(denoise)), int(N))
@@ -300,11 +278,9 @@ class Engine:
         B, _, T = mix_norm.shape
         info = _lib.OdeInfo()
         with torch.cuda.device(self.device):
-            check(self._L.diffsep_ode_sample(self._h, C.byref(sc), C.byref(oc), _ptr(mix_norm), _ptr(x_init), _ptr(noise),
-                                             int(seed) % (1 << 64), _ptr(out), B, T, C.byref(info),
-                                             _stream_ptr(self.device)), self._L)
-        return out, dict(nfev=info.nfev, n_accepted=info.n_accepted, n_rejected=info.n_rejected, status=info.status,
-                         t_final=info.t_final)
+            call(self._L, "diffsep_ode_sample", self._h, C.byref(sc), C.byref(oc), _ptr(mix_norm), _ptr(x_init), _ptr(noise),
+                 int(seed) % (1 << 64), _ptr(out), B, T, C.byref(info), _stream_ptr(self.device))
+        return out, _lib.ode_info_dict(info)
 
     def ode_sample_each(self, mix_norm, sde, lengths=None, seeds=None, method="RK45", rtol=1e-5, atol=1e-5, eps=3e-2,
                         first_step=None, max_step=None, max_nfe=0, denoise=True, N=30, x_init=None, noise=None, seed=0):
@@ -317,22 +293,15 @@ class Engine:
         mix_norm, sc, oc, x_init, noise, out = self._ode_setup(mix_norm, sde, method, rtol, atol, eps, first_step, max_step,
                                                                max_nfe, denoise, N, x_init, noise)
         B, _, T = mix_norm.shape
-        ext, keep = _lib.OdeExt(), []
+        ext = _lib.OdeExt()  # (la / sa below: the host arrays its pointers refer to, alive until this method returns)
         if lengths is not None:
-            la = np.ascontiguousarray(lengths, dtype=np.int64)
-            assert la.shape == (B,), "lengths must be [B]"
-            ext.lengths_host = la.ctypes.data_as(C.POINTER(C.c_int64))
-            keep.append(la)
+            la, ext.lengths_host = _lib.host_array(lengths, np.int64, B, "lengths")
         if seeds is not None:
-            sa = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
-            assert sa.shape == (B,), "seeds must be [B]"
-            ext.seeds_host = sa.ctypes.data_as(C.POINTER(C.c_uint64))
-            keep.append(sa)
+            sa, ext.seeds_host = _lib.host_array(seeds, np.uint64, B, "seeds")
         infos = (_lib.OdeInfo * B)()
         evals = C.c_int32()
         with torch.cuda.device(self.device):
-            check(self._L.diffsep_ode_sample_each(self._h, C.byref(sc), C.byref(oc), C.byref(ext), _ptr(mix_norm),
-                                                  _ptr(x_init), _ptr(noise), int(seed) % (1 << 64), _ptr(out), B, T, infos,
-                                                  C.byref(evals), _stream_ptr(self.device)), self._L)
-        return out, [dict(nfev=i.nfev, n_accepted=i.n_accepted, n_rejected=i.n_rejected, status=i.status,
-                          t_final=i.t_final) for i in infos], int(evals.value)
+            call(self._L, "diffsep_ode_sample_each", self._h, C.byref(sc), C.byref(oc), C.byref(ext), _ptr(mix_norm),
+                 _ptr(x_init), _ptr(noise), int(seed) % (1 << 64), _ptr(out), B, T, infos, C.byref(evals),
+                 _stream_ptr(self.device))
+        return out, [_lib.ode_info_dict(i) for i in infos], int(evals.value)

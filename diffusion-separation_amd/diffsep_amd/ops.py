@@ -6,16 +6,21 @@ import math
 import numpy as np
 import torch
 
-from ._lib import F32_SPLIT, F32, BF16, GN_ROUTES, ODE_WORKSPACE_BYTES, LossConfig, SdeConfig, SDE_MIX, check, lib
-from .engine import _ptr, _stream_ptr
+from . import _lib
+from ._lib import (F32_SPLIT, F32, BF16, GN_ROUTES, ODE_WORKSPACE_BYTES, LossConfig, _ptr, _stream_ptr, call, check, host_array, lib,
+                   sde_config)
+
+
+def _dt_of(dtype):
+    if dtype == torch.float32:
+        return F32
+    if dtype in (torch.bfloat16, torch.float16):  # the 16-bit storage format of the library _L(t) picks
+        return BF16
+    raise TypeError("float32, bfloat16 or float16 expected")
 
 
 def _dt(t):
-    if t.dtype == torch.float32:
-        return F32
-    if t.dtype in (torch.bfloat16, torch.float16):  # the 16-bit storage format of the library _L(t) picks
-        return BF16
-    raise TypeError("float32, bfloat16 or float16 expected")
+    return _dt_of(t.dtype)
 
 
 def _L(t):
@@ -28,6 +33,40 @@ def _dts(t, split):
     if split and t.dtype != torch.float32:
         raise TypeError("split products are a mode of fp32 tensors")
     return F32_SPLIT if split else _dt(t)
+
+
+def _stats_arg(stats, B, C, device):
+    """stats= of a launch: False -> None, True -> zeroed int64 accumulators [B,C,2], a tensor -> itself (the launch adds into it)"""
+    if stats is True:
+        return torch.zeros((B, C, 2), dtype=torch.int64, device=device)
+    return None if stats is False else stats
+
+
+def _gn_arg(gn):
+    """gn = (scale, shift) | None"""
+    return gn if gn is not None else (None, None)
+
+
+def _gn_acc_arg(gn_acc, n):
+    """gn_acc = (acc1[, acc2 | None], gamma, beta, groups) | None: n = 5 / 4 elements"""
+    return gn_acc if gn_acc is not None else (None,) * (n - 1) + (0,)
+
+
+def _skip_arg(skip):
+    """skip = (sx, sx2 | None, weights) | None -> (sx, sx2, weights, channels of sx, channels of both)"""
+    sx, sx2, sw = skip if skip is not None else (None, None, None)
+    sC1 = sx.shape[-1] if sx is not None else 0
+    return sx, sx2, sw, sC1, sC1 + (sx2.shape[-1] if sx2 is not None else 0)
+
+
+def _resampled(mode, H, W):
+    """output size of resample mode 0 / 1 / 2 = none / x2 up / x2 down"""
+    return {0: (H, W), 1: (2 * H, 2 * W), 2: (H // 2, W // 2)}[mode]
+
+
+def _params_blob(params):
+    """a list of parameter arrays as one flat float32 host blob"""
+    return np.ascontiguousarray(np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in params]))
 
 
 def to_nhwc(x, cpad=None):
@@ -100,22 +139,15 @@ def conv3x3_streamed(x, w_frag, cout, x2=None, gn=None, bias=None, bias_b=None, 
     B, H, W, C1 = x.shape
     Cin = C1 + (x2.shape[-1] if x2 is not None else 0)
     y = torch.zeros((B, H, W, cout), dtype=x.dtype, device=x.device) if out is None else out
-    sc, sh = gn if gn is not None else (None, None)
-    st = None
-    if stats is True:
-        st = torch.zeros((B, cout, 2), dtype=torch.int64, device=x.device)
-    elif stats is not False:
-        st = stats  # (a tensor: the launch adds into it)
-    sx, sx2, swf = skip if skip is not None else (None, None, None)
-    sC1 = sx.shape[-1] if sx is not None else 0
-    sCin = sC1 + (sx2.shape[-1] if sx2 is not None else 0)
-    a1, a2, gam, bet, grp = gn_acc if gn_acc is not None else (None, None, None, None, 0)
+    sc, sh = _gn_arg(gn)
+    st = _stats_arg(stats, B, cout, x.device)
+    sx, sx2, swf, sC1, sCin = _skip_arg(skip)
+    a1, a2, gam, bet, grp = _gn_acc_arg(gn_acc, 5)
     split = x.dtype == torch.float32
     L = lib("bf16") if split else _L(x)
-    check(L.diffsep_conv3x3_streamed(_ptr(x), _ptr(x2), C1, _ptr(sc), _ptr(sh), _ptr(w_frag), _ptr(bias), _ptr(bias_b),
-                                     _ptr(sx), _ptr(sx2), sC1, sCin, _ptr(swf), _ptr(y), B, H, W, Cin, cout, out_scale,
-                                     F32_SPLIT if split else _dt(x), _ptr(st), _ptr(res), _ptr(ident_frag), _ptr(a1), _ptr(a2), _ptr(gam),
-                                     _ptr(bet), grp, _stream_ptr()), L)
+    call(L, "diffsep_conv3x3_streamed", _ptr(x), _ptr(x2), C1, _ptr(sc), _ptr(sh), _ptr(w_frag), _ptr(bias), _ptr(bias_b),
+         _ptr(sx), _ptr(sx2), sC1, sCin, _ptr(swf), _ptr(y), B, H, W, Cin, cout, out_scale, F32_SPLIT if split else _dt(x),
+         _ptr(st), _ptr(res), _ptr(ident_frag), _ptr(a1), _ptr(a2), _ptr(gam), _ptr(bet), grp, _stream_ptr())
     return (y, st) if stats is not False else y
 
 
@@ -127,37 +159,35 @@ def conv3x3_regweight(x, wpacked, cout, x2=None, gn=None, bias=None, bias_b=None
     B, H, W, C1 = x.shape
     Cin = C1 + (x2.shape[-1] if x2 is not None else 0)
     y = torch.zeros((B, H, W, cout), dtype=x.dtype, device=x.device)
-    sc, sh = gn if gn is not None else (None, None)
+    sc, sh = _gn_arg(gn)
     st = torch.zeros((B, cout, 2), dtype=torch.int64, device=x.device) if stats else None
-    sx, sx2, sw = skip if skip is not None else (None, None, None)
-    sC1 = sx.shape[-1] if sx is not None else 0
-    sCin = sC1 + (sx2.shape[-1] if sx2 is not None else 0)
-    check(_L(x).diffsep_conv3x3_regweight(_ptr(x), _ptr(x2), C1, _ptr(sc), _ptr(sh), _ptr(wpacked), w_chunk, _ptr(bias), _ptr(bias_b),
-                                          _ptr(sx), _ptr(sx2), sC1, sCin, _ptr(sw), _ptr(res), _ptr(y), B, H, W, Cin, cout, out_scale,
-                                          _dt(x), _ptr(st), _stream_ptr()), _L(x))
+    sx, sx2, sw, sC1, sCin = _skip_arg(skip)
+    call(_L(x), "diffsep_conv3x3_regweight", _ptr(x), _ptr(x2), C1, _ptr(sc), _ptr(sh), _ptr(wpacked), w_chunk, _ptr(bias),
+         _ptr(bias_b), _ptr(sx), _ptr(sx2), sC1, sCin, _ptr(sw), _ptr(res), _ptr(y), B, H, W, Cin, cout, out_scale, _dt(x),
+         _ptr(st), _stream_ptr())
     return (y, st) if stats else y
 
 
 def conv2d_chunk(ksize, dtype):
-    return lib().diffsep_conv2d_chunk(ksize, F32 if dtype == torch.float32 else BF16)  # (the same in both builds)
+    return lib().diffsep_conv2d_chunk(ksize, _dt_of(dtype))  # (the same in both builds)
 
 
 def upfirdn2d(x, up):
     B, H, W, Cc = x.shape
-    Ho, Wo = (2 * H, 2 * W) if up else (H // 2, W // 2)
+    Ho, Wo = _resampled(1 if up else 2, H, W)
     y = torch.empty((B, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
-    check(_L(x).diffsep_upfirdn2d(_ptr(x), _ptr(y), B, H, W, Cc, Cc, Cc, int(up), _dt(x), _stream_ptr()), _L(x))
+    call(_L(x), "diffsep_upfirdn2d", _ptr(x), _ptr(y), B, H, W, Cc, Cc, Cc, int(up), _dt(x), _stream_ptr())
     return y
 
 
 def groupnorm_act(x, gamma, beta, groups, eps=1e-6, act=1, resample=0, want_xr=False):
     B, H, W, Cc = x.shape
-    Ho, Wo = {0: (H, W), 1: (2 * H, 2 * W), 2: (H // 2, W // 2)}[resample]
+    Ho, Wo = _resampled(resample, H, W)
     y = torch.empty((B, Ho, Wo, Cc), dtype=x.dtype, device=x.device)
     xr = torch.empty_like(y) if want_xr else None
     ws = torch.empty(B * 64 * Cc * 16 + 2 * B * Cc * 4 + 4096, dtype=torch.uint8, device=x.device)
-    check(_L(x).diffsep_groupnorm_act(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(xr), B, H, W, Cc, Cc, Cc, Cc,
-                                      groups, eps, act, resample, _dt(x), _ptr(ws), ws.numel(), _stream_ptr()), _L(x))
+    call(_L(x), "diffsep_groupnorm_act", _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(xr), B, H, W, Cc, Cc, Cc, Cc, groups,
+         eps, act, resample, _dt(x), _ptr(ws), ws.numel(), _stream_ptr())
     return (y, xr) if want_xr else y
 
 
@@ -169,14 +199,14 @@ def gn_apply(x, scale, shift, act, resample, want_y=True, want_xr=False, route=N
     of x's buffer but x itself, and both outputs entirely, are prefilled with NaN.  Returns (y, xr, ybuf, xrbuf): views of the
     first C lanes and the full buffers (None where not wanted)."""
     B, H, W, Cc = x.shape
-    Ho, Wo = {0: (H, W), 1: (2 * H, 2 * W), 2: (H // 2, W // 2)}[resample]
+    Ho, Wo = _resampled(resample, H, W)
     nan = float("nan")
     xb = torch.full((B, H, W, Cc + pad[0]), nan, dtype=x.dtype, device=x.device)
     xb[..., :Cc] = x
     yb = torch.full((B, Ho, Wo, Cc + pad[1]), nan, dtype=x.dtype, device=x.device) if want_y else None
     xrb = torch.full((B, Ho, Wo, Cc + pad[2]), nan, dtype=x.dtype, device=x.device) if want_xr else None
-    check(_L(x).diffsep_gn_apply(_ptr(xb), _ptr(scale), _ptr(shift), _ptr(yb), _ptr(xrb), B, H, W, Cc, Cc + pad[0], Cc + pad[1],
-                                 Cc + pad[2], int(act), resample, _dt(x), GN_ROUTES[route or "auto"], _stream_ptr()), _L(x))
+    call(_L(x), "diffsep_gn_apply", _ptr(xb), _ptr(scale), _ptr(shift), _ptr(yb), _ptr(xrb), B, H, W, Cc, Cc + pad[0],
+         Cc + pad[1], Cc + pad[2], int(act), resample, _dt(x), GN_ROUTES[route or "auto"], _stream_ptr())
     return (yb[..., :Cc] if want_y else None, xrb[..., :Cc] if want_xr else None, yb, xrb)
 
 
@@ -184,8 +214,8 @@ def gn_route_name(kind, resample, affine, dtype, B, H, W, C, pad=(0, 0, 0), has_
     """name of the kernel the dispatch picks for a GroupNorm-apply / FIR launch in library `kind` on a device of `cus` compute
     units (diffsep_gn_route_name: host arithmetic, nothing is launched and no device is needed); dtype: torch type of the tensors"""
     l = lib(kind)
-    name = l.diffsep_gn_route_name(resample, int(affine), F32 if dtype == torch.float32 else BF16, B, H, W, C, C + pad[0], C + pad[1],
-                                   C + pad[2], int(has_xr), cus)
+    name = l.diffsep_gn_route_name(resample, int(affine), _dt_of(dtype), B, H, W, C, C + pad[0], C + pad[1], C + pad[2],
+                                   int(has_xr), cus)
     if name is None:
         check(1, l)
     return name.decode()
@@ -195,9 +225,8 @@ def conv2d(x, wpacked, bias, cout, ksize, bias_b=None, res=None, out_scale=1.0, 
     B, H, W, Cin = x.shape
     cp = cout if cout_pad is None else cout_pad
     y = torch.zeros((B, H, W, cp), dtype=x.dtype, device=x.device)
-    check(_L(x).diffsep_conv2d(_ptr(x), _ptr(wpacked), _ptr(bias), _ptr(bias_b), _ptr(res), _ptr(y), B, H, W, Cin,
-                               cout, ksize, Cin, res.shape[-1] if res is not None else 0, cp, out_scale, _dt(x),
-                               _stream_ptr()), _L(x))
+    call(_L(x), "diffsep_conv2d", _ptr(x), _ptr(wpacked), _ptr(bias), _ptr(bias_b), _ptr(res), _ptr(y), B, H, W, Cin, cout,
+         ksize, Cin, res.shape[-1] if res is not None else 0, cp, out_scale, _dt(x), _stream_ptr())
     return y
 
 
@@ -208,9 +237,8 @@ def groupnorm_stats(x, gamma, beta, groups, eps=1e-6, x2=None):
     scale = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
     shift = torch.empty_like(scale)
     ws = torch.empty(B * 64 * Cc * 16 + 4096, dtype=torch.uint8, device=x.device)
-    check(_L(x).diffsep_groupnorm_stats(_ptr(x), _ptr(x2), C1, _ptr(gamma), _ptr(beta), _ptr(scale), _ptr(shift), B, H,
-                                        W, Cc, C1, x2.shape[-1] if x2 is not None else 0, groups, eps, _dt(x), _ptr(ws),
-                                        ws.numel(), _stream_ptr()), _L(x))
+    call(_L(x), "diffsep_groupnorm_stats", _ptr(x), _ptr(x2), C1, _ptr(gamma), _ptr(beta), _ptr(scale), _ptr(shift), B, H, W,
+         Cc, C1, x2.shape[-1] if x2 is not None else 0, groups, eps, _dt(x), _ptr(ws), ws.numel(), _stream_ptr())
     return scale, shift
 
 
@@ -226,18 +254,13 @@ def conv2d_fused(x, wpacked, bias, cout, ksize, x2=None, gn=None, gn_act=1, bias
     Cin = C1 + (x2.shape[-1] if x2 is not None else 0)
     cp = cout if cout_pad is None else cout_pad
     y = torch.zeros((B, H, W, cp), dtype=x.dtype, device=x.device) if out is None else out
-    sc, sh = gn if gn is not None else (None, None)
-    st = None
-    if stats is True:
-        st = torch.zeros((B, cout, 2), dtype=torch.int64, device=x.device)
-    elif stats is not False:
-        st = stats
-    a1, a2, gam, bet, grp = gn_acc if gn_acc is not None else (None, None, None, None, 0)
-    check(_L(x).diffsep_conv2d_fused(_ptr(x), _ptr(x2), C1, _ptr(sc), _ptr(sh), gn_act, _ptr(wpacked), _ptr(bias),
-                                     _ptr(bias_b), _ptr(res), _ptr(y), B, H, W, Cin, cout, ksize, C1,
-                                     x2.shape[-1] if x2 is not None else 0, res.shape[-1] if res is not None else 0, cp,
-                                     out_scale, _dts(x, split), _ptr(st), w_chunk, _ptr(a1), _ptr(a2), _ptr(gam), _ptr(bet), grp,
-                                     _stream_ptr()), _L(x))
+    sc, sh = _gn_arg(gn)
+    st = _stats_arg(stats, B, cout, x.device)
+    a1, a2, gam, bet, grp = _gn_acc_arg(gn_acc, 5)
+    call(_L(x), "diffsep_conv2d_fused", _ptr(x), _ptr(x2), C1, _ptr(sc), _ptr(sh), gn_act, _ptr(wpacked), _ptr(bias),
+         _ptr(bias_b), _ptr(res), _ptr(y), B, H, W, Cin, cout, ksize, C1, x2.shape[-1] if x2 is not None else 0,
+         res.shape[-1] if res is not None else 0, cp, out_scale, _dts(x, split), _ptr(st), w_chunk, _ptr(a1), _ptr(a2), _ptr(gam),
+         _ptr(bet), grp, _stream_ptr())
     return (y, st) if stats is not False else y
 
 
@@ -257,8 +280,8 @@ def groupnorm_from_acc(sa, sb, gamma, beta, groups, npix, eps=1e-6):
     C2 = sb.shape[1] if sb is not None else 0
     scale = torch.empty((B, C1 + C2), dtype=torch.float32, device=sa.device)
     shift = torch.empty_like(scale)
-    check(lib().diffsep_gn_finalize_acc(_ptr(sa), C1, _ptr(sb), C2, B, npix, groups, eps, _ptr(gamma), _ptr(beta), _ptr(scale),
-                                        _ptr(shift), _stream_ptr()))
+    call(lib(), "diffsep_gn_finalize_acc", _ptr(sa), C1, _ptr(sb), C2, B, npix, groups, eps, _ptr(gamma), _ptr(beta),
+         _ptr(scale), _ptr(shift), _stream_ptr())
     return scale, shift
 
 
@@ -272,17 +295,14 @@ def attn_fused(x, wqk, wv, wo, bqk, bv, bo, gn=None, gn_acc=None, stats=False, o
                             or out.shape[0] < B or tuple(out.shape[1:]) != (L, Cc)):
         raise ValueError("attn_fused: out must be a dense [>= B, L, C] tensor of x's type on x's device")
     y = torch.empty_like(x) if out is None else out
-    st = None
-    if stats is True:
-        st = torch.zeros((B, Cc, 2), dtype=torch.int64, device=x.device)
-    elif stats is not False:
-        st = stats
-        if st.dtype != torch.int64 or not st.is_contiguous() or st.dim() != 3 or st.shape[0] < B or tuple(st.shape[1:]) != (Cc, 2):
-            raise ValueError("attn_fused: stats must be a dense int64 [>= B, C, 2] tensor")
-    sc, sh = gn if gn is not None else (None, None)
-    acc, gam, bet, grp = gn_acc if gn_acc is not None else (None, None, None, 0)
-    check(_L(x).diffsep_attn_fused(_ptr(x), _ptr(acc), _ptr(gam), _ptr(bet), grp, _ptr(sc), _ptr(sh), _ptr(wqk), _ptr(wv), _ptr(wo),
-                                   _ptr(bqk), _ptr(bv), _ptr(bo), _ptr(y), _ptr(st), B, L, Cc, _stream_ptr()), _L(x))
+    st = _stats_arg(stats, B, Cc, x.device)
+    if stats is not True and stats is not False and (st.dtype != torch.int64 or not st.is_contiguous() or st.dim() != 3
+                                                     or st.shape[0] < B or tuple(st.shape[1:]) != (Cc, 2)):
+        raise ValueError("attn_fused: stats must be a dense int64 [>= B, C, 2] tensor")
+    sc, sh = _gn_arg(gn)
+    acc, gam, bet, grp = _gn_acc_arg(gn_acc, 4)
+    call(_L(x), "diffsep_attn_fused", _ptr(x), _ptr(acc), _ptr(gam), _ptr(bet), grp, _ptr(sc), _ptr(sh), _ptr(wqk), _ptr(wv),
+         _ptr(wo), _ptr(bqk), _ptr(bv), _ptr(bo), _ptr(y), _ptr(st), B, L, Cc, _stream_ptr())
     return (y, st) if stats is not False else y
 
 
@@ -298,8 +318,8 @@ def attention(q, k, vt, split=False):
     assert vt.shape == (B, Cc, Lp)
     o = torch.empty_like(q)
     ws = torch.empty(2 * (B * L * Lp * q.element_size() + 256), dtype=torch.uint8, device=q.device)
-    check(_L(q).diffsep_attention(_ptr(q), _ptr(k), _ptr(vt), _ptr(o), B, L, Cc, Cc, _dts(q, split), _ptr(ws), ws.numel(),
-                                  _stream_ptr()), _L(q))
+    call(_L(q), "diffsep_attention", _ptr(q), _ptr(k), _ptr(vt), _ptr(o), B, L, Cc, Cc, _dts(q, split), _ptr(ws), ws.numel(),
+         _stream_ptr())
     return o
 
 
@@ -307,22 +327,22 @@ def resblock_forward(params, x, temb, out_ch, up=False, down=False):
     """ResnetBlockBigGANpp through the engine's block code.  params: list of float32 arrays in reference state_dict
     order; x [B,H,W,Cin] NHWC, temb [B,D] f32 -> [B,H',W',out_ch]."""
     B, H, W, cin = x.shape
-    blob = np.ascontiguousarray(np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in params]))
-    Ho, Wo = (2 * H, 2 * W) if up else ((H // 2, W // 2) if down else (H, W))
+    blob = _params_blob(params)
+    Ho, Wo = _resampled(1 if up else (2 if down else 0), H, W)
     y = torch.empty((B, Ho, Wo, out_ch), dtype=x.dtype, device=x.device)
-    check(_L(x).diffsep_resblock_forward(cin, out_ch, int(up), int(down), temb.shape[1], _dt(x),
-                                         blob.ctypes.data_as(C.c_void_p), blob.size, _ptr(x.contiguous()),
-                                         _ptr(temb.contiguous()), _ptr(y), B, H, W, _stream_ptr()), _L(x))
+    call(_L(x), "diffsep_resblock_forward", cin, out_ch, int(up), int(down), temb.shape[1], _dt(x),
+         blob.ctypes.data_as(C.c_void_p), blob.size, _ptr(x.contiguous()), _ptr(temb.contiguous()), _ptr(y), B, H, W,
+         _stream_ptr())
     return y
 
 
 def attnblock_forward(params, x):
     """AttnBlockpp through the engine's block code.  params: GroupNorm_0.{weight,bias}, NIN_0..3.{W,b}."""
     B, H, W, Cc = x.shape
-    blob = np.ascontiguousarray(np.concatenate([np.asarray(p, np.float32).reshape(-1) for p in params]))
+    blob = _params_blob(params)
     y = torch.empty_like(x)
-    check(_L(x).diffsep_attnblock_forward(Cc, _dt(x), blob.ctypes.data_as(C.c_void_p), blob.size, _ptr(x.contiguous()),
-                                          _ptr(y), B, H, W, _stream_ptr()), _L(x))
+    call(_L(x), "diffsep_attnblock_forward", Cc, _dt(x), blob.ctypes.data_as(C.c_void_p), blob.size, _ptr(x.contiguous()),
+         _ptr(y), B, H, W, _stream_ptr())
     return y
 
 
@@ -333,9 +353,8 @@ def stft_pack(xt, mix, W, cpad, n_fft=510, hop=128, exponent=0.5, factor=0.33, s
     y = torch.empty((B, n_fft // 2 + 1, W, cpad), dtype=dtype, device=xt.device)
     F_ = 1 + (T + n_fft - hop) // hop
     ws = torch.empty(2 * ((B * (S + 1) * F_ + 8) * 512 + 64), dtype=torch.float32, device=xt.device)
-    check(_L(y).diffsep_stft_pack_ex(_ptr(xt), _ptr(mix), _ptr(y), B, S, T, n_fft, hop, exponent, factor, W, cpad,
-                                     int(shift), F32 if dtype == torch.float32 else BF16, _ptr(ws), ws.numel() * 4,
-                                     _stream_ptr(), int(bool(split))), _L(y))
+    call(_L(y), "diffsep_stft_pack_ex", _ptr(xt), _ptr(mix), _ptr(y), B, S, T, n_fft, hop, exponent, factor, W, cpad,
+         int(shift), _dt_of(dtype), _ptr(ws), ws.numel() * 4, _stream_ptr(), int(bool(split)))
     return y
 
 
@@ -357,30 +376,24 @@ def istft_unpack(x, S, T, n_fft=510, hop=128, exponent=0.5, factor=0.33, split=F
             if t_.dtype != torch.float32 or not t_.is_contiguous() or tuple(t_.shape) != shp or t_.device != x.device:
                 raise ValueError("istft_unpack: ow [2S, ow_cin], ob [2S], tdiv [B] must be dense float32 tensors on x's device")
         ow_cin = ow.shape[1]
-    check(_L(x).diffsep_istft_unpack_ex(_ptr(x), _ptr(out), B, S, T, n_fft, hop, exponent, factor, W, cpad, _dt(x),
-                                        _ptr(ws), ws.numel() * 4, _stream_ptr(), int(bool(split)), _ptr(ow), _ptr(ob),
-                                        _ptr(tdiv), ow_cin), _L(x))
+    call(_L(x), "diffsep_istft_unpack_ex", _ptr(x), _ptr(out), B, S, T, n_fft, hop, exponent, factor, W, cpad, _dt(x), _ptr(ws),
+         ws.numel() * 4, _stream_ptr(), int(bool(split)), _ptr(ow), _ptr(ob), _ptr(tdiv), ow_cin)
     return out
-
-
-def _sde(s):
-    return SdeConfig(s.get("kind", SDE_MIX), s["ndim"], s["d_lambda"], s["sigma_min"], s["sigma_max"],
-                     s.get("avg_len", 0))
 
 
 def sde_sigma_mix(mix, avg_len=510):
     """PriorMixSDE per-sample noise scale: mix [B,1,T] -> [B,T]."""
     B, _, T = mix.shape
     out = torch.empty((B, T), dtype=torch.float32, device=mix.device)
-    check(lib().diffsep_sde_sigma_mix(_ptr(mix), _ptr(out), B, T, avg_len, _stream_ptr()))
+    call(lib(), "diffsep_sde_sigma_mix", _ptr(mix), _ptr(out), B, T, avg_len, _stream_ptr())
     return out
 
 
 def sde_prior(sde, y, z, sigma_mix=None):
     B, S, T = z.shape
     x = torch.empty_like(z)
-    sc = _sde(sde)
-    check(lib().diffsep_sde_prior(C.byref(sc), _ptr(y), _ptr(z), _ptr(x), B, S, T, _ptr(sigma_mix), _stream_ptr()))
+    call(lib(), "diffsep_sde_prior", C.byref(sde_config(sde)), _ptr(y), _ptr(z), _ptr(x), B, S, T, _ptr(sigma_mix),
+         _stream_ptr())
     return x
 
 
@@ -388,19 +401,16 @@ def sde_corrector_update(sde, snr, x, t, score, z, sigma_mix=None, variant=0):
     """variant 0: ald2, 1: ald."""
     B, S, T = x.shape
     xo, xm = torch.empty_like(x), torch.empty_like(x)
-    sc = _sde(sde)
-    check(lib().diffsep_sde_corrector_update(C.byref(sc), snr, _ptr(x), _ptr(t), _ptr(score), _ptr(z), _ptr(xo),
-                                             _ptr(xm), B, S, T, _ptr(sigma_mix), variant, _stream_ptr()))
+    call(lib(), "diffsep_sde_corrector_update", C.byref(sde_config(sde)), snr, _ptr(x), _ptr(t), _ptr(score), _ptr(z), _ptr(xo),
+         _ptr(xm), B, S, T, _ptr(sigma_mix), variant, _stream_ptr())
     return xo, xm
 
 
 def sde_predictor_update(sde, N, x, t, score, z, sigma_mix=None, probability_flow=False):
     B, S, T = x.shape
     xo, xm = torch.empty_like(x), torch.empty_like(x)
-    sc = _sde(sde)
-    check(lib().diffsep_sde_predictor_update(C.byref(sc), N, _ptr(x), _ptr(t), _ptr(score), _ptr(z), _ptr(xo),
-                                             _ptr(xm), B, S, T, _ptr(sigma_mix), int(bool(probability_flow)),
-                                             _stream_ptr()))
+    call(lib(), "diffsep_sde_predictor_update", C.byref(sde_config(sde)), N, _ptr(x), _ptr(t), _ptr(score), _ptr(z), _ptr(xo),
+         _ptr(xm), B, S, T, _ptr(sigma_mix), int(bool(probability_flow)), _stream_ptr())
     return xo, xm
 
 
@@ -409,17 +419,15 @@ def sde_coefficients(sde, x, t, sigma_mix=None, f_scale=1.0, g_scale=1.0):
     B, S, T = x.shape
     drift = torch.empty_like(x)
     diff = torch.empty_like(x) if sigma_mix is not None else torch.empty(B, dtype=torch.float32, device=x.device)
-    sc = _sde(sde)
-    check(lib().diffsep_sde_coefficients(C.byref(sc), _ptr(x), _ptr(t), _ptr(sigma_mix), _ptr(drift), _ptr(diff), B, S, T,
-                                         f_scale, g_scale, _stream_ptr()))
+    call(lib(), "diffsep_sde_coefficients", C.byref(sde_config(sde)), _ptr(x), _ptr(t), _ptr(sigma_mix), _ptr(drift),
+         _ptr(diff), B, S, T, f_scale, g_scale, _stream_ptr())
     return drift, diff
 
 
 def sde_mean(sde, x0, t):
     B, S, T = x0.shape
     out = torch.empty_like(x0)
-    sc = _sde(sde)
-    check(lib().diffsep_sde_mean(C.byref(sc), _ptr(x0), _ptr(t), _ptr(out), B, S, T, _stream_ptr()))
+    call(lib(), "diffsep_sde_mean", C.byref(sde_config(sde)), _ptr(x0), _ptr(t), _ptr(out), B, S, T, _stream_ptr())
     return out
 
 
@@ -428,8 +436,7 @@ def sde_std(sde, t, S, T=1, sigma_mix=None):
     B = t.shape[0]
     shape = (B, S, S, T) if sigma_mix is not None else (B, S, S)
     out = torch.empty(shape, dtype=torch.float32, device=t.device)
-    sc = _sde(sde)
-    check(lib().diffsep_sde_std(C.byref(sc), _ptr(t), _ptr(sigma_mix), _ptr(out), B, S, T, _stream_ptr()))
+    call(lib(), "diffsep_sde_std", C.byref(sde_config(sde)), _ptr(t), _ptr(sigma_mix), _ptr(out), B, S, T, _stream_ptr())
     return out
 
 
@@ -439,7 +446,7 @@ def sde_mult_std(std, x):
     per = std.dim() == 4
     assert std.shape == ((B, S, S, T) if per else (B, S, S)), "std must be [B,S,S] or [B,S,S,T]"
     out = torch.empty_like(x)
-    check(lib().diffsep_sde_mult_std(_ptr(std.contiguous()), _ptr(x), _ptr(out), B, S, T, int(per), _stream_ptr()))
+    call(lib(), "diffsep_sde_mult_std", _ptr(std.contiguous()), _ptr(x), _ptr(out), B, S, T, int(per), _stream_ptr())
     return out
 
 
@@ -449,7 +456,7 @@ def sde_mult_std_inv(std, x):
     per = std.dim() == 4
     assert std.shape == ((B, S, S, T) if per else (B, S, S)), "std must be [B,S,S] or [B,S,S,T]"
     out = torch.empty_like(x)
-    check(lib().diffsep_sde_mult_std_inv(_ptr(std.contiguous()), _ptr(x), _ptr(out), B, S, T, int(per), _stream_ptr()))
+    call(lib(), "diffsep_sde_mult_std_inv", _ptr(std.contiguous()), _ptr(x), _ptr(out), B, S, T, int(per), _stream_ptr())
     return out
 
 
@@ -460,8 +467,8 @@ def sde_reverse_drift(f, G, score, probability_flow=False):
     full = G.numel() != B
     assert (not full) or G.shape == f.shape
     out = torch.empty_like(f)
-    check(lib().diffsep_sde_reverse_drift(_ptr(f), _ptr(G.contiguous()), _ptr(score), _ptr(out), B, n, int(full),
-                                          int(bool(probability_flow)), _stream_ptr()))
+    call(lib(), "diffsep_sde_reverse_drift", _ptr(f), _ptr(G.contiguous()), _ptr(score), _ptr(out), B, n, int(full),
+         int(bool(probability_flow)), _stream_ptr())
     return out
 
 
@@ -470,8 +477,8 @@ def sde_langevin_update(snr, x, score, z):
     n = x.numel() // B
     xo, xm = torch.empty_like(x), torch.empty_like(x)
     ws = torch.empty(16 * B + 64, dtype=torch.uint8, device=x.device)
-    check(lib().diffsep_sde_langevin_update(snr, _ptr(x), _ptr(score), _ptr(z), _ptr(xo), _ptr(xm), B, n, _ptr(ws),
-                                            ws.numel(), _stream_ptr()))
+    call(lib(), "diffsep_sde_langevin_update", snr, _ptr(x), _ptr(score), _ptr(z), _ptr(xo), _ptr(xm), B, n, _ptr(ws),
+         ws.numel(), _stream_ptr())
     return xo, xm
 
 
@@ -480,14 +487,14 @@ def normalize_batch(mix):
     out = torch.empty_like(mix)
     mean = torch.empty(B, dtype=torch.float32, device=mix.device)
     std = torch.empty(B, dtype=torch.float32, device=mix.device)
-    check(lib().diffsep_normalize_batch(_ptr(mix), _ptr(out), _ptr(mean), _ptr(std), B, T, _stream_ptr()))
+    call(lib(), "diffsep_normalize_batch", _ptr(mix), _ptr(out), _ptr(mean), _ptr(std), B, T, _stream_ptr())
     return out, mean.view(B, 1, 1), std.view(B, 1, 1)
 
 
 def scale_output(mix, sep):
     B, S, T = sep.shape
     out = sep.clone()
-    check(lib().diffsep_scale_output(_ptr(mix), _ptr(out), B, S, T, _stream_ptr()))
+    call(lib(), "diffsep_scale_output", _ptr(mix), _ptr(out), B, S, T, _stream_ptr())
     return out
 
 
@@ -497,13 +504,13 @@ def time_embedding(t, fourier_w, w1, b1, w2, b2):
     ts = [x.contiguous().float() for x in (t, fourier_w, w1, b1, w2, b2)]
     out = torch.empty((B, 4 * nf), dtype=torch.float32, device=t.device)
     ws = torch.empty(B * 6 * nf, dtype=torch.float32, device=t.device)
-    check(lib().diffsep_time_embedding(*[_ptr(x) for x in ts], _ptr(out), B, nf, _ptr(ws), ws.numel() * 4, _stream_ptr()))
+    call(lib(), "diffsep_time_embedding", *[_ptr(x) for x in ts], _ptr(out), B, nf, _ptr(ws), ws.numel() * 4, _stream_ptr())
     return out
 
 
 def randn(n, seed, stream_id, device="cuda"):
     out = torch.empty(n, dtype=torch.float32, device=device)
-    check(lib().diffsep_randn(_ptr(out), n, seed, stream_id, _stream_ptr()))
+    call(lib(), "diffsep_randn", _ptr(out), n, seed, stream_id, _stream_ptr())
     return out
 
 
@@ -512,7 +519,7 @@ def randn_batch(B, S, T, seeds, lengths, stream_id, device="cuda"):
     out = torch.empty((B, S, T), dtype=torch.float32, device=device)
     sd = torch.as_tensor(np.asarray(seeds, dtype=np.uint64).view(np.int64), device=device)
     ln = torch.as_tensor(np.asarray(lengths, dtype=np.int32), device=device)
-    check(lib().diffsep_randn_batch(_ptr(out), B, S, T, _ptr(sd), _ptr(ln), stream_id, _stream_ptr()))
+    call(lib(), "diffsep_randn_batch", _ptr(out), B, S, T, _ptr(sd), _ptr(ln), stream_id, _stream_ptr())
     return out
 
 
@@ -520,7 +527,7 @@ def gram(ref, est):
     """[B,S,T] x2 -> float64 [B,3,S,S] = (ref ref^T, ref est^T, est est^T)."""
     B, S, T = ref.shape
     out = torch.empty((B, 3, S, S), dtype=torch.float64, device=ref.device)
-    check(lib().diffsep_gram(_ptr(ref.contiguous()), _ptr(est.contiguous()), _ptr(out), B, S, T, _stream_ptr()))
+    call(lib(), "diffsep_gram", _ptr(ref.contiguous()), _ptr(est.contiguous()), _ptr(out), B, S, T, _stream_ptr())
     return out
 
 
@@ -531,7 +538,8 @@ def longform_plan(T, Tw, Tv):
     K = l.diffsep_longform_plan(int(T), int(Tw), int(Tv), None, 0)
     check(0 if K >= 1 else 1, l)
     starts = (C.c_int64 * K)()
-    check(0 if l.diffsep_longform_plan(int(T), int(Tw), int(Tv), starts, K) == K else 1, l)
+    if l.diffsep_longform_plan(int(T), int(Tw), int(Tv), starts, K) != K:
+        check(1, l)
     return list(starts)
 
 
@@ -553,8 +561,8 @@ def longform_stitch(win, T, Tv, want_gram=False, out=None):
     perm = torch.empty((K, S), dtype=torch.int32, device=win.device)
     gram_ = torch.empty((max(K - 1, 0), S, S), dtype=torch.float64, device=win.device) if want_gram else None
     ws = torch.empty(nbytes, dtype=torch.uint8, device=win.device)
-    check(l.diffsep_longform_stitch(_ptr(win), K, S, Tw, int(T), int(Tv), _ptr(out), _ptr(perm),
-                                    _ptr(gram_) if (want_gram and K > 1) else None, _ptr(ws), nbytes, _stream_ptr()), l)
+    call(l, "diffsep_longform_stitch", _ptr(win), K, S, Tw, int(T), int(Tv), _ptr(out), _ptr(perm), _ptr(gram_) if (want_gram
+         and K > 1) else None, _ptr(ws), nbytes, _stream_ptr())
     return (out, perm, gram_) if want_gram else (out, perm)
 
 
@@ -603,8 +611,8 @@ def stoi(ref, est, fs, extended=True, lengths=None, perm=None):
     nbytes = stoi_workspace_bytes(B, S, T, fs)
     out = torch.empty((B, S), dtype=torch.float64, device=ref.device)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=ref.device)
-    check(lib().diffsep_stoi(_ptr(ref), _ptr(est), _ptr(out), B, S, T, _ptr(ln), _ptr(pm), int(fs), int(bool(extended)),
-                             _ptr(ws), nbytes, _stream_ptr()))
+    call(lib(), "diffsep_stoi", _ptr(ref), _ptr(est), _ptr(out), B, S, T, _ptr(ln), _ptr(pm), int(fs), int(bool(extended)),
+         _ptr(ws), nbytes, _stream_ptr())
     return out
 
 
@@ -628,12 +636,13 @@ def composite(ref, est, fs=16000, lengths=None, perm=None, frames=False):
         from . import metrics  # (metrics imports this module: resolved at the call, no cycle)
         cap = max(1, metrics.composite_num_frames(T, fs))
         fr = torch.full((B, S, 3, cap), float("nan"), dtype=torch.float64, device=ref.device)
-    check(lib().diffsep_composite(_ptr(ref), _ptr(est), _ptr(out), _ptr(fr), cap, B, S, T, _ptr(ln), _ptr(pm), int(fs),
-                                  _ptr(ws), nbytes, _stream_ptr()))
+    call(lib(), "diffsep_composite", _ptr(ref), _ptr(est), _ptr(out), _ptr(fr), cap, B, S, T, _ptr(ln), _ptr(pm), int(fs),
+         _ptr(ws), nbytes, _stream_ptr())
     return (out, fr) if frames else out
 
 
-PIT_MODES = {None: 0, "none": 0, "true_mix": 1, "init_hack_pit": 1, "mean0": 2, "allthetime": 2}
+PIT_MODES = {None: _lib.PIT_NONE, "none": _lib.PIT_NONE, "true_mix": _lib.PIT_TRUE_MIX, "init_hack_pit": _lib.PIT_TRUE_MIX,
+             "mean0": _lib.PIT_MEAN0, "allthetime": _lib.PIT_MEAN0}
 
 
 def _f32c(v):
@@ -651,10 +660,9 @@ def sde_perturb(sde, x0, mix, t, z=None, sigma_mix=None, beta=None, redefine_z=F
     ln = None if lengths is None else _dev_i32(lengths, x0.device)
     x_t = torch.empty_like(x0)
     z_out = torch.empty_like(x0) if z_out is None else z_out
-    sc = _sde(sde)
-    check(lib().diffsep_sde_perturb(C.byref(sc), _ptr(x0), _ptr(mix), _ptr(t), _ptr(z), _ptr(sigma_mix), _ptr(beta),
-                                    int(bool(redefine_z)), _ptr(ln), int(seed) % (1 << 64), int(stream_id), _ptr(x_t),
-                                    _ptr(z_out), B, S, T, _stream_ptr()))
+    call(lib(), "diffsep_sde_perturb", C.byref(sde_config(sde)), _ptr(x0), _ptr(mix), _ptr(t), _ptr(z), _ptr(sigma_mix),
+         _ptr(beta), int(bool(redefine_z)), _ptr(ln), int(seed) % (1 << 64), int(stream_id), _ptr(x_t), _ptr(z_out), B, S, T,
+         _stream_ptr())
     return x_t, z_out
 
 
@@ -678,10 +686,9 @@ def score_loss_reduce(sde, score, z, t, x0=None, mix=None, sigma_mix=None, lengt
     coef = torch.empty((B, 3), dtype=torch.float32, device=score.device) if want_coef else None
     nbytes = score_loss_workspace_bytes(B, S, T)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=score.device)
-    sc = _sde(sde)
-    check(lib().diffsep_score_loss_reduce(C.byref(sc), _ptr(score), _ptr(z), _ptr(x0), _ptr(mix), _ptr(t), _ptr(sigma_mix),
-                                          _ptr(ln), mode, _ptr(out), _ptr(best), _ptr(arg), _ptr(coef), B, S, T, _ptr(ws),
-                                          nbytes, _stream_ptr()))
+    call(lib(), "diffsep_score_loss_reduce", C.byref(sde_config(sde)), _ptr(score), _ptr(z), _ptr(x0), _ptr(mix), _ptr(t),
+         _ptr(sigma_mix), _ptr(ln), mode, _ptr(out), _ptr(best), _ptr(arg), _ptr(coef), B, S, T, _ptr(ws), nbytes,
+         _stream_ptr())
     return (out, best, arg, coef) if want_coef else (out, best, arg)
 
 
@@ -700,17 +707,14 @@ def score_loss(engine, sde, mix_norm, target, t, beta=None, z=None, seed=0, leng
     arg = torch.empty(B, dtype=torch.int32, device=dev)
     x_t = torch.empty_like(target) if debug else None
     score = torch.empty_like(target) if debug else None
-    la = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int64)
-    assert la is None or la.shape == (B,), "lengths must be [B]"
+    la, lp = (None, None) if lengths is None else host_array(lengths, np.int64, B, "lengths")
     nbytes = score_loss_workspace_bytes(B, S, T)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    sc, lc = _sde(sde), LossConfig(mode, int(bool(redefine_z)))
+    sc, lc = sde_config(sde), LossConfig(mode, int(bool(redefine_z)))
     with torch.cuda.device(engine.device):
-        check(engine._L.diffsep_score_loss(engine._h, C.byref(sc), C.byref(lc), _ptr(mix_norm), _ptr(target), _ptr(t),
-                                           _ptr(beta), _ptr(z), int(seed) % (1 << 64),
-                                           la.ctypes.data_as(C.c_void_p) if la is not None else None, _ptr(out), _ptr(best),
-                                           _ptr(arg), _ptr(x_t), _ptr(score), B, T, _ptr(ws), nbytes,
-                                           _stream_ptr(engine.device)), engine._L)
+        call(engine._L, "diffsep_score_loss", engine._h, C.byref(sc), C.byref(lc), _ptr(mix_norm), _ptr(target), _ptr(t),
+             _ptr(beta), _ptr(z), int(seed) % (1 << 64), lp, _ptr(out),
+             _ptr(best), _ptr(arg), _ptr(x_t), _ptr(score), B, T, _ptr(ws), nbytes, _stream_ptr(engine.device))
     return (out, best, arg, x_t, score) if debug else (out, best, arg)
 
 
@@ -732,10 +736,9 @@ def ode_stage_update(sde, K, coef, h, y, k_out=-1, x=None, t=None, score=None, s
     acc = sum_j coef[j] K[j]: x_out = fp32(y + acc h), or (y_new_out given) y_new_out = y + h acc and x_out = fp32 of it.
     K: list of float32 [B,S,T] tensors (written in place at k_out); y float64 [B,S,T]."""
     B, S, T, c = _ode_unit(K, coef, k_out)
-    sc = _sde(sde)
-    check(lib().diffsep_ode_stage_update(C.byref(sc), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y),
-                                         _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), float(h),
-                                         _ptr(x_out), _ptr(y_new_out), B, S, T, _stream_ptr()))
+    call(lib(), "diffsep_ode_stage_update", C.byref(sde_config(sde)), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y),
+         _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), float(h), _ptr(x_out), _ptr(y_new_out), B, S, T,
+         _stream_ptr())
     return x_out, y_new_out
 
 
@@ -745,11 +748,9 @@ def ode_error_norm(sde, K, coef, h, y, rtol, atol, y_new=None, k_out=-1, x=None,
     B, S, T, c = _ode_unit(K, coef, k_out)
     out = torch.empty(2, dtype=torch.float64, device=K[0].device)
     ws = torch.empty(ODE_WORKSPACE_BYTES, dtype=torch.uint8, device=K[0].device)
-    sc = _sde(sde)
-    check(lib().diffsep_ode_error_norm(C.byref(sc), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y), _ptr(y_new),
-                                       _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), float(h),
-                                       float(rtol), float(atol), _ptr(out), B, S, T, _ptr(ws), ws.numel(),
-                                       _stream_ptr()))
+    call(lib(), "diffsep_ode_error_norm", C.byref(sde_config(sde)), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y),
+         _ptr(y_new), _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), float(h), float(rtol), float(atol),
+         _ptr(out), B, S, T, _ptr(ws), ws.numel(), _stream_ptr())
     return out
 
 
@@ -768,10 +769,9 @@ def ode_stage_update_each(sde, K, coef, h, active, lengths, y, k_out=-1, x=None,
     are skipped, samples t >= lengths[b] are never read and written as exact zeros."""
     B, S, T, c = _ode_unit(K, coef, k_out)
     hd, ad, ld = _ode_tables(h, active, lengths, B, K[0].device)
-    sc = _sde(sde)
-    check(lib().diffsep_ode_stage_update_each(C.byref(sc), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y),
-                                              _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), _ptr(hd),
-                                              _ptr(ad), _ptr(ld), _ptr(x_out), _ptr(y_new_out), B, S, T, _stream_ptr()))
+    call(lib(), "diffsep_ode_stage_update_each", C.byref(sde_config(sde)), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix),
+         _ptr(y), _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), _ptr(hd), _ptr(ad), _ptr(ld), _ptr(x_out),
+         _ptr(y_new_out), B, S, T, _stream_ptr())
     return x_out, y_new_out
 
 
@@ -785,9 +785,7 @@ def ode_error_norm_each(sde, K, coef, h, active, lengths, y, rtol, atol, y_new=N
         out = torch.zeros(B, 2, dtype=torch.float64, device=K[0].device)
     assert out.shape == (B, 2) and out.dtype == torch.float64 and out.is_contiguous()
     ws = torch.empty(B * ODE_WORKSPACE_BYTES, dtype=torch.uint8, device=K[0].device)
-    sc = _sde(sde)
-    check(lib().diffsep_ode_error_norm_each(C.byref(sc), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix), _ptr(y),
-                                            _ptr(y_new), _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out),
-                                            _ptr(hd), _ptr(ad), _ptr(ld), float(rtol), float(atol), _ptr(out), B, S, T,
-                                            _ptr(ws), ws.numel(), _stream_ptr()))
+    call(lib(), "diffsep_ode_error_norm_each", C.byref(sde_config(sde)), _ptr(x), _ptr(t), _ptr(score), _ptr(sigma_mix),
+         _ptr(y), _ptr(y_new), _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), _ptr(hd), _ptr(ad), _ptr(ld),
+         float(rtol), float(atol), _ptr(out), B, S, T, _ptr(ws), ws.numel(), _stream_ptr())
     return out

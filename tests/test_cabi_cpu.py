@@ -8,12 +8,14 @@ import re
 import numpy as np
 import pytest
 
+import cabi_header as H
 import diffsep_oracle as O
 from diffsep_amd import _lib
-from diffsep_amd.engine import pack_state_dict, param_table
+from diffsep_amd.engine import Engine, pack_state_dict, param_table
 from diffsep_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+STRUCT_CLASSES = {name: getattr(_lib, cls) for name, cls in H.STRUCTS.items()}
 
 
 @pytest.mark.parametrize("kind", ["bf16", "f16"])
@@ -115,26 +117,64 @@ def test_engine_refuses_to_run_without_gpu():
 
 def test_ctypes_structs_mirror_the_header():
     # field order and C types of every struct of the boundary: a silent mismatch would shift every argument after it
-    hdr = open(os.path.join(ROOT, "include", "diffsep_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    ctype = {"int32_t": C.c_int32, "float": C.c_float, "const int64_t*": C.POINTER(C.c_int64),
-             "const uint64_t*": C.POINTER(C.c_uint64), "diffsep_engine*": C.c_void_p}
-    want = {"diffsep_model_config": _lib.ModelConfig, "diffsep_sde_config": _lib.SdeConfig,
-            "diffsep_sampler_config": _lib.SamplerConfig, "diffsep_sampler_ext": _lib.SamplerExt}
-    for body, name in re.findall(r"typedef struct \{(.*?)\}\s*(\w+);", hdr, flags=re.S):
-        if name not in want:
-            continue
-        fields = []
-        for decl in [d.strip() for d in body.split(";") if d.strip()]:
-            m = re.match(r"(.+?[\s*])([\w\[\], ]+)$", decl)
-            typ, names = m.group(1).strip().replace(" *", "*"), m.group(2)
-            for nm in [n.strip() for n in names.split(",")]:
-                arr = re.match(r"(\w+)\[(\d+)\]", nm)
-                fields.append((arr.group(1), ctype[typ] * int(arr.group(2))) if arr else (nm, ctype[typ]))
-        mine = [(n, t) for n, t in want.pop(name)._fields_]
-        assert [n for n, _ in mine] == [n for n, _ in fields], name
-        assert all(C.sizeof(a) == C.sizeof(b) for (_, a), (_, b) in zip(mine, fields)), name
+    # (names, classes, sizes AND offsets: H.compare_structs lays the header's own types out with ctypes)
+    parsed = H.parse(H.read_header())
+    want = dict(STRUCT_CLASSES)
+    assert len(want) == 9
+    for name, fields in parsed[1].items():
+        assert name in want, f"{name}: struct of the header that this test does not list"
+        mine = want.pop(name)._fields_
+        assert [n for n, _ in mine] == [n for n, _, _ in fields], name
+        assert all(C.sizeof(a) == C.sizeof(H.field_ctype(typ, arr)) for (_, a), (_, typ, arr) in zip(mine, fields)), name
     assert not want, f"structs not found in the header: {list(want)}"
+    assert H.compare_structs(parsed, STRUCT_CLASSES) == []
+
+
+def test_ctypes_signatures_mirror_the_header():
+    # result type, argument count and every argument's class of all prototypes: ctypes converts to whatever _SIGS says
+    # without a word (a truncated int64_t, a float where a double is read, every later argument shifted)
+    parsed = H.parse(H.read_header())
+    assert len(parsed[0]) >= 86 and set(parsed[0]) == set(_lib.EXPORTS)
+    assert H.compare_prototypes(parsed, _lib._SIGS, STRUCT_CLASSES) == []
+
+
+def test_header_constants_have_python_twins():
+    parsed = H.parse(H.read_header())
+    assert len(parsed[2]) >= 26 and "DIFFSEP_GN_UP_TILED" in parsed[2] and "DIFFSEP_ODE_WORKSPACE_BYTES" in parsed[2]
+    assert H.compare_constants(parsed, _lib, Engine.CONV_CLASSES) == []
+
+
+def test_header_check_sees_what_it_should():
+    """the checker can fail: each mutation of the header text (in memory; nothing is written, no library is loaded) yields a
+    difference that names the function or struct it touches, and the header as it is yields none"""
+    hdr = H.read_header()
+
+    def diffs(text):
+        parsed = H.parse(text)
+        return H.compare(parsed, _lib._SIGS, STRUCT_CLASSES) + H.compare_constants(parsed, _lib, Engine.CONV_CLASSES)
+
+    def mutated(old, new, count=1):
+        assert hdr.count(old) == count, old
+        return hdr.replace(old, new)
+    assert diffs(hdr) == []
+    swapped = mutated("int32_t method; ", "int32_t max_nfe; ")
+    assert swapped.count("int32_t max_nfe;     /* 0: unbounded") == 1
+    swapped = swapped.replace("int32_t max_nfe;     /* 0: unbounded", "int32_t method;     /* 0: unbounded")
+    cases = [
+        (mutated("const int32_t* perm, int32_t fs, int32_t extended,", "const int32_t* perm, int32_t fs,"), "diffsep_stoi:"),
+        (mutated("int32_t diffsep_gram(const float* ref, const float* est, double* out, int32_t B, int32_t S, int64_t T,",
+                 "int32_t diffsep_gram(const float* ref, const float* est, double* out, int32_t B, int32_t S, int32_t T,"),
+         "diffsep_gram argument 5 (T)"),
+        (mutated("int32_t ldx, int32_t ldr, int32_t ldy, float out_scale,", "int32_t ldx, int32_t ldr, int32_t ldy, double out_scale,"),
+         "diffsep_conv2d argument 15 (out_scale)"),
+        (swapped, "diffsep_ode_config:"),
+        (mutated("char kernel[128];", "char kernel[64];"), "diffsep_prof_record"),
+        (mutated("#define DIFFSEP_GN_UP_TILED 7", "#define DIFFSEP_GN_UP_TILED 8"), "DIFFSEP_GN_UP_TILED:"),
+        (mutated("#ifdef __cplusplus\n}", "int32_t diffsep_new_thing(void* p);\n#ifdef __cplusplus\n}"), "diffsep_new_thing:"),
+    ]
+    for text, where in cases:
+        found = diffs(text)
+        assert found and all(d.startswith(where) for d in found), (where, found)
 
 
 def test_dtype_codes_match_the_header():
