@@ -29,12 +29,13 @@
 #include "common.h"
 #include "pair_metrics.h"
 #include "reduce_device.h"
+#include "resample_design.h"
 
 namespace {
 
 constexpr int kFs = 10000, kNw = 256, kHop = 128, kNfft = 512, kBands = 15, kSeg = 30;
 constexpr double kDyn = 40.0, kEps = 2.220446049250313e-16;  // np.finfo(float64).eps
-constexpr int kMaxRatio = 1000;  // largest p or q of the reduced 10000 / fs the tap table is built for
+constexpr int kMaxRatio = kResampleMaxRatio;  // largest p or q of the reduced 10000 / fs the tap table is built for
 
 struct Ratio { int p, q, L; };
 
@@ -45,10 +46,8 @@ bool stoi_ratio(int fs, Ratio* r) {
   while (b) { int t = a % b; a = b; b = t; }
   r->p = kFs / a;
   r->q = fs / a;
-  const int m = r->p > r->q ? r->p : r->q;
-  if (m > kMaxRatio) return false;
-  const double fc = 1.0 / (2.0 * m);
-  r->L = (r->p == 1 && r->q == 1) ? 0 : (int)std::ceil((60.0 - 8.0) / (28.714 * fc / 10.0));
+  if ((r->p > r->q ? r->p : r->q) > kMaxRatio) return false;
+  r->L = ds_resample_half_length(r->p, r->q);
   return true;
 }
 
@@ -106,21 +105,7 @@ void stoi_build_table(const Ratio& r, std::vector<double>& t) {
     t[kTabCos + j] = std::cos(2.0 * pi * j / kNfft);
     t[kTabSin + j] = -std::sin(2.0 * pi * j / kNfft);
   }
-  if (r.L > 0) {  // Kaiser-windowed sinc, unit DC gain after the zero stuffing
-    const int m = r.p > r.q ? r.p : r.q;
-    const double fc = 1.0 / (2.0 * m), beta = 0.1102 * (60.0 - 8.7), i0b = std::cyl_bessel_i(0.0, beta);
-    double sum = 0.0;
-    for (int k = 0; k <= 2 * r.L; ++k) {
-      const double tt = (double)(k - r.L), u = tt / r.L, a = 2.0 * fc * tt;
-      const double win = std::cyl_bessel_i(0.0, beta * std::sqrt(std::fmax(0.0, 1.0 - u * u))) / i0b;
-      const double sinc = (k == r.L) ? 1.0 : std::sin(pi * a) / (pi * a);
-      t[kTabTaps + k] = win * (2.0 * r.p * fc * sinc);
-      sum += t[kTabTaps + k];
-    }
-    for (int k = 0; k <= 2 * r.L; ++k) t[kTabTaps + k] = t[kTabTaps + k] / sum * r.p;
-  } else {
-    t[kTabTaps] = 1.0;
-  }
+  ds_resample_design(r.p, r.q, r.L, &t[kTabTaps]);  // Kaiser-windowed sinc, unit DC gain after the zero stuffing
 }
 
 struct StoiBandsP { int lo[kBands], hi[kBands]; };

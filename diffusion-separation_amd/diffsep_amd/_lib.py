@@ -12,6 +12,7 @@ LIB_PATHS = {"bf16": LIB_PATH, "f16": os.environ.get("DIFFSEP_LIB_F16", os.path.
 F32, BF16 = 0, 1
 F32_SPLIT = 2  # fp32 tensors; matrix products as 3 bf16 MFMAs on hi / lo halves (include/diffsep_hip.h)
 F16 = 3        # Python-side only: dtype code 1 (16-bit storage) of the half-precision build
+F64 = 4        # float64 rows: an output type of diffsep_resample only
 SDE_MIX, SDE_PRIORMIX = 0, 1
 PRED_REVERSE_DIFFUSION, PRED_EULER_MARUYAMA, PRED_NONE = 0, 1, 2
 CORR_ALD2, CORR_NONE, CORR_ALD, CORR_LANGEVIN = 0, 1, 2, 3
@@ -208,6 +209,12 @@ _SIGS = {
     "diffsep_stoi": (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _I, _I, _P, _L, _P]),
     "diffsep_composite_workspace_bytes": (_L, [_I, _I, _L, _I]),
     "diffsep_composite": (_I, [_P, _P, _P, _P, _L, _I, _I, _L, _P, _P, _I, _P, _L, _P]),
+    "diffsep_resample_ratio": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "diffsep_resample_length": (_L, [_L, _I, _I]),
+    "diffsep_resample_design": (_I, [_I, _I, _P, _I]),
+    "diffsep_resampler_create": (_I, [_I, _I, _P, _I, C.POINTER(_P)]),
+    "diffsep_resampler_destroy": (None, [_P]),
+    "diffsep_resample": (_I, [_P, _P, _L, _P, _L, _I, _L, _P, _I, _P, _I, _P]),
     "diffsep_longform_plan": (_I, [_L, _L, _L, C.POINTER(_L), _I]),
     "diffsep_longform_locate": (_I, [_L, _L, _L, _L, C.POINTER(_I), C.POINTER(_L), C.POINTER(_L)]),
     "diffsep_longform_workspace_bytes": (_L, [_I, _I]),

@@ -14,9 +14,12 @@ Extensions: every channel record also holds llr / wss / segsnr, the three signal
 is not restated: --pesq-json FILE ({sample: [pesq per channel]}, computed elsewhere) supplies it; without the file the package is
 used if it imports; without both csig / cbak / covl are null and the summary lists them under "not_computed".
 
-Differences from the reference, on purpose: it resamples every file to 16 kHz with librosa; here a file at another rate is
-refused by name.  Its PESQ call sees the signals after SSNR has removed their means and rescaled the estimate in place (a quirk,
-kept: the package, when present, is handed the same signals)."""
+Differences from the reference, on purpose: it resamples every file to 16 kHz with librosa's default resampler; here a file at
+another rate is refused by name, unless --resample asks for the conversion: then it is converted with the PROJECT's filter
+(metrics.resample_filter: Octave's Kaiser-windowed sinc, 60 dB; not librosa's), by the HIP resampler --batch files at a time with
+--on device and by metrics.resample with --on host, both on the same taps, rounded to float32 like a loaded file.  Its PESQ
+call sees the signals after SSNR has removed their means and rescaled the estimate in place (a quirk, kept: the package, when
+present, is handed the same signals)."""
 import argparse
 import json
 import re
@@ -39,12 +42,44 @@ def filename_tgt2enh(tgt_path, enhanced_path):
     return int(m.group(1)), int(m.group(2)), enhanced_path / f"{m.group(1)}{sep}enh{m.group(2)}.wav"
 
 
-def _load(path):
+def _load(path, resample=False):
+    """channel 0 of the file; resample=False: refused unless it is at 16 kHz, True: (samples, rate) whatever the rate"""
     wav, sr = wavio.load(path)
+    if resample:
+        return wav[0].numpy(), sr
     if sr != FS:
         raise SystemExit(f"{path}: sample rate {sr}, not {FS} (the reference resamples with librosa; this tool does not: "
-                         "resample the file first)")
+                         "resample the file first, or pass --resample for the project's own filter)")
     return wav[0].numpy()
+
+
+def _to_16k(loaded, on, batch):
+    """[(samples, rate)] -> float32 samples at 16 kHz: files at another rate through the project's filter, on the device `batch`
+    rows of one rate per launch (ops.Resampler on the taps metrics.resample uses) or on the host (metrics.resample)"""
+    out = [x if sr == FS else None for x, sr in loaded]
+    for sr in sorted({sr for _, sr in loaded if sr != FS}):
+        sel = [i for i, (_, r) in enumerate(loaded) if r == sr]
+        if on == "host":
+            for i in sel:
+                out[i] = metrics.resample(loaded[i][0].astype(np.float64), FS, sr).astype(np.float32)
+            continue
+        import torch
+        from . import ops
+        if not torch.cuda.is_available():
+            raise SystemExit("--on device needs a GPU (use --on host)")
+        h, p, _ = metrics.resample_filter(FS, sr)
+        rs = ops.Resampler(sr, FS, taps=h * p)
+        for k in range(0, len(sel), batch):
+            part = sel[k:k + batch]
+            lens = [len(loaded[i][0]) for i in part]
+            x = np.zeros((len(part), max(lens)), np.float32)
+            for b, i in enumerate(part):
+                x[b, :lens[b]] = loaded[i][0]
+            y, new = rs(torch.from_numpy(x).cuda(), lengths=lens)
+            y = y.cpu().numpy()
+            for b, i in enumerate(part):
+                out[i] = y[b, :new[b]]
+    return out
 
 
 def _pesq_fn():
@@ -89,6 +124,9 @@ def main(argv=None):
     ap.add_argument("--on", choices=["host", "device"], default="device",
                     help="where LLR / WSS / segmental SNR are computed: numpy on the host, or the HIP kernels (default)")
     ap.add_argument("--batch", type=int, default=16, help="--on device: files per kernel call (zero-padded to the longest)")
+    ap.add_argument("--resample", action="store_true",
+                    help="convert files that are not at 16 kHz with the project's filter (--on device: the HIP resampler, --batch "
+                         "files per launch; --on host: numpy) instead of refusing them")
     ap.add_argument("--pesq-json", type=Path, default=None, help="{sample index: [PESQ per channel]} computed elsewhere")
     args = ap.parse_args(argv)
 
@@ -101,8 +139,10 @@ def main(argv=None):
     if not todo:
         raise SystemExit(f"{args.clean_path}: no NNNN.tgtK.wav file")
     pairs = []
-    for _, _, tgt, enh in todo:
-        ref, est = _load(tgt), _load(enh)
+    if args.resample:
+        loaded = _to_16k([_load(f, True) for _, _, tgt, enh in todo for f in (tgt, enh)], args.on, max(1, args.batch))
+    for k, (_, _, tgt, enh) in enumerate(todo):
+        ref, est = (loaded[2 * k], loaded[2 * k + 1]) if args.resample else (_load(tgt), _load(enh))
         n = min(len(ref), len(est))  # (evaluate_covl.py:23-26)
         pairs.append((ref[:n], est[:n]))
 

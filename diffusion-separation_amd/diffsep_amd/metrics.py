@@ -98,6 +98,11 @@ def _resample(x, fs_to, fs_from):
     return resample_poly(x, p, q, window=h)
 
 
+# the host form under public names (ops.Resampler is the device form of the same definition with the same filter)
+resample_filter = _resample_filter
+resample = _resample
+
+
 def _thirdoct(fs, nfft, num_bands, min_freq):
     """[num_bands, nfft/2+1] 0/1 matrix: DFT bins of each one-third octave band (band edges snapped to the nearest bin)"""
     f = np.linspace(0, fs, nfft + 1)[: nfft // 2 + 1]

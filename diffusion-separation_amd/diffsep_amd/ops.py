@@ -641,6 +641,114 @@ def composite(ref, est, fs=16000, lengths=None, perm=None, frames=False):
     return (out, fr) if frames else out
 
 
+def resample_ratio(fs_in, fs_out):
+    """(p, q) = fs_out / fs_in reduced (diffsep_resample_ratio: host arithmetic; raises for rates <= 0 or a factor beyond 1000)"""
+    p, q = C.c_int32(), C.c_int32()
+    call(lib(), "diffsep_resample_ratio", int(fs_in), int(fs_out), C.byref(p), C.byref(q))
+    return p.value, q.value
+
+
+def resample_length(n, p, q):
+    """ceil(n p / q): the samples a row of n samples becomes (diffsep_resample_length: host arithmetic)"""
+    return _workspace_bytes(lib().diffsep_resample_length, n, p, q)
+
+
+def resample_design(p, q):
+    """the project's anti-aliasing FIR of the reduced ratio p / q as the library designs it: float64 [2 L + 1], summing to p
+    (diffsep_resample_design: host arithmetic; metrics.resample_filter(p, q)[0] * p up to libm's Bessel and sine)"""
+    l = lib()
+    n = l.diffsep_resample_design(int(p), int(q), None, 0)
+    check(0 if n >= 1 else 1, l)
+    taps = np.zeros(n, dtype=np.float64)
+    check(0 if l.diffsep_resample_design(int(p), int(q), taps.ctypes.data_as(C.c_void_p), n) == n else 1, l)
+    return taps
+
+
+class _ResamplerHandle:
+    """a diffsep_resampler of the current device: the polyphase-ordered tap table of (p, q, taps)"""
+
+    def __init__(self, p, q, taps):
+        taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float64))
+        if taps.ndim != 1:
+            raise ValueError("Resampler: taps must be a vector")
+        self.ptr = C.c_void_p()
+        self.device = torch.cuda.current_device()
+        call(lib(), "diffsep_resampler_create", p, q, taps.ctypes.data_as(C.c_void_p), taps.size, C.byref(self.ptr))
+
+    def __del__(self):
+        if getattr(self, "ptr", None):
+            try:
+                lib().diffsep_resampler_destroy(self.ptr)
+            except Exception:  # (interpreter shutdown: the library may be gone already)
+                pass
+            self.ptr = None
+
+
+class Resampler:
+    """Band-limited sample-rate conversion fs_in -> fs_out on the device (csrc/resample.hip): y[m] = sum_j h[m q + L - p j] x[j]
+    with p / q = fs_out / fs_in reduced, in float64 from the fp32 samples on.  taps=None: the project's filter
+    (resample_design(p, q); one device table per (device, p, q) for the life of the process); otherwise any odd-length float64
+    FIR h, applied as given, with a table of this object's own.
+
+    resampler(x, lengths=None, out=None, dtype=torch.float32): x [..., T] float32 device tensor, lengths (one per index of x's
+    first dimension, host values or a device int32 tensor; default T) -> (y [..., ceil(T p / q)] of dtype float32 / float64, new
+    lengths: host ints for host lengths, a device int32 tensor for device lengths).  Columns past a row's own new length are
+    zeros; T = 0 gives empty rows.  out: a dense tensor of y's shape and dtype to write into.  Asynchronous on the current stream, no readback."""
+    _designed = {}
+
+    def __init__(self, fs_in, fs_out, taps=None):
+        self.fs_in, self.fs_out = int(fs_in), int(fs_out)
+        self.p, self.q = resample_ratio(fs_in, fs_out)
+        self._taps = taps
+        self._own = {}
+
+    def _handle(self, device):
+        cache, key = (Resampler._designed, (device.index, self.p, self.q)) if self._taps is None else (self._own, device.index)
+        if key not in cache:
+            with torch.cuda.device(device):
+                cache[key] = _ResamplerHandle(self.p, self.q, resample_design(self.p, self.q) if self._taps is None else self._taps)
+        return cache[key]
+
+    def length(self, n):
+        return resample_length(n, self.p, self.q)
+
+    def __call__(self, x, lengths=None, out=None, dtype=torch.float32):
+        if x.dim() < 1 or x.dtype != torch.float32 or not x.is_cuda:
+            raise ValueError("Resampler: x must be a float32 [..., T] device tensor")
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError("Resampler: dtype must be float32 or float64")
+        x = x.contiguous()
+        T = x.shape[-1]
+        rows = x.numel() // max(T, 1)
+        groups = x.shape[0] if x.dim() > 1 else 1
+        n_max = self.length(T)
+        shape = tuple(x.shape[:-1]) + (n_max,)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=x.device)
+        elif out.dtype != dtype or not out.is_contiguous() or tuple(out.shape) != shape or out.device != x.device:
+            raise ValueError(f"Resampler: out must be a dense {dtype} tensor of shape {shape} on x's device")
+        ln = ln_out = None
+        if lengths is None:
+            new = [n_max] * groups
+        else:
+            on_device = isinstance(lengths, torch.Tensor) and lengths.is_cuda
+            ln = _dev_i32(lengths, x.device)
+            if ln.numel() != groups:
+                raise ValueError("Resampler: one length per index of x's first dimension")
+            if on_device:
+                new = ln_out = torch.empty(groups, dtype=torch.int32, device=x.device)
+            else:
+                new = [self.length(min(max(int(v), 0), T)) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        if rows == 0 or T == 0:  # nothing to convert (a file without samples): empty rows, lengths 0
+            if ln_out is not None:
+                ln_out.zero_()
+            return out, new
+        with torch.cuda.device(x.device):
+            call(lib(), "diffsep_resample", self._handle(x.device).ptr, _ptr(x), T, _ptr(out), n_max, rows, T, _ptr(ln),
+                 max(1, rows // max(groups, 1)), _ptr(ln_out), _lib.F32 if dtype == torch.float32 else _lib.F64, _stream_ptr(x.device))
+        return out, new
+
+
 PIT_MODES = {None: _lib.PIT_NONE, "none": _lib.PIT_NONE, "true_mix": _lib.PIT_TRUE_MIX, "init_hack_pit": _lib.PIT_TRUE_MIX,
              "mean0": _lib.PIT_MEAN0, "allthetime": _lib.PIT_MEAN0}
 

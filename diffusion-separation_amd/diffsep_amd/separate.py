@@ -16,7 +16,12 @@ cut into windows of that length (ops.longform_plan; the overlap defaults to an e
 what --batch groups and --streams keeps in flight, and a file is stitched on the device (ops.longform_stitch: source orders
 aligned over the overlaps, seams cross-faded) and written when its last window has been collected; a file
 no longer than the chunk is handled as without --chunk.  --sampler ode [--rtol --atol --max-nfe] runs the
-probability-flow ODE sampler (sdes.get_ode_sampler, adaptive RK45 on the device) instead of the PC sampler.  With
+probability-flow ODE sampler (sdes.get_ode_sampler, adaptive RK45 on the device) instead of the PC sampler.
+--resample {file,model}: a file whose rate is not the model's is converted to the model's rate on the device (ops.Resampler,
+csrc/resample.hip: the project's Kaiser-windowed sinc; channel 0, one launch per distinct rate of a batch) and separated exactly as
+a file of ceil(n p / q) samples at that rate would be; `file` converts every source back and crops it to the file's own n samples
+(written at the file's rate), `model` writes at the model's rate.  With --chunk the whole file is converted first (one launch per
+file, not per rate of a batch), then cut into windows.  A file already at the model's rate meets no resampler; without the flag such files only draw the reference's warning.  With
 --batch 1 a file is one engine call; with --batch K > 1 the files of a batch (the same plan as the PC path) share every
 network evaluation while each keeps its own step controller (diffsep_ode_sample_each), so with --dtype f32 the written
 files are those of --batch 1, bit for bit wherever the network evaluation does not depend on the batch.  --streams stays 1 there: the ODE driver blocks on a readback per step
@@ -55,6 +60,81 @@ def get_model(args):
 def scale_output(mix, sep):
     """separate.py:73-78, in the HIP kernel."""
     return ops.scale_output(mix.contiguous(), sep.contiguous())
+
+
+class Rates:
+    """The files' sample rates against the model's.  mode None (no --resample): a mismatch draws the reference's warning
+    (separate.py:151-155, quirk Q9) and the samples go to the model as they are.  mode "file" / "model": such a file is converted
+    to the model's rate on the device before anything else sees it; `lengths` are then the files' lengths at that rate, which is
+    what batches and windows are planned with."""
+
+    def __init__(self, mode, model_sr, files):
+        info = [wavio.info(p) for p in files]
+        self.mode, self.model_sr, self.files = mode, model_sr, files
+        self.rates, self.ns = [sr for sr, _ in info], [n for _, n in info]
+        self.lengths = [ops.Resampler(sr, model_sr).length(n) if self.converts(sr) else n for sr, n in zip(self.rates, self.ns)]
+
+    def converts(self, sr):
+        return self.mode is not None and sr != self.model_sr
+
+    def load(self, i):
+        """channel 0 of file i as a host tensor [1, n] (with the warning where the rate is wrong and nothing converts it)"""
+        wav, sr = wavio.load(self.files[i])
+        if sr != self.model_sr and self.mode is None:
+            print(f"Warning: {self.files[i].stem}: this model expects {self.model_sr} Hz, but the file is {sr} Hz.")
+        return wav[:1]
+
+    def rows(self, idx, wavs, device):
+        """files idx, loaded as wavs -> their [1, n] rows at the model's rate: the host tensors themselves where nothing is
+        converted, device tensors from ONE resample launch per distinct rate otherwise"""
+        out = list(wavs)
+        for sr in sorted({self.rates[i] for i in idx if self.converts(self.rates[i])}):
+            sel = [k for k, i in enumerate(idx) if self.rates[i] == sr]
+            x, _, ns = datasets.pad_batch([(wavs[k], wavs[k]) for k in sel], side="right")
+            y, new = ops.Resampler(sr, self.model_sr)(inflight.upload(x, device), lengths=ns)
+            for r, k in enumerate(sel):
+                out[k] = y[r, :, :new[r]]
+        return out
+
+    def restore(self, idx, seps):
+        """seps[k] [S, lengths[i]] on the device, the sources of file i = idx[k] at the model's rate -> [(sources [S, n], rate)]
+        as they are written: at the file's rate and cropped to its own n samples (mode "file": ceil(ceil(n p / q) q / p) >= n,
+        always a crop; one launch per distinct rate), else untouched at the model's rate (at the file's without --resample)"""
+        out = [(x, self.rates[i] if self.mode is None else self.model_sr) for i, x in zip(idx, seps)]
+        if self.mode != "file":
+            return out
+        for sr in sorted({self.rates[i] for i in idx if self.converts(self.rates[i])}):
+            sel = [k for k, i in enumerate(idx) if self.rates[i] == sr]
+            tmax = max(seps[k].shape[-1] for k in sel)
+            x = torch.stack([torch.nn.functional.pad(seps[k], (0, tmax - seps[k].shape[-1])) for k in sel])
+            y, _ = ops.Resampler(self.model_sr, sr)(x, lengths=[seps[k].shape[-1] for k in sel])
+            for r, k in enumerate(sel):
+                out[k] = (y[r, :, :self.ns[idx[k]]], sr)
+        return out
+
+
+def padded_on_device(parts, to, device):
+    """[1, n_b] rows on the host or on the device -> (mix [B,1,to] on the device, right-zero-padded; lengths [B])"""
+    if not any(p.is_cuda for p in parts):
+        mix, _, lens = datasets.pad_batch([(p, p) for p in parts], side="right", to=to)
+        return inflight.upload(mix, device), lens
+    lens = [int(p.shape[-1]) for p in parts]
+    mix_d = torch.zeros((len(parts), 1, int(to)), dtype=torch.float32, device=device)
+    host = [b for b, p in enumerate(parts) if not p.is_cuda]
+    if host:
+        up = inflight.upload(datasets.pad_batch([(parts[b], parts[b]) for b in host], side="right")[0], device)
+    for b, p in enumerate(parts):
+        mix_d[b, :, :lens[b]] = p if p.is_cuda else up[host.index(b), :, :lens[b]]
+    return mix_d, lens
+
+
+def write_sources(output_dir, stem, sources, sr):
+    """sources [S, n] -> output_dir/s{k}/stem.wav, 32-bit float (separate.py:157-162)"""
+    sources = sources.cpu()
+    for k in range(sources.shape[0]):
+        d = output_dir / f"s{k}"
+        d.mkdir(parents=True, exist_ok=True)
+        wavio.save(d / f"{stem}.wav", sources[k:k + 1], sr, bits=32)
 
 
 def separate_on_device(mix, model, sampler_kwargs, device, lengths=None, seeds=None, check_finite=False):
@@ -130,10 +210,12 @@ def chunk_samples(args, fs):
     return window, overlap
 
 
-def separate_chunked(args, files, lengths, seeds, models, streams, kw, model_sr):
+def separate_chunked(args, files, rates, seeds, models, streams, kw):
     """--chunk: the windows of all files (file-major) are the items of the batches in flight; window results stay on the device
-    until their file's last one has been collected, then the file is stitched there and written."""
-    window, overlap = chunk_samples(args, model_sr)
+    until their file's last one has been collected, then the file is stitched there and written.  (--resample: a file is
+    converted whole, one launch per file, when its first window is launched; windows are cut from the converted row.)"""
+    lengths = rates.lengths
+    window, overlap = chunk_samples(args, rates.model_sr)
     eng = models[0].score_model.engine()
     items, item_lengths, starts = inflight.plan_windows(lengths, window, overlap, ops.longform_plan)
     if seeds is None:  # one draw of torch's generator per file, as a file without --seed gets one per engine call
@@ -141,37 +223,42 @@ def separate_chunked(args, files, lengths, seeds, models, streams, kw, model_sr)
     wseeds = [inflight.window_seeds(seeds[i], len(starts[i])) for i in range(len(files))]
     batches = inflight.plan_batches(range(len(items)), item_lengths, eng.padded_frames, max(1, args.batch))
     inflight.reserve_largest(models, batches, item_lengths)
-    wavs, done = {}, {}  # per file: (samples, rate) while windows of it are still to be launched; collected windows by index
+    wavs, done = {}, {}  # per file: its row while windows of it are still to be launched; collected windows by index
 
     def load(i):
+        """file i's row at the model's rate, for one more window.  A converted row lives on the device and was written on the
+        stream of the launch that met the file first; later windows are cut on other workers' streams.  So the conversion
+        leaves an event, every stream waits for it before it reads the row, and the row is marked as in use on that stream
+        (record_stream): its memory, from the converting stream's pool, is not handed out again while a read is pending."""
         if i not in wavs:
-            wav, sr = wavio.load(files[i])
-            if sr != model_sr:  # the reference only warns (separate.py:151-155, quirk Q9)
-                print(f"Warning: {files[i].stem}: this model expects {model_sr} Hz, but the file is {sr} Hz.")
-            wavs[i] = (wav[:1], sr, len(starts[i]))
-        wav, sr, left = wavs[i]
-        wavs[i] = (wav, sr, left - 1)
+            row = rates.rows([i], [rates.load(i)], args.device)[0]
+            ready = None
+            if row.is_cuda:
+                ready = torch.cuda.Event()
+                ready.record()
+            wavs[i] = (row, ready, len(starts[i]))
+        row, ready, left = wavs[i]
+        wavs[i] = (row, ready, left - 1)
         if left == 1:
             del wavs[i]
-        return wav, sr
+        if ready is not None:
+            cur = torch.cuda.current_stream()
+            cur.wait_event(ready)
+            row.record_stream(cur)
+        return row
 
     def launch(w, j, group):
-        parts, srs = [], []
+        parts = []
         for n in group:
             i, k = items[n]
-            wav, sr = load(i)
-            seg = wav[:, starts[i][k]:starts[i][k] + item_lengths[n]]
-            parts.append((seg, seg))
-            srs.append(sr)
-        mix, _, lens = datasets.pad_batch(parts, side="right",
-                                          to=eng.bucket_length(eng.padded_frames(max(item_lengths[n] for n in group))))
+            parts.append(load(i)[:, starts[i][k]:starts[i][k] + item_lengths[n]])
+        mix_d, lens = padded_on_device(parts, eng.bucket_length(eng.padded_frames(max(item_lengths[n] for n in group))), args.device)
         sds = [wseeds[items[n][0]][items[n][1]] for n in group]
-        mix_d = inflight.upload(mix, args.device)
         sep = separate_on_device(mix_d, models[w], kw, args.device, lengths=lens, seeds=sds)
-        return group, lens, srs, sep, mix_d, sds
+        return group, lens, sep, mix_d, sds, parts  # (parts: what the copies into mix_d read stays referenced until the stream drains)
 
     def collect(w, item):
-        group, lens, srs, sep, mix_d, sds = item
+        group, lens, sep, mix_d, sds, _ = item
         sep = inflight.finite_or_rerun(
             models[w], streams[w], (sep,),
             lambda fb: (separate_on_device(mix_d, fb, kw, args.device, lengths=lens, seeds=sds),),
@@ -188,12 +275,10 @@ def separate_chunked(args, files, lengths, seeds, models, streams, kw, model_sr)
                     out = got[0]
                 else:
                     out, _ = ops.longform_stitch(torch.stack([got[q] for q in range(len(got))]), lengths[i], overlap)
+                (out, sr), = rates.restore([i], [out])
                 out = out.cpu()
             del done[i]
-            for q in range(out.shape[0]):
-                d = args.output_dir / f"s{q}"
-                d.mkdir(parents=True, exist_ok=True)
-                wavio.save(d / f"{files[i].stem}.wav", out[q:q + 1], srs[b], bits=32)
+            write_sources(args.output_dir, files[i].stem, out, sr)
 
     inflight.Ring(streams, launch, collect).run(batches)
     print(f"separated {len(files)} files into {args.output_dir} ({len(items)} windows of up to {window} samples)")
@@ -229,6 +314,10 @@ def main(argv=None):
                          "separate the windows as the items of --batch / --streams and stitch them on the device")
     ap.add_argument("--overlap", type=float, default=None, metavar="SECONDS",
                     help="with --chunk: overlap of neighbouring windows (default: an eighth of the chunk; at most a third)")
+    ap.add_argument("--resample", default=None, choices=["file", "model"],
+                    help="convert a file whose rate is not the model's to the model's rate on the device, separate it there, and "
+                         "write the sources back at the file's rate, cropped to its length (file), or at the model's rate (model); "
+                         "default: such a file only draws a warning and its samples go to the model as they are")
     args = ap.parse_args(argv)
     if args.chunk is None and args.overlap is not None:
         raise SystemExit("--overlap goes with --chunk")
@@ -254,79 +343,55 @@ def main(argv=None):
         raise ValueError("Output directory is a file")
     args.output_dir.mkdir(parents=True, exist_ok=True)
     files = sorted(args.input_dir.glob("*.wav"))
-    lengths = [wavio.info(p)[1] for p in files]
+    rates = Rates(args.resample, model_sr, files)
+    lengths = rates.lengths
     seeds = inflight.utterance_seeds(len(files), args.seed) if args.seed is not None else None
     if args.sampler == "ode" and args.batch > 1:
         ode_kw = {"N": kw["N"], "denoise": args.denoise, "rtol": args.rtol, "atol": args.atol, "max_nfe": args.max_nfe}
         eng = model.score_model.engine()
         for group in inflight.plan_batches(range(len(files)), lengths, eng.padded_frames, args.batch):
-            items, srs = [], []
-            for i in group:
-                wav, sr = wavio.load(files[i])
-                if sr != model_sr:  # the reference only warns (separate.py:151-155, quirk Q9)
-                    print(f"Warning: {files[i].stem}: this model expects {model_sr} Hz, but the file is {sr} Hz.")
-                items.append((wav[:1], wav[:1]))
-                srs.append(sr)
-            mix, _, lens = datasets.pad_batch(items, side="right",
-                                              to=eng.bucket_length(eng.padded_frames(max(lengths[i] for i in group))))
+            parts = rates.rows(group, [rates.load(i) for i in group], args.device)
+            mix, lens = padded_on_device(parts, eng.bucket_length(eng.padded_frames(max(lengths[i] for i in group))), args.device)
             # (files without --seed: one draw of torch's generator per file, as the --batch 1 loop takes them)
             sds = [seeds[i] if seeds is not None else int(torch.randint(0, 2 ** 62, (1,)).item()) for i in group]
             sep, _ = separate_ode_batch(mix, model, ode_kw, args.device, lens, seeds=sds)
-            sep = sep.cpu()
-            for b, i in enumerate(group):
-                for k in range(sep.shape[1]):
-                    d = args.output_dir / f"s{k}"
-                    d.mkdir(parents=True, exist_ok=True)
-                    wavio.save(d / f"{files[i].stem}.wav", sep[b, k:k + 1, :lens[b]], srs[b], bits=32)
+            for i, (out, sr) in zip(group, rates.restore(group, [sep[b, :, :lens[b]] for b in range(len(group))])):
+                write_sources(args.output_dir, files[i].stem, out, sr)
         print(f"separated {len(files)} files into {args.output_dir} (probability-flow ODE, {args.batch} files per call)")
         return
     if args.sampler == "ode":
         ode_kw = {"N": kw["N"], "denoise": args.denoise, "rtol": args.rtol, "atol": args.atol, "max_nfe": args.max_nfe}
         for i, f in enumerate(files):
-            wav, sr = wavio.load(f)
-            if sr != model_sr:  # the reference only warns (separate.py:151-155, quirk Q9)
-                print(f"Warning: {f.stem}: this model expects {model_sr} Hz, but the file is {sr} Hz.")
-            sep, _ = separate_ode(wav[:1], model, ode_kw, args.device, seed=seeds[i] if seeds is not None else None)
-            sep = sep.cpu()
-            for k in range(sep.shape[1]):
-                d = args.output_dir / f"s{k}"
-                d.mkdir(parents=True, exist_ok=True)
-                wavio.save(d / f"{f.stem}.wav", sep[0, k:k + 1], sr, bits=32)
+            row, = rates.rows([i], [rates.load(i)], args.device)
+            sep, _ = separate_ode(row, model, ode_kw, args.device, seed=seeds[i] if seeds is not None else None)
+            (out, sr), = rates.restore([i], [sep[0]])
+            write_sources(args.output_dir, f.stem, out, sr)
         print(f"separated {len(files)} files into {args.output_dir} (probability-flow ODE)")
         return
     if args.chunk is not None:
-        return separate_chunked(args, files, lengths, seeds, models, streams, kw, model_sr)
+        return separate_chunked(args, files, rates, seeds, models, streams, kw)
     eng = model.score_model.engine()
     batches = inflight.plan_batches(range(len(files)), lengths, eng.padded_frames, max(1, args.batch))
     inflight.reserve_largest(models, batches, lengths)
 
     def launch(w, j, group):
-        """-> (file indices, lengths, sample rates, device result, and what a repeat of the request needs)"""
-        items, srs = [], []
-        for i in group:
-            wav, sr = wavio.load(files[i])
-            if sr != model_sr:  # the reference only warns (separate.py:151-155, quirk Q9)
-                print(f"Warning: {files[i].stem}: this model expects {model_sr} Hz, but the file is {sr} Hz.")
-            items.append((wav[:1], wav[:1]))
-            srs.append(sr)
-        mix, _, lens = datasets.pad_batch(items, side="right",
-                                          to=eng.bucket_length(eng.padded_frames(max(lengths[i] for i in group))))
+        """-> (file indices, lengths, device result, and what a repeat of the request needs)"""
+        parts = rates.rows(group, [rates.load(i) for i in group], args.device)
+        mix_d, lens = padded_on_device(parts, eng.bucket_length(eng.padded_frames(max(lengths[i] for i in group))), args.device)
         sds = [seeds[i] for i in group] if seeds is not None else None
-        mix_d = inflight.upload(mix, args.device)
         sep = separate_on_device(mix_d, models[w], kw, args.device, lengths=lens, seeds=sds)
-        return group, lens, srs, sep, mix_d, sds
+        return group, lens, sep, mix_d, sds
 
     def collect(w, item):
-        group, lens, srs, sep, mix_d, sds = item
+        group, lens, sep, mix_d, sds = item
         sep = inflight.finite_or_rerun(
             models[w], streams[w], (sep,),
             lambda fb: (separate_on_device(mix_d, fb, kw, args.device, lengths=lens, seeds=sds),),
-            what=str([files[i].name for i in group]))[0].cpu()
-        for b, i in enumerate(group):
-            for k in range(sep.shape[1]):
-                d = args.output_dir / f"s{k}"
-                d.mkdir(parents=True, exist_ok=True)
-                wavio.save(d / f"{files[i].stem}.wav", sep[b, k:k + 1, :lens[b]], srs[b], bits=32)
+            what=str([files[i].name for i in group]))[0]
+        with torch.cuda.stream(streams[w]):  # (the conversion back, if any, runs on the drained worker's stream)
+            outs = [(out.cpu(), sr) for out, sr in rates.restore(group, [sep[b, :, :lens[b]] for b in range(len(group))])]
+        for i, (out, sr) in zip(group, outs):
+            write_sources(args.output_dir, files[i].stem, out, sr)
 
     inflight.Ring(streams, launch, collect).run(batches)
     print(f"separated {len(files)} files into {args.output_dir}")

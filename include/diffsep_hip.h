@@ -45,6 +45,7 @@ extern "C" {
  * 2^-24), ~2x the speed of DIFFSEP_F32.  Accepted by diffsep_engine_create and by the unit convolution / attention
  * entry points; tensors are fp32 exactly as for DIFFSEP_F32. */
 #define DIFFSEP_F32_SPLIT 2
+#define DIFFSEP_F64 4 /* float64 rows: an output type of diffsep_resample only (3 is the Python binding's name for the half build) */
 
 #define DIFFSEP_SDE_MIX 0      /* sdes/sdes.py:180-349  MixSDE      */
 #define DIFFSEP_SDE_PRIORMIX 1 /* sdes/sdes.py:352-590  PriorMixSDE */
@@ -63,6 +64,7 @@ extern "C" {
 #define DIFFSEP_ODE_WORKSPACE_BYTES 16384 /* workspace of the error-norm unit entry: per-block fp64 partial sums */
 
 typedef struct diffsep_engine diffsep_engine; /* opaque */
+typedef struct diffsep_resampler diffsep_resampler; /* opaque (sample-rate conversion, below) */
 
 /* Hyper-parameters of ScoreModelNCSNpp + its NCSNpp backbone.
  * Replaces: models/score_models.py:11-39 (ctor kwargs), models/ncsnpp.py:45-70 (ctor defaults),
@@ -651,6 +653,38 @@ int64_t diffsep_composite_workspace_bytes(int32_t B, int32_t S, int64_t T, int32
 int32_t diffsep_composite(const float* ref, const float* est, double* out, double* frames_out, int64_t frames_cap,
                           int32_t B, int32_t S, int64_t T, const int32_t* lengths, const int32_t* perm, int32_t fs,
                           void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Band-limited sample-rate conversion of fp32 rows by a reduced ratio p / q (fs_out / fs_in) with an odd-length FIR
+ * h[0 .. 2 L] in float64, applied as given — the zero-stuffed direct form, centred:
+ *   y[m] = sum_j h[m q + L - p j] (double)x[j],  0 <= j < len, tap index in [0, 2 L],  0 <= m < n_out = ceil(len p / q),
+ * what scipy.signal.resample_poly(x, p, q, window=h / p) computes.  Float64 throughout, each term entering by one fused
+ * multiply-add (the product is not rounded on its own: an unfused float64 reference agrees within the summation bound, bit for
+ * bit only where every sum is exact), one rounding at the end for fp32 output; every output is summed in a fixed order that depends on p, q and L only (no atomics): a row comes out bit for
+ * bit the same alone, inside any batch and on any stream.
+ * Host arithmetic only, no device needed:
+ *   diffsep_resample_ratio   p / q = fs_out / fs_in reduced; refuses (non-zero, message) rates <= 0 and max(p, q) > 1000;
+ *   diffsep_resample_length  ceil(n p / q), or -1 and a message for n < 0, p, q < 1 or an n p beyond 64 bits;
+ *   diffsep_resample_design  the project's filter for a reduced p / q (Octave's resample design: Kaiser-windowed sinc, 60 dB
+ *                            rejection, L = ceil(52 / (28.714 / (20 max(p, q)))), taps summing to p; p = q = 1: the one tap 1.0):
+ *                            returns 2 L + 1 and fills taps_out (NULL: the count only), or -1 and a message (p / q not reduced
+ *                            or beyond 1000, cap < 2 L + 1).
+ * diffsep_resampler_create builds the polyphase-ordered tap table on the current device from the CALLER's taps (any odd-length
+ * FIR); it refuses null taps, an even or zero ntaps, ntaps > 2^17 and a p / q that is not reduced or beyond 1000.  The handle
+ * is read-only afterwards: any number of streams may use it at once.  diffsep_resampler_destroy frees it (NULL: no-op).
+ * diffsep_resample — x [rows][ldx] fp32 -> y [rows][ldy] of out_dtype (DIFFSEP_F32 or DIFFSEP_F64); rows r with
+ * r div rows_per_length = g count lengths[g] samples (device int32, clamped to [0, T]; NULL: T everywhere).  Every column
+ * below ceil(T p / q) is written, those from the row's own n_out on as zeros (a valid zero-padded batch); columns from
+ * ceil(T p / q) on are left alone.  lengths_out (nullable device int32) receives each group's n_out.  Asynchronous on
+ * `stream`, no host readback, no workspace.  Refusals (null pointers, an unknown out_dtype, T outside 1 .. 2^31 - 1, ldx < T,
+ * ldy < ceil(T p / q), rows outside 1 .. 65535, rows_per_length < 1, a handle of another device) return non-zero with a message
+ * and write nothing. */
+int32_t diffsep_resample_ratio(int32_t fs_in, int32_t fs_out, int32_t* p, int32_t* q);
+int64_t diffsep_resample_length(int64_t n, int32_t p, int32_t q);
+int32_t diffsep_resample_design(int32_t p, int32_t q, double* taps_out, int32_t cap);
+int32_t diffsep_resampler_create(int32_t p, int32_t q, const double* taps, int32_t ntaps, diffsep_resampler** out);
+void diffsep_resampler_destroy(diffsep_resampler* r);
+int32_t diffsep_resample(const diffsep_resampler* r, const float* x, int64_t ldx, void* y, int64_t ldy, int32_t rows, int64_t T,
+                         const int32_t* lengths, int32_t rows_per_length, int32_t* lengths_out, int32_t out_dtype, void* stream);
 
 /* Long recordings: a file of T samples as K windows of Tw samples with a nominal overlap of Tv, stitched on the device.
  * The plan (host arithmetic only, no device needed): refused (-1 and a message) unless T >= 1, Tv >= 1 and 3 Tv <= Tw.
