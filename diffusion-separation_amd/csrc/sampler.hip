@@ -43,13 +43,29 @@ static int mixture_scale(diffsep_engine* e, const diffsep_sde_config* sde, int B
   return 0;
 }
 
-extern "C" int32_t diffsep_pc_sample_ex(diffsep_engine* e, const diffsep_sde_config* sde,
-                                        const diffsep_sampler_config* smp, const diffsep_sampler_ext* ext,
-                                        const float* mix_norm, float* out, int32_t B, int64_t T, const float* noise,
-                                        uint64_t seed, const float* timesteps_host, int32_t* nfe_out, void* stream) {
+// The sampler, with an optional tap on its intermediate states (reference sdes/__init__.py:168-186, `intermediate`; the
+// figure of evaluate.py:29-61 is drawn from them).  In reverse step i, after the corrector step(s) and before the predictor —
+// where the reference appends (xt, xt_mean) — one launch (sde.hip: trace_tap_kernel) copies the state of the chosen steps and
+// adds up the Gram sums of every step against `target`.  The state lives on `e` whichever engine evaluates the score, and the
+// tap is a stream launch between graph replays: the captured graphs are those of the untraced call.  With nothing to trace
+// (n_snap == 0, target == NULL) not one launch, copy or allocation is added: that is diffsep_pc_sample_ex.
+extern "C" int32_t diffsep_pc_sample_trace(diffsep_engine* e, const diffsep_sde_config* sde,
+                                           const diffsep_sampler_config* smp, const diffsep_sampler_ext* ext,
+                                           const float* mix_norm, float* out, int32_t B, int64_t T, const float* noise,
+                                           uint64_t seed, const float* timesteps_host, int32_t* nfe_out, int32_t n_snap,
+                                           const int32_t* snap_steps_host, float* snap_x, float* snap_xm,
+                                           const float* target, double* gram, void* stream) {
   DS_CHECK(e && sde && smp && mix_norm && out, "pc_sample: null argument");
   if (check_sde(e, sde, "pc_sample")) return 1;
   DS_CHECK(smp->N >= 1 && smp->N <= 4096, "pc_sample: N must be in [1,4096]");
+  DS_CHECK(n_snap >= 0 && (n_snap == 0 || snap_steps_host), "pc_sample: n_snap snapshot steps are needed");
+  DS_CHECK(n_snap == 0 || snap_x, "pc_sample: snapshots were requested without a buffer (snap_x == NULL)");
+  for (int k = 0; k < n_snap; ++k)
+    DS_CHECK(snap_steps_host[k] >= 0 && snap_steps_host[k] < smp->N && (k == 0 || snap_steps_host[k] > snap_steps_host[k - 1]),
+             "pc_sample: the snapshot steps must be strictly ascending and in [0, N)");
+  DS_CHECK(!target == !gram, "pc_sample: target and gram are given together or not at all");
+  DS_CHECK(!(n_snap || target) || e->cfg.num_sources <= DS_MAX_SRC, "pc_sample: too many sources to trace");
+  if (n_snap == 0) snap_x = snap_xm = nullptr;
   DS_CHECK(smp->predictor == DIFFSEP_PRED_REVERSE_DIFFUSION || smp->predictor == DIFFSEP_PRED_EULER_MARUYAMA ||
                smp->predictor == DIFFSEP_PRED_NONE,
            "pc_sample: predictor must be reverse_diffusion, euler_maruyama or none");
@@ -87,6 +103,8 @@ extern "C" int32_t diffsep_pc_sample_ex(diffsep_engine* e, const diffsep_sde_con
   if (ensure_plan(e, B, T, st)) return 1;
   if (tail && ensure_plan(tail, B, T, st)) return 1;
   const size_t nst = (size_t)B * S * T;
+  const size_t ngram = (size_t)B * 3 * S * S;  // doubles of one row of `gram`
+  int snap_next = 0;
   const SdeP sp = to_sdep(sde);
   // time steps -> device rows [N][B]
   std::vector<float> ts(N);
@@ -177,6 +195,20 @@ extern "C" int32_t diffsep_pc_sample_ex(diffsep_engine* e, const diffsep_sde_con
         return 1;
       }
     }
+    if (snap_next < n_snap || target) {  // the tap: (x, x_mean) as the corrector left them
+      const int k = (snap_next < n_snap && snap_steps_host[snap_next] == i) ? snap_next++ : -1;
+      if (k >= 0 || target) {
+        float* sx = k >= 0 ? snap_x + (size_t)k * nst : nullptr;
+        float* sxm = (k >= 0 && snap_xm) ? snap_xm + (size_t)k * nst : nullptr;
+        // without a corrector step the reference's "corrector" returns (x, x): st_xm still holds the last predictor's mean
+        const float* xm = csteps > 0 ? e->st_xm : e->st_x;
+        double* g = target ? gram + (size_t)i * ngram : nullptr;
+        const double words = 1.0 + (target ? 1.0 : 0.0) + (sx ? 1.0 : 0.0) + (sxm ? 2.0 : 0.0);
+        if (prof_launch(e, st, hbm_rec("trace_tap (state snapshot + Gram sums)", 4.0 * nst * words, B, 1, (int)T, S),
+                        [&]() { return ds_launch_trace_tap(e->st_x, xm, target, sx, sxm, g, B, S, T, st); }))
+          return 1;
+      }
+    }
     if (smp->predictor != DIFFSEP_PRED_NONE) {
       // euler_maruyama (sdes/predictors.py:39-52) takes x + f*dt with the reverse drift f = drift - g^2 score and
       // noise g sqrt(dt): algebraically the reverse_diffusion step (dt = 1/N, G = g sqrt(dt)) — one kernel for both
@@ -191,8 +223,17 @@ extern "C" int32_t diffsep_pc_sample_ex(diffsep_engine* e, const diffsep_sde_con
     }
   }
   DS_HIP(hipMemcpyAsync(out, smp->denoise ? e->st_xm : e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
+  if (target && ds_launch_gram(target, out, gram + (size_t)N * ngram, B, S, T, st)) return 1;  // row N: the result itself
   if (nfe_out) *nfe_out = N * (csteps + 1);
   return 0;
+}
+
+extern "C" int32_t diffsep_pc_sample_ex(diffsep_engine* e, const diffsep_sde_config* sde,
+                                        const diffsep_sampler_config* smp, const diffsep_sampler_ext* ext,
+                                        const float* mix_norm, float* out, int32_t B, int64_t T, const float* noise,
+                                        uint64_t seed, const float* timesteps_host, int32_t* nfe_out, void* stream) {
+  return diffsep_pc_sample_trace(e, sde, smp, ext, mix_norm, out, B, T, noise, seed, timesteps_host, nfe_out, 0, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int32_t diffsep_pc_sample(diffsep_engine* e, const diffsep_sde_config* sde, const diffsep_sampler_config* smp,

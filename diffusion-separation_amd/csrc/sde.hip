@@ -419,29 +419,20 @@ int ds_launch_scale_output(const float* mix, float* sep, int B, int S, long T, h
 // ------------------------------------------------------------------ Gram matrices for the BSS metrics
 // out[b] = { ref ref^T, ref est^T, est est^T } (each [S][S], fp64): everything SI-SDR / SI-SIR / SI-SAR and the
 // best permutation need (evaluate.py:103-132 -> fast_bss_eval.si_bss_eval_sources); one pass over the waveforms.
-__global__ __launch_bounds__(1024) void gram_kernel(const float* __restrict__ ref, const float* __restrict__ est,
-                                                    double* __restrict__ out, int S, long T) {
-  __shared__ double sh[16];
-  const int b = blockIdx.x;
-  double acc[3 * DS_MAX_SRC * DS_MAX_SRC];
+// The two halves of that pass, shared with the sampler's tap below so that both add the same products in the same order:
+// one sample of every row into the thread's partial sums, then the block totals (reduce_device.h) of utterance b.
+constexpr int kGramAcc = 3 * DS_MAX_SRC * DS_MAX_SRC;
+__device__ inline void gram_add(double* acc, const double* r, const double* e) {
 #pragma unroll
-  for (int k = 0; k < 3 * DS_MAX_SRC * DS_MAX_SRC; ++k) acc[k] = 0.0;
-  for (long i = threadIdx.x; i < T; i += blockDim.x) {
-    double r[DS_MAX_SRC], e[DS_MAX_SRC];
+  for (int a = 0; a < DS_MAX_SRC; ++a)
 #pragma unroll
-    for (int a = 0; a < DS_MAX_SRC; ++a) {
-      r[a] = a < S ? (double)ref[((long)b * S + a) * T + i] : 0.0;
-      e[a] = a < S ? (double)est[((long)b * S + a) * T + i] : 0.0;
+    for (int c = 0; c < DS_MAX_SRC; ++c) {
+      acc[(0 * DS_MAX_SRC + a) * DS_MAX_SRC + c] += r[a] * r[c];
+      acc[(1 * DS_MAX_SRC + a) * DS_MAX_SRC + c] += r[a] * e[c];
+      acc[(2 * DS_MAX_SRC + a) * DS_MAX_SRC + c] += e[a] * e[c];
     }
-#pragma unroll
-    for (int a = 0; a < DS_MAX_SRC; ++a)
-#pragma unroll
-      for (int c = 0; c < DS_MAX_SRC; ++c) {
-        acc[(0 * DS_MAX_SRC + a) * DS_MAX_SRC + c] += r[a] * r[c];
-        acc[(1 * DS_MAX_SRC + a) * DS_MAX_SRC + c] += r[a] * e[c];
-        acc[(2 * DS_MAX_SRC + a) * DS_MAX_SRC + c] += e[a] * e[c];
-      }
-  }
+}
+__device__ inline void gram_store(const double* acc, double* __restrict__ out, int b, int S, double* sh) {
   for (int m = 0; m < 3; ++m)
     for (int a = 0; a < S; ++a)
       for (int c = 0; c < S; ++c) {
@@ -449,9 +440,67 @@ __global__ __launch_bounds__(1024) void gram_kernel(const float* __restrict__ re
         if (threadIdx.x == 0) out[(((long)b * 3 + m) * S + a) * S + c] = t;
       }
 }
+
+__global__ __launch_bounds__(1024) void gram_kernel(const float* __restrict__ ref, const float* __restrict__ est,
+                                                    double* __restrict__ out, int S, long T) {
+  __shared__ double sh[16];
+  const int b = blockIdx.x;
+  double acc[kGramAcc];
+#pragma unroll
+  for (int k = 0; k < kGramAcc; ++k) acc[k] = 0.0;
+  for (long i = threadIdx.x; i < T; i += blockDim.x) {
+    double r[DS_MAX_SRC], e[DS_MAX_SRC];
+#pragma unroll
+    for (int a = 0; a < DS_MAX_SRC; ++a) {
+      r[a] = a < S ? (double)ref[((long)b * S + a) * T + i] : 0.0;
+      e[a] = a < S ? (double)est[((long)b * S + a) * T + i] : 0.0;
+    }
+    gram_add(acc, r, e);
+  }
+  gram_store(acc, out, b, S, sh);
+}
 int ds_launch_gram(const float* ref, const float* est, double* out, int B, int S, long T, hipStream_t st) {
   DS_CHECK(S >= 1 && S <= DS_MAX_SRC, "gram: too many sources");
   hipLaunchKernelGGL(gram_kernel, dim3(B), dim3(1024), 0, st, ref, est, out, S, T);
+  DS_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------ the sampler's tap (diffsep_pc_sample_trace)
+// One pass over the state of a reverse step between its corrector and its predictor (reference sdes/__init__.py:179-181:
+// `intermediate.append((xt, xt_mean))`): x -> snap_x and x_mean -> snap_xm when given, and, with a target, the Gram sums of
+// (target, x) -> gram [B][3][S][S], thread stride and reduction order of gram_kernel: bit for bit diffsep_gram(target, x).
+// One block of 1024 threads per utterance; every pointer but x may be null.  Rows [B][S][T]; the zero tails of a mixed-length
+// batch are copied as they are and add nothing to the sums.
+__global__ __launch_bounds__(1024) void trace_tap_kernel(const float* __restrict__ x, const float* __restrict__ xm,
+                                                         const float* __restrict__ target, float* __restrict__ snap_x,
+                                                         float* __restrict__ snap_xm, double* __restrict__ gram, int S,
+                                                         long T) {
+  __shared__ double sh[16];
+  const int b = blockIdx.x;
+  double acc[kGramAcc];
+#pragma unroll
+  for (int k = 0; k < kGramAcc; ++k) acc[k] = 0.0;
+  for (long i = threadIdx.x; i < T; i += blockDim.x) {
+    double r[DS_MAX_SRC], e[DS_MAX_SRC];
+#pragma unroll
+    for (int a = 0; a < DS_MAX_SRC; ++a) {
+      const long at = ((long)b * S + a) * T + i;
+      const float v = a < S ? x[at] : 0.f;
+      if (a < S && snap_x) snap_x[at] = v;
+      if (a < S && snap_xm) snap_xm[at] = xm[at];
+      r[a] = (a < S && target) ? (double)target[at] : 0.0;
+      e[a] = (double)v;
+    }
+    if (target) gram_add(acc, r, e);
+  }
+  if (target) gram_store(acc, gram, b, S, sh);  // (uniform over the block: every thread reaches the barriers)
+}
+int ds_launch_trace_tap(const float* x, const float* xm, const float* target, float* snap_x, float* snap_xm, double* gram,
+                        int B, int S, long T, hipStream_t st) {
+  DS_CHECK(S >= 1 && S <= DS_MAX_SRC, "trace tap: too many sources");
+  DS_CHECK(x && (!snap_xm || xm) && (!target == !gram), "trace tap: inconsistent pointers");
+  hipLaunchKernelGGL(trace_tap_kernel, dim3(B), dim3(1024), 0, st, x, xm, target, snap_x, snap_xm, gram, S, T);
   DS_LAUNCH_CHECK();
   return 0;
 }

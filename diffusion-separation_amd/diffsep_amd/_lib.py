@@ -134,6 +134,8 @@ _SIGS = {
                                C.POINTER(_I), _P]),
     "diffsep_pc_sample_ex": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(SamplerConfig), C.POINTER(SamplerExt), _P, _P, _I,
                                   _L, _P, _U64, _P, C.POINTER(_I), _P]),
+    "diffsep_pc_sample_trace": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(SamplerConfig), C.POINTER(SamplerExt), _P, _P, _I,
+                                     _L, _P, _U64, _P, C.POINTER(_I), _I, C.POINTER(_I), _P, _P, _P, _P, _P]),
     "diffsep_ode_sample": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(OdeConfig), _P, _P, _P, _U64, _P, _I, _L,
                                 C.POINTER(OdeInfo), _P]),
     "diffsep_ode_sample_each": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(OdeConfig), C.POINTER(OdeExt), _P, _P, _P, _U64, _P,

@@ -56,6 +56,26 @@ def pack_state_dict(cfg, state, prefix=""):
     return blob
 
 
+class SamplerTrace:
+    """What a traced Engine.pc_sample leaves behind: steps (the snapshot steps), x / x_mean [len(steps),B,S,T] (one buffer
+    each; x_mean None when not kept) and gram [N+1,B,3,S,S] float64 (None without a target), all on the device."""
+
+    def __init__(self, steps, x, x_mean, gram):
+        self.steps, self.x, self.x_mean, self.gram = list(steps), x, x_mean, gram
+
+    def intermediates(self):
+        """[(xt, xt_mean)] of the snapshot steps, views of the two buffers: the reference's `intermediate` list"""
+        return [(self.x[k], self.x_mean[k] if self.x_mean is not None else None) for k in range(len(self.steps))]
+
+    @staticmethod
+    def cat(traces):
+        """the traces of the minibatches of one batch, joined along the batch"""
+        t0 = traces[0]
+        return SamplerTrace(t0.steps, torch.cat([t.x for t in traces], dim=1),
+                            None if t0.x_mean is None else torch.cat([t.x_mean for t in traces], dim=1),
+                            None if t0.gram is None else torch.cat([t.gram for t in traces], dim=1))
+
+
 class Engine:
     """Owns the repacked weights and workspace on the current CUDA(HIP) device."""
 
@@ -201,8 +221,13 @@ class Engine:
 
     def pc_sample(self, mix_norm, sde, N=30, corrector_steps=1, snr=0.5, eps=0.03, denoise=True,
                   predictor="reverse_diffusion", corrector="ald2", noise=None, seed=0, timesteps=None, lengths=None,
-                  seeds=None, tail=None, tail_steps=0, head_steps=0):
+                  seeds=None, tail=None, tail_steps=0, head_steps=0, snapshots=None, snapshot_means=True, target=None):
         """The whole sampler (sdes.get_pc_sampler(...)()).  sde: dict(kind, ndim, d_lambda, sigma_min, sigma_max).
+        Tracing (diffsep_pc_sample_trace; with snapshots or target the result is (out, nfe, trace), a SamplerTrace):
+        snapshots = the reverse steps whose state (x, and x_mean unless snapshot_means=False) is kept, as the reference's
+        intermediate=True appends it between corrector and predictor — a strictly ascending list of steps in [0, N) (the
+        library refuses anything else) or "all"; target [B,S,T] (zero beyond each utterance's length) = also the Gram sums of every step's state, and last of
+        the result, against it: trace.gram [N+1,B,3,S,S] float64, row i bit for bit ops.gram(target, trace.x[i]).
         Extensions (diffsep_sampler_ext): lengths [B] = a zero-padded batch of utterances of different lengths that share
         one padded frame count; seeds [B] = per-utterance device-RNG seeds; tail / head_steps / tail_steps = evaluate the
         score of the FIRST head_steps and / or the last tail_steps reverse steps on another Engine (dtype "hybrid" of
@@ -237,11 +262,29 @@ class Engine:
                     raise _lib.DiffsepError(f"the other engine was created by the '{tail.kind}' build of the library, this one "
                                             f"by the '{self.kind}' build: create it with Engine(..., lib_kind='{self.kind}')")
                 ext.tail_engine, ext.tail_steps, ext.head_steps = tail._h, int(tail_steps), int(head_steps)
+        if snapshots is None and target is None:
+            with torch.cuda.device(self.device):
+                call(self._L, "diffsep_pc_sample_ex", self._h, C.byref(sc), C.byref(sm), C.byref(ext) if ext is not None else None,
+                     _ptr(mix_norm), _ptr(out), B, T, _ptr(noise), seed, ts.ctypes.data_as(C.c_void_p) if ts is not None else None,
+                     C.byref(nfe), _stream_ptr(self.device))
+            return out, int(nfe.value)
+        steps = list(range(N)) if isinstance(snapshots, str) and snapshots == "all" else [int(s) for s in (snapshots or [])]
+        n_snap = len(steps)
+        dev = mix_norm.device
+        snap_x = torch.empty((n_snap, B, self.S, T), dtype=torch.float32, device=dev)
+        snap_xm = torch.empty_like(snap_x) if (snapshot_means and n_snap) else None
+        gram = None
+        if target is not None:
+            target = self._f32(target)
+            assert tuple(target.shape) == (B, self.S, T), "target must be [B,S,T]"
+            gram = torch.empty((N + 1, B, 3, self.S, self.S), dtype=torch.float64, device=dev)
+        sa_ = np.ascontiguousarray(steps, dtype=np.int32)
         with torch.cuda.device(self.device):
-            call(self._L, "diffsep_pc_sample_ex", self._h, C.byref(sc), C.byref(sm), C.byref(ext) if ext is not None else None,
+            call(self._L, "diffsep_pc_sample_trace", self._h, C.byref(sc), C.byref(sm), C.byref(ext) if ext is not None else None,
                  _ptr(mix_norm), _ptr(out), B, T, _ptr(noise), seed, ts.ctypes.data_as(C.c_void_p) if ts is not None else None,
-                 C.byref(nfe), _stream_ptr(self.device))
-        return out, int(nfe.value)
+                 C.byref(nfe), n_snap, sa_.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(snap_x) if n_snap else None,
+                 _ptr(snap_xm), _ptr(target), _ptr(gram), _stream_ptr(self.device))
+        return out, int(nfe.value), SamplerTrace(steps, snap_x, snap_xm, gram)
 
     def _ode_setup(self, mix_norm, sde, method, rtol, atol, eps, first_step, max_step, max_nfe, denoise, N, x_init, noise):
         """what both ODE entries make of their arguments: (mix_norm, SdeConfig, OdeConfig, x_init, noise, out)"""

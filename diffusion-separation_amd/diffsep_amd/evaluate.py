@@ -13,8 +13,9 @@ sets come from `<ckpt>/../../hparams.yaml` -> datamodule.{val,test}.dataset like
 Output tree (evaluate.py:306-323,436-443): `<output_dir>/<exp>_<ckpt>_<tag_inf>/` (or `<tag>_<tag_inf>`), tag_inf =
 `N-.._snr-.._corrstep-.._denoise-.._schedule-..`, holding `<split>.json`, `<split>_summary.json` and
 `wav/<split>/NNN_{mix,enh0,enh1,tgt0,tgt1}.wav` (scaled to peak 0.95 together, estimates in the permutation that matches
-the targets) for the first --save-n utterances (default: all).  Not produced: `fig/` (matplotlib spectrogram plots of the
-intermediate states) and the PESQ field (ITU-T P.862 C code, third-party `pesq`; null, named under `not_computed`).  STOI /
+the targets) for the first --save-n utterances (default: all), and with --fig `fig/<split>/evo_NNN.pdf` for the same
+utterances (evaluate.py:29-61,362-376,413-436: the state of six reverse steps next to the clean sources; below).  Not
+produced: the PESQ field (ITU-T P.862 C code, third-party `pesq`; null, named under `not_computed`).  STOI /
 ESTOI is computed on loader threads (diffsep_amd.metrics.stoi, `--stoi-on host`, the default) or on the GPU
 (diffsep_amd.metrics.stoi_batch, `--stoi-on device`: no waveform leaves the device unless it is saved).  --composite (off by
 default; without it records and summaries are what they were) adds the signal measures of the reference's evaluate_covl.py to
@@ -43,6 +44,18 @@ its batch needed, each record carries its `ode_status` (0 reached eps, -1 step t
 summary counts them (`ode_status_counts`) and names the `sampler`.  An ODE call blocks the host on one readback per step
 attempt, so --streams adds nothing to it.
 
+--fig and --trajectory look inside the fused sampler through its tap (diffsep_pc_sample_trace: one small launch between the
+corrector and the predictor of a reverse step; batches, streams, seeds, --dtype hybrid and the records are what they are
+without them).  --fig: the batches that hold an utterance --save-n selects ask for snapshots of the figure's steps
+(figures.snapshot_request: the unique ones of round(linspace(0, 1, 6) (N - 1)), x only) and diffsep_amd.figures draws them,
+estimates in the targets' order like the saved wavs; it needs matplotlib and ends with a SystemExit that names it otherwise.
+--trajectory: every record gets `si_sdr_steps`, N + 1 lists of the SI-SDR of its sources — the state after each step's
+corrector, last the result — under the record's OWN final permutation at every step (a curve follows one source), from the
+Gram sums the tap adds up on the device ((N + 1) 3 S^2 doubles per utterance cross PCIe); the last list is the record's
+`si_sdr`, and the summary's `si_sdr_steps` is the mean over the utterances (measured: about 5 % of the run's rate, the Gram
+pass of every step).  Warm-up calls trace nothing.  Neither runs with
+--sampler ode (no fixed steps) or `__no_proc__` (no sampler).
+
 --streams K such calls are in flight on K engines / K HIP streams.  What that takes (hardware queues, engines before
 streams, workspace reserve, per-utterance seeds and normalisation, pinned uploads, the launch / collect ring, the overflow
 re-run) is inflight.py's, shared with separate.py.  Here: main() sets the run up, a SplitRun holds one split's state and
@@ -61,7 +74,7 @@ from typing import Callable
 import torch
 import torch.distributed as dist
 
-from . import datasets, inflight, metrics, ops, synth, wavio
+from . import datasets, figures, inflight, metrics, ops, synth, wavio
 from .dist_utils import gather_objects, rank_indices
 from .inflight import plan_batches  # (its callers import it from here)
 from .pl_model import DiffSepModel, cfg_get, default_config, enhancement_config
@@ -219,6 +232,12 @@ def build_parser():
     ap.add_argument("--atol", type=float, default=1e-5, help="--sampler ode: absolute tolerance (reference default)")
     ap.add_argument("--max-nfe", type=int, default=0,
                     help="--sampler ode: no step attempt of an utterance starts beyond this many network evaluations (0: unbounded)")
+    ap.add_argument("--fig", action="store_true",
+                    help="write fig/<split>/evo_NNN.pdf for the utterances --save-n selects (the reference's figure of the reverse "
+                         "diffusion: the state of six steps next to the clean sources); needs matplotlib")
+    ap.add_argument("--trajectory", action="store_true",
+                    help="record si_sdr_steps: the SI-SDR of every source after each reverse step's corrector, and last of the "
+                         "result, under the record's final permutation (Gram sums added up on the device inside the sampler)")
     ap.add_argument("--streams", type=int, default=4,
                     help="engine calls (batches) in flight per GPU: K engines on K HIP streams; the records do not "
                          "depend on K.  'runtime' of an utterance is its batch's latency / batch size.")
@@ -240,6 +259,13 @@ def main(argv=None):
     no_proc = str(args.ckpt) == "__no_proc__"
     if args.ckpt is None and not args.synthetic_weights and not no_proc:
         ap.error("a checkpoint (or --synthetic-weights NF) is required")
+    for flag, on in (("--fig", args.fig), ("--trajectory", args.trajectory)):
+        if on and args.sampler == "ode":
+            raise SystemExit(f"{flag}: the ODE sampler has no fixed reverse steps to look at (--sampler pc)")
+        if on and no_proc:
+            raise SystemExit(f"{flag}: __no_proc__ scores the mixture itself, there is no sampler to look into")
+    if args.fig:
+        figures.require_matplotlib("--fig")
     if args.streams > 1:
         inflight.default_hw_queues()  # (before the first torch.cuda call)
 
@@ -352,6 +378,7 @@ class SplitRun:
     fallbacks: list = field(default_factory=list)  # batches repeated on the split-precision engine after non-finite f16 samples
     ahead: dict = field(default_factory=dict)  # batch number -> future of its host_stage()
     ode_reruns: dict = field(default_factory=dict)  # first utterance of a repeated ODE batch -> the repeat's per-utterance infos
+    trace_reruns: dict = field(default_factory=dict)  # first utterance of a repeated traced batch -> the repeat's trace
 
     def __post_init__(self):
         a = self.args
@@ -367,6 +394,12 @@ class SplitRun:
         self.mine = rank_indices(self.n, self.world, self.rank, self.lengths, a.balance)
         self.batches = plan_batches(self.mine, self.lengths, self.width_of, max(1, a.batch))
         self.seeds = inflight.utterance_seeds(self.n, a.seed)
+        # --fig: the unique steps of the figure's panels (what the tap is asked for) and each panel's place among them
+        self.fig_steps, self.fig_panels = figures.snapshot_request(self.sampler_kw["N"]) if a.fig else (None, None)
+
+    def wants_fig(self, i):
+        """is utterance i one of those --fig draws (the ones --save-n saves)?"""
+        return self.args.fig and (self.args.save_n is None or i < self.args.save_n)
 
     def host_stage(self, group):
         """load and pad one batch on the host (runs on a loader thread, ahead of the GPU): mix / tgt + lengths"""
@@ -389,14 +422,21 @@ class SplitRun:
             return mix, mix, tgt, lens
         return (mix, *inflight.normalize_padded(self.models[w], lens, mix, tgt), lens)
 
-    def sampler_for(self, model, group, lens, mix_n):
+    def sampler_for(self, model, group, lens, mix_n, tgt_n=None, trace=True):
+        """trace: ask the sampler's tap for what --fig (snapshots, in the batches that hold such an utterance) and
+        --trajectory (Gram sums against tgt_n) need; False for a warm-up call"""
         if self.args.sampler == "ode":  # one step controller per utterance; sampler.info: the utterances' own counts
             a = self.args
             return model.get_ode_sampler(mix_n, N=self.sampler_kw["N"], denoise=a.denoise, rtol=a.rtol, atol=a.atol,
                                          max_nfe=a.max_nfe, lengths=lens, seeds=[self.seeds[i] for i in group])
+        tap = {}
+        if trace and any(self.wants_fig(i) for i in group):
+            tap["snapshots"] = self.fig_steps
+        if trace and self.args.trajectory:
+            tap["target"] = tgt_n
         return model.get_pc_sampler("reverse_diffusion", "ald2", mix_n, **self.sampler_kw, denoise=self.args.denoise,
                                     intermediate=False, schedule=self.args.schedule, lengths=lens,
-                                    seeds=[self.seeds[i] for i in group], check_finite=False)
+                                    seeds=[self.seeds[i] for i in group], check_finite=False, **tap)
 
     def score_loss(self, model, group, lens, mix_n, tgt_n):
         """mean over K times of the plain score-matching loss of every utterance of the batch -> float64 [B] device tensor,
@@ -423,7 +463,7 @@ class SplitRun:
             est = mix_n.expand(-1, tgt_n.shape[1], -1).contiguous()  # x_result = broadcast_to(mix, target.shape)
             return _Batch(group, lens, mix, mix_n, tgt_n, est, 0, None, None)
         sloss = self.score_loss(self.models[w], group, lens, mix_n, tgt_n) if self.args.score_loss > 0 else None
-        sampler = self.sampler_for(self.models[w], group, lens, mix_n)
+        sampler = self.sampler_for(self.models[w], group, lens, mix_n, tgt_n, trace=j is not None)
         if len(self.streams) == 1:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -431,11 +471,15 @@ class SplitRun:
         return _Batch(group, lens, mix, mix_n, tgt_n, est, nfe, t0, sampler, sloss)
 
     def reissue(self, fb, b):
+        """the same request on the fallback model: the same trace arguments, and the repeat's trace replaces the first"""
         self.fallbacks.append(list(b.group))
-        sampler = self.sampler_for(fb, b.group, b.lens, b.mix_n)
+        traced = getattr(b.sampler, "trace", None) is not None
+        sampler = self.sampler_for(fb, b.group, b.lens, b.mix_n, b.tgt_n, trace=traced)
         out = sampler()
         if self.args.sampler == "ode":
             self.ode_reruns[b.group[0]] = sampler.info
+        elif traced:
+            self.trace_reruns[b.group[0]] = sampler.trace
         return out
 
     def collect(self, w, b):
@@ -450,6 +494,15 @@ class SplitRun:
             ode = self.ode_reruns.pop(group[0], None) or b.sampler.info
         with torch.cuda.stream(stream):
             mets = compute_metrics(est, tgt_n, self.n_src)
+        trace = None  # what the sampler's tap left (--fig, --trajectory; none for a warm-up call)
+        if not self.no_proc and a.sampler == "pc":
+            trace = self.trace_reruns.pop(group[0], None) or getattr(b.sampler, "trace", None)
+        steps_sdr = None
+        if trace is not None and trace.gram is not None:  # [N+1,B,3,S,S] -> per step the SI-SDR under the FINAL permutation
+            with torch.cuda.stream(stream):
+                G = metrics.gram_to_host(trace.gram)
+            perms = [m["perm"] for m in mets]
+            steps_sdr = [metrics.si_bss_from_gram(G[i], perm=perms)[0] for i in range(G.shape[0])]
         need_host = needs_host_waveforms(a, group)
         stoi_dev = None
         if not a.no_stoi and a.stoi_on == "device":  # every source against its permuted estimate, whole batch at once
@@ -477,6 +530,16 @@ class SplitRun:
             self.records.append(rec)
             perm = mets[k]["perm"]
             k_src = len(perm) if self.n_src is None else self.n_src
+            if steps_sdr is not None:
+                rec["si_sdr_steps"] = [[float(v) for v in row[k, :k_src]] for row in steps_sdr]
+            if trace is not None and trace.x.shape[0] and self.wants_fig(i):
+                with torch.cuda.stream(stream):  # this utterance's snapshots [steps,S,L], sources in the targets' order
+                    snaps = trace.x[:, k][:, perm, :lens[k]].cpu().numpy()
+                    clean = tgt_n[k, :, :lens[k]].cpu().numpy()
+                fig_dir = self.output_dir / "fig" / self.split
+                fig_dir.mkdir(parents=True, exist_ok=True)
+                figures.evolution_figure(snaps[self.fig_panels], [self.fig_steps[p] for p in self.fig_panels],
+                                         self.sampler_kw["N"], clean, fig_dir / f"evo_{i:03d}.pdf")
             if stoi_dev is not None:
                 rec["stoi"] = [float(v) for v in stoi_dev[k, :k_src]]
             if comp_dev is not None:
@@ -497,7 +560,11 @@ class SplitRun:
         flat = sorted([r for part in allrec for r in part], key=lambda r: r["batch_idx"])
         with open(self.output_dir / f"{self.split}.json", "w") as f:
             json.dump(flat, f, indent=2)
-        summary = datasets.summarize([{k: v for k, v in r.items() if k not in ("batch_idx", "perm", "ode_status")} for r in flat])
+        summary = datasets.summarize([{k: v for k, v in r.items() if k not in ("batch_idx", "perm", "ode_status", "si_sdr_steps")}
+                                      for r in flat])
+        if a.trajectory and flat:  # per reverse step (and last the result): the mean over the utterances, per source
+            import numpy as np
+            summary["si_sdr_steps"] = np.mean([r["si_sdr_steps"] for r in flat], axis=0).tolist()
         tot_rt = sum(r["runtime"] for r in flat)
         summary.update({"rtf": tot_rt / max(sum(r["len_s"] for r in flat), 1e-9), "world_size": self.world,
                         "streams": len(self.streams), "batch": a.batch, "engine_calls_rank0": len(self.batches),

@@ -24,12 +24,24 @@ def _db(num, den):
 def si_bss_eval_sources(ref, est, clamp_db=100.0):
     """ref, est [B,S,T] device tensors -> (si_sdr, si_sir, si_sar [B,S] numpy, perm [B,S] int) with est[:, perm] aligned
     to ref."""
-    Gd = ops.gram(ref.float(), est.float())
-    # device -> pinned host on the CURRENT stream only (a pageable copy would stall every other stream's work)
+    return si_bss_from_gram(gram_to_host(ops.gram(ref.float(), est.float())), clamp_db=clamp_db)
+
+
+def gram_to_host(Gd):
+    """float64 Gram sums on the device -> numpy, through pinned memory on the CURRENT stream only (a pageable copy would
+    stall every other stream's work)"""
     Gh = torch.empty(Gd.shape, dtype=Gd.dtype, pin_memory=True)
     Gh.copy_(Gd, non_blocking=True)
     torch.cuda.current_stream().synchronize()
-    G = Gh.numpy()
+    return Gh.numpy()
+
+
+def si_bss_from_gram(G, clamp_db=100.0, perm=None):
+    """The host algebra of si_bss_eval_sources on its own (pure numpy): G [B,3,S,S] float64 = {ref ref^T, ref est^T,
+    est est^T} per utterance (diffsep_gram, or a row of the sampler's trace) -> (si_sdr, si_sir, si_sar [B,S], perm [B,S]).
+    perm None: the permutation maximising the mean SI-SDR, as there; perm [B,S] given: the values of that fixed assignment
+    (reference i against estimate perm[b][i]) — what lets a curve over the reverse steps follow one source."""
+    G = np.asarray(G, dtype=np.float64)
     B, _, S, _ = G.shape
     sdr = np.zeros((B, S, S)); sir = np.zeros((B, S, S)); sar = np.zeros((B, S, S))
     for b in range(B):
@@ -50,8 +62,11 @@ def si_bss_eval_sources(ref, est, clamp_db=100.0):
     out = [np.zeros((B, S)) for _ in range(3)]
     best = np.zeros((B, S), dtype=np.int64)
     for b in range(B):
-        scores = [np.mean([sdr[b, i, p[i]] for i in range(S)]) for p in perms]
-        p = perms[int(np.argmax(scores))]
+        if perm is None:
+            scores = [np.mean([sdr[b, i, p[i]] for i in range(S)]) for p in perms]
+            p = perms[int(np.argmax(scores))]
+        else:
+            p = tuple(int(v) for v in perm[b])
         best[b] = p
         for i in range(S):
             out[0][b, i], out[1][b, i], out[2][b, i] = sdr[b, i, p[i]], sir[b, i, p[i]], sar[b, i, p[i]]

@@ -10,7 +10,7 @@ import warnings
 import torch
 
 from . import ops, sdes
-from .engine import param_table
+from .engine import SamplerTrace, param_table
 from .score_models import ScoreModelNCSNpp
 from .sdes import MixSDE, PriorMixSDE
 
@@ -269,45 +269,74 @@ class DiffSepModel:
                        **kwargs):
         """check_finite (extension): the returned sampler looks at its samples and repeats the request on fallback_model()
         when an f16 / hybrid run overflowed (rerun_if_nonfinite).  That look synchronises with the sampler's stream: a caller
-        that keeps several batches in flight passes check_finite=False and calls rerun_if_nonfinite when it collects one."""
+        that keeps several batches in flight passes check_finite=False and calls rerun_if_nonfinite when it collects one.
+        The tracing extensions snapshots= / target= of sdes.get_pc_sampler pass through: the returned sampler's .trace is the
+        trace of its last call (with minibatch=: the minibatches' traces joined along the batch, and the third result the
+        joined [(xt, xt_mean)]); an overflow re-run repeats the request with the same trace arguments and its trace replaces
+        the first one."""
         sde = self.sde.copy()
         sde.N = self.sde.N if N is None else N
         kwargs = {"eps": self.t_eps, **kwargs}
 
-        def make_on(model, y_part):
+        def make_on(model, y_part, kw):
             if schedule is None:
-                return sdes.get_pc_sampler(predictor_name, corrector_name, sde=sde, score_fn=model, y=y_part, **kwargs)
+                return sdes.get_pc_sampler(predictor_name, corrector_name, sde=sde, score_fn=model, y=y_part, **kw)
             return sdes.get_pc_scheduled_sampler(predictor_name, corrector_name, sde=sde, score_fn=model, y=y_part,
-                                                 schedule=schedule, **kwargs)
+                                                 schedule=schedule, **kw)
 
-        def make(y_part):
-            inner = make_on(self, y_part)
+        def make(y_part, kw):
+            inner = make_on(self, y_part, kw)
             if not check_finite or not self.has_fallback():  # (decided from the mode: the fallback is BUILT at the first overflow)
                 return inner
-            return lambda: self.rerun_if_nonfinite(inner(), lambda fb: make_on(fb, y_part)())
+
+            def rerun(fb):
+                again = make_on(fb, y_part, kw)
+                result = again()
+                checked.trace = getattr(again, "trace", None)
+                return result
+
+            def checked():
+                result = inner()
+                checked.trace = getattr(inner, "trace", None)
+                return self.rerun_if_nonfinite(result, rerun)
+
+            checked.trace = None
+            return checked
 
         if minibatch is None:
-            return make(y)
+            return make(y, kwargs)
 
         seed0 = kwargs.pop("seed", None)
         if kwargs.get("lengths") is not None or kwargs.get("seeds") is not None:
             raise ValueError("lengths= / seeds= describe one engine batch; they cannot be combined with minibatch=")
+        target = kwargs.get("target")
 
         def batched_sampling_fn():
-            samples, ns, inter = [], [], []
+            samples, ns, inter, traces = [], [], [], []
             for i in range(int(math.ceil(y.shape[0] / minibatch))):
+                part = slice(i * minibatch, (i + 1) * minibatch)
+                kw = dict(kwargs)
                 # an explicit seed is advanced per minibatch: the same seed would give every minibatch of the same
                 # shape the same device noise
                 if seed0 is not None:
-                    kwargs["seed"] = (int(seed0) + 0x9E3779B97F4A7C15 * i) % (1 << 64)
-                sample, n, *other = make(y[i * minibatch:(i + 1) * minibatch])()
+                    kw["seed"] = (int(seed0) + 0x9E3779B97F4A7C15 * i) % (1 << 64)
+                if target is not None:
+                    kw["target"] = target[part]
+                sampler = make(y[part], kw)
+                sample, n, *other = sampler()
                 samples.append(sample)
                 ns.append(n)
-                if other:
+                if getattr(sampler, "trace", None) is not None:
+                    traces.append(sampler.trace)
+                elif other:
                     inter.append(other[0])
             samples = torch.cat(samples, dim=0)
+            if traces:
+                batched_sampling_fn.trace = SamplerTrace.cat(traces)
+                return samples, ns, batched_sampling_fn.trace.intermediates()
             return (samples, ns, inter) if inter else (samples, ns)
 
+        batched_sampling_fn.trace = None
         return batched_sampling_fn
 
     def separate(self, mix, **kwargs):

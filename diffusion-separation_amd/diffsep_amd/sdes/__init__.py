@@ -57,7 +57,7 @@ class _HybridScore:
 
 
 def _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, denoise, eps, snr, corrector_steps,
-                  probability_flow, intermediate, schedule, seed=None, lengths=None, seeds=None):
+                  probability_flow, intermediate, schedule, seed=None, lengths=None, seeds=None, snapshots=None, target=None):
     predictor = PredictorRegistry.get_by_name(predictor_name)(sde, score_fn, probability_flow=probability_flow)
     corrector = CorrectorRegistry.get_by_name(corrector_name)(sde, score_fn, snr=snr, n_steps=corrector_steps)
     eng = _engine_of(score_fn)
@@ -66,10 +66,11 @@ def _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, d
              and corrector_name in ("ald2", "ald", "langevin", "none") and isinstance(sde, MixSDE)
              and not (corrector_name == "ald" and type(sde) is not MixSDE))
 
-    if not fused and (seed is not None or lengths is not None or seeds is not None):
-        # the step-by-step loop draws from torch's global generator like the reference (torch.manual_seed governs it)
-        # and has no notion of a zero-padded batch
-        raise ValueError("seed= / seeds= / lengths= are extensions of the fused engine sampler; this request "
+    traced = snapshots is not None or target is not None
+    if not fused and (seed is not None or lengths is not None or seeds is not None or traced):
+        # the step-by-step loop draws from torch's global generator like the reference (torch.manual_seed governs it),
+        # has no notion of a zero-padded batch, and hands its states out itself (intermediate=True)
+        raise ValueError("seed= / seeds= / lengths= / snapshots= / target= are extensions of the fused engine sampler; this request "
                          "(intermediate, true_mean or a user predictor / corrector) runs the generic loop")
 
     # dtype="hybrid" outside the fused sampler (intermediate=True, true_mean, a user-written predictor / corrector — calls the
@@ -91,10 +92,14 @@ def _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, d
                 s_ = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
                 ts = None if schedule is None else _timesteps(sde, eps, schedule, "cpu").numpy()
                 tail = getattr(score_fn, "tail_engine", lambda: None)()
-                x, _ = eng.pc_sample(y, sde.engine_config(), N=sde.N, corrector_steps=corrector.n_steps, snr=snr,
-                                     eps=eps, denoise=denoise, predictor=predictor_name, corrector=corrector_name,
-                                     seed=s_, timesteps=ts, lengths=lengths, seeds=seeds, tail=tail,
-                                     head_steps=getattr(score_fn, "head_steps", 0) if tail is not None else 0)
+                x, _, *tr = eng.pc_sample(y, sde.engine_config(), N=sde.N, corrector_steps=corrector.n_steps, snr=snr,
+                                          eps=eps, denoise=denoise, predictor=predictor_name, corrector=corrector_name,
+                                          seed=s_, timesteps=ts, lengths=lengths, seeds=seeds, tail=tail,
+                                          head_steps=getattr(score_fn, "head_steps", 0) if tail is not None else 0,
+                                          snapshots=snapshots, target=target)
+                if traced:  # the tap of the fused sampler: the requested steps in the shape of `intermediate`
+                    pc_sampler.trace = tr[0]
+                    return x, ns, tr[0].intermediates()
                 return x, ns
             im = []
             xt = sde.prior_sampling((true_mean if true_mean is not None else y).shape,
@@ -112,25 +117,31 @@ def _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, d
             res = xt_mean if denoise else xt
             return (res, ns, im) if intermediate else (res, ns)
 
+    pc_sampler.trace = None
     return pc_sampler
 
 
 def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean=None, denoise=True, eps=3e-2, snr=0.1,
                    corrector_steps=1, probability_flow=False, intermediate=False, **kwargs):
     """Reference: sdes/__init__.py:132-190.  Extensions through **kwargs (fused engine path only): seed, and for a
-    zero-padded batch of utterances of different lengths lengths=[B] (+ seeds=[B], per-utterance RNG seeds)."""
+    zero-padded batch of utterances of different lengths lengths=[B] (+ seeds=[B], per-utterance RNG seeds); snapshots=
+    (a strictly ascending list of reverse steps, or "all") and / or target= ([B,S,T], zero beyond each length) trace the fused
+    sampler (Engine.pc_sample): it then returns (x, ns, im), im = [(xt, xt_mean)] of the requested steps as intermediate=True
+    would list them, and pc_sampler.trace (an engine.SamplerTrace) holds the steps and the Gram rows against the target."""
     return _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, denoise, eps, snr,
                          corrector_steps, probability_flow, intermediate, None, seed=kwargs.get("seed"),
-                         lengths=kwargs.get("lengths"), seeds=kwargs.get("seeds"))
+                         lengths=kwargs.get("lengths"), seeds=kwargs.get("seeds"), snapshots=kwargs.get("snapshots"),
+                         target=kwargs.get("target"))
 
 
 def get_pc_scheduled_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=True, true_mean=None, eps=3e-2,
                              snr=0.1, corrector_steps=1, probability_flow=False, intermediate=False,
                              schedule="linear", **kwargs):
-    """Reference: sdes/__init__.py:46-129."""
+    """Reference: sdes/__init__.py:46-129.  The extensions through **kwargs are get_pc_sampler's."""
     return _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, denoise, eps, snr,
                          corrector_steps, probability_flow, intermediate, schedule, seed=kwargs.get("seed"),
-                         lengths=kwargs.get("lengths"), seeds=kwargs.get("seeds"))
+                         lengths=kwargs.get("lengths"), seeds=kwargs.get("seeds"), snapshots=kwargs.get("snapshots"),
+                         target=kwargs.get("target"))
 
 
 _ODE_KWARGS = ("first_step", "max_step", "max_nfe", "seed", "noise", "per_utterance", "lengths", "seeds")

@@ -193,6 +193,28 @@ int32_t diffsep_pc_sample_ex(diffsep_engine* e, const diffsep_sde_config* sde, c
                              const float* noise, uint64_t seed, const float* timesteps_host, int32_t* nfe_out,
                              void* stream);
 
+/* diffsep_pc_sample_ex with a tap on the intermediate states of the reverse diffusion: what the reference's sampler returns
+ * with intermediate=True (sdes/__init__.py:168-186: `(xt, xt_mean)` appended after the corrector and before the predictor of
+ * every step) and what evaluate.py:29-61 draws its `fig/<split>/evo_NNN.pdf` from.  In reverse step i, at that same place, one
+ * launch of one 1024-thread block per utterance makes one pass over the state:
+ *   snap_steps_host [n_snap] : HOST, the steps to copy, strictly ascending, each in [0, N);
+ *   snap_x, snap_xm          : [n_snap][B][S][T] device f32: x (and x_mean; snap_xm may be NULL) of those steps.  Without a
+ *                              corrector step (corrector none, or corrector_steps 0) x_mean is x, as in the reference's loop;
+ *   target                   : [B][S][T] device f32, or NULL.  It must be ZERO beyond each utterance's length (the state's tail
+ *                              is, so that the tails add nothing to the sums);
+ *   gram                     : [N+1][B][3][S][S] device float64, given with target or not at all.  Row i < N is bit for bit
+ *                              diffsep_gram(target, x of step i) (the same per-thread stride and reduction order), row N is
+ *                              diffsep_gram(target, out): the SI-SDR / SI-SIR / SI-SAR of every step follow on the host.
+ * The state lives on `e` whichever engine evaluates a step (ext->tail_engine), and `out` is bit for bit that of the untraced
+ * call.  Refused with an error text before anything is enqueued: steps unordered, repeated or out of range; n_snap > 0 with
+ * snap_x NULL; exactly one of target / gram.  With n_snap == 0 and target == NULL this IS diffsep_pc_sample_ex: not one
+ * launch, copy or allocation more. */
+int32_t diffsep_pc_sample_trace(diffsep_engine* e, const diffsep_sde_config* sde, const diffsep_sampler_config* smp,
+                                const diffsep_sampler_ext* ext, const float* mix_norm, float* out, int32_t B, int64_t T,
+                                const float* noise, uint64_t seed, const float* timesteps_host, int32_t* nfe_out,
+                                int32_t n_snap, const int32_t* snap_steps_host, float* snap_x, float* snap_xm,
+                                const float* target, double* gram, void* stream);
+
 /* The probability-flow ODE sampler: sdes.get_ode_sampler(...)() (sdes/__init__.py:193-278), i.e.
  * scipy.integrate.solve_ivp(method = RK45 | RK23) on dx/dt = f(x,t) - 0.5 G(t)^2 score(x,t,mix) (RSDE.sde with
  * probability_flow, sdes/sdes.py:130-160) from t = 1 down to eps, the whole batch [B,S,T] as ONE system (one error
