@@ -21,28 +21,17 @@
 //     contiguous per wave instruction; the 8 waves read the same fragments: L1 hits) a whole matrix ahead of their use: Wv and
 //     M at kernel start, Wo while P V frees the score registers; LDS fragments are read one k-block ahead of their MFMAs and
 //     consecutive MFMAs go to different accumulators (the first version, with every operand fetched where it is used, took
-//     40 us per block: tools/attn_timing.sh).
+//     40 us per block: tools/phase_timing.py --kernel attn_fused).
 // Rounding points: h, V, P and the output in the storage type like the unfused path; M in the storage type instead of Q and K.
 // Both paths are compared with the CPU oracle at the 16-bit tolerance (tests/test_round4_gpu.py: the fused one is the closer).
 #include <type_traits>
 
 #include "conv_device.h"
 
-#ifdef ATTN_TIMING  // profiling build only (tools/attn_timing.sh): per-phase cycle totals of wave 0 of every block
-__device__ unsigned long long g_attn_dbg[16];
-#define AT_DECL unsigned long long at_prev = __builtin_readcyclecounter(), at_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define AT_MARK(i) { unsigned long long at_now = __builtin_readcyclecounter(); at_acc[i] += at_now - at_prev; at_prev = at_now; }
-#define AT_FLUSH if (threadIdx.x == 0) { for (int q = 0; q < 12; ++q) atomicAdd(&g_attn_dbg[q], at_acc[q]); atomicAdd(&g_attn_dbg[15], 1ull); }
-extern "C" int diffsep_attn_debug_read(unsigned long long* out, int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_attn_dbg), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_dbg), z, sizeof(z)); }
-  return 0;
-}
-#else
-#define AT_DECL
-#define AT_MARK(i)
-#define AT_FLUSH
+#ifdef ATTN_TIMING  // profiling build only (tools/phase_timing.py --kernel attn_fused): per-phase cycle totals of wave 0 of every block
+#define PT_NAME attn  // (diffsep_attn_debug_read)
 #endif
+#include "phase_timing.h"
 
 namespace {
 
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
   const int l32 = lane & 31, h = lane >> 5;
   const int b = blockIdx.x, L = p.L;
   const bf16_t* xb = p.x + (long)b * p.x_bs;
-  AT_DECL
+  PT_DECL
 
   // Weight fragments: global loads issued a whole matrix ahead of their use (file header)
   const unsigned wlane = (unsigned)lane * 16u;  // fragment (kb, n tile) at ((kb * 4 + nt) * 64 + lane) * 16 B
@@ -150,9 +139,9 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
     const int w = tid / C - 1, c = tid % C;  // waves 2 - 7: the three bias vectors
     sTab[(2 + w) * C + c] = (w == 0 ? p.bqk : (w == 1 ? p.bv : p.bo))[c];
   }
-  AT_MARK(0)
+  PT_MARK(0)
   __syncthreads();
-  AT_MARK(1)
+  PT_MARK(1)
   {
     const int sl = tid % PPP;
     float sc[8], sh[8];
@@ -169,9 +158,9 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
       if (px < LT * 32) *reinterpret_cast<u32x4_t*>(sH + px * PH + sl * 16) = o;
     }
   }
-  AT_MARK(2)
+  PT_MARK(2)
   __syncthreads();
-  AT_MARK(3)
+  PT_MARK(3)
 
   auto hfrag = [&](int tile, int kb) {  // h rows 32 tile + l32, channels 16 kb + 8 h ..
     return *reinterpret_cast<const u32x4_t*>(sH + (tile * 32 + l32) * PH + kb * 32 + h * 16);
@@ -206,9 +195,9 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
       }
     }
   }
-  AT_MARK(4)
+  PT_MARK(4)
   __syncthreads();
-  AT_MARK(5)
+  PT_MARK(5)
 
   // ---- this wave's query rows
   const int i0 = wave * 32;
@@ -238,7 +227,7 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
         }
       }
     }
-    AT_MARK(6)
+    PT_MARK(6)
     // S[i][j] = Q'[i] . h[j]: lane = row i, registers = pixels j (LT tiles of 32); k-blocks outside (consecutive MFMAs on
     // different accumulators), h fragments through a ring of 8 read 6 MFMAs ahead
     f32x16 s[LT];
@@ -255,7 +244,7 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
         s[t % LT] = mma(ring[t % 8], q2[t / LT], s[t % LT]);
       }
     }
-    AT_MARK(7)
+    PT_MARK(7)
     // softmax over j: the lane holds half of its row (the other k-half lane the rest); pixels past L are masked
     float mx = -3.0e38f, sum = 0.f;
     auto soft = [&](auto FULL_) __attribute__((always_inline)) {
@@ -282,7 +271,7 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
     if (L == LT * 32) soft(std::true_type{}); else soft(std::false_type{});
     sum += __shfl_xor(sum, 32, 64);
     const float inv_sum = __builtin_amdgcn_rcpf(sum);
-    AT_MARK(8)
+    PT_MARK(8)
     // O = P V (P normalised: the storage-type rounding of the probabilities matches the unfused path's softmax output); the
     // output projection's fragments are issued as the score tiles die
     const char* vr = sVt + l32 * PV + h * 16;
@@ -303,7 +292,7 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
 #pragma unroll
       for (int q = 0; q < WPT; ++q) wa[(jt * WPT + q) % 4][(jt * WPT + q) / 4] = wfrag(p.wo, (jt * WPT + q) / 4, (jt * WPT + q) % 4);
     }
-    AT_MARK(9)
+    PT_MARK(9)
     u32x4_t of[NKB];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) acc_to_frags(oacc[nt], of[2 * nt], of[2 * nt + 1]);
@@ -315,7 +304,7 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) oacc[nt] = mma(wa[nt][kb], of[kb], oacc[nt]);
   }
-  AT_MARK(10)
+  PT_MARK(10)
   // ---- store pass.  The projected tile goes through LDS (fp32, the h / V^T area: free once every wave is past its P V) so
   // that the residual is read and the output written in full 128-byte lines — in the accumulator layout a wave instruction
   // touches 32 rows, 16 bytes each (measured: the slowest phase of the first version) — and the statistics of the output for
@@ -363,7 +352,7 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
         for (int j = 0; j < 8; ++j) { ssum[j] += v[j]; ssq[j] = fmaf(v[j], v[j], ssq[j]); }
       }
     }
-    if (!p.stats) { AT_FLUSH return; }
+    if (!p.stats) { PT_FLUSH return; }
     __syncthreads();  // (sO is read: reuse it for the partial sums [32 row groups][C][2])
     float* sP = sO;
 #pragma unroll
@@ -380,8 +369,8 @@ __global__ __launch_bounds__(NT_) void attn_fused_kernel(AttnK p) {
       ds_stat_flush(p.stats + ((long)b * C + c) * 2, st, a);
     }
   }
-  AT_MARK(11)
-  AT_FLUSH
+  PT_MARK(11)
+  PT_FLUSH
 }
 
 }  // namespace

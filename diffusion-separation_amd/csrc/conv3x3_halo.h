@@ -1,12 +1,11 @@
 // conv3x3_halo.h — what the persistent halo-tile 3x3 convolutions share word for word: conv3x3_rw.hip (register-resident
 // weights), conv3x3_sw.hip (streamed weights) and conv3x3_sws.hip (split mode).  Included once by each of them, before its own
-// code.  Device side: the per-phase timing scaffolding of the profiling builds and the tile constants (the buffer helpers and
-// everything else that is not specific to the halo tile come with conv_device.h).  Host side: the parameter struct of sw and sws
+// code.  Device side: the tile constants (the buffer helpers and everything else that is not specific to the halo tile come with
+// conv_device.h, the per-phase counters of the profiling builds with phase_timing.h).  Host side: the parameter struct of sw and sws
 // and what fills it from ConvArgs, the launch tail, the clauses the three ds_conv_*_supported predicates share and the addressing
 // preconditions of the kernels' 32-bit offsets and "no tile" pixel indices (halo_addressing_ok).  The kernel BODIES stay apart:
 // every function boundary between them moved registers (profiles/experiments/README.md, "Sharing the halo-tile pipeline").
-// Everything lives in an anonymous namespace; the profiling build's counters (g_<name>_dbg) and read-back function keep the names
-// and external linkage they had in each kernel file.
+// Everything lives in an anonymous namespace; the profiling builds' launch hooks (halo_env) are host code of these kernels alone.
 #pragma once
 
 #include <ctype.h>
@@ -17,36 +16,21 @@
 
 #include "conv_device.h"
 
-// ---- profiling build only (the including file defines HALO_TIMING as rw / sw / sws): per-phase cycle totals of wave 0,
-// read back through diffsep_<name>_debug_read
-#ifdef HALO_TIMING
-#define HALO_CAT_(a, b, c) a##b##c
-#define HALO_CAT(a, b, c) HALO_CAT_(a, b, c)
-#define HALO_DBG HALO_CAT(g_, HALO_TIMING, _dbg)
-__device__ unsigned long long HALO_DBG[16];
-extern "C" int HALO_CAT(diffsep_, HALO_TIMING, _debug_read)(unsigned long long* out, int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(HALO_DBG), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(HALO_DBG), z, sizeof(z)); }
-  return 0;
-}
-#define RT_DECL unsigned rt_prev = (unsigned)__builtin_readcyclecounter(), rt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define RT_MARK(i) { unsigned rt_now = (unsigned)__builtin_readcyclecounter(); rt_acc[i] += rt_now - rt_prev; rt_prev = rt_now; }
-#define RT_FLUSH if (threadIdx.x == 0) { for (int q = 0; q < 8; ++q) atomicAdd(&HALO_DBG[q], (unsigned long long)rt_acc[q]); atomicAdd(&HALO_DBG[15], 1ull); }
+// ---- profiling build only (the including file defines PT_NAME as rw / rw4 / sw / sws under its -D<X>_TIMING): per-phase cycle
+// totals of wave 0, read back through diffsep_<name>_debug_read
+#include "phase_timing.h"
+#ifdef PT_NAME
 // the launch hooks of the profiling builds: DIFFSEP_<RW | SW | SWS>_G (blocks per image: fewer, fatter blocks) and
 // DIFFSEP_<..>_DBG (bit 0 = stores fall outside the tensor, bit 1 = loads do; the kernels that read p.dbg), else `dflt`
 #define HALO_STR_(a) #a
 #define HALO_STR(a) HALO_STR_(a)
 static int halo_env(const char* what, int dflt) {
   char n[32];
-  snprintf(n, sizeof(n), "DIFFSEP_%s_%s", HALO_STR(HALO_TIMING), what);
+  snprintf(n, sizeof(n), "DIFFSEP_%s_%s", HALO_STR(PT_NAME), what);
   for (char* c = n + 8; *c != '_'; ++c) *c = (char)toupper(*c);
   const char* v = getenv(n);
   return v ? atoi(v) : dflt;
 }
-#else
-#define RT_DECL
-#define RT_MARK(i)
-#define RT_FLUSH
 #endif
 
 namespace {
@@ -95,7 +79,7 @@ void halo_fill_common(K& k, const ConvArgs& a) {
   k.y = reinterpret_cast<T*>(a.y); k.y_bs = a.y_bs; k.ldy = a.ldy;
   k.stats = a.stats_acc;
   k.H = a.H; k.W = a.W; k.G = 0; k.tiles_x = 0; k.tiles_per_img = 0;
-#ifdef HALO_TIMING
+#ifdef PT_NAME
   k.dbg = halo_env("DBG", 0);
 #else
   k.dbg = 0;
@@ -126,7 +110,7 @@ int halo_fill_skip(HaloK<T>& k, const ConvArgs& a) {
 inline int halo_tiles(const ConvArgs& a, int tile_h) { return (a.H / tile_h) * (a.W / TW); }
 inline int halo_blocks_wanted(const ConvArgs& a, int ncb) {
   const int g = ds_num_cus() / (a.B * ncb);
-#ifdef HALO_TIMING
+#ifdef PT_NAME
   return halo_env("G", g);
 #else
   return g;

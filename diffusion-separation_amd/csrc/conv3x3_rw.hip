@@ -45,11 +45,12 @@
 // 32-cycle MFMA, the GroupNorm variant has ~9).  K order (chunk, tap, 16-channel block) as in conv_mfma.hip / conv3x3_ws.hip.
 #include <stdlib.h>
 
-#ifdef RW_TIMING  // profiling build only: per-phase cycle totals of wave 0 (diffsep_rw_debug_read; conv3x3_rw4.hip: diffsep_rw4_debug_read)
+#ifdef RW_TIMING  // profiling build only: per-phase cycle totals of wave 0 in row 0 and of the helper role's wave 4 in row 1
+                  // (phase_timing.h; diffsep_rw_debug_read; conv3x3_rw4.hip: diffsep_rw4_debug_read)
 #ifdef RW_FOUR_WAVE_TU
-#define HALO_TIMING rw4
+#define PT_NAME rw4
 #else
-#define HALO_TIMING rw
+#define PT_NAME rw
 #endif
 #endif
 #include "conv3x3_halo.h"
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
   const int b = blockIdx.x / p.G, part = blockIdx.x % p.G;
   const int t0 = (int)((long)part * p.tiles_per_img / p.G);
   const int nt = (int)((long)(part + 1) * p.tiles_per_img / p.G) - t0;
-  RT_DECL
+  PT_DECL
 
   // ---- tables: GroupNorm scale / shift of image b, bias.  The operands are LOADED here, ahead of the first chunk's loads and
   // the weight fragments (loads return in order), and turned into the LDS tables after those have been issued: the fp64
@@ -238,7 +239,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
   }
   const int ldi0 = (HW_ + 1 + ixp) * AROW + slot * 16;  // tile pixel (0, ixp): piece k < NI is HW_ pixels (one halo row) further
 
-  RT_MARK(6)
+  PT_MARK(6)
   const int M = p.H * p.W;
   const __amdgpu_buffer_rsrc_t rx1 = rsrc(p.x + (long)b * p.x_bs, (unsigned)M * p.ldx * 2u);
   const __amdgpu_buffer_rsrc_t rx2 = p.x2 ? rsrc(p.x2 + (long)b * p.x2_bs, (unsigned)M * p.ldx2 * 2u) : rx1;
@@ -553,7 +554,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
 #pragma unroll
       for (int k = 0; k < NL; ++k) issue_one(C0{}, hc, k, k < NI ? 0 : hrel[k < NI ? 0 : k - NI]);
       sync_lds();  // BAR_PRO_H: the matrix role's tables
-      RT_MARK(0)
+      PT_MARK(0)
 #pragma unroll
       for (int k = 0; k < NI; ++k) {  // the first phase's chunk; ps[] goes on to the next skip chunk
         put_skip(0, k);
@@ -563,7 +564,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
       act_tab(0);  // (one 3x3 chunk: its scale / shift stay in registers for the whole launch)
 #pragma unroll
       for (int u = 0; u < NL * 4; ++u) act_inplace(u);
-      RT_MARK(1)
+      PT_MARK(1)
       int hph = 0;
       int hy2 = (t0 + 2) / p.tiles_x, hx2 = (t0 + 2) - hy2 * p.tiles_x;
       for (int i = 0; i < nt; ++i) {
@@ -571,7 +572,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
         auto stage_phase = [&](auto self, auto P_) __attribute__((always_inline)) {
           constexpr int P = decltype(P_)::value;
           sync_lds();  // BAR_PH_H: the matrix role has read the slot written now; the chunk staged last phase is visible to it
-          RT_MARK(2)
+          PT_MARK(2)
           const int sl = (hph & 1) ^ 1;
           if constexpr (P == NSK - 1) {  // the next phase is this tile's long one: its 3x3 chunk, activated a tile ago
 #pragma unroll
@@ -593,7 +594,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
             }
           }
           ++hph;
-          RT_MARK(3)
+          PT_MARK(3)
           if constexpr (P + 1 < NPH) self(self, std::integral_constant<int, P + 1>{});
         };
         stage_phase(stage_phase, std::integral_constant<int, 0>{});
@@ -605,11 +606,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
         __syncthreads();
         __syncthreads();
       }
-#ifdef RW_TIMING  // the helper role's marks: counters 8 .. 11 (wave 4; the matrix role's are 0 .. 7 of wave 0)
-      if (threadIdx.x == NT) {
-        for (int q = 0; q < 4; ++q) atomicAdd(&HALO_DBG[8 + q], (unsigned long long)rt_acc[q]);
-      }
-#endif
+      PT_FLUSH_IF(threadIdx.x == NT, 1)  // the helper role's marks: row 1 (wave 4; the matrix role's are row 0 of wave 0)
       return;
     }
   }
@@ -624,12 +621,12 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
 #pragma unroll
       for (int k = 0; k < NB; ++k) hrel[k] = sDesc[k * NT + tid];  // (the thread's own entries: no barrier)
       sync_lds();  // BAR_PRO_H: the matrix role's tables
-      RT_MARK(0)   // (profiling build, wave 4: 0 = up to the tables, 1 = first chunk, 2 = waiting at phase barriers, 3 = staging)
+      PT_MARK(0)   // (profiling build, wave 4: 0 = up to the tables, 1 = first chunk, 2 = waiting at phase barriers, 3 = staging)
       act_tab(HC0);
 #pragma unroll
       for (int u = 0; u < NL * 4; ++u)
         unit(std::integral_constant<int, HC0>{}, std::integral_constant<int, HC1>{}, hc, h1st, 0, u, (u >> 2) < NI ? 0 : hrel[(u >> 2) < NI ? 0 : (u >> 2) - NI]);
-      RT_MARK(1)
+      PT_MARK(1)
       int hph = 0;
       TileG hnc = tile_geom(1);
       int hy2 = (t0 + 2) / p.tiles_x, hx2 = (t0 + 2) - hy2 * p.tiles_x;
@@ -639,7 +636,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
           constexpr int P = decltype(P_)::value;
           constexpr int C1 = G::chunk_of((P + 1) % NPH), C2 = G::chunk_of((P + 2) % NPH);
           sync_lds();  // BAR_PH_H: the matrix role has read the slot written now; the chunk staged last phase is visible to it
-          RT_MARK(2)
+          PT_MARK(2)
           const int sl = (hph & 1) ^ 1;
           const TileG& g1 = (P + 1) / NPH == 0 ? hc : hn;
           const TileG& g2 = (P + 2) / NPH == 0 ? hc : ((P + 2) / NPH == 1 ? hn : hnn);
@@ -648,7 +645,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
           for (int u = 0; u < NL * 4; ++u)
             unit(std::integral_constant<int, C1>{}, std::integral_constant<int, C2>{}, g1, g2, sl, u, (u >> 2) < NI ? 0 : hrel[(u >> 2) < NI ? 0 : (u >> 2) - NI]);
           ++hph;
-          RT_MARK(3)
+          PT_MARK(3)
           if constexpr (P + 1 < NPH) self(self, std::integral_constant<int, P + 1>{});
         };
         stage_phase(stage_phase, std::integral_constant<int, 0>{});
@@ -660,11 +657,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
         __syncthreads();
         __syncthreads();
       }
-#ifdef RW_TIMING  // the helper role's marks: counters 8 .. 11 (wave 4; the matrix role's are 0 .. 7 of wave 0)
-      if (threadIdx.x == NT) {
-        for (int q = 0; q < 4; ++q) atomicAdd(&HALO_DBG[8 + q], (unsigned long long)rt_acc[q]);
-      }
-#endif
+      PT_FLUSH_IF(threadIdx.x == NT, 1)  // the helper role's marks: row 1 (wave 4; the matrix role's are row 0 of wave 0)
       return;
     }
   }
@@ -1012,7 +1005,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
     load_weights();
     build_tables();
     sync_lds();  // tables (and the LDS-resident weight fragments) visible (BAR_PRO_M)
-    RT_MARK(7)
+    PT_MARK(7)
     if constexpr (REL_REGS && !HLP) {
 #pragma unroll
       for (int k = 0; k < NB; ++k) relreg[k] = sDesc[k * NT + tid];
@@ -1033,7 +1026,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
              (u >> 2) < NI ? 0 : sDesc[((u >> 2) < NI ? 0 : (u >> 2) - NI) * NT + tid]);
     }
   }
-  RT_MARK(0)
+  PT_MARK(0)
   TileG gp = tile_geom(nt);  // "previous tile" of the first one: no tile (its stores fall outside every tensor)
   int ph = 0;                 // phases done: the chunk of phase ph sits in ring slot ph & 1
   // tile i + 2 by increments (a division per tile and geometry is ~45 scalar instructions in a stream whose issue slots
@@ -1046,7 +1039,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
     auto run = [&](auto self, auto P_) __attribute__((always_inline)) {
       constexpr int P = decltype(P_)::value;
       sync_lds();
-      RT_MARK(1)
+      PT_MARK(1)
       const int slot_r = ph & 1;
       half(P_, std::integral_constant<int, 0>{}, std::integral_constant<bool, P == 0>{}, slot_r, gp, ((P + 1) / NPH == 0 ? gc : gn), ((P + 2) / NPH == 0 ? gc : ((P + 2) / NPH == 1 ? gn : gnn)));
       if constexpr (P == 0) {
@@ -1057,7 +1050,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
       }
       half(P_, std::integral_constant<int, 1>{}, std::integral_constant<bool, P == NPH - 1>{}, slot_r, gc, ((P + 1) / NPH == 0 ? gc : gn), ((P + 2) / NPH == 0 ? gc : ((P + 2) / NPH == 1 ? gn : gnn)));
       ++ph;
-      RT_MARK(G::chunk_of(P) < NCH ? 2 : 3)
+      PT_MARK(G::chunk_of(P) < NCH ? 2 : 3)
       if constexpr (P + 1 < NPH) self(self, std::integral_constant<int, P + 1>{});
     };
     run(run, std::integral_constant<int, 0>{});
@@ -1077,7 +1070,7 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
     epi_bias(e & 1, t0, t1);
     epi_unit(gp, RH + (e >> 1), e & 1, t0, t1);
   }
-  RT_MARK(4)
+  PT_MARK(4)
   if (has_stats) {
     __syncthreads();
     // per lane 16 couts (cg * 32 + 8 q + 4 h + i) of pixel column l32 of its rows: sum over the 32 columns and the two
@@ -1102,8 +1095,8 @@ __global__ __launch_bounds__(rw_helper_form(NCH, MODE, NCG) ? 2 * NT : NT, rw_he
       ds_stat_flush(p.stats + ((long)b * CO + co) * 2, st, a);
     }
   }
-  RT_MARK(5)
-  RT_FLUSH
+  PT_MARK(5)
+  PT_FLUSH
 }
 
 // blocks per image: the compute units over the batch, then the A/B options

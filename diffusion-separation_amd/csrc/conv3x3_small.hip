@@ -23,7 +23,7 @@
 //
 // Measured (B = 16, 128 -> 128, inside the captured graph): 16^2 19.2 -> ~14 us, 8^2 18.8 -> ~11, 4^2 18.8 -> ~9.5 per
 // launch, of which ~5 us is the floor of any kernel node; one batch alone 371 -> 350 ms, four in flight unchanged.
-// tools/small_timing.sh (-DSM_TIMING) prints the per-phase cycles of a block.
+// tools/phase_timing.py --kernel conv3x3_small (-DSM_TIMING) prints the per-phase cycles of a block.
 //
 // ESZ = 4 instantiates the same kernel for fp32 tensors in split mode (DIFFSEP_F32_SPLIT): 64-channel phases (the bytes of
 // 128 bf16 channels), values split into hi / lo bf16 planes on the way to LDS, three MFMAs per k-block, fp32 epilogue
@@ -36,23 +36,10 @@
 
 #include "conv_device.h"
 
-#ifdef SM_TIMING  // profiling build only (tools/small_timing.sh): per-phase cycle totals of wave 0 of every block
-__device__ unsigned long long g_sm_dbg[16];
-#define ST_DECL unsigned long long st_prev = __builtin_readcyclecounter(), st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; const unsigned long long st_rt0 = __builtin_amdgcn_s_memrealtime();
-#define ST_MARK(i) { unsigned long long st_now = __builtin_readcyclecounter(); st_acc[i] += st_now - st_prev; st_prev = st_now; }
-#define ST_WAIT asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#define ST_FLUSH if (threadIdx.x == 0) { st_acc[11] = __builtin_amdgcn_s_memrealtime() - st_rt0; /* 100 MHz ticks */ for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&g_sm_dbg[i_], st_acc[i_]); atomicAdd(&g_sm_dbg[15], 1ull); }
-extern "C" int diffsep_small_debug_read(unsigned long long* out, int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sm_dbg), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sm_dbg), z, sizeof(z)); }
-  return 0;
-}
-#else
-#define ST_DECL
-#define ST_MARK(i)
-#define ST_WAIT
-#define ST_FLUSH
+#ifdef SM_TIMING  // profiling build only (tools/phase_timing.py --kernel conv3x3_small): per-phase cycle totals of wave 0 of every block
+#define PT_NAME small  // (diffsep_small_debug_read)
 #endif
+#include "phase_timing.h"
 
 namespace {
 
@@ -136,7 +123,7 @@ __global__ __launch_bounds__(SmTile<GW>::NT, 2) void conv3x3_small_kernel(SmK p)
   constexpr int THT = G::THT, NT = G::NT, NWAVES = NT / 64;
   constexpr int HWS = G::HWS, HWSP = G::HWSP, HP = G::HP, NVEC = G::NVEC, RPS = G::RPS, PSTR = G::PSTR, NA = G::NA, NWV = G::NWV,
                 NGRP = G::NGRP;
-  ST_DECL
+  PT_DECL
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* sIn = smem;
   char* sW = smem + G::LDS_IN;
@@ -334,10 +321,10 @@ __global__ __launch_bounds__(SmTile<GW>::NT, 2) void conv3x3_small_kernel(SmK p)
   };
 
   // ---- prologue: the first two phases in flight while the GroupNorm table is built
-  ST_MARK(0)
+  PT_MARK(0)
   issue(0, s0);
   if (nph > 1) issue(1, s1);
-  ST_MARK(1)
+  PT_MARK(1)
   if (MODE != 0 && p.gn_acc1) {
     long long* tmp = reinterpret_cast<long long*>(smem);  // [Cin][2]: the staging area is still unused
     for (int c = tid; c < p.Cin; c += NT) {
@@ -379,7 +366,7 @@ __global__ __launch_bounds__(SmTile<GW>::NT, 2) void conv3x3_small_kernel(SmK p)
   }
   fetch_gn(0, s0);
   if (nph > 1) fetch_gn(1, s1);
-  ST_MARK(2)
+  PT_MARK(2)
 
   // residual of this lane's output quad: in flight during the K loop
   const __amdgpu_buffer_rsrc_t rr = rsrc(p.res ? (const char*)p.res + (long)b * p.res_bs * ESZ : (const char*)p.y,
@@ -401,18 +388,18 @@ __global__ __launch_bounds__(SmTile<GW>::NT, 2) void conv3x3_small_kernel(SmK p)
   }
 
   auto step = [&](int ph, Stage& S) __attribute__((always_inline)) {
-    ST_WAIT
-    ST_MARK(3)
+    PT_WAIT
+    PT_MARK(3)
     activate(S);
-    ST_MARK(4)
+    PT_MARK(4)
     if (ph) __syncthreads();  // the previous phase's fragment reads are done
     write(S);
     const bool raw = S.raw;
     if (ph + 2 < nph) { issue(ph + 2, S); fetch_gn(ph + 2, S); }
     __syncthreads();
-    ST_MARK(5)
+    PT_MARK(5)
     mma(raw);
-    ST_MARK(6)
+    PT_MARK(6)
   };
   for (int ph = 0; ph < nph; ph += 2) {
     step(ph, s0);
@@ -446,7 +433,7 @@ __global__ __launch_bounds__(SmTile<GW>::NT, 2) void conv3x3_small_kernel(SmK p)
       st8(ry, yo, make_uint2(pack_h2(v[h][0], v[h][1]), pack_h2(v[h][2], v[h][3])));
     }
   }
-  ST_MARK(7)
+  PT_MARK(7)
   if (p.stats) {
     const float keep = mo >= 0 ? 1.f : 0.f;
     float ssum[NH][4], ssq[NH][4];
@@ -481,8 +468,8 @@ __global__ __launch_bounds__(SmTile<GW>::NT, 2) void conv3x3_small_kernel(SmK p)
       ds_stat_add(o + 1, (long long)llrint(s2 * DS_STAT_SQ_SCALE));
     }
   }
-  ST_MARK(8)
-  ST_FLUSH
+  PT_MARK(8)
+  PT_FLUSH
 }
 
 template <int GW, int PC, int NS, int MODE, int ESZ>

@@ -27,7 +27,7 @@
 #include <stdlib.h>
 
 #ifdef SW_TIMING  // profiling build only: per-phase cycle totals of wave 0 (diffsep_sw_debug_read)
-#define HALO_TIMING sw
+#define PT_NAME sw
 #endif
 #include "conv3x3_halo.h"
 
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
   const int b = blockIdx.x / (p.G * p.ncb), cb = (blockIdx.x / p.G) % p.ncb, part = blockIdx.x % p.G;
   const int t0 = (int)((long)part * p.tiles_per_img / p.G);
   const int nt = (int)((long)(part + 1) * p.tiles_per_img / p.G) - t0;
-  RT_DECL
+  PT_DECL
 
   // ---- tables: GroupNorm scale / shift of image b, bias.  The operands are LOADED here, ahead of the first chunk's loads and
   // the first weight fragments (loads return in order), and turned into the LDS tables after those have been issued
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
   }
   const int ldi0 = (HW_ + 1 + ixp) * AROW + slot * 16;  // tile pixel (0, ixp): piece k < NI is HW_ pixels (one halo row) further
 
-  RT_MARK(6)
+  PT_MARK(6)
   const int M = p.H * p.W;
   const __amdgpu_buffer_rsrc_t rx1 = rsrc(p.x + (long)b * p.x_bs, (unsigned)M * p.ldx * 2u);
   const __amdgpu_buffer_rsrc_t rx2 = p.x2 ? rsrc(p.x2 + (long)b * p.x2_bs, (unsigned)M * p.ldx2 * 2u) : rx1;
@@ -710,7 +710,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
     for (int k = 0; k < NL; ++k) issue_one(std::integral_constant<int, CH0>{}, gc, k, k < NI ? 0 : sDesc[(k < NI ? 0 : k - NI) * NT + tid]);
     build_tables();
     sync_lds();  // tables visible
-    RT_MARK(7)
+    PT_MARK(7)
     if constexpr (REL_REGS) {
 #pragma unroll
       for (int k = 0; k < NB; ++k) relreg[k] = sDesc[k * NT + tid];
@@ -741,13 +741,13 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
       for (int u = 0; u < NL * 4; ++u)
         unit(std::integral_constant<int, CH0>{}, std::integral_constant<int, CH1>{}, gc, g1st, 0, u,
              (u >> 2) < NI ? 0 : sDesc[((u >> 2) < NI ? 0 : (u >> 2) - NI) * NT + tid]);
-      RT_MARK(0)
+      PT_MARK(0)
     }
     // phase P stages the chunk of phase P + 1 and issues that of phase P + 2: both belong to the next tile once they wrap
     auto run = [&](auto self, auto P_) __attribute__((always_inline)) {
       constexpr int P = decltype(P_)::value;
       sync_lds();
-      RT_MARK(1)
+      PT_MARK(1)
       const int slot_r = ph & 1;
       if constexpr (G::mid(P)) {
         half(P_, std::integral_constant<int, 2>{}, std::false_type{}, slot_r, gp, ((P + 1) / NPH == 0 ? gc : gn), ((P + 2) / NPH == 0 ? gc : ((P + 2) / NPH == 1 ? gn : gnn)));
@@ -762,7 +762,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
       half(P_, std::integral_constant<int, 1>{}, std::integral_constant<bool, P == NPH - 1>{}, slot_r, gc, ((P + 1) / NPH == 0 ? gc : gn), ((P + 2) / NPH == 0 ? gc : ((P + 2) / NPH == 1 ? gn : gnn)));
       }
       ++ph;
-      RT_MARK(G::chunk_of(P) < NCH ? 2 : 3)
+      PT_MARK(G::chunk_of(P) < NCH ? 2 : 3)
       if constexpr (P + 1 < NPH) self(self, std::integral_constant<int, P + 1>{});
     };
     run(run, std::integral_constant<int, 0>{});
@@ -780,7 +780,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
     epi_bias(e & 1, t0, t1);
     epi_unit(gp, RH + (e >> 1), e & 1, t0, t1);
   }
-  RT_MARK(4)
+  PT_MARK(4)
   if (has_stats) {
     __syncthreads();
     // per lane 16 couts (cg * 32 + 8 q + 4 h + i) of pixel column l32 of its rows: sum over the 32 columns and the two
@@ -805,8 +805,8 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sw_kernel(SwK p) {
       ds_stat_flush(p.stats + ((long)b * p.cout + cb * CO + co) * 2, st, a);
     }
   }
-  RT_MARK(5)
-  RT_FLUSH
+  PT_MARK(5)
+  PT_FLUSH
 }
 
 template <int NCH, int NSK, int MODE, int RPW, int NCG>

@@ -25,7 +25,7 @@
 #include <stdlib.h>
 
 #ifdef SWS_TIMING  // profiling build only: per-phase cycle totals of wave 0 (diffsep_sws_debug_read)
-#define HALO_TIMING sws
+#define PT_NAME sws
 #endif
 #include "conv3x3_halo.h"
 
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
   const int b = blockIdx.x / (p.G * p.ncb), cb = (blockIdx.x / p.G) % p.ncb, part = blockIdx.x % p.G;
   const int t0 = (int)((long)part * p.tiles_per_img / p.G);
   const int nt = (int)((long)(part + 1) * p.tiles_per_img / p.G) - t0;
-  RT_DECL
+  PT_DECL
 
   // ---- tables: GroupNorm scale / shift of image b, bias (as conv3x3_rw.hip: operands loaded first, tables built behind the
   // first loads)
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
   }
   const int ldi0 = (HW_ + 1 + ixp) * AROW + slot * 8;  // tile pixel (0, ixp): piece k < NI is one halo row further
 
-  RT_MARK(6)
+  PT_MARK(6)
   const int M = p.H * p.W;
   const __amdgpu_buffer_rsrc_t rx1 = rsrc(p.x + (long)b * p.x_bs, (unsigned)M * p.ldx * 4u);
   const __amdgpu_buffer_rsrc_t rx2 = p.x2 ? rsrc(p.x2 + (long)b * p.x2_bs, (unsigned)M * p.ldx2 * 4u) : rx1;
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
     for (int k = 0; k < NL; ++k) issue_one(std::integral_constant<int, CH0>{}, gc, k, k < NI ? 0 : sDesc[(k < NI ? 0 : k - NI) * NT + tid]);
     build_tables();
     sync_lds();  // tables visible
-    RT_MARK(7)
+    PT_MARK(7)
 #pragma unroll
     for (int k = 0; k < NB; ++k) relreg[k] = sDesc[k * NT + tid];
 #pragma unroll
@@ -413,12 +413,12 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
 #pragma unroll
       for (int k = 0; k < NL; ++k)
         unit(std::integral_constant<int, CH0>{}, std::integral_constant<int, CH1>{}, gc, g1st, 0, k, k < NI ? 0 : relreg[k < NI ? 0 : k - NI]);
-      RT_MARK(0)
+      PT_MARK(0)
     }
     auto run = [&](auto self, auto P_) __attribute__((always_inline)) {
       constexpr int P = decltype(P_)::value;
       sync_lds();
-      RT_MARK(1)
+      PT_MARK(1)
       const int slot_r = ph & 1;
       half(P_, std::integral_constant<int, 0>{}, std::integral_constant<bool, P == 0>{}, slot_r, gp, ((P + 1) / NPH == 0 ? gc : gn), ((P + 2) / NPH == 0 ? gc : ((P + 2) / NPH == 1 ? gn : gnn)));
       if constexpr (P == 0) {
@@ -429,7 +429,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
       }
       half(P_, std::integral_constant<int, 1>{}, std::integral_constant<bool, P == NPH - 1>{}, slot_r, gc, ((P + 1) / NPH == 0 ? gc : gn), ((P + 2) / NPH == 0 ? gc : ((P + 2) / NPH == 1 ? gn : gnn)));
       ++ph;
-      RT_MARK(G::chunk_of(P) < NCH ? 2 : 3)
+      PT_MARK(G::chunk_of(P) < NCH ? 2 : 3)
       if constexpr (P + 1 < NPH) self(self, std::integral_constant<int, P + 1>{});
     };
     run(run, std::integral_constant<int, 0>{});
@@ -442,7 +442,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
   asm volatile("s_nop 11" : "+a"(acc[RH]), "+a"(acc[RH + 1]));
 #pragma unroll
   for (int e = 0; e < RH * 4; ++e) epi_quad(gp, RH + e / 4, e % 4);
-  RT_MARK(4)
+  PT_MARK(4)
   if (has_stats) {
     __syncthreads();
     // per lane 16 couts (cg * 32 + 8 q + 4 h + i) of pixel column l32 of its rows: sum over the 32 columns and the pixel groups
@@ -466,8 +466,8 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_sws_kernel(SwsK p) {
       ds_stat_flush(p.stats + ((long)b * p.cout + cb * CO + co) * 2, st, a);
     }
   }
-  RT_MARK(5)
-  RT_FLUSH
+  PT_MARK(5)
+  PT_FLUSH
 }
 
 template <int NCH, int NSK, int MODE, int NCG>

@@ -35,20 +35,9 @@
 #include "conv_device.h"
 
 #ifdef WS_TIMING  // profiling build only: per-phase cycle totals of wave 0 (group 0) and wave 4 (group 1)
-__device__ unsigned long long g_ws_dbg[32];
-#define WT_DECL unsigned wt_prev = (unsigned)__builtin_readcyclecounter(), wt_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define WT_MARK(i) { unsigned wt_now = (unsigned)__builtin_readcyclecounter(); wt_acc[i] += wt_now - wt_prev; wt_prev = wt_now; }
-#define WT_FLUSH if ((threadIdx.x & 255) == 0) { for (int q = 0; q < 12; ++q) atomicAdd(&g_ws_dbg[(threadIdx.x >> 8) * 16 + q], (unsigned long long)wt_acc[q]); atomicAdd(&g_ws_dbg[(threadIdx.x >> 8) * 16 + 15], 1ull); }
-extern "C" int diffsep_ws_debug_read(unsigned long long* out, int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ws_dbg), sizeof(unsigned long long) * 32);
-  if (reset) { unsigned long long z[32] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ws_dbg), z, sizeof(z)); }
-  return 0;
-}
-#else
-#define WT_DECL
-#define WT_MARK(i)
-#define WT_FLUSH
+#define PT_NAME ws  // (row 0 = wave 0, row 1 = wave 4; diffsep_ws_debug_read)
 #endif
+#include "phase_timing.h"
 
 #ifdef ABL_NOSTORE  // profiling: keep the epilogue arithmetic, drop (almost) all output traffic
 #define WS_STORE(v, r, off, so, aux) if ((v).x == 0x12345678u) __builtin_amdgcn_raw_buffer_store_b128(v, r, off, so, aux)
@@ -424,7 +413,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws1_kernel(WsK p) {
       for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
   };
 
-  WT_DECL
+  PT_DECL
   sync_lds();  // weights, tables, descriptors visible
   issue(0, 0);
   if (Q > 1) issue(1, 1);
@@ -432,37 +421,37 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws1_kernel(WsK p) {
 #pragma unroll
   for (int k = 0; k < NA1; ++k) act_one(0, k);
   write(0);
-  WT_MARK(4)
+  PT_MARK(4)
   for (int q = 0; q < Q; q += 2) {
     const int t = t0 + (q >> 1);
     const bool more = q + 2 < Q;
     // ---- chunk 0 (slot 0); set 1 = the tile's second chunk (issued a phase ago), set 0 <- next tile's first
     sync_lds();
-    WT_MARK(0)
+    PT_MARK(0)
     if (more) prep(q + 2);
     if (has_res) prep_res(t);        // (the residual is consumed by the epilogue at the end of the next phase)
     if constexpr (SKB > 0) prep_skip(t);
-    WT_MARK(1)
+    PT_MARK(1)
     mma(0, 0, std::true_type{}, more, has_res);   // activates set 1, fetches set 0 + the residual meanwhile
-    WT_MARK(2)
+    PT_MARK(2)
     write(1);
-    WT_MARK(3)
+    PT_MARK(3)
     // ---- chunk 1 (slot 1); set 0 = next tile's first chunk, set 1 <- next tile's second
     sync_lds();
-    WT_MARK(0)
+    PT_MARK(0)
     if (more) {
       prep(q + 3);
-      WT_MARK(1)
+      PT_MARK(1)
       mma(1, 1, std::true_type{}, true, false);   // activates set 0, fetches set 1 meanwhile
-      WT_MARK(2)
+      PT_MARK(2)
       write(0);
-      WT_MARK(3)
+      PT_MARK(3)
     } else {
       mma(1, 1, std::false_type{}, false, false);
-      WT_MARK(2)
+      PT_MARK(2)
     }
     epilogue(t);
-    WT_MARK(6)
+    PT_MARK(6)
   }
   if (has_stats) {
     __syncthreads();
@@ -482,8 +471,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws1_kernel(WsK p) {
       ds_stat_add(p.stats + ((long)b * C + co) * 2 + st, (long long)llrint(a * (st ? DS_STAT_SQ_SCALE : DS_STAT_SUM_SCALE)));
     }
   }
-  WT_MARK(5)
-  WT_FLUSH
+  PT_MARK(5)
+  PT_FLUSH_IF((threadIdx.x & 255) == 0, threadIdx.x >> 8)
 }
 
 // ---- the network's first layer: conv3x3 8 -> 64 (ncsnpp.py:352-357; 6 real input channels padded to 8) on the same

@@ -32,23 +32,11 @@
 
 #include "conv_device.h"
 
-#ifdef CONV_TIMING  // profiling build only (tools/conv_timing.sh): per-phase cycle totals of wave 0 of every block
-__device__ unsigned long long g_conv_dbg[16];
-#define CT_DECL unsigned long long ct_prev = __builtin_readcyclecounter(), ct_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define CT_MARK(i) { unsigned long long ct_now = __builtin_readcyclecounter(); ct_acc[i] += ct_now - ct_prev; ct_prev = ct_now; }
-#define CT_WAIT __builtin_amdgcn_s_waitcnt(0);
-#define CT_FLUSH if (threadIdx.x == 0) { for (int q = 0; q < 12; ++q) atomicAdd(&g_conv_dbg[q], ct_acc[q]); atomicAdd(&g_conv_dbg[15], 1ull); }
-extern "C" int diffsep_debug_read(unsigned long long* out, int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_conv_dbg), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_conv_dbg), z, sizeof(z)); }
-  return 0;
-}
-#else
-#define CT_DECL
-#define CT_MARK(i)
-#define CT_WAIT
-#define CT_FLUSH
+#ifdef CONV_TIMING  // profiling build only (tools/phase_timing.py --kernel conv_mfma): per-phase cycle totals of wave 0 of every block
+#define PT_NAME conv
+#define PT_READ diffsep_debug_read
 #endif
+#include "phase_timing.h"
 
 template <typename T> struct Mma;
 template <> struct Mma<float> {
@@ -180,7 +168,7 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
   static_assert(KC % (2 * KV) == 0, "KC must hold whole k-blocks");
   static_assert(NT % NVEC == 0, "a thread keeps one channel offset across its vectors");
 
-  CT_DECL
+  PT_DECL
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* sA = smem;
   char* sB = smem + G::LDS_A;
@@ -545,32 +533,32 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
         }
       }
     };
-    CT_MARK(0)
+    PT_MARK(0)
     load_chunk(0);
     if (p.gn_acc1) build_gn_table();  // (behind the first chunk's loads: they are needed next anyway)
     load_gn(0);
-    CT_MARK(1)
-    CT_WAIT
-    CT_MARK(2)
+    PT_MARK(1)
+    PT_WAIT
+    PT_MARK(2)
 #pragma unroll
     for (int k = 0; k < NA; ++k) act(k);
-    CT_MARK(3)
+    PT_MARK(3)
     for (int c = 0; c < nch; ++c) {
       __syncthreads();  // previous chunk's fragment reads are done
       write_chunk(false);
       __syncthreads();
-      CT_MARK(4)
+      PT_MARK(4)
       if (c + 1 < nch) {
         load_chunk(c + 1);  // in flight during the first third of the MFMA loop below
         load_gn(c + 1);
-        CT_MARK(5)
+        PT_MARK(5)
         mma_chunk(std::true_type{}, std::false_type{});
       } else {
         if (c + 1 < ncht) load_chunk(c + 1);  // first skip chunk (raw: nothing to activate)
-        CT_MARK(5)
+        PT_MARK(5)
         mma_chunk(std::false_type{}, std::false_type{});
       }
-      CT_MARK(6)
+      PT_MARK(6)
     }
     if constexpr (SKIP_OK) {
       for (int c = nch; c < ncht; ++c) {  // fused 1x1 skip convolution: extra K through the centre tap
@@ -696,7 +684,7 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
       for (int q = 0; q < RV; ++q) rraw[it][q] = ld16(rr, vor[it], 16u * q);
     }
     __syncthreads();
-    CT_MARK(7)
+    PT_MARK(7)
     uint4 oraw[NROW][RV];
     if (lean) {
       const float osc = p.out_scale;
@@ -764,12 +752,12 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
         pack8<T>(v, oraw[it]);
       }
     }
-    CT_MARK(8)
+    PT_MARK(8)
 #pragma unroll
     for (int it = 0; it < NROW; ++it)
 #pragma unroll
       for (int q = 0; q < RV; ++q) buf_store16(ry, voy[it], 16u * q, oraw[it][q]);
-    CT_MARK(9)
+    PT_MARK(9)
   }
   if (p.stats) {  // block-reduce the per-thread partials: 256/NCG threads share a cout group
     __syncthreads();
@@ -794,8 +782,8 @@ __global__ __launch_bounds__(NT, OCC) void conv_mfma_kernel(ConvK p) {
       ds_stat_add(o + 1, (long long)llrint(q * DS_STAT_SQ_SCALE));
     }
   }
-  CT_MARK(10)
-  CT_FLUSH
+  PT_MARK(10)
+  PT_FLUSH
 }
 
 template <typename T, int TAPS, int TH, int TW, int BN, int WM, int WN, int KC, int EP = 1, int OCC = 2, int SP = 0, int NT = 256>

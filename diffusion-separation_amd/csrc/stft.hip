@@ -184,19 +184,10 @@ __global__ __launch_bounds__(256) void stft_pack_kernel(const float* __restrict_
 //     ONE frame for every channel, i.e. exactly the 16 bytes of two output pixels' channel vectors;
 //   * epilogue in the accumulator layout: |z|^e e^{j angle} * factor, (2x - 1), channel pack, frame padding — 16-byte stores
 //     that run 512 bytes contiguous along the frame axis.
-#ifdef ST_TIMING  // profiling build only: phase ticks of wave 0 of every block (tools/stft_timing.sh)
-__device__ unsigned long long g_st_dbg[16];
-#define ST_DECL unsigned long long st_prev = __builtin_readcyclecounter();
-#define ST_MARK(i) { const unsigned long long st_now = __builtin_readcyclecounter(); if (threadIdx.x == 0) atomicAdd(&g_st_dbg[i], st_now - st_prev); st_prev = st_now; }
-extern "C" int diffsep_st_debug_read(unsigned long long* out, int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_st_dbg), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_st_dbg), z, sizeof(z)); }
-  return 0;
-}
-#else
-#define ST_DECL
-#define ST_MARK(i)
+#ifdef ST_TIMING  // profiling build only (tools/phase_timing.py --kernel stft): phase ticks of wave 0 of every block; the
+#define PT_NAME st  // (diffsep_st_debug_read) forward kernel marks phases 0 .. 2, the inverse kernel 4 .. 7 of the same counter set
 #endif
+#include "phase_timing.h"
 constexpr int SF_PITCH = 272, SF_ROWS = 35, SF_CH = SF_ROWS * SF_PITCH, SF_NS = 32 * 128 + 382;
 // (waves per block: 8 — one 32-row DFT tile per wave — measured the same as 4, tools/istft_ab.sh: 32.7 vs 33.2 us: unlike the inverse
 // kernel's, this product phase is within 1.4x of its MFMA time and the staging / epilogue phases are short)
@@ -215,7 +206,7 @@ __global__ __launch_bounds__(SF_NT) void stft_fused_kernel(const float* __restri
   const int rh = blockIdx.x & 1, ft = (blockIdx.x >> 1) % ntile, b = (blockIdx.x >> 1) / ntile;
   const int f0 = ft * 32;
   const float pv = shift ? -1.f : 0.f;
-  ST_DECL
+  PT_DECL
   if (f0 >= F) {  // a tile of padding frames only (score_models.py:83-91): the pad value, no transform
     float o[8];
 #pragma unroll
@@ -263,7 +254,7 @@ __global__ __launch_bounds__(SF_NT) void stft_fused_kernel(const float* __restri
     }
   }
   __syncthreads();
-  ST_MARK(0)
+  PT_MARK(0)
   // ---- 32 frames x 32 RT DFT rows per wave (row tiles rt0 .. rt0 + RT - 1), NC channels
   constexpr int RT = SF_RT;
   f32x16 acc[RT][NC];
@@ -316,7 +307,7 @@ __global__ __launch_bounds__(SF_NT) void stft_fused_kernel(const float* __restri
         acc[t][c] = mfma_bf32(ah[t], bl[c], acc[t][c]);
       }
   }
-  ST_MARK(1)
+  PT_MARK(1)
   // ---- epilogue: lane (frame l32, half h) holds rows 8 q + 4 h + i of each row tile = bins 16 rt + 4 q + 2 h + {0, 1}, Re / Im.
   // The exponent case is decided ONCE (uniform): with the three cases inside the loops every one of the 48 compressions carried
   // an inlined powf and IEEE sqrt / divide sequences — 11k VALU instructions per lane, 60 of the first version's 72 us.  The
@@ -359,7 +350,8 @@ __global__ __launch_bounds__(SF_NT) void stft_fused_kernel(const float* __restri
   if (expo == 0.5f) epilogue(std::integral_constant<int, 0>{});
   else if (expo == 1.0f) epilogue(std::integral_constant<int, 1>{});
   else epilogue(std::integral_constant<int, 2>{});
-  ST_MARK(2)
+  PT_MARK(2)
+  PT_FLUSH
 }
 
 long ds_stft_workspace_bytes(int B, int S, long T, int n_fft, int hop) {
@@ -541,7 +533,7 @@ __global__ __launch_bounds__(SI_NT, NS == 1 ? 2 : 1) void istft_fused_kernel(con
   const int nsg = S / NS;
   const int seg = blockIdx.x % nseg, s0 = ((blockIdx.x / nseg) % nsg) * NS, b = blockIdx.x / (nseg * nsg);
   const int g0 = 29 * seg, fA = g0 - 1;  // frame r of the block = frame fA + r
-  ST_DECL
+  PT_DECL
   // ---- U: thread -> (frame r fastest: 32 x 16 B contiguous per bin, then the bin)
   {
     const float inv_fac = 1.0f / fabsf(factor);
@@ -606,7 +598,7 @@ __global__ __launch_bounds__(SI_NT, NS == 1 ? 2 : 1) void istft_fused_kernel(con
     }
   }
   __syncthreads();
-  ST_MARK(4)
+  PT_MARK(4)
   // ---- frames[r][n]: 32 frames x 32 SI_CT taps per wave (column tiles SI_CT wave .. + SI_CT - 1)
   constexpr int CT = SI_CT;
   f32x16 acc[NS][CT];
@@ -655,7 +647,7 @@ __global__ __launch_bounds__(SI_NT, NS == 1 ? 2 : 1) void istft_fused_kernel(con
         acc[ns][c] = mfma_bf32(ah[ns], bl_[c], acc[ns][c]);
       }
   }
-  ST_MARK(5)
+  PT_MARK(5)
   // ---- overlap-add: lane (tap n = 32 (4 wave + c) + l32, half h) holds frames r = 8 q + 4 h + i.  Sample p of the segment
   // receives frame r's tap n = p + 383 - 128 r: consecutive frames' taps are 128 apart, i.e. ONE contribution per wave — every wave
   // writes its own copy of the segment with plain stores (no atomics: float atomics would make the sum's order, and with it the
@@ -682,7 +674,7 @@ __global__ __launch_bounds__(SI_NT, NS == 1 ? 2 : 1) void istft_fused_kernel(con
     }
   }
   __syncthreads();
-  ST_MARK(6)
+  PT_MARK(6)
   // ---- out[b, s, t] = ola / sum_f w^2[t + 255 - 128 f]   (torch.istft, center = True; zeros beyond 128 (F - 1): adjust_length)
   for (int i = tid; i < SI_SEG; i += SI_NT) {
     const long t = 128L * g0 + i;
@@ -712,7 +704,8 @@ __global__ __launch_bounds__(SI_NT, NS == 1 ? 2 : 1) void istft_fused_kernel(con
       for (int ns = 0; ns < NS; ++ns) out[((long)b * S + s0 + ns) * Tlen + t] = 0.f;
     }
   }
-  ST_MARK(7)
+  PT_MARK(7)
+  PT_FLUSH
 }
 
 long ds_istft_workspace_bytes(int B, int S, long T, int n_fft, int hop) {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Static instruction mix per basic block of one kernel in a hipcc --save-temps .s file.
+"""Static instruction mix per basic block of one kernel in a --save-temps .s file (csrc/Makefile's compile line).
 usage: isa_blocks.py file.s kernel_symbol_substring"""
 import re, sys
 from collections import Counter

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Count, per kernel of a `hipcc -S --cuda-device-only` file, the sites where a scalar VALU instruction writes a VGPR
+"""Count, per kernel of a device assembly file (csrc/Makefile's compile line with `-S --cuda-device-only`), the sites where a scalar VALU instruction writes a VGPR
 that the very next instruction reads as half of a packed-FP32 operand (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32,
 optionally only with op_sel).  This is the shape of the GroupNorm-statistics code that returned a wrong sum lane
 under co-resident kernels (profiles/experiments/README.md, "Streams"); after the fix the conv kernels have none

@@ -9,8 +9,10 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=${1:-gpurun_out/pmc_traffic}
 DT=${2:-f16}
 mkdir -p $OUT
+# each pass under its own time limit (two fit the 900 s tools/collect_evidence.sh gives this script); a pass that fails, faults
+# or runs out of time ends the script with its status: the next pass is not started on the same card after it
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c -d /tmp/pmc_traffic/$c -o pmc --output-format csv -- python bench.py --full --dtype $DT --steps 1 --warmup 0 -N 4 --in-flight 1 --no-cpu-baseline --no-roofline --no-graph --no-extra-modes > $OUT/$c.log 2>&1
+  timeout -k 10 420 rocprofv3 --kernel-trace --pmc $c -d /tmp/pmc_traffic/$c -o pmc --output-format csv -- python bench.py --full --dtype $DT --steps 1 --warmup 0 -N 4 --in-flight 1 --no-cpu-baseline --no-roofline --no-graph --no-extra-modes > $OUT/$c.log 2>&1 || { rc=$?; echo "pmc_traffic: the $c pass exited $rc, nothing further started (see $OUT/$c.log)" >&2; exit $rc; }
 done
 OUT=$OUT DT=$DT python - <<'PY'
 import csv, glob, json, os, re

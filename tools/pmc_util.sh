@@ -11,8 +11,10 @@ P1="SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTI
 P2="SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_INSTS_MFMA"
 CMD="python bench.py --full --dtype $DT --in-flight 1 --steps 1 --warmup 0 -N 4 --no-cpu-baseline --no-roofline --no-graph --no-extra-modes"
 rm -rf /tmp/pmc_r03
-rocprofv3 --kernel-trace --pmc $P1 -d /tmp/pmc_r03/p1 -o pmc --output-format csv -- $CMD > $OUT/run1.log 2>&1
-rocprofv3 --kernel-trace --pmc $P2 -d /tmp/pmc_r03/p2 -o pmc --output-format csv -- $CMD > $OUT/run2.log 2>&1
+# each pass under its own time limit (two fit the 900 s tools/collect_evidence.sh gives this script); a pass that fails, faults
+# or runs out of time ends the script with its status: the second pass is not started on the same card after it
+timeout -k 10 420 rocprofv3 --kernel-trace --pmc $P1 -d /tmp/pmc_r03/p1 -o pmc --output-format csv -- $CMD > $OUT/run1.log 2>&1 || { rc=$?; echo "pmc_util: pass 1 exited $rc, pass 2 not started (see $OUT/run1.log)" >&2; exit $rc; }
+timeout -k 10 420 rocprofv3 --kernel-trace --pmc $P2 -d /tmp/pmc_r03/p2 -o pmc --output-format csv -- $CMD > $OUT/run2.log 2>&1 || { rc=$?; echo "pmc_util: pass 2 exited $rc (see $OUT/run2.log)" >&2; exit $rc; }
 DT=$DT python - "$OUT" "$CMD" <<'PY'
 import csv, glob, json, os, re, sys
 out, cmd = sys.argv[1], sys.argv[2]
