@@ -500,6 +500,10 @@ int ds_launch_ode_commit_each(double* y, const double* ynew, float* k0, const fl
 int ds_launch_linear(const float* x, const float* W, const float* bias, float* y, int B, int K, int O, int silu_in,
                      hipStream_t st);
 // wide outputs, weights transposed [K][O] (ds_launch_dense_transpose builds that layout block by block)
+// K <= DS_LINEAR_T_MAX_K: the generic kernel stages act(x) of 16 batch entries in 16 * K * 4 bytes of dynamic LDS, and 64 KiB
+// (hipDeviceProp_t::sharedMemPerBlock) is what a launch may ask for without raising hipFuncAttributeMaxDynamicSharedMemorySize,
+// which this launcher does not do.  The engine's K is 4 nf <= 512.
+#define DS_LINEAR_T_MAX_K 1024
 int ds_launch_linear_t(const float* x, const float* Wt, const float* bias, float* y, int B, int K, int O, int silu_in,
                        hipStream_t st);
 int ds_launch_dense_transpose(const float* src, float* dst, int O, int K, int ldo, int off, hipStream_t st);

@@ -591,6 +591,7 @@ __global__ __launch_bounds__(256) void convert_kernel(const SRC* __restrict__ s,
     Elt<DST>::st(d + i, Elt<SRC>::ld(s + i));
 }
 int ds_launch_convert(const void* src, void* dst, long n, int sd, int dd, hipStream_t st) {
+  DS_CHECK((sd == DS_F32 || sd == DS_BF16) && (dd == DS_F32 || dd == DS_BF16), "convert: dtype must be float32 (0) or the 16-bit storage format (1)");
   if (n <= 0) return 0;
   long nb = (n + 255) / 256;
   if (nb > 8192) nb = 8192;
@@ -740,7 +741,7 @@ __global__ __launch_bounds__(256) void linear_t16_kernel(const float* __restrict
 }
 int ds_launch_linear_t(const float* x, const float* Wt, const float* bias, float* y, int B, int K, int O, int silu_in,
                        hipStream_t st) {
-  DS_CHECK(K % 4 == 0 && K <= 2048, "linear_t: K must be a multiple of 4 (at most 2048)");
+  DS_CHECK(K >= 4 && K % 4 == 0 && K <= DS_LINEAR_T_MAX_K, "linear_t: K must be a multiple of 4 (at most 1024)");
   if (K == 256 || K == 512 || K == 64 || K == 128) {
     const dim3 grid(cdiv(O, 16), cdiv(B, 16));
     const size_t lds = (size_t)(16 * K + 16 * 16 * 16) * 4;

@@ -18,6 +18,33 @@ extern "C" int32_t diffsep_time_embedding(const float* t, const float* fourier_w
   return ds_launch_linear(t1, w2, b2, temb, B, 4 * nf, 4 * nf, 1, st);
 }
 
+// The wide Dense_0 projection of net_forward in isolation: y [B][sum O_i] = act(x) W^T + bias for n_blocks nn.Linear weight
+// blocks [O_i][K] stored one after the other in w (block i at row sum_{j<i} O_j), through the two launchers the engine uses —
+// ds_launch_dense_transpose per block into the transposed concatenation [K][sum O_i] (arch.hip builds d_dense_w the same way),
+// then ds_launch_linear_t.  out_ch_host [n_blocks] (host); bias [sum O_i] or null; workspace >= K * sum O_i floats.
+extern "C" int32_t diffsep_dense_projection(const float* x, const float* w, const float* bias, const int32_t* out_ch_host,
+                                            int32_t n_blocks, float* y, int32_t B, int32_t K, int32_t silu_in, void* workspace,
+                                            int64_t workspace_bytes, void* stream) {
+  DS_CHECK(x && w && out_ch_host && y && workspace, "dense_projection: null pointer");
+  DS_CHECK(B >= 1 && n_blocks >= 1, "dense_projection: bad B / n_blocks");
+  DS_CHECK(K >= 4 && K % 4 == 0 && K <= DS_LINEAR_T_MAX_K, "dense_projection: K must be a multiple of 4 (at most 1024)");  // (before any launch)
+  long total = 0;
+  for (int i = 0; i < n_blocks; ++i) {
+    DS_CHECK(out_ch_host[i] >= 1, "dense_projection: empty weight block");
+    total += out_ch_host[i];
+  }
+  DS_CHECK(total * K < (1L << 31), "dense_projection: weights too large for the transpose's 32-bit index");
+  DS_CHECK(workspace_bytes >= total * K * 4, "dense_projection: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  float* wt = (float*)workspace;
+  int off = 0;
+  for (int i = 0; i < n_blocks; ++i) {
+    if (ds_launch_dense_transpose(w + (long)off * K, wt, out_ch_host[i], K, (int)total, off, st)) return 1;
+    off += out_ch_host[i];
+  }
+  return ds_launch_linear_t(x, wt, bias, y, B, K, (int)total, silu_in, st);
+}
+
 extern "C" int32_t diffsep_upfirdn2d(const void* x, void* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ldx,
                                      int32_t ldy, int32_t up, int32_t dtype, void* stream) {
   DS_CHECK(x && y, "upfirdn2d: null pointer");
@@ -505,7 +532,7 @@ extern "C" int32_t diffsep_gram(const float* ref, const float* est, double* out,
   return ds_launch_gram(ref, est, out, B, S, T, (hipStream_t)stream);
 }
 extern "C" int32_t diffsep_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream) {
-  DS_CHECK(out, "randn: null pointer");
+  DS_CHECK(out || n <= 0, "randn: null pointer");  // (an empty tensor has no address: n = 0 draws nothing and launches nothing)
   return ds_launch_randn(out, n, seed, stream_id, (hipStream_t)stream);
 }
 extern "C" int32_t diffsep_randn_batch(float* out, int32_t B, int32_t S, int64_t T, const uint64_t* seeds,

@@ -508,6 +508,35 @@ def time_embedding(t, fourier_w, w1, b1, w2, b2):
     return out
 
 
+def dense_projection(x, weights, biases=None, silu_in=True):
+    """y [B, sum O_i] = act(x) W_i^T + b_i for nn.Linear weights [O_i, K] side by side (the engine's Dense_0 projection of the
+    time embedding: diffsep_dense_projection); x [B, K] float32, biases: one [O_i] per block, or None for no bias at all."""
+    B, K = x.shape
+    outs = [int(w.shape[0]) for w in weights]
+    assert all(w.shape == (o, K) for w, o in zip(weights, outs)) and (biases is None or [int(b.shape[0]) for b in biases] == outs)
+    total = sum(outs)
+    w = torch.cat([wi.contiguous().float() for wi in weights], 0)
+    b = torch.cat([bi.contiguous().float() for bi in biases]) if biases is not None else None
+    y = torch.empty((B, total), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(1, K * total), dtype=torch.float32, device=x.device)
+    oc, ocp = host_array(outs, np.int32, len(outs), "out_ch")
+    call(lib(), "diffsep_dense_projection", _ptr(x.contiguous()), _ptr(w), _ptr(b), ocp, len(outs), _ptr(y), B, K,
+         int(bool(silu_in)), _ptr(ws), ws.numel() * 4, _stream_ptr())
+    return y
+
+
+def convert(src, dst_dtype, kind="bf16"):
+    """diffsep_convert of the library build `kind` ("bf16" | "f16": what dtype code 1 stores): a flat float32 or 16-bit tensor
+    to float32 or that build's 16-bit type, round to nearest even."""
+    half = torch.bfloat16 if kind == "bf16" else torch.float16
+    if src.dtype not in (torch.float32, half) or dst_dtype not in (torch.float32, half):
+        raise TypeError(f"float32 or {half} expected in the {kind} build")
+    src = src.contiguous()
+    dst = torch.empty(src.shape, dtype=dst_dtype, device=src.device)
+    call(lib(kind), "diffsep_convert", _ptr(src), _ptr(dst), src.numel(), _dt_of(src.dtype), _dt_of(dst_dtype), _stream_ptr())
+    return dst
+
+
 def randn(n, seed, stream_id, device="cuda"):
     out = torch.empty(n, dtype=torch.float32, device=device)
     call(lib(), "diffsep_randn", _ptr(out), n, seed, stream_id, _stream_ptr())

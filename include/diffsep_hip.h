@@ -376,6 +376,15 @@ int32_t diffsep_time_embedding(const float* t, const float* fourier_w, const flo
                                const float* b2, float* temb, int32_t B, int32_t nf, void* workspace,
                                int64_t workspace_bytes, void* stream);
 
+/* The wide Dense_0 projection of the backbone in isolation: y[B][sum O_i] = act(x) W^T + bias, act = SiLU when silu_in != 0,
+ * for n_blocks nn.Linear weight blocks [O_i][K] stored one after the other in w (every ResnetBlockBigGANpp's Dense_0 at once,
+ * layerspp.py:311-312), through the launchers the engine uses: each block is transposed into the concatenation [K][sum O_i] in
+ * the workspace, then one product runs over all of them.  x [B][K], w [sum O_i][K], bias [sum O_i] or NULL, y: float32 device
+ * pointers; out_ch_host [n_blocks]: host array of the O_i; K a multiple of 4, at most 1024; workspace >= K * sum O_i floats. */
+int32_t diffsep_dense_projection(const float* x, const float* w, const float* bias, const int32_t* out_ch_host,
+                                 int32_t n_blocks, float* y, int32_t B, int32_t K, int32_t silu_in, void* workspace,
+                                 int64_t workspace_bytes, void* stream);
+
 /* upfirdn2d with the [1,3,3,1] FIR, factor 2: upsample_2d / downsample_2d
  * (models/ncsnpp_utils/up_or_down_sampling.py:206-273; native op op/upfirdn2d.cpp:12-23,
  * op/upfirdn2d_kernel.cu:107-207).  up!=0: [B,H,W,C] -> [B,2H,2W,C]; else -> [B,H/2,W/2,C]. */
@@ -798,7 +807,8 @@ int32_t diffsep_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, 
 int32_t diffsep_randn_batch(float* out, int32_t B, int32_t S, int64_t T, const uint64_t* seeds, const int32_t* lengths,
                             uint64_t stream_id, void* stream);
 
-/* float32 <-> engine dtype conversion helper for the tests (n elements). */
+/* float32 <-> engine dtype conversion helper for the tests (n elements); dtype codes DIFFSEP_F32 and DIFFSEP_BF16 (the 16-bit
+ * storage format of the build) only, any other is an error. */
 int32_t diffsep_convert(const void* src, void* dst, int64_t n, int32_t src_dtype, int32_t dst_dtype, void* stream);
 
 #ifdef __cplusplus
