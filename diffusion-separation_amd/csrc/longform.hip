@@ -19,6 +19,7 @@
 
 #include "../../include/diffsep_hip.h"
 #include "common.h"
+#include "perm_search.h"    // the permutation rule (lexicographic candidates, strict >), shared with ensemble.hip
 #include "reduce_device.h"  // the fixed-order fp64 block totals of the cross-Gram partials
 
 namespace {
@@ -60,14 +61,6 @@ __host__ __device__ inline void lf_locate(const LfPlan& p, long t, int* k, long*
   const long off = t - q * p.hop;
   if (q >= 1 && off < p.Tv) { *k = (int)q - 1; *j = off; *n = p.Tv; return; }
   *k = (int)q;
-}
-
-__device__ inline int lf_perm_entry(int S, int p, int i) {  // entry i of the p-th permutation of 0 .. S - 1, lexicographic
-  if (S == 3) {
-    const int tab[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
-    return tab[p][i];
-  }
-  return S == 2 && p == 1 ? 1 - i : i;
 }
 
 // part[pair][blk][S][S]: block blk of pair sums its contiguous share of the overlap, thread t the samples t, t + 256, ... of it,
@@ -117,18 +110,10 @@ __global__ __launch_bounds__(256) void lf_perm_kernel(const double* __restrict__
   if (threadIdx.x != 0) return;
   int g[kLfMaxS];
   for (int i = 0; i < S; ++i) { g[i] = i; perm_out[i] = i; }
-  const int nperm = S == 3 ? 6 : S;
   for (int k = 0; k + 1 < K; ++k) {
-    const double* c = cmat + (long)k * SS;
-    int best = 0;
-    double bestv = 0.0;
-    for (int q = 0; q < nperm; ++q) {
-      double v = 0.0;
-      for (int i = 0; i < S; ++i) v += c[i * S + lf_perm_entry(S, q, i)];
-      if (q == 0 || v > bestv) { best = q; bestv = v; }
-    }
+    const int best = ds_best_perm(cmat + (long)k * SS, S);
     int gn[kLfMaxS];
-    for (int i = 0; i < S; ++i) gn[i] = lf_perm_entry(S, best, g[i]);
+    for (int i = 0; i < S; ++i) gn[i] = ds_perm_entry(S, best, g[i]);
     for (int i = 0; i < S; ++i) { g[i] = gn[i]; perm_out[(long)(k + 1) * S + i] = gn[i]; }
   }
 }

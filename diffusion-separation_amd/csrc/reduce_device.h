@@ -4,7 +4,7 @@
 //   2. the NW wave totals through LDS, folded first to last: ((w0 + w1) + w2) + ... + w[NW-1], no leading zero.
 // No floating-point atomics, nothing that depends on the grid, the stream or the batch.  tests/reduce_ref.py restates the order
 // in NumPy and tests/test_reduce_order_gpu.py holds two entry points to it bit for bit.  Free functions only, all __device__
-// inline in an anonymous namespace.  Included by stoi.hip, composite.hip, sde.hip, ode.hip, score_loss.hip and longform.hip;
+// inline in an anonymous namespace.  Included by stoi.hip, composite.hip, sde.hip, ode.hip, score_loss.hip, longform.hip and ensemble.hip;
 // the block has NW * 64 threads and every thread of it makes the call.
 #pragma once
 

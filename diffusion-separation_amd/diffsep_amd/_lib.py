@@ -222,6 +222,8 @@ _SIGS = {
     "diffsep_longform_locate": (_I, [_L, _L, _L, _L, C.POINTER(_I), C.POINTER(_L), C.POINTER(_L)]),
     "diffsep_longform_workspace_bytes": (_L, [_I, _I]),
     "diffsep_longform_stitch": (_I, [_P, _I, _I, _L, _L, _L, _P, _P, _P, _P, _L, _P]),
+    "diffsep_ensemble_workspace_bytes": (_L, [_I, _I, _I]),
+    "diffsep_ensemble": (_I, [_P, _P, _P, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "diffsep_randn": (_I, [_P, _L, _U64, _U64, _P]),
     "diffsep_randn_batch": (_I, [_P, _I, _I, _L, _P, _P, _U64, _P]),
     "diffsep_convert": (_I, [_P, _P, _L, _I, _I, _P]),

@@ -56,6 +56,17 @@ Gram sums the tap adds up on the device ((N + 1) 3 S^2 doubles per utterance cro
 pass of every step).  Warm-up calls trace nothing.  Neither runs with
 --sampler ode (no fixed steps) or `__no_proc__` (no sampler).
 
+--draws K [--draws-out {mean,medoid,all}] (off by default; without it records and summaries are what they were): every
+utterance is separated K times in ONE engine call (it takes K rows of a --batch, which is filled with whole utterances; draw k
+under the seed inflight.draw_seeds(utterance seed, K)[k], draw 0 being the run without the flag), the draws are aligned to one
+source order and reduced on the device (DiffSepModel.separate_draws, ops.ensemble), and the record's
+existing fields are those of the chosen estimate: the mean of the draws (default, and with `all`) or the draw nearest to it.
+Added per record: `si_sdr_draws` [K][S], `si_sdr_mean` [S] and `si_sdr_medoid` [S] — each under its own best permutation against
+the target, all from one diffsep_gram call — `draws_medoid` and `draws_dist` [K]; the summary gets their means (not of the
+index), `draws` and `draws_out`.  `runtime` covers all K draws; `utt_per_s_rank0` counts utterances, i.e. files, not draws.
+This is the instrument for the question nobody has measured here: what the mean of K draws buys over one draw.  Not with
+--sampler ode, `__no_proc__`, --fig or --trajectory.
+
 --streams K such calls are in flight on K engines / K HIP streams.  What that takes (hardware queues, engines before
 streams, workspace reserve, per-utterance seeds and normalisation, pinned uploads, the launch / collect ring, the overflow
 re-run) is inflight.py's, shared with separate.py.  Here: main() sets the run up, a SplitRun holds one split's state and
@@ -238,6 +249,13 @@ def build_parser():
     ap.add_argument("--trajectory", action="store_true",
                     help="record si_sdr_steps: the SI-SDR of every source after each reverse step's corrector, and last of the "
                          "result, under the record's final permutation (Gram sums added up on the device inside the sampler)")
+    ap.add_argument("--draws", type=int, default=None, metavar="K",
+                    help="K posterior draws per utterance in one engine call (an utterance takes K rows of a --batch), aligned "
+                         "and reduced on the device; the record's metrics are those of the estimate --draws-out names, and "
+                         "si_sdr_draws / si_sdr_mean / si_sdr_medoid / draws_medoid / draws_dist are added (default: off)")
+    ap.add_argument("--draws-out", default=None, choices=["mean", "medoid", "all"],
+                    help="with --draws: the estimate that is scored and saved: the mean of the draws (default; also with `all`) or "
+                         "the draw nearest to the mean")
     ap.add_argument("--streams", type=int, default=4,
                     help="engine calls (batches) in flight per GPU: K engines on K HIP streams; the records do not "
                          "depend on K.  'runtime' of an utterance is its batch's latency / batch size.")
@@ -264,6 +282,19 @@ def main(argv=None):
             raise SystemExit(f"{flag}: the ODE sampler has no fixed reverse steps to look at (--sampler pc)")
         if on and no_proc:
             raise SystemExit(f"{flag}: __no_proc__ scores the mixture itself, there is no sampler to look into")
+    if args.draws is None and args.draws_out is not None:
+        raise SystemExit("--draws-out goes with --draws")
+    if args.draws is not None:
+        for flag, on in (("--sampler ode", args.sampler == "ode"), ("__no_proc__", no_proc), ("--fig", args.fig),
+                         ("--trajectory", args.trajectory)):
+            if on:
+                raise SystemExit(f"--draws with {flag} is not supported: the draws are whole runs of the predictor-corrector sampler")
+        if not 1 <= args.draws <= 32:
+            raise SystemExit(f"--draws {args.draws}: 1 to 32 draws")
+        if args.draws > max(1, args.batch):
+            raise SystemExit(f"--draws {args.draws} does not fit --batch {args.batch}: an utterance takes one row of an engine "
+                             "call per draw")
+        args.draws_out = args.draws_out or "mean"
     if args.fig:
         figures.require_matplotlib("--fig")
     if args.streams > 1:
@@ -354,7 +385,8 @@ def main(argv=None):
 # One engine call in flight: what collect needs (utterance indices, their lengths in samples, ..., t0 = host time at which the
 # sampler was enqueued, None when nothing was separated) and every tensor the asynchronous sampler reads (they stay referenced
 # until the worker's stream has drained).
-_Batch = namedtuple("_Batch", "group lens mix mix_n tgt_n est nfe t0 sampler sloss", defaults=(None,))
+# draws (--draws): (ops.EnsembleResult, aligned draws [B,K,S,T]) of the call.
+_Batch = namedtuple("_Batch", "group lens mix mix_n tgt_n est nfe t0 sampler sloss draws", defaults=(None, None))
 
 
 @dataclass
@@ -392,7 +424,8 @@ class SplitRun:
             self.width_of, self.bucket = eng0.padded_frames, eng0.bucket_length
         # the reference's contiguous ranges (evaluate_mp.py:495-503), or sorted by length and dealt round-robin
         self.mine = rank_indices(self.n, self.world, self.rank, self.lengths, a.balance)
-        self.batches = plan_batches(self.mine, self.lengths, self.width_of, max(1, a.batch))
+        self.draws = getattr(a, "draws", None) or 0  # --draws K: an utterance takes K rows of an engine call
+        self.batches = inflight.plan_draw_batches(self.mine, self.lengths, self.width_of, max(1, a.batch), max(1, self.draws))
         self.seeds = inflight.utterance_seeds(self.n, a.seed)
         # --fig: the unique steps of the figure's panels (what the tap is asked for) and each panel's place among them
         self.fig_steps, self.fig_panels = figures.snapshot_request(self.sampler_kw["N"]) if a.fig else (None, None)
@@ -463,6 +496,12 @@ class SplitRun:
             est = mix_n.expand(-1, tgt_n.shape[1], -1).contiguous()  # x_result = broadcast_to(mix, target.shape)
             return _Batch(group, lens, mix, mix_n, tgt_n, est, 0, None, None)
         sloss = self.score_loss(self.models[w], group, lens, mix_n, tgt_n) if self.args.score_loss > 0 else None
+        if self.draws:
+            if len(self.streams) == 1:
+                torch.cuda.synchronize()
+            t0 = time.perf_counter()  # (the runtime covers all K draws and their reduction)
+            _, est, nfe, extra = self.draw(self.models[w], group, lens, mix)
+            return _Batch(group, lens, mix, mix_n, tgt_n, est, nfe, t0, None, sloss, extra)
         sampler = self.sampler_for(self.models[w], group, lens, mix_n, tgt_n, trace=j is not None)
         if len(self.streams) == 1:
             torch.cuda.synchronize()
@@ -470,9 +509,41 @@ class SplitRun:
         est, nfe, *_ = sampler()  # enqueues the whole sampler on the worker's stream
         return _Batch(group, lens, mix, mix_n, tgt_n, est, nfe, t0, sampler, sloss)
 
+    def draw(self, model, group, lens, mix):
+        """--draws: K draws of every utterance of the batch in ONE engine call, aligned and reduced on the current stream
+        (DiffSepModel.separate_draws on the raw mixture: it normalises per utterance as stage() does, and the identity in place
+        of the rescaling keeps the draws in the normalised domain the metrics are taken in)
+        -> (mean of the draws, the estimate --draws-out names [B,S,T], nfe, (ops.EnsembleResult, aligned draws [B,K,S,T])).
+        The mean comes first because it is what the overflow net looks at: a non-finite sample of any draw is a non-finite
+        sample of their mean."""
+        a = self.args
+        mean, res, aligned = model.separate_draws(mix, self.draws, lengths=lens, seeds=[self.seeds[i] for i in group], out="all",
+                                                  rescale=lambda mix_f, rows: rows, check_finite=False, **self.sampler_kw,
+                                                  denoise=a.denoise, intermediate=False, schedule=a.schedule)
+        return mean, (res.pick if a.draws_out == "medoid" else mean), model.draws_info["nfe"], (res, aligned)
+
+    def draw_fields(self, b, extra, stream):
+        """per utterance of batch b the record fields of --draws: SI-SDR of every aligned draw, of the mean and of the medoid,
+        each under its own best permutation against the target (ONE diffsep_gram call over all of them), the medoid's index
+        and every draw's squared distance to the mean"""
+        res, aligned = extra
+        B, K = aligned.shape[:2]
+        with torch.cuda.stream(stream):
+            cand = torch.cat([aligned.reshape(B * K, *aligned.shape[2:]), res.mean, res.pick])
+            refs = torch.cat([b.tgt_n.repeat_interleave(K, dim=0), b.tgt_n, b.tgt_n])
+            sdr = metrics.si_bss_eval_sources(refs, cand)[0]
+            dist, medoid = metrics.gram_to_host(res.dist), metrics.gram_to_host(res.medoid)
+        k_src = sdr.shape[1] if self.n_src is None else self.n_src
+        row = lambda r: [float(v) for v in sdr[r, :k_src]]
+        return [{"si_sdr_draws": [row(u * K + k) for k in range(K)], "si_sdr_mean": row(B * K + u),
+                 "si_sdr_medoid": row(B * K + B + u), "draws_medoid": int(medoid[u]), "draws_dist": [float(v) for v in dist[u]]}
+                for u in range(B)]
+
     def reissue(self, fb, b):
         """the same request on the fallback model: the same trace arguments, and the repeat's trace replaces the first"""
         self.fallbacks.append(list(b.group))
+        if self.draws:
+            return self.draw(fb, b.group, b.lens, b.mix)
         traced = getattr(b.sampler, "trace", None) is not None
         sampler = self.sampler_for(fb, b.group, b.lens, b.mix_n, b.tgt_n, trace=traced)
         out = sampler()
@@ -485,7 +556,11 @@ class SplitRun:
     def collect(self, w, b):
         """batch b, whose sampler has drained from worker w's stream, into records (+ STOI jobs, saved samples)"""
         a, stream, (group, lens, tgt_n, est, nfe) = self.args, self.streams[w], (b.group, b.lens, b.tgt_n, b.est, b.nfe)
-        if not self.no_proc:
+        extra = b.draws
+        if self.draws:
+            _, est, nfe, extra = inflight.finite_or_rerun(self.models[w], stream, (extra[0].mean, est, nfe, extra),
+                                                          lambda fb: self.reissue(fb, b), what=f"utterances {group[:3]}...")
+        elif not self.no_proc:
             est, nfe, *_ = inflight.finite_or_rerun(self.models[w], stream, (est, nfe), lambda fb: self.reissue(fb, b),
                                                     what=f"utterances {group[:3]}...")
         runtime = 0.0 if b.t0 is None else (time.perf_counter() - b.t0) / len(group)
@@ -503,6 +578,7 @@ class SplitRun:
                 G = metrics.gram_to_host(trace.gram)
             perms = [m["perm"] for m in mets]
             steps_sdr = [metrics.si_bss_from_gram(G[i], perm=perms)[0] for i in range(G.shape[0])]
+        dfields = self.draw_fields(b, extra, stream) if self.draws else None
         need_host = needs_host_waveforms(a, group)
         stoi_dev = None
         if not a.no_stoi and a.stoi_on == "device":  # every source against its permuted estimate, whole batch at once
@@ -527,6 +603,8 @@ class SplitRun:
                 rec["ode_status"] = int(ode[k]["status"])
             if sloss is not None:
                 rec["score_loss"] = float(sloss[k])
+            if dfields is not None:
+                rec.update(dfields[k])
             self.records.append(rec)
             perm = mets[k]["perm"]
             k_src = len(perm) if self.n_src is None else self.n_src
@@ -560,7 +638,7 @@ class SplitRun:
         flat = sorted([r for part in allrec for r in part], key=lambda r: r["batch_idx"])
         with open(self.output_dir / f"{self.split}.json", "w") as f:
             json.dump(flat, f, indent=2)
-        summary = datasets.summarize([{k: v for k, v in r.items() if k not in ("batch_idx", "perm", "ode_status", "si_sdr_steps")}
+        summary = datasets.summarize([{k: v for k, v in r.items() if k not in ("batch_idx", "perm", "ode_status", "si_sdr_steps", "draws_medoid")}
                                       for r in flat])
         if a.trajectory and flat:  # per reverse step (and last the result): the mean over the utterances, per source
             import numpy as np
@@ -570,6 +648,7 @@ class SplitRun:
                         "streams": len(self.streams), "batch": a.batch, "engine_calls_rank0": len(self.batches),
                         "dtype": model.dtype if model is not None else None,
                         "sampler": None if model is None else a.sampler,
+                        **({"draws": self.draws, "draws_out": a.draws_out} if self.draws else {}),
                         "utt_per_s_rank0": len(self.mine) / max(wall, 1e-9), "split_fallback_batches_rank0": len(self.fallbacks),
                         # PESQ is ITU-T P.862 reference C code behind the third-party `pesq` package: not restated here
                         # (DESIGN.md section 7); STOI / ESTOI is diffsep_amd.metrics.stoi (published algorithm, restated)
@@ -589,7 +668,7 @@ def _stoi_rows(tgt_rows, est_rows, fs, extended):
 def run_split(run):
     if run.rank == 0:
         print(f"Processing {run.split}: {run.n} samples")
-    inflight.reserve_largest(run.models, run.batches, run.lengths)
+    inflight.reserve_largest(run.models, run.batches, run.lengths, rows_per_item=max(1, run.draws))
     # warm every worker up on the first batch's shape (workspace plan, graph capture) outside the timed region
     if run.batches and not run.no_proc:
         for w, stream in enumerate(run.streams):

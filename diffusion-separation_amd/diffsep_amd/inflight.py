@@ -64,6 +64,22 @@ def window_seeds(seed, K):
     return [(int(seed) + WINDOW_SEED_STRIDE * k) % (1 << 64) for k in range(K)]
 
 
+def draw_seeds(seed, K):
+    """Device RNG seeds of the K posterior draws of one file (DiffSepModel.separate_draws, separate / evaluate --draws): draw 0
+    has the file's seed — it is the file's ordinary output — and draw k (seed + WINDOW_SEED_STRIDE k) mod 2^64: the stride the
+    fused sampler itself applies to row k of a batch under one seed, so the draws are the rows of
+    get_pc_sampler(..., seed=seed, lengths=[n] * K) on the mixture repeated K times."""
+    return window_seeds(seed, int(K))
+
+
+def plan_draw_batches(indices, lengths, width_of, batch, K):
+    """plan_batches for files that each take K rows of an engine call: batches are filled with whole files, batch // K of
+    them.  K must fit the batch (the CLIs refuse it by name before they get here)."""
+    if K > batch:
+        raise ValueError(f"--draws {K} does not fit --batch {batch}")
+    return plan_batches(indices, lengths, width_of, batch // K)
+
+
 def plan_windows(lengths, window, overlap, plan):
     """The windows of all files in file-major order: -> (items, item_lengths, starts), items[n] = (file index, window
     index), item_lengths[n] = its samples (min(file length, window)), starts[i] = plan(lengths[i], window, overlap), the
@@ -95,13 +111,13 @@ def setup_workers(model, K, own_stream=True):
     return models, [torch.cuda.Stream() for _ in range(K)]
 
 
-def reserve_largest(models, batches, lengths):
+def reserve_largest(models, batches, lengths, rows_per_item=1):
     """Workspace of every engine for the largest planned call, now: growing it later synchronises the whole device,
-    i.e. stalls every stream."""
+    i.e. stalls every stream.  rows_per_item: rows of an engine call that an item of a batch takes (--draws K: K)."""
     if not batches or not models:
         return
     eng = models[0].score_model.engine()
-    bmax = max(len(g) for g in batches)
+    bmax = max(len(g) for g in batches) * rows_per_item
     tmax = eng.bucket_length(eng.padded_frames(max(lengths[i] for g in batches for i in g)))
     for m in models:
         for e in (m.score_model.engine(), m.tail_engine()):

@@ -595,6 +595,61 @@ def longform_stitch(win, T, Tv, want_gram=False, out=None):
     return (out, perm, gram_) if want_gram else (out, perm)
 
 
+class EnsembleResult:
+    """what ops.ensemble leaves on the device: mean [B,S,T] float32, std / pick [B,S,T] float32 or None, perm [B,K,S] int32
+    (aligned source i of draw k is its row perm[b,k,i]), dist [B,K] float64, medoid [B] int32, gram [B,K,S,S] float64 or None"""
+    __slots__ = ("mean", "std", "pick", "perm", "dist", "medoid", "gram")
+
+    def __init__(self, mean, std, pick, perm, dist, medoid, gram):
+        self.mean, self.std, self.pick, self.perm, self.dist, self.medoid, self.gram = mean, std, pick, perm, dist, medoid, gram
+
+    def aligned(self, draws):
+        """draws [B,K,S,T] with every draw's sources in the common order (a gather by perm)"""
+        return torch.gather(draws, 2, self.perm.long()[..., None].expand_as(draws))
+
+
+def ensemble_workspace_bytes(B, K, S):
+    """bytes of workspace diffsep_ensemble needs (host arithmetic; raises for a shape it refuses)"""
+    return _workspace_bytes(lib().diffsep_ensemble_workspace_bytes, B, K, S)
+
+
+def ensemble(draws, lengths=None, anchor=None, want_std=False, want_pick=False, want_gram=False, out=None):
+    """diffsep_ensemble: draws [B,K,S,T] float32 device tensor, K posterior draws of each of B zero-padded utterances of
+    lengths[b] (default T) samples -> EnsembleResult.  Every draw's sources are permuted to the order of least squared distance
+    to anchor [B,S,T] (default: draw 0 of the utterance), then reduced over the draws in float64: the mean, with want_std the
+    population standard deviation, every draw's squared distance to the mean, the medoid (the draw nearest to the mean) and with
+    want_pick that draw itself, aligned; want_gram: the cross-Grams the permutations were chosen from.  Samples beyond a length
+    are never read and come out as zeros.  Asynchronous on the current stream, no readback, no synchronisation.  out: a dense
+    float32 [B,S,T] tensor for the mean (every element is written)."""
+    if draws.dim() != 4 or draws.dtype != torch.float32 or not draws.is_cuda:
+        raise ValueError("ensemble: draws must be a float32 [B,K,S,T] device tensor")
+    draws = draws.contiguous()
+    B, K, S, T = draws.shape
+    dev = draws.device
+    if anchor is not None:
+        if tuple(anchor.shape) != (B, S, T) or anchor.dtype != torch.float32 or anchor.device != dev:
+            raise ValueError("ensemble: anchor must be a float32 [B,S,T] tensor on draws' device")
+        anchor = anchor.contiguous()
+    ln = None if lengths is None else _dev_i32(lengths, dev)
+    if ln is not None and ln.numel() != B:
+        raise ValueError("ensemble: lengths must have B entries")
+    nbytes = ensemble_workspace_bytes(B, K, S)
+    if out is None:
+        out = torch.empty((B, S, T), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (B, S, T) or out.device != dev:
+        raise ValueError("ensemble: out must be a dense float32 [B,S,T] tensor on draws' device")
+    std = torch.empty((B, S, T), dtype=torch.float32, device=dev) if want_std else None
+    pick = torch.empty((B, S, T), dtype=torch.float32, device=dev) if want_pick else None
+    perm = torch.empty((B, K, S), dtype=torch.int32, device=dev)
+    dist = torch.empty((B, K), dtype=torch.float64, device=dev)
+    medoid = torch.empty((B,), dtype=torch.int32, device=dev)
+    gram_ = torch.empty((B, K, S, S), dtype=torch.float64, device=dev) if want_gram else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    call(lib(), "diffsep_ensemble", _ptr(draws), _ptr(anchor), _ptr(ln), B, K, S, T, _ptr(out), _ptr(std), _ptr(pick), _ptr(perm),
+         _ptr(dist), _ptr(medoid), _ptr(gram_), _ptr(ws), nbytes, _stream_ptr())
+    return EnsembleResult(out, std, pick, perm, dist, medoid, gram_)
+
+
 def _dev_i32(v, device):
     """host list / array or tensor -> contiguous int32 device tensor (host values through pinned memory on the current
     stream: a pageable copy would stall every other stream's work)"""

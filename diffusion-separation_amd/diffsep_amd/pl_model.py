@@ -381,6 +381,64 @@ class DiffSepModel:
         self.longform_info = {"starts": starts, "perm": perm, "seeds": seeds, "K": K}
         return out
 
+    def separate_draws(self, mix, K, lengths=None, seeds=None, out="mean", rescale=None, check_finite=True, want_std=False,
+                       **sampler_kwargs):
+        """K posterior draws per mixture, aligned and reduced on the device (extension).  Every call of
+        the sampler is ONE random draw of the sources given the mixture, with its sources in an arbitrary order; this runs K of
+        them per file in one engine call and hands back their mean (out="mean", the default), the draw nearest to the mean
+        (out="medoid") or the mean together with all K draws in one source order (out="all").
+        mix [F,1,T] (or [1,T]) on the device, right-zero-padded, file f being lengths[f] (default T) samples long; files of one
+        call must share a padded frame count, as in every mixed-length engine call.  Each file is normalised once over its own
+        samples and repeated K times in the batch; draw k of file f has the device RNG seed inflight.draw_seeds(seeds[f], K)[k]
+        (seeds None: one draw of torch's generator per file), so draw 0 is what `separate` gives for the file under seeds[f].
+        The rows of the fused PC sampler are first rescaled exactly as a single draw is — rescale(mix_f [1,1,n], rows
+        [K,S,n]) -> [K,S,n], default: denormalize_batch with the file's mean and std, what `separate` does — and THEN aligned
+        and reduced by ops.ensemble: the mean that comes back is the float64 mean of the very draws that come back, bit for
+        bit.  check_finite: the overflow net of the 16-bit modes around the engine call, as in get_pc_sampler.
+        Returns (estimate [F,S,T], ops.EnsembleResult) and with out="all" also the aligned draws [F,K,S,T]; tails beyond a
+        length are zero.  self.draws_info = {"K", "seeds" (per file, per draw), "nfe"}."""
+        from . import inflight
+        if out not in ("mean", "medoid", "all"):
+            raise ValueError(f"separate_draws: out = {out!r} (mean, medoid or all)")
+        K = int(K)
+        if not 1 <= K <= 32:
+            raise ValueError(f"separate_draws: K = {K} draws (1..32)")
+        if mix.dim() == 2:
+            mix = mix[None]
+        if mix.dim() != 3 or mix.shape[1] != 1 or not mix.is_cuda:
+            raise ValueError("separate_draws: mix must be a [1,T] or [F,1,T] device tensor of single-channel mixtures")
+        mix = mix.float().contiguous()
+        F, _, T = mix.shape
+        lengths = [T] * F if lengths is None else [int(n) for n in lengths]
+        if seeds is None:
+            seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(F)]
+        if len(lengths) != F or len(seeds) != F:
+            raise ValueError("separate_draws: lengths and seeds must have one entry per mixture")
+        mix_n, stats = torch.zeros_like(mix), []
+        for f, n in enumerate(lengths):  # every file normalised once, over ITS samples (pl_model.py:81-88)
+            (m_f, _), mean, std = self.normalize_batch((mix[f:f + 1, :, :n], None))
+            mix_n[f, :, :n] = m_f[0]
+            stats.append((mean, std))
+        dseeds = [inflight.draw_seeds(s, K) for s in seeds]
+        skw = dict(cfg_get(self.config, "model.sampler", {}))
+        skw.update(sampler_kwargs)
+        sampler = self.get_pc_sampler("reverse_diffusion", "ald2", mix_n.repeat_interleave(K, dim=0), check_finite=check_finite,
+                                      lengths=[n for n in lengths for _ in range(K)], seeds=[s for ds in dseeds for s in ds],
+                                      **skw)
+        with torch.no_grad():
+            rows, nfe, *_ = sampler()
+        draws = torch.zeros_like(rows)
+        for f, n in enumerate(lengths):
+            r = rows[f * K:(f + 1) * K, :, :n]
+            draws[f * K:(f + 1) * K, :, :n] = self.denormalize_batch(r, *stats[f]) if rescale is None else \
+                rescale(mix[f:f + 1, :, :n], r)
+        draws = draws.view(F, K, *rows.shape[1:])
+        res = ops.ensemble(draws, lengths=lengths, want_std=want_std, want_pick=out != "mean")
+        self.draws_info = {"K": K, "seeds": dseeds, "nfe": nfe}
+        if out == "all":
+            return res.mean, res, res.aligned(draws)
+        return (res.pick if out == "medoid" else res.mean), res
+
     # ---- denoising score-matching loss, forward values (pl_model.py:166-247, 327-424) --------------------------
     FORWARD_ONLY = ("the score-matching loss is implemented forward-only (diffsep_score_loss): backward passes, optimiser, EMA "
                     "update, gradient clipping and compute_score_loss_with_pit (train_source_order 'pit', init_hack 6) are "

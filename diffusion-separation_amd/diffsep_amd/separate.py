@@ -26,6 +26,14 @@ file, not per rate of a batch), then cut into windows.  A file already at the mo
 network evaluation while each keeps its own step controller (diffsep_ode_sample_each), so with --dtype f32 the written
 files are those of --batch 1, bit for bit wherever the network evaluation does not depend on the batch.  --streams stays 1 there: the ODE driver blocks on a readback per step
 attempt.  Output files are 32-bit float WAV like torchaudio.save of a float tensor (separate.py:160-162).
+--draws K [--draws-out {mean,medoid,all}]: K posterior draws per file in one engine call (a file takes K rows of a --batch, which
+is filled with whole files; draw k under the seed inflight.draw_seeds(file seed, K)[k], draw 0 being the file's ordinary output),
+each rescaled as a single draw is, their source orders aligned and the draws reduced on the device (DiffSepModel.separate_draws,
+ops.ensemble): the mean (default) or the draw nearest to it is written where the file's output goes, and
+with `all` the aligned draws next to the mean as <stem>_draw<k>.wav — their float64 mean, rounded, is the mean file sample for
+sample wherever nothing is converted on the way out (with --resample file the mean and every draw are converted back
+separately, and the identity holds only to that conversion's rounding).  The overflow net looks at the mean of the call's draws,
+whatever is written: one non-finite sample in any draw repeats the call.  --draws 1 is the ordinary run.  Not with --chunk or --sampler ode in this version.
 """
 import argparse
 from pathlib import Path
@@ -284,6 +292,86 @@ def separate_chunked(args, files, rates, seeds, models, streams, kw):
     print(f"separated {len(files)} files into {args.output_dir} ({len(items)} windows of up to {window} samples)")
 
 
+def add_draws_arguments(ap):
+    ap.add_argument("--draws", type=int, default=None, metavar="K",
+                    help="K posterior draws per file (seeds inflight.draw_seeds: draw 0 is the file's ordinary output), their "
+                         "source orders aligned and the draws reduced on the device (ops.ensemble); a file takes K rows of a "
+                         "--batch, so K must fit it")
+    ap.add_argument("--draws-out", default=None, choices=["mean", "medoid", "all"],
+                    help="with --draws: what is written — the mean of the draws (default), the draw nearest to the mean, or the "
+                         "mean and every draw in the common source order")
+
+
+def check_draws_arguments(args, chunk):
+    """SystemExit, naming the flags, for a --draws request this version does not run; args.draws_out gets its default"""
+    if args.draws is None:
+        if args.draws_out is not None:
+            raise SystemExit("--draws-out goes with --draws")
+        return
+    if chunk:
+        raise SystemExit("--draws with --chunk is not supported: windows of several draws would have to be stitched per draw")
+    if args.sampler == "ode":
+        raise SystemExit("--draws with --sampler ode is not supported: the draws come from the predictor-corrector sampler")
+    if not 1 <= args.draws <= 32:
+        raise SystemExit(f"--draws {args.draws}: 1 to 32 draws")
+    if args.draws > max(1, args.batch):
+        raise SystemExit(f"--draws {args.draws} does not fit --batch {args.batch}: a file takes one row of an engine call per draw")
+    args.draws_out = args.draws_out or "mean"
+
+
+def scale_draws(mix_f, rows):
+    """the least-squares scale of separate.py:73-78 for every draw of one file, each exactly as a single draw gets it"""
+    return torch.cat([scale_output(mix_f, rows[k:k + 1]) for k in range(rows.shape[0])])
+
+
+def draws_request(model, mix_d, K, lens, sds, draws_out, kw):
+    """One engine call of --draws on the current stream -> (mean of the draws, the estimate draws_out names, EnsembleResult,
+    aligned draws or None).  The MEAN comes first whatever is written: the overflow net (inflight.finite_or_rerun,
+    DiffSepModel.rerun_if_nonfinite) looks at element 0, and a non-finite sample of ANY draw of the call is a non-finite
+    sample of their mean — whereas the medoid may be a finite draw beside an overflowed one (every distance is then NaN and
+    the strict < of the medoid search keeps draw 0)."""
+    est, res, *al = model.separate_draws(mix_d, K, lengths=lens, seeds=sds, out=draws_out, rescale=scale_draws, check_finite=False,
+                                         **kw)
+    return res.mean, est, res, (al[0] if al else None)
+
+
+def separate_with_draws(args, files, rates, seeds, models, streams, kw):
+    """--draws K: an engine call holds batch // K whole files, K rows each (DiffSepModel.separate_draws); the mean / medoid is
+    written where the file's output goes, with --draws-out all the aligned draws next to it as <stem>_draw<k>."""
+    K, lengths = args.draws, rates.lengths
+    eng = models[0].score_model.engine()
+    if seeds is None:  # one draw of torch's generator per file, as a file without --seed gets one per engine call
+        seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in files]
+    batches = inflight.plan_draw_batches(range(len(files)), lengths, eng.padded_frames, max(1, args.batch), K)
+    inflight.reserve_largest(models, batches, lengths, rows_per_item=K)
+
+    def run(model, mix_d, lens, sds):
+        return draws_request(model, mix_d, K, lens, sds, args.draws_out, kw)
+
+    def launch(w, j, group):
+        parts = rates.rows(group, [rates.load(i) for i in group], args.device)
+        mix_d, lens = padded_on_device(parts, eng.bucket_length(eng.padded_frames(max(lengths[i] for i in group))), args.device)
+        sds = [seeds[i] for i in group]
+        return group, lens, run(models[w], mix_d, lens, sds), mix_d, sds
+
+    def collect(w, item):
+        group, lens, result, mix_d, sds = item
+        _, est, res, al = inflight.finite_or_rerun(models[w], streams[w], result, lambda fb: run(fb, mix_d, lens, sds),
+                                                   what=str([files[i].name for i in group]))
+        rows = range(len(group))
+        with torch.cuda.stream(streams[w]):
+            outs = [(out.cpu(), sr) for out, sr in rates.restore(group, [est[b, :, :lens[b]] for b in rows])]
+            each = [] if al is None else [[(out.cpu(), sr) for out, sr in rates.restore(group, [al[b, k, :, :lens[b]] for b in rows])]
+                                          for k in range(K)]
+        for b, i in enumerate(group):
+            write_sources(args.output_dir, files[i].stem, *outs[b])
+            for k, outs_k in enumerate(each):
+                write_sources(args.output_dir, f"{files[i].stem}_draw{k}", *outs_k[b])
+
+    inflight.Ring(streams, launch, collect).run(batches)
+    print(f"separated {len(files)} files into {args.output_dir} ({K} draws each, {args.draws_out})")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Separate all the wav files in a specified folder")
     ap.add_argument("input_dir", type=Path)
@@ -318,7 +406,9 @@ def main(argv=None):
                     help="convert a file whose rate is not the model's to the model's rate on the device, separate it there, and "
                          "write the sources back at the file's rate, cropped to its length (file), or at the model's rate (model); "
                          "default: such a file only draws a warning and its samples go to the model as they are")
+    add_draws_arguments(ap)
     args = ap.parse_args(argv)
+    check_draws_arguments(args, chunk=args.chunk is not None)
     if args.chunk is None and args.overlap is not None:
         raise SystemExit("--overlap goes with --chunk")
     if args.chunk is not None and args.sampler == "ode":
@@ -370,6 +460,8 @@ def main(argv=None):
         return
     if args.chunk is not None:
         return separate_chunked(args, files, rates, seeds, models, streams, kw)
+    if args.draws is not None and (args.draws > 1 or args.draws_out != "mean"):  # (--draws 1 = one draw: the ordinary run)
+        return separate_with_draws(args, files, rates, seeds, models, streams, kw)
     eng = model.score_model.engine()
     batches = inflight.plan_batches(range(len(files)), lengths, eng.padded_frames, max(1, args.batch))
     inflight.reserve_largest(models, batches, lengths)

@@ -748,6 +748,38 @@ int64_t diffsep_longform_workspace_bytes(int32_t K, int32_t S);
 int32_t diffsep_longform_stitch(const float* win, int32_t K, int32_t S, int64_t Tw, int64_t T, int64_t Tv, float* out,
                                 int32_t* perm_out, double* gram_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Posterior draws: K draws of every utterance of a zero-padded batch, brought to one source order and reduced on the device
+ * (extension: the reference returns one draw per call and has no counterpart).  draws [B][K][S][T] float32; anchor [B][S][T]
+ * or NULL = draw 0 of each utterance; lengths device int32 [B] or NULL (= T); n = lengths[b].  Asynchronous on `stream`, no
+ * host readback, no floating-point atomics; five launches (four without pick_out).  For utterance b:
+ *   cross-Gram  C[k][i][j] = sum_{t<n} (double)a[i][t] (double)d[k][j][t], a = the anchor: products exact in float64, sums in the
+ *               fixed order of the block reductions, the 32 block partials of an entry folded in index order;
+ *               gram_out [B][K][S][S] (nullable) receives them;
+ *   permutation r_k = the permutation maximising sum_i C[k][i][r(i)] (= least squared distance to the anchor), candidates in
+ *               lexicographic order with a strict >: a tie, an all-silent draw included, keeps the identity — the rule of
+ *               diffsep_longform_stitch, the same code.  With anchor == NULL r_0 is the identity by construction (draw 0 is
+ *               not searched against itself).  perm_out [B][K][S] = r: aligned source i of draw k is its row r_k[i],
+ *               v_k[i][t] = d[k][r_k[i]][t];
+ *   mean        m[i][t] = (((v_0 + v_1) + ...) + v_{K-1}) / K in float64, mean_out = (float)m;
+ *   spread      std_out (nullable) = (float)sqrt(sum_k (v_k - m)^2 / K), the population form, k ascending, each operation
+ *               rounded on its own in float64;
+ *   distance    dist_out [B][K]: dist[k] = sum_{i, t<n} (v_k[i][t] - m[i][t])^2 in float64 against the unrounded m, in a fixed
+ *               order (block partials folded source-major);
+ *   medoid      medoid_out [B] = argmin_k dist[k], scanning from k = 0 with a strict <; pick_out (nullable) = v_medoid, bit for
+ *               bit.
+ * Samples at t >= n are never read; mean_out, std_out and pick_out [B][S][T] are written as exact +0.0 there (no pre-zeroing).
+ * Every output of utterance b is bit for bit what the call gives for that utterance alone (B = 1, T = n), in any batch, at any
+ * padded width, on any stream: the partition of the time axis into blocks is a function of n alone.  Rows are read with 16-byte
+ * loads where all base pointers are 16-byte aligned and T is a multiple of 4, sample by sample otherwise and at ragged ends; the
+ * two paths give the same bits.  K in 1..32, S in 1..3, B in 1..65535, 1 <= T < 2^31.  Refusals (K, S, B, T, a null required
+ * pointer, a workspace below diffsep_ensemble_workspace_bytes(B, K, S) or not 8-byte aligned) are checked before the first
+ * device call, return non-zero with a message that names the argument, and write nothing.
+ * diffsep_ensemble_workspace_bytes: host arithmetic only; -1 and a message for a refused shape. */
+int64_t diffsep_ensemble_workspace_bytes(int32_t B, int32_t K, int32_t S);
+int32_t diffsep_ensemble(const float* draws, const float* anchor, const int32_t* lengths, int32_t B, int32_t K, int32_t S,
+                         int64_t T, float* mean_out, float* std_out, float* pick_out, int32_t* perm_out, double* dist_out,
+                         int32_t* medoid_out, double* gram_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- the denoising score-matching loss (forward values only): DiffSepModel.sample_prior (pl_model.py:179-247),
  * compute_score_loss (:411-424), compute_score_loss_init_hack_pit (:370-405), compute_score_loss_with_pit_allthetime
  * (:327-368).  With true_mix = mix / S, mean = (A + exp(-lambda t) Pn) x0 and L the marginal std (times sigma_mix for
