@@ -212,6 +212,8 @@ _SIGS = {
     "diffsep_stoi": (_I, [_P, _P, _P, _I, _I, _L, _P, _P, _I, _I, _P, _L, _P]),
     "diffsep_composite_workspace_bytes": (_L, [_I, _I, _L, _I]),
     "diffsep_composite": (_I, [_P, _P, _P, _P, _L, _I, _I, _L, _P, _P, _I, _P, _L, _P]),
+    "diffsep_bss_eval_workspace_bytes": (_L, [_I, _I, _L, _I]),
+    "diffsep_bss_eval": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _P, _P, _I, C.c_double, _P, _L, _P]),
     "diffsep_resample_ratio": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_I)]),
     "diffsep_resample_length": (_L, [_L, _I, _I]),
     "diffsep_resample_design": (_I, [_I, _I, _P, _I]),

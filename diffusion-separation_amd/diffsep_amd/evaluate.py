@@ -20,7 +20,11 @@ ESTOI is computed on loader threads (diffsep_amd.metrics.stoi, `--stoi-on host`,
 (diffsep_amd.metrics.stoi_batch, `--stoi-on device`: no waveform leaves the device unless it is saved).  --composite (off by
 default; without it records and summaries are what they were) adds the signal measures of the reference's evaluate_covl.py to
 every record: per-source llr, wss, segsnr from the GPU (diffsep_amd.metrics.composite_batch) and csig / cbak / covl as null
-(they need PESQ: diffsep_amd.evaluate_covl takes it from a file).
+(they need PESQ: diffsep_amd.evaluate_covl takes it from a file).  --bss-eval [--bss-filter-length L] (off by default; without
+it records and summaries are what they were) adds the BSS-eval measures with an L-tap distortion filter (default 512:
+mir_eval's bss_eval_sources, fast_bss_eval.bss_eval_sources(filter_length=512)) to every record: per-source sdr, sir, sar
+under the record's final permutation, clamped to +-100 dB like the SI forms, from the GPU on the worker's stream
+(diffsep_amd.metrics.bss_eval_batch; 3 B S numbers cross PCIe); the summary holds their means and `bss_filter_length`.
 
 Utterances are sharded over ranks in contiguous ranges (evaluate_mp.py:495-503); each rank separates its
 share, records {batch_idx, si_sdr, si_sir, si_sar, pesq, stoi, nfe, runtime, len_s} per utterance (evaluate.py:394-405;
@@ -224,6 +228,11 @@ def build_parser():
                     help="also record the signal measures of the composite enhancement scores (evaluate_covl.py): per-source "
                          "llr, wss, segsnr from the HIP kernels of diffsep_composite on the worker's stream, and csig / cbak / covl "
                          "as null (they need PESQ: python -m diffsep_amd.evaluate_covl --pesq-json).  8 or 16 kHz models only")
+    ap.add_argument("--bss-eval", action="store_true",
+                    help="also record the BSS-eval SDR / SIR / SAR with a time-invariant distortion filter (mir_eval's "
+                         "bss_eval_sources): per-source sdr, sir, sar from the HIP kernels of diffsep_bss_eval on the worker's stream")
+    ap.add_argument("--bss-filter-length", type=int, default=512, metavar="L",
+                    help="taps of the distortion filter of --bss-eval (default 512, 1..1024)")
     ap.add_argument("--score-loss", type=int, default=0, metavar="K",
                     help="also record every utterance's denoising score-matching loss (the reference's val/score_loss): the mean "
                          "of K plain losses at times linspace(t_eps, 1, K) with device noise keyed by the utterance's seed, one "
@@ -277,6 +286,8 @@ def main(argv=None):
     no_proc = str(args.ckpt) == "__no_proc__"
     if args.ckpt is None and not args.synthetic_weights and not no_proc:
         ap.error("a checkpoint (or --synthetic-weights NF) is required")
+    if args.bss_eval and not 1 <= args.bss_filter_length <= 1024:
+        ap.error("--bss-filter-length: 1..1024 taps")
     for flag, on in (("--fig", args.fig), ("--trajectory", args.trajectory)):
         if on and args.sampler == "ode":
             raise SystemExit(f"{flag}: the ODE sampler has no fixed reverse steps to look at (--sampler pc)")
@@ -589,6 +600,11 @@ class SplitRun:
         if a.composite:  # LLR / WSS / segmental SNR of every source against its permuted estimate: 4 B S numbers cross PCIe
             with torch.cuda.stream(stream):
                 comp_dev = metrics.composite_batch(tgt_n, est, self.fs, lengths=lens, perm=[m["perm"] for m in mets])
+        bss_dev = None
+        if a.bss_eval:  # SDR / SIR / SAR of every source against its permuted estimate: 3 B S numbers cross PCIe
+            with torch.cuda.stream(stream):
+                bss_dev = metrics.bss_eval_batch(tgt_n, est, a.bss_filter_length, clamp_db=100.0, lengths=lens,
+                                                 perm=[m["perm"] for m in mets])
         if need_host:
             with torch.cuda.stream(stream):
                 est_h, tgt_h, mix_h = est.cpu(), tgt_n.cpu(), b.mix_n.cpu()
@@ -624,6 +640,9 @@ class SplitRun:
                 for q, name in enumerate(("llr", "wss", "segsnr")):
                     rec[name] = [float(v) for v in comp_dev[k, :k_src, q]]
                 rec.update({"csig": None, "cbak": None, "covl": None})  # (they need PESQ)
+            if bss_dev is not None:
+                for q, name in enumerate(("sdr", "sir", "sar")):
+                    rec[name] = [float(v) for v in bss_dev[k, q, :k_src]]
             if need_host:
                 est_k = est_h[k, perm, :lens[k]]  # "fix the permutation" (evaluate.py:392): estimates in the targets' order
                 if not a.no_stoi and a.stoi_on == "host":
@@ -649,6 +668,7 @@ class SplitRun:
                         "dtype": model.dtype if model is not None else None,
                         "sampler": None if model is None else a.sampler,
                         **({"draws": self.draws, "draws_out": a.draws_out} if self.draws else {}),
+                        **({"bss_filter_length": a.bss_filter_length} if a.bss_eval else {}),
                         "utt_per_s_rank0": len(self.mine) / max(wall, 1e-9), "split_fallback_batches_rank0": len(self.fallbacks),
                         # PESQ is ITU-T P.862 reference C code behind the third-party `pesq` package: not restated here
                         # (DESIGN.md section 7); STOI / ESTOI is diffsep_amd.metrics.stoi (published algorithm, restated)

@@ -73,6 +73,135 @@ def si_bss_from_gram(G, clamp_db=100.0, perm=None):
     return out[0], out[1], out[2], best
 
 
+# ---------------------------------------------------------------------------------------------------------------- BSS-eval
+# SDR / SIR / SAR with a time-invariant distortion filter of L taps: mir_eval.separation.bss_eval_sources, and
+# fast_bss_eval.bss_eval_sources(ref, est, filter_length=512) of the package the reference imports for the SI forms
+# (evaluate.py:103-132).  Where SI-SDR allows the estimate one gain, SDR allows it an L-tap FIR.  With A_i the (n + L - 1) x L
+# matrix whose column tau is reference i delayed by tau, A = [A_0 ... A_{S-1}], P_i and P the orthogonal projections onto
+# their column spans:  s_target = P_i e_j,  e_interf = P e_j - P_i e_j,  e_artif = e_j - P e_j.  From correlations:
+#   R = A^T A (block Toeplitz, S L x S L),  b_j = A^T e_j,  E_j = |e_j|^2,  q_ij = b_ij^T R_ii^-1 b_ij,  Q_j = b_j^T R^-1 b_j
+#   SDR[i][j] = 10 log10(q_ij / (E_j - q_ij)),  SIR[i][j] = 10 log10(q_ij / (Q_j - q_ij)),  SAR[j] = 10 log10(Q_j / (E_j - Q_j))
+# A denominator <= 0: +inf.  A non-positive Cholesky pivot (a silent reference): NaN for what depends on that factorisation
+# (R_ii: row i of SDR and SIR; R: every SIR and SAR).  Neither package is installed here: parity with them is unpinned, and
+# the explicit least-squares form of the definition above (tests/bss_eval_cases.py) stands in for them.
+def _xcorr(x, y, L):
+    """X(x, y, l) = sum_m x[m] y[m + l], l = 0 .. L - 1 (direct sums in float64; lags beyond the length are zero)"""
+    n = len(x)
+    return np.array([np.dot(x[:n - l], y[l:]) if l < n else 0.0 for l in range(L)])
+
+
+def _bss_quad(R, rhs):
+    """(y = chol(R)^-1 rhs [N, S], True), or (None, False) for a non-positive pivot"""
+    import scipy.linalg
+    if not np.all(np.isfinite(R)):
+        return None, False
+    try:
+        c = scipy.linalg.cho_factor(R, lower=True, check_finite=False)[0]
+    except np.linalg.LinAlgError:
+        return None, False
+    return scipy.linalg.solve_triangular(c, rhs, lower=True, check_finite=False), True
+
+
+def _bss_db(num, den, clamp_db):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v = np.inf if den <= 0.0 else 10.0 * np.log10(num / den)
+    if clamp_db and v == v:
+        v = min(max(v, -clamp_db), clamp_db)
+    return float(v)
+
+
+def bss_eval_host(ref, est, filter_length=512, clamp_db=None, lengths=None, perm=None):
+    """The float64 numpy / scipy form of diffsep_bss_eval (same Toeplitz algebra, scipy.linalg.cho_factor): ref, est [B,S,T]
+    arrays -> dict(sdr, sir, sar [B,S], perm [B,S] int64, sdr_pairs, sir_pairs [B,S,S] indexed [reference][estimate],
+    sar_all [B,S] per estimate).  perm None: the permutation of largest summed clamped SDR (NaN as -inf), the earliest of
+    itertools.permutations on a tie."""
+    import scipy.linalg
+    ref, est = np.asarray(ref, dtype=np.float32), np.asarray(est, dtype=np.float32)
+    if ref.shape != est.shape or ref.ndim != 3:
+        raise ValueError("bss_eval: ref and est must be [B,S,T] arrays of one shape")
+    B, S, T = ref.shape
+    L, clamp = int(filter_length), float(clamp_db or 0.0)
+    if not (1 <= S <= 3 and 1 <= L <= 1024):
+        raise ValueError("bss_eval: S in 1..3 and filter_length in 1..1024")
+    res = {"sdr": np.zeros((B, S)), "sir": np.zeros((B, S)), "sar": np.zeros((B, S)), "perm": np.zeros((B, S), dtype=np.int64),
+           "sdr_pairs": np.zeros((B, S, S)), "sir_pairs": np.zeros((B, S, S)), "sar_all": np.zeros((B, S))}
+    perms = list(itertools.permutations(range(S)))
+    for b in range(B):
+        n = T if lengths is None else min(max(int(lengths[b]), 0), T)
+        r, e = ref[b, :, :n].astype(np.float64), est[b, :, :n].astype(np.float64)
+        G = [[_xcorr(r[i], r[k], L) for k in range(S)] for i in range(S)]
+        R = np.block([[scipy.linalg.toeplitz(G[i][k], G[k][i]) for k in range(S)] for i in range(S)])
+        rhs = np.stack([np.concatenate([_xcorr(r[i], e[j], L) for i in range(S)]) for j in range(S)], axis=1)  # [S L, S]
+        E = [float(np.dot(e[j], e[j])) for j in range(S)]
+        y, ok = _bss_quad(R, rhs)
+        q, okq = np.zeros((S, S)), [False] * S
+        for i in range(S):
+            if i == 0 and ok:  # chol(R_00) is the leading block of chol(R): the first L terms of the same sum
+                yi, okq[i] = y[:L], True
+            else:
+                yi, okq[i] = _bss_quad(R[i * L:(i + 1) * L, i * L:(i + 1) * L], rhs[i * L:(i + 1) * L])
+            if okq[i]:
+                q[i] = [float(np.dot(yi[:, j], yi[:, j])) for j in range(S)]
+        Q = [float(np.dot(y[:, j], y[:, j])) if ok else np.nan for j in range(S)]
+        sdr, sir = res["sdr_pairs"][b], res["sir_pairs"][b]
+        for j in range(S):
+            res["sar_all"][b, j] = _bss_db(Q[j], E[j] - Q[j], clamp) if ok else np.nan
+            for i in range(S):
+                sdr[i, j] = _bss_db(q[i, j], E[j] - q[i, j], clamp) if okq[i] else np.nan
+                sir[i, j] = _bss_db(q[i, j], Q[j] - q[i, j], clamp) if okq[i] and ok else np.nan
+        if perm is None:
+            cost = np.where(np.isnan(sdr), -np.inf, sdr)
+            best, bestv = 0, 0.0
+            for k, p in enumerate(perms):  # perm_search.h: sums from 0.0 with i ascending, strict >
+                v = 0.0
+                with np.errstate(invalid="ignore"):
+                    for i in range(S):
+                        v = v + cost[i, p[i]]
+                if k == 0 or v > bestv:
+                    best, bestv = k, v
+            p = perms[best]
+        else:
+            p = tuple(min(max(int(v), 0), S - 1) for v in perm[b])
+        res["perm"][b] = p
+        for i in range(S):
+            res["sdr"][b, i], res["sir"][b, i], res["sar"][b, i] = sdr[i, p[i]], sir[i, p[i]], res["sar_all"][b, p[i]]
+    return res
+
+
+def _to_host(d):
+    h = torch.empty(d.shape, dtype=d.dtype, pin_memory=True)
+    h.copy_(d, non_blocking=True)
+    return h
+
+
+def bss_eval_sources(ref, est, filter_length=512, clamp_db=None, lengths=None, perm=None, on="device"):
+    """BSS-eval SDR / SIR / SAR with a filter_length-tap distortion filter: ref, est [B,S,T] -> (sdr, sir, sar [B,S] float64
+    numpy, perm [B,S] int64) with est[:, perm] aligned to ref, shaped like si_bss_eval_sources.  clamp_db None / 0: no clamp.
+    on="device": device tensors through diffsep_bss_eval (ops.bss_eval), one pinned readback on the current stream;
+    on="host": bss_eval_host on arrays or host tensors (no GPU needed)."""
+    if on == "host":
+        as_np = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        r = bss_eval_host(as_np(ref), as_np(est), filter_length, clamp_db, None if lengths is None else as_np(lengths),
+                          None if perm is None else as_np(perm))
+        return r["sdr"], r["sir"], r["sar"], r["perm"]
+    if on != "device":
+        raise ValueError("bss_eval_sources: on must be 'device' or 'host'")
+    out, _, pout = ops.bss_eval(ref, est, filter_length, float(clamp_db or 0.0), lengths=lengths, perm=perm)
+    oh, ph = _to_host(out), _to_host(pout)
+    torch.cuda.current_stream().synchronize()
+    o = oh.numpy().copy()
+    return o[:, 0], o[:, 1], o[:, 2], ph.numpy().astype(np.int64)
+
+
+def bss_eval_batch(ref, est, filter_length=512, clamp_db=100.0, lengths=None, perm=None):
+    """bss_eval_sources on the device for evaluate: ref, est [B,S,T] device tensors -> [B,3,S] float64 numpy array {sdr, sir,
+    sar} per source; estimate row perm[b][i] against reference row i over the first lengths[b] (default T) samples.  One
+    pinned, non-blocking readback of 3 B S numbers on the current stream."""
+    h = _to_host(ops.bss_eval(ref, est, filter_length, float(clamp_db or 0.0), lengths=lengths, perm=perm)[0])
+    torch.cuda.current_stream().synchronize()
+    return h.numpy().copy()
+
+
 # ---------------------------------------------------------------------------------------------------------------- STOI / ESTOI
 # The reference scores every source with pystoi's stoi(ref, est, fs, extended=True) (evaluate.py:113-130).  pystoi is a
 # third-party package that is not installed here and is not under /root/reference: what follows restates the PUBLISHED

@@ -725,6 +725,38 @@ def composite(ref, est, fs=16000, lengths=None, perm=None, frames=False):
     return (out, fr) if frames else out
 
 
+BSS_EVAL_WORKSPACE_CAP = 1 << 29  # bytes of workspace one diffsep_bss_eval call of bss_eval() may take (512 MiB)
+
+
+def bss_eval_workspace_bytes(B, S, T, L):
+    """bytes of workspace diffsep_bss_eval needs (host arithmetic; raises for a shape it refuses)"""
+    return _workspace_bytes(lib().diffsep_bss_eval_workspace_bytes, B, S, T, L)
+
+
+def bss_eval(ref, est, filter_length=512, clamp_db=0.0, lengths=None, perm=None):
+    """BSS-eval SDR / SIR / SAR with a filter_length-tap distortion filter of every utterance of a zero-padded batch on the
+    device: ref, est [B,S,T] float32 device tensors -> (out float64 [B,3,S] {sdr, sir, sar} per source, pairs float64
+    [B,2,S,S] the SDR and SIR tables [reference][estimate], perm int32 [B,S]) device tensors; perm None: searched (largest mean
+    clamped SDR).  The algebra of metrics.bss_eval_host in float64 (csrc/bss_eval.hip); asynchronous on the current stream.  A
+    batch whose workspace would exceed BSS_EVAL_WORKSPACE_CAP goes as several calls (a row's result does not depend on its
+    batch); one utterance always goes, whatever it needs."""
+    ref, est, B, S, T, ln, pm = _pair_call("bss_eval", ref, est, lengths, perm)
+    L = int(filter_length)
+    per = max(1, bss_eval_workspace_bytes(1, S, T, L))
+    step = max(1, min(B, BSS_EVAL_WORKSPACE_CAP // per))
+    dev = ref.device
+    out = torch.empty((B, 3, S), dtype=torch.float64, device=dev)
+    pairs = torch.empty((B, 2, S, S), dtype=torch.float64, device=dev)
+    pout = torch.empty((B, S), dtype=torch.int32, device=dev)
+    ws = torch.empty(bss_eval_workspace_bytes(step, S, T, L), dtype=torch.uint8, device=dev)
+    for b0 in range(0, B, step):
+        nb = min(step, B - b0)
+        call(lib(), "diffsep_bss_eval", _ptr(ref[b0:]), _ptr(est[b0:]), _ptr(out[b0:]), _ptr(pairs[b0:]), _ptr(pout[b0:]), nb, S, T,
+             _ptr(None if ln is None else ln[b0:]), _ptr(None if pm is None else pm[b0:]), L, float(clamp_db), _ptr(ws),
+             ws.numel(), _stream_ptr())
+    return out, pairs, pout
+
+
 def resample_ratio(fs_in, fs_out):
     """(p, q) = fs_out / fs_in reduced (diffsep_resample_ratio: host arithmetic; raises for rates <= 0 or a factor beyond 1000)"""
     p, q = C.c_int32(), C.c_int32()

@@ -685,6 +685,37 @@ int32_t diffsep_composite(const float* ref, const float* est, double* out, doubl
                           int32_t B, int32_t S, int64_t T, const int32_t* lengths, const int32_t* perm, int32_t fs,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* BSS-eval SDR / SIR / SAR with a time-invariant distortion filter of L taps for every utterance of a zero-padded batch
+ * (mir_eval.separation.bss_eval_sources; fast_bss_eval.bss_eval_sources(ref, est, filter_length=L), the package that
+ * evaluate.py:103-132 imports for the scale-invariant forms).  ref, est [B,S,T] float32; the first lengths[b] (NULL: T)
+ * samples count and samples beyond them are never read; float64 from the samples on.  With A_i the (n + L - 1) x L matrix
+ * whose column tau is reference i delayed by tau, A = [A_0 ... A_{S-1}] and P_i, P the orthogonal projections onto their
+ * column spans: s_target = P_i e_j, e_interf = P e_j - P_i e_j, e_artif = e_j - P e_j.  Computed from correlations:
+ *   c_ik(l) = sum_m r_i[m] r_k[m + l], |l| < L;   R[(i,tau),(k,tau')] = c_ik(tau - tau')  (S L x S L, block Toeplitz);
+ *   b_j[(i,tau)] = sum_m r_i[m - tau] e_j[m];   E_j = sum e_j^2;   q_ij = b_ij^T R_ii^-1 b_ij;   Q_j = b_j^T R^-1 b_j
+ *   SDR[i][j] = 10 log10(q_ij / (E_j - q_ij)),  SIR[i][j] = 10 log10(q_ij / (Q_j - q_ij)),  SAR[j] = 10 log10(Q_j / (E_j - Q_j))
+ * by direct time-domain sums and dense Cholesky factorisations (no approximation).  A denominator <= 0 gives +inf (S = 1:
+ * every SIR, exactly).  A non-positive Cholesky pivot (a silent reference) makes what depends on that factorisation NaN: of
+ * R_ii, row i of the SDR and SIR tables; of R, every SIR and SAR of the utterance; no other utterance is touched and the
+ * call returns normally.  clamp_db > 0 clamps every value that is not NaN, the infinite ones included, to [-clamp_db,
+ * clamp_db]; 0: no clamp.  perm (device int32 [B][S], entries clamped to [0, S)) NULL: the permutation of largest summed
+ * clamped SDR[i][perm[i]], NaN counting as -inf, the earliest in lexicographic order on a tie (the enumeration of
+ * diffsep_longform_stitch and diffsep_ensemble).  out [B][3][S] = { SDR[i][perm[i]], SIR[i][perm[i]], SAR[perm[i]] };
+ * pair_out (nullable) [B][2][S][S] = the SDR and SIR tables [i][j]; perm_out (nullable) [B][S] = the permutation used.
+ * S in 1..3, L in 1..1024, B S <= 65535, T < 2^31; n < L is legal (the missing lags are zero).  Asynchronous on stream, no
+ * host readback.  Every sum has a fixed order that depends on n and L alone (no atomics): row b is bit for bit what the call
+ * gives for that utterance alone, at any padded T, in any batch, on any stream.  A refusal (shape, a null ref / est / out /
+ * workspace, clamp_db < 0, workspace_bytes too small, a workspace not 8-byte aligned) is decided before the first device
+ * call, returns non-zero with a message naming the argument and writes nothing.
+ * Caller-owned workspace of diffsep_bss_eval_workspace_bytes(B, S, T, L) bytes (host arithmetic only; -1 and a message for a
+ * refused shape): with J = 2 S^2 + S correlation rows and C = ceil(T / 2048) time chunks, four pieces, each rounded up to
+ * 256 bytes:  8 B J C L  +  8 B J L  +  8 B ((S L + S) S L + (S - 1)(L + S) L)  +  4 B S
+ * (S = 3, L = 512: 23.1 MB per utterance for the systems and their right-hand sides). */
+int64_t diffsep_bss_eval_workspace_bytes(int32_t B, int32_t S, int64_t T, int32_t L);
+int32_t diffsep_bss_eval(const float* ref, const float* est, double* out, double* pair_out, int32_t* perm_out, int32_t B,
+                         int32_t S, int64_t T, const int32_t* lengths, const int32_t* perm, int32_t L, double clamp_db,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Band-limited sample-rate conversion of fp32 rows by a reduced ratio p / q (fs_out / fs_in) with an odd-length FIR
  * h[0 .. 2 L] in float64, applied as given — the zero-stuffed direct form, centred:
  *   y[m] = sum_j h[m q + L - p j] (double)x[j],  0 <= j < len, tap index in [0, 2 L],  0 <= m < n_out = ceil(len p / q),
