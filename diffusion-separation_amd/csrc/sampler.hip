@@ -44,25 +44,34 @@ static int mixture_scale(diffsep_engine* e, const diffsep_sde_config* sde, int B
 }
 
 // The sampler, with an optional tap on its intermediate states (reference sdes/__init__.py:168-186, `intermediate`; the
-// figure of evaluate.py:29-61 is drawn from them).  In reverse step i, after the corrector step(s) and before the predictor —
-// where the reference appends (xt, xt_mean) — one launch (sde.hip: trace_tap_kernel) copies the state of the chosen steps and
-// adds up the Gram sums of every step against `target`.  The state lives on `e` whichever engine evaluates the score, and the
-// tap is a stream launch between graph replays: the captured graphs are those of the untraced call.  With nothing to trace
-// (n_snap == 0, target == NULL) not one launch, copy or allocation is added: that is diffsep_pc_sample_ex.
-extern "C" int32_t diffsep_pc_sample_trace(diffsep_engine* e, const diffsep_sde_config* sde,
-                                           const diffsep_sampler_config* smp, const diffsep_sampler_ext* ext,
-                                           const float* mix_norm, float* out, int32_t B, int64_t T, const float* noise,
-                                           uint64_t seed, const float* timesteps_host, int32_t* nfe_out, int32_t n_snap,
-                                           const int32_t* snap_steps_host, float* snap_x, float* snap_xm,
-                                           const float* target, double* gram, void* stream) {
+// figure of evaluate.py:29-61 is drawn from them) and with both ends open: a caller-supplied state instead of the prior and a
+// range [first_step, last_step) of the N reverse steps (diffsep_pc_sample_from; the three older entries forward to it with
+// {NULL, 0, 0}).  In reverse step i, after the corrector step(s) and before the predictor — where the reference appends
+// (xt, xt_mean) — one launch (sde.hip: trace_tap_kernel) copies the state of the chosen steps and adds up the Gram sums of
+// every step against `target`.  The state lives on `e` whichever engine evaluates the score, and the tap is a stream launch
+// between graph replays: the captured graphs are those of the untraced call.  With nothing to trace (n_snap == 0,
+// target == NULL) and no range not one launch, copy or allocation is added: that is diffsep_pc_sample_ex.
+// Steps are absolute indices of the N-point grid: step i runs at ts[i] with dt = 1/N and consumes the draws
+// 1 + i (csteps + npred) ... of the device RNG (draw 0 is the prior's), whatever step the call starts at.
+extern "C" int32_t diffsep_pc_sample_from(diffsep_engine* e, const diffsep_sde_config* sde,
+                                          const diffsep_sampler_config* smp, const diffsep_sampler_ext* ext,
+                                          const float* mix_norm, float* out, int32_t B, int64_t T, const float* noise,
+                                          uint64_t seed, const float* timesteps_host, int32_t* nfe_out, int32_t n_snap,
+                                          const int32_t* snap_steps_host, float* snap_x, float* snap_xm,
+                                          const float* target, double* gram, const float* x_init, int32_t first_step,
+                                          int32_t last_step, void* stream) {
   DS_CHECK(e && sde && smp && mix_norm && out, "pc_sample: null argument");
   if (check_sde(e, sde, "pc_sample")) return 1;
   DS_CHECK(smp->N >= 1 && smp->N <= 4096, "pc_sample: N must be in [1,4096]");
+  const int first = first_step, last = last_step == 0 ? smp->N : last_step;
+  DS_CHECK(first >= 0 && first < last && last <= smp->N,
+           "pc_sample: the step range must satisfy 0 <= first_step < last_step <= N (last_step 0 = N)");
+  DS_CHECK(first == 0 || x_init, "pc_sample: first_step > 0 needs the state to start from (x_init == NULL)");
   DS_CHECK(n_snap >= 0 && (n_snap == 0 || snap_steps_host), "pc_sample: n_snap snapshot steps are needed");
   DS_CHECK(n_snap == 0 || snap_x, "pc_sample: snapshots were requested without a buffer (snap_x == NULL)");
   for (int k = 0; k < n_snap; ++k)
-    DS_CHECK(snap_steps_host[k] >= 0 && snap_steps_host[k] < smp->N && (k == 0 || snap_steps_host[k] > snap_steps_host[k - 1]),
-             "pc_sample: the snapshot steps must be strictly ascending and in [0, N)");
+    DS_CHECK(snap_steps_host[k] >= first && snap_steps_host[k] < last && (k == 0 || snap_steps_host[k] > snap_steps_host[k - 1]),
+             "pc_sample: the snapshot steps must be strictly ascending and in [0, N), within the executed steps [first_step, last_step)");
   DS_CHECK(!target == !gram, "pc_sample: target and gram are given together or not at all");
   DS_CHECK(!(n_snap || target) || e->cfg.num_sources <= DS_MAX_SRC, "pc_sample: too many sources to trace");
   if (n_snap == 0) snap_x = snap_xm = nullptr;
@@ -85,6 +94,8 @@ extern "C" int32_t diffsep_pc_sample_trace(diffsep_engine* e, const diffsep_sde_
     a.dtype = b2.dtype = 0;
     DS_CHECK(memcmp(&a, &b2, sizeof(a)) == 0, "pc_sample: the tail engine must have the same architecture");
   }
+  // (head_steps / tail_steps are absolute steps: a range that holds none of them never touches the other engine)
+  if (tail && !(first < head_steps || last > smp->N - tail_steps)) tail = nullptr;
   DS_CHECK(!lengths || smp->corrector != DIFFSEP_CORR_LANGEVIN,
            "pc_sample: the 'langevin' corrector couples the batch entries; it cannot run on a mixed-length batch");
   DS_CHECK(!seeds || !noise, "pc_sample: per-utterance seeds are for device noise (noise == NULL)");
@@ -100,6 +111,7 @@ extern "C" int32_t diffsep_pc_sample_trace(diffsep_engine* e, const diffsep_sde_
   hipStream_t st = sc_.st;
   const int S = e->cfg.num_sources, N = smp->N;
   const int csteps = smp->corrector == DIFFSEP_CORR_NONE ? 0 : smp->corrector_steps;
+  const int npred = smp->predictor == DIFFSEP_PRED_NONE ? 0 : 1;
   if (ensure_plan(e, B, T, st)) return 1;
   if (tail && ensure_plan(tail, B, T, st)) return 1;
   const size_t nst = (size_t)B * S * T;
@@ -142,7 +154,7 @@ extern "C" int32_t diffsep_pc_sample_trace(diffsep_engine* e, const diffsep_sde_
   }
   const bool batch_rng = !noise && (seeds || lengths);
 
-  long draw = 0;
+  long draw = x_init ? 1 + (long)first * (csteps + npred) : 0;  // (a given state: draw 0, the prior's, is not generated)
   auto next_noise = [&](const float** z) -> int {
     if (noise) { *z = noise + (size_t)draw * nst; }
     else {
@@ -157,10 +169,15 @@ extern "C" int32_t diffsep_pc_sample_trace(diffsep_engine* e, const diffsep_sde_
     return 0;
   };
   const float* z = nullptr;
-  if (next_noise(&z)) return 1;
+  if (!x_init && next_noise(&z)) return 1;
   const float* smix = nullptr;
   if (mixture_scale(e, sde, B, T, st, &smix)) return 1;
-  if (ds_launch_sde_prior(sp, e->st_mix, z, e->st_x, B, S, T, smix, st, lens)) return 1;
+  if (x_init) {  // the caller's state instead of the prior; its tail zero like the mixture's
+    DS_HIP(hipMemcpyAsync(e->st_x, x_init, nst * 4, hipMemcpyDeviceToDevice, st));
+    if (lens && ds_launch_mask_tail(e->st_x, B, S, T, lens, st)) return 1;
+  } else if (ds_launch_sde_prior(sp, e->st_mix, z, e->st_x, B, S, T, smix, st, lens)) {
+    return 1;
+  }
   DS_HIP(hipMemcpyAsync(e->st_xm, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
   // one score evaluation of reverse step i: on this engine, or — in the last tail_steps steps — on the tail engine
   // (state and time step copied over, the score read from there)
@@ -180,7 +197,7 @@ extern "C" int32_t diffsep_pc_sample_trace(diffsep_engine* e, const diffsep_sde_
     score = e->st_score;
     return run_nfe(e, B, T, st);
   };
-  for (int i = 0; i < N; ++i) {
+  for (int i = first; i < last; ++i) {
     DS_HIP(hipMemcpyAsync(e->st_t, e->st_ts + (size_t)i * B, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
     for (int k = 0; k < csteps; ++k) {
       if (eval_score(i)) return 1;
@@ -222,10 +239,21 @@ extern "C" int32_t diffsep_pc_sample_trace(diffsep_engine* e, const diffsep_sde_
       DS_HIP(hipMemcpyAsync(e->st_xm, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
     }
   }
-  DS_HIP(hipMemcpyAsync(out, smp->denoise ? e->st_xm : e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
-  if (target && ds_launch_gram(target, out, gram + (size_t)N * ngram, B, S, T, st)) return 1;  // row N: the result itself
-  if (nfe_out) *nfe_out = N * (csteps + 1);
+  // a run that stops before step N hands out the state x itself, whatever `denoise` says: it can be resumed from it
+  DS_HIP(hipMemcpyAsync(out, (smp->denoise && last == N) ? e->st_xm : e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
+  if (target && last == N && ds_launch_gram(target, out, gram + (size_t)N * ngram, B, S, T, st)) return 1;  // row N: the result itself
+  if (nfe_out) *nfe_out = (last - first) * (csteps + 1);
   return 0;
+}
+
+extern "C" int32_t diffsep_pc_sample_trace(diffsep_engine* e, const diffsep_sde_config* sde,
+                                           const diffsep_sampler_config* smp, const diffsep_sampler_ext* ext,
+                                           const float* mix_norm, float* out, int32_t B, int64_t T, const float* noise,
+                                           uint64_t seed, const float* timesteps_host, int32_t* nfe_out, int32_t n_snap,
+                                           const int32_t* snap_steps_host, float* snap_x, float* snap_xm,
+                                           const float* target, double* gram, void* stream) {
+  return diffsep_pc_sample_from(e, sde, smp, ext, mix_norm, out, B, T, noise, seed, timesteps_host, nfe_out, n_snap,
+                                snap_steps_host, snap_x, snap_xm, target, gram, nullptr, 0, 0, stream);
 }
 
 extern "C" int32_t diffsep_pc_sample_ex(diffsep_engine* e, const diffsep_sde_config* sde,

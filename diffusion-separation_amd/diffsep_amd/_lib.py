@@ -67,6 +67,10 @@ GN_ROUTES = {"auto": 0, "apply": 1, "block2x2": 2, "down_strip4": 3, "down_strip
              "up_tiled": 7}
 
 PIT_NONE, PIT_TRUE_MIX, PIT_MEAN0 = 0, 1, 2
+WARM_SCALE_NONE, WARM_SCALE_LS = 0, 1       # diffsep_warm_start: the gain fit
+WARM_MEAN_MIX, WARM_MEAN_ESTIMATE = 0, 1    # ... and where the perturbation's source average comes from
+WARM_SCALES = {"none": WARM_SCALE_NONE, "ls": WARM_SCALE_LS}
+WARM_MEANS = {"mix": WARM_MEAN_MIX, "estimate": WARM_MEAN_ESTIMATE}
 
 
 class LossConfig(C.Structure):  # diffsep_loss_config
@@ -136,6 +140,8 @@ _SIGS = {
                                   _L, _P, _U64, _P, C.POINTER(_I), _P]),
     "diffsep_pc_sample_trace": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(SamplerConfig), C.POINTER(SamplerExt), _P, _P, _I,
                                      _L, _P, _U64, _P, C.POINTER(_I), _I, C.POINTER(_I), _P, _P, _P, _P, _P]),
+    "diffsep_pc_sample_from": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(SamplerConfig), C.POINTER(SamplerExt), _P, _P, _I,
+                                    _L, _P, _U64, _P, C.POINTER(_I), _I, C.POINTER(_I), _P, _P, _P, _P, _P, _I, _I, _P]),
     "diffsep_ode_sample": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(OdeConfig), _P, _P, _P, _U64, _P, _I, _L,
                                 C.POINTER(OdeInfo), _P]),
     "diffsep_ode_sample_each": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(OdeConfig), C.POINTER(OdeExt), _P, _P, _P, _U64, _P,
@@ -226,6 +232,9 @@ _SIGS = {
     "diffsep_longform_stitch": (_I, [_P, _I, _I, _L, _L, _L, _P, _P, _P, _P, _L, _P]),
     "diffsep_ensemble_workspace_bytes": (_L, [_I, _I, _I]),
     "diffsep_ensemble": (_I, [_P, _P, _P, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "diffsep_warm_start_workspace_bytes": (_L, [_I, _I]),
+    "diffsep_warm_start": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _I, _I, _P, _P, _P, _I, _I,
+                                _L, _P, _L, _P]),
     "diffsep_randn": (_I, [_P, _L, _U64, _U64, _P]),
     "diffsep_randn_batch": (_I, [_P, _I, _I, _L, _P, _P, _U64, _P]),
     "diffsep_convert": (_I, [_P, _P, _L, _I, _I, _P]),

@@ -221,7 +221,8 @@ class Engine:
 
     def pc_sample(self, mix_norm, sde, N=30, corrector_steps=1, snr=0.5, eps=0.03, denoise=True,
                   predictor="reverse_diffusion", corrector="ald2", noise=None, seed=0, timesteps=None, lengths=None,
-                  seeds=None, tail=None, tail_steps=0, head_steps=0, snapshots=None, snapshot_means=True, target=None):
+                  seeds=None, tail=None, tail_steps=0, head_steps=0, snapshots=None, snapshot_means=True, target=None,
+                  x_init=None, first_step=0, last_step=None):
         """The whole sampler (sdes.get_pc_sampler(...)()).  sde: dict(kind, ndim, d_lambda, sigma_min, sigma_max).
         Tracing (diffsep_pc_sample_trace; with snapshots or target the result is (out, nfe, trace), a SamplerTrace):
         snapshots = the reverse steps whose state (x, and x_mean unless snapshot_means=False) is kept, as the reference's
@@ -232,7 +233,14 @@ class Engine:
         one padded frame count; seeds [B] = per-utterance device-RNG seeds; tail / head_steps / tail_steps = evaluate the
         score of the FIRST head_steps and / or the last tail_steps reverse steps on another Engine (dtype "hybrid" of
         pl_model: a split-fp32 engine for the first HYBRID_HEAD_STEPS steps of a 16-bit one — the early steps carry
-        the rounding error)."""
+        the rounding error).
+        Both ends open (diffsep_pc_sample_from): x_init [B,S,T] = the state to start from instead of the
+        prior sample (ops.warm_start builds one from another separator's estimates); only the reverse steps
+        [first_step, last_step) of the N-point grid run (last_step None = N; first_step > 0 needs x_init), each at its own time
+        ts[i], with dt = 1/N and its own draws of `noise` (always the full [draws,B,S,T]) or of the device RNG, so that
+        pc_sample(last_step=k) followed by pc_sample(x_init=<its result>, first_step=k) is bit for bit the full call.  With
+        last_step < N the result is the state x whatever denoise says; nfe counts the executed steps; snapshots lie in the
+        range, "all" means all of it, and of trace.gram only the rows of executed steps (and row N with last_step = N) are written."""
         mix_norm = self._f32(mix_norm)
         B, one, T = mix_norm.shape
         assert one == 1
@@ -262,13 +270,26 @@ class Engine:
                     raise _lib.DiffsepError(f"the other engine was created by the '{tail.kind}' build of the library, this one "
                                             f"by the '{self.kind}' build: create it with Engine(..., lib_kind='{self.kind}')")
                 ext.tail_engine, ext.tail_steps, ext.head_steps = tail._h, int(tail_steps), int(head_steps)
+        ranged = x_init is not None or first_step != 0 or last_step is not None
+        first, last = int(first_step), int(N if last_step is None else last_step)
+        if x_init is not None:
+            x_init = self._f32(x_init)
+            assert tuple(x_init.shape) == (B, self.S, T), "x_init must be [B,S,T]"
+        if ranged and (last_step == 0 or not 0 <= first < last <= N):  # (0 means N to the library: an empty range is refused here)
+            raise _lib.DiffsepError(f"pc_sample: the step range must satisfy 0 <= first_step < last_step <= N, got [{first}, {last}) of {N}")
+        tail_args = (_ptr(x_init), first, last, _stream_ptr(self.device)) if ranged else (_stream_ptr(self.device),)
         if snapshots is None and target is None:
             with torch.cuda.device(self.device):
+                if ranged:
+                    call(self._L, "diffsep_pc_sample_from", self._h, C.byref(sc), C.byref(sm), C.byref(ext) if ext is not None else None,
+                         _ptr(mix_norm), _ptr(out), B, T, _ptr(noise), seed, ts.ctypes.data_as(C.c_void_p) if ts is not None else None,
+                         C.byref(nfe), 0, None, None, None, None, None, *tail_args)
+                    return out, int(nfe.value)
                 call(self._L, "diffsep_pc_sample_ex", self._h, C.byref(sc), C.byref(sm), C.byref(ext) if ext is not None else None,
                      _ptr(mix_norm), _ptr(out), B, T, _ptr(noise), seed, ts.ctypes.data_as(C.c_void_p) if ts is not None else None,
                      C.byref(nfe), _stream_ptr(self.device))
             return out, int(nfe.value)
-        steps = list(range(N)) if isinstance(snapshots, str) and snapshots == "all" else [int(s) for s in (snapshots or [])]
+        steps = list(range(first, last)) if isinstance(snapshots, str) and snapshots == "all" else [int(s) for s in (snapshots or [])]
         n_snap = len(steps)
         dev = mix_norm.device
         snap_x = torch.empty((n_snap, B, self.S, T), dtype=torch.float32, device=dev)
@@ -278,12 +299,15 @@ class Engine:
             target = self._f32(target)
             assert tuple(target.shape) == (B, self.S, T), "target must be [B,S,T]"
             gram = torch.empty((N + 1, B, 3, self.S, self.S), dtype=torch.float64, device=dev)
+            if first > 0 or last < N:  # (the rows of steps that do not run are not written: NaN marks them)
+                gram.fill_(float("nan"))
         sa_ = np.ascontiguousarray(steps, dtype=np.int32)
         with torch.cuda.device(self.device):
-            call(self._L, "diffsep_pc_sample_trace", self._h, C.byref(sc), C.byref(sm), C.byref(ext) if ext is not None else None,
+            call(self._L, "diffsep_pc_sample_from" if ranged else "diffsep_pc_sample_trace", self._h, C.byref(sc), C.byref(sm),
+                 C.byref(ext) if ext is not None else None,
                  _ptr(mix_norm), _ptr(out), B, T, _ptr(noise), seed, ts.ctypes.data_as(C.c_void_p) if ts is not None else None,
                  C.byref(nfe), n_snap, sa_.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(snap_x) if n_snap else None,
-                 _ptr(snap_xm), _ptr(target), _ptr(gram), _stream_ptr(self.device))
+                 _ptr(snap_xm), _ptr(target), _ptr(gram), *tail_args)
         return out, int(nfe.value), SamplerTrace(steps, snap_x, snap_xm, gram)
 
     def _ode_setup(self, mix_norm, sde, method, rtol, atol, eps, first_step, max_step, max_nfe, denoise, N, x_init, noise):

@@ -890,6 +890,53 @@ def sde_perturb(sde, x0, mix, t, z=None, sigma_mix=None, beta=None, redefine_z=F
     return x_t, z_out
 
 
+def batch_seeds(seed, B):
+    """the per-utterance seeds the sampler derives from one seed on a mixed-length batch (diffsep_sampler_ext): seed + b * 0x9E3779B97F4A7C15"""
+    return [(int(seed) + 0x9E3779B97F4A7C15 * b) % (1 << 64) for b in range(B)]
+
+
+def warm_start(sde, est, mix, mix_norm, mean, std, t, *, scale="ls", mean_from="mix", noise=None, seed=0, seeds=None, lengths=None):
+    """diffsep_warm_start — from another separator's estimates est [B,S,T] to the state the sampler starts from at the
+    per-utterance times t [B] (Engine.pc_sample(x_init=, first_step=)): (x_init [B,S,T], gains [B,S] float64, fallback [B] int32).
+    sde: the dict of an SDE's engine_config(), or the SDE object.  mix [B,1,T] raw, mix_norm / mean / std as normalize_batch
+    returns them (per utterance over its own samples on a zero-padded batch, mix_norm zero beyond lengths).
+    scale "ls": per utterance the gains g minimising || mix - sum_s g_s est_s ||^2 (an SI-SDR-trained separator's output has
+    arbitrary scale and sign) — all 1 with fallback[b] = 1 where the estimates are silent or proportional; "none": gains of 1.
+    x0 = (g est - mean) / std; x_init = m + exp(-lambda t)(x0 - m) + L(t) z with m = mix_norm / S (mean_from "mix") or the
+    source average of x0 (mean_from "estimate": the reference's marginal_prob exactly).  z = noise [B,S,T], or generated in the
+    kernel: draw 0 of randn_batch(seeds, lengths) with seeds (or with lengths: the seeds the sampler derives from seed), else draw
+    0 of randn(B S T, seed) — the draw the sampler's prior would have used.  Asynchronous on the current stream, no readback."""
+    sde = sde if isinstance(sde, dict) else sde.engine_config()
+    est, mix, mix_norm, noise = (_f32c(v) for v in (est, mix, mix_norm, noise))
+    B, S, T = est.shape
+    dev = est.device
+    mean, std, t = (_f32c(v).reshape(-1) for v in (mean, std, t))
+    assert mean.numel() == B and std.numel() == B and t.numel() == B, "mean, std and t hold one value per utterance"
+    for name, v in (("mix", mix), ("mix_norm", mix_norm)):
+        assert v is None or tuple(v.shape) == (B, 1, T), f"{name} must be [B,1,T]"
+    assert noise is None or tuple(noise.shape) == (B, S, T), "noise must be [B,S,T]"
+    if scale not in _lib.WARM_SCALES or mean_from not in _lib.WARM_MEANS:
+        raise ValueError(f"warm_start: scale is one of {list(_lib.WARM_SCALES)}, mean_from one of {list(_lib.WARM_MEANS)}")
+    ln = None if lengths is None else _dev_i32(lengths, dev)
+    if noise is None and seeds is None and lengths is not None:
+        seeds = batch_seeds(seed, B)
+    sd = None
+    if seeds is not None and noise is None:
+        h = torch.as_tensor(np.ascontiguousarray(np.asarray([int(s) % (1 << 64) for s in seeds], dtype=np.uint64)).view(np.int64))
+        assert h.numel() == B, "seeds must be [B]"
+        sd = h.pin_memory().to(dev, non_blocking=True)
+    smix = sde_sigma_mix(mix_norm, sde.get("avg_len", 510)) if sde.get("kind", _lib.SDE_MIX) == _lib.SDE_PRIORMIX else None
+    x = torch.empty_like(est)
+    gains = torch.empty((B, S), dtype=torch.float64, device=dev)
+    fallback = torch.empty((B,), dtype=torch.int32, device=dev)
+    nbytes = _workspace_bytes(lib().diffsep_warm_start_workspace_bytes, B, S) if scale == "ls" else 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    call(lib(), "diffsep_warm_start", C.byref(sde_config(sde)), _ptr(est), _ptr(mix), _ptr(mix_norm), _ptr(mean), _ptr(std), _ptr(t),
+         _ptr(noise), _ptr(smix), _ptr(ln), _ptr(sd), int(seed) % (1 << 64), _lib.WARM_SCALES[scale], _lib.WARM_MEANS[mean_from],
+         _ptr(x), _ptr(gains), _ptr(fallback), B, S, T, _ptr(ws), nbytes, _stream_ptr())
+    return x, gains, fallback
+
+
 def score_loss_workspace_bytes(B, S, T):
     """bytes of workspace the loss entries need (host arithmetic; raises for a shape they refuse)"""
     return _workspace_bytes(lib().diffsep_score_loss_workspace_bytes, B, S, T)

@@ -273,7 +273,8 @@ class DiffSepModel:
         The tracing extensions snapshots= / target= of sdes.get_pc_sampler pass through: the returned sampler's .trace is the
         trace of its last call (with minibatch=: the minibatches' traces joined along the batch, and the third result the
         joined [(xt, xt_mean)]); an overflow re-run repeats the request with the same trace arguments and its trace replaces
-        the first one."""
+        the first one.  So do x_init= / first_step= / last_step= (both ends of the sampler open): with
+        minibatch= x_init is split along the batch, and an overflow re-run repeats the request with the same x_init."""
         sde = self.sde.copy()
         sde.N = self.sde.N if N is None else N
         kwargs = {"eps": self.t_eps, **kwargs}
@@ -309,7 +310,7 @@ class DiffSepModel:
         seed0 = kwargs.pop("seed", None)
         if kwargs.get("lengths") is not None or kwargs.get("seeds") is not None:
             raise ValueError("lengths= / seeds= describe one engine batch; they cannot be combined with minibatch=")
-        target = kwargs.get("target")
+        target, x_init = kwargs.get("target"), kwargs.get("x_init")
 
         def batched_sampling_fn():
             samples, ns, inter, traces = [], [], [], []
@@ -322,6 +323,8 @@ class DiffSepModel:
                     kw["seed"] = (int(seed0) + 0x9E3779B97F4A7C15 * i) % (1 << 64)
                 if target is not None:
                     kw["target"] = target[part]
+                if x_init is not None:
+                    kw["x_init"] = x_init[part]
                 sampler = make(y[part], kw)
                 sample, n, *other = sampler()
                 samples.append(sample)
@@ -345,6 +348,51 @@ class DiffSepModel:
         skw.update(kwargs)
         est, *others = self.get_pc_sampler("reverse_diffusion", "ald2", mix_n, **skw)()
         return self.denormalize_batch(est, mean, std)
+
+    def refine(self, mix, est, t_start=0.5, lengths=None, seeds=None, scale="ls", mean_from="mix", check_finite=True,
+               **sampler_kwargs):
+        """Refine another separator's estimates (extension): est [B,S,T] is diffused forward to the step
+        time ts[first] nearest below t_start with the SDE's own marginal (ops.warm_start: least-squares gains per file with
+        scale "ls", the source average taken from the mixture with mean_from "mix"), and only the reverse steps [first, N) of the
+        fused sampler run — (N - first) (corrector_steps + 1) network evaluations instead of N (corrector_steps + 1).  Per file
+        it does what separate.separate_on_device does: mix [B,1,T] (a right-zero-padded batch of files of `lengths`) is
+        normalised over each file's own samples, the result rescaled per file (separate.py:73-78).  seeds [B]: per-file device
+        RNG seeds (default: one draw of torch's generator each); file b's perturbation is draw 0 of its seed — the prior draw of
+        a full run — and its steps take the draws the full run's would.  Returns (sep [B,S,T], info): first_step, t (the start
+        time), nfe, gains [B,S] float64 and fallback [B] int32 (1: the fit of that file met silent or proportional estimates
+        and used gains of 1) — both left on the device, nothing is read back here.  check_finite: as in get_pc_sampler."""
+        from .separate import scale_output
+        if mix.dim() == 2:
+            mix = mix[None]
+        mix, est = mix.float().contiguous(), est.float().contiguous()
+        B, _, T = mix.shape
+        if tuple(est.shape) != (B, est.shape[1], T) or est.device != mix.device:
+            raise ValueError("refine: est must be [B,S,T] on the mixture's device, with the mixture's B and T")
+        lens = [T] * B if lengths is None else [int(L) for L in lengths]
+        skw = dict(sampler_kwargs)
+        N = self.sde.N if skw.get("N") is None else int(skw["N"])
+        ts = sdes.sampler_timesteps(N, skw.get("eps", self.t_eps), skw.get("schedule"), T=self.sde.T)
+        first = sdes.first_step_for(t_start, ts)
+        t0 = float(ts[first])
+        mix_n = torch.zeros_like(mix)
+        mean, std = (torch.empty(B, dtype=torch.float32, device=mix.device) for _ in range(2))
+        for b, L in enumerate(lens):  # every file over ITS samples (pl_model.py:81-88), the tail left at zero
+            (m_b, _), mu, sd = self.normalize_batch((mix[b:b + 1, :, :L], None))
+            mix_n[b, :, :L], mean[b], std[b] = m_b[0], mu.reshape(()), sd.reshape(())
+        if seeds is None:
+            seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in range(B)]
+        seeds = [int(s) for s in seeds]
+        t = torch.full((B,), t0, dtype=torch.float32, device=mix.device)
+        x_init, gains, fallback = ops.warm_start(self.sde, est, mix, mix_n, mean, std, t, scale=scale, mean_from=mean_from,
+                                                 seeds=seeds, lengths=lens)
+        sampler = self.get_pc_sampler("reverse_diffusion", "ald2", mix_n, check_finite=check_finite,
+                                      **{**skw, "lengths": lens, "seeds": seeds, "x_init": x_init, "first_step": first})
+        with torch.no_grad():
+            sep, nfe, *_ = sampler()
+        out = torch.zeros_like(sep)
+        for b, L in enumerate(lens):
+            out[b, :, :L] = scale_output(mix[b:b + 1, :, :L], sep[b:b + 1, :, :L])[0]
+        return out, {"first_step": first, "t": t0, "nfe": nfe, "gains": gains, "fallback": fallback}
 
     def separate_long(self, mix, window, overlap, batch=16, seed=None, **sampler_kwargs):
         """A recording of any length as windows of the shape the engine is fast at (extension): mix

@@ -18,7 +18,7 @@ from .predictors import Predictor, PredictorRegistry, ReverseDiffusionPredictor
 from .sdes import MixSDE, PriorMixSDE, SDERegistry
 
 __all__ = ["PredictorRegistry", "CorrectorRegistry", "SDERegistry", "Predictor", "Corrector", "MixSDE", "PriorMixSDE",
-           "get_pc_sampler", "get_pc_scheduled_sampler", "get_ode_sampler"]
+           "get_pc_sampler", "get_pc_scheduled_sampler", "get_ode_sampler", "sampler_timesteps", "first_step_for"]
 
 
 def _timesteps(sde, eps, schedule, device):
@@ -33,6 +33,31 @@ def _timesteps(sde, eps, schedule, device):
     if schedule == "revlog":
         return torch.logspace(math.log10(eps), math.log10(sde.T), sde.N + 1, base=10, device=device).flip(dims=(0,))
     raise NotImplementedError(f"Schedule '{schedule}' does not exist")
+
+
+def sampler_timesteps(N, eps=3e-2, schedule=None, T=1.0):
+    """The float32 times ts[0 .. N) at which the N reverse steps of a sampler run (host numpy): linspace(T, eps, N), or the first N
+    points of a schedule's N + 1."""
+    class _G:
+        pass
+    g = _G()
+    g.T, g.N = T, int(N)
+    return _timesteps(g, eps, schedule, "cpu").to(torch.float32).numpy()[:int(N)].copy()
+
+
+def first_step_for(t_start, timesteps):
+    """The reverse step a warm start at diffusion time t_start begins with: the smallest i with timesteps[i] <= t_start, on the
+    float32 grid the sampler uses (timesteps: the descending step times, e.g. sampler_timesteps(N, eps, schedule)); the call then
+    starts AT timesteps[i], never above t_start.  t_start >= T gives 0 (the whole run); t_start below the last step time raises
+    ValueError.  Pure host code."""
+    import numpy as np
+    ts = np.asarray(timesteps.detach().cpu().numpy() if hasattr(timesteps, "detach") else timesteps, dtype=np.float32).reshape(-1)
+    if ts.size == 0:
+        raise ValueError("first_step_for: an empty grid")
+    t = float(t_start)
+    if not t >= float(ts[-1]):
+        raise ValueError(f"first_step_for: t_start = {t_start} lies below the last step time {float(ts[-1])}: no step is left to run")
+    return int(np.nonzero(ts.astype(np.float64) <= t)[0][0])
 
 
 def _engine_of(score_fn):
@@ -57,7 +82,8 @@ class _HybridScore:
 
 
 def _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, denoise, eps, snr, corrector_steps,
-                  probability_flow, intermediate, schedule, seed=None, lengths=None, seeds=None, snapshots=None, target=None):
+                  probability_flow, intermediate, schedule, seed=None, lengths=None, seeds=None, snapshots=None, target=None,
+                  x_init=None, first_step=0, last_step=None):
     predictor = PredictorRegistry.get_by_name(predictor_name)(sde, score_fn, probability_flow=probability_flow)
     corrector = CorrectorRegistry.get_by_name(corrector_name)(sde, score_fn, snr=snr, n_steps=corrector_steps)
     eng = _engine_of(score_fn)
@@ -67,6 +93,12 @@ def _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, d
              and not (corrector_name == "ald" and type(sde) is not MixSDE))
 
     traced = snapshots is not None or target is not None
+    # both ends open, on either path: the steps [first, last) of the N-point grid, from x_init
+    first, last = int(first_step), int(sde.N if last_step is None else last_step)
+    if not 0 <= first < last <= sde.N:
+        raise ValueError(f"the step range must satisfy 0 <= first_step < last_step <= N, got [{first}, {last}) of {sde.N}")
+    if first > 0 and x_init is None:
+        raise ValueError("first_step > 0 needs the state to start from (x_init=)")
     if not fused and (seed is not None or lengths is not None or seeds is not None or traced):
         # the step-by-step loop draws from torch's global generator like the reference (torch.manual_seed governs it),
         # has no notion of a zero-padded batch, and hands its states out itself (intermediate=True)
@@ -85,7 +117,7 @@ def _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, d
 
     def pc_sampler():
         with torch.no_grad():
-            ns = sde.N * (corrector.n_steps + 1)
+            ns = (last - first) * (corrector.n_steps + 1)
             if fused:
                 # torch.manual_seed() governs reproducibility; seed=... (an extension) fixes the device RNG seed of
                 # this sampler explicitly, e.g. when several samplers are driven from different threads
@@ -96,17 +128,21 @@ def _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, d
                                           eps=eps, denoise=denoise, predictor=predictor_name, corrector=corrector_name,
                                           seed=s_, timesteps=ts, lengths=lengths, seeds=seeds, tail=tail,
                                           head_steps=getattr(score_fn, "head_steps", 0) if tail is not None else 0,
-                                          snapshots=snapshots, target=target)
+                                          snapshots=snapshots, target=target, x_init=x_init, first_step=first,
+                                          last_step=last if (last < sde.N or first > 0 or x_init is not None) else None)
                 if traced:  # the tap of the fused sampler: the requested steps in the shape of `intermediate`
                     pc_sampler.trace = tr[0]
                     return x, ns, tr[0].intermediates()
                 return x, ns
             im = []
-            xt = sde.prior_sampling((true_mean if true_mean is not None else y).shape,
-                                    true_mean if true_mean is not None else y)
+            if x_init is not None:  # (no draw for the prior)
+                xt = x_init
+            else:
+                xt = sde.prior_sampling((true_mean if true_mean is not None else y).shape,
+                                        true_mean if true_mean is not None else y)
             ts = _timesteps(sde, eps, schedule, y.device)
             xt_mean = xt
-            for i in range(sde.N):
+            for i in range(first, last):
                 if hybrid is not None:
                     hybrid.head = i < hybrid.head_steps
                 vec_t = torch.ones(y.shape[0], device=y.device) * ts[i]
@@ -114,7 +150,7 @@ def _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, d
                 if intermediate:
                     im.append((xt, xt_mean))
                 xt, xt_mean = predictor.update_fn(xt, vec_t, y)
-            res = xt_mean if denoise else xt
+            res = xt_mean if (denoise and last == sde.N) else xt  # (a run that stops early hands out the state itself)
             return (res, ns, im) if intermediate else (res, ns)
 
     pc_sampler.trace = None
@@ -127,11 +163,16 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean=N
     zero-padded batch of utterances of different lengths lengths=[B] (+ seeds=[B], per-utterance RNG seeds); snapshots=
     (a strictly ascending list of reverse steps, or "all") and / or target= ([B,S,T], zero beyond each length) trace the fused
     sampler (Engine.pc_sample): it then returns (x, ns, im), im = [(xt, xt_mean)] of the requested steps as intermediate=True
-    would list them, and pc_sampler.trace (an engine.SamplerTrace) holds the steps and the Gram rows against the target."""
+    would list them, and pc_sampler.trace (an engine.SamplerTrace) holds the steps and the Gram rows against the target.
+    On BOTH paths (the fused call and the step-by-step loop, so a user-written predictor or corrector too): x_init= ([B,S,T], the
+    state to start from: no prior sample is drawn), first_step= / last_step= (only the reverse steps [first_step, last_step) of
+    the N-point grid run, each at its own time and with dt = 1/N; a run that stops before N returns the state x; ns counts the
+    executed steps).  first_step_for(t_start, sampler_timesteps(N, eps)) turns a diffusion time into a step."""
     return _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, denoise, eps, snr,
                          corrector_steps, probability_flow, intermediate, None, seed=kwargs.get("seed"),
                          lengths=kwargs.get("lengths"), seeds=kwargs.get("seeds"), snapshots=kwargs.get("snapshots"),
-                         target=kwargs.get("target"))
+                         target=kwargs.get("target"), x_init=kwargs.get("x_init"), first_step=kwargs.get("first_step", 0),
+                         last_step=kwargs.get("last_step"))
 
 
 def get_pc_scheduled_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=True, true_mean=None, eps=3e-2,
@@ -141,7 +182,8 @@ def get_pc_scheduled_sampler(predictor_name, corrector_name, sde, score_fn, y, d
     return _make_sampler(predictor_name, corrector_name, sde, score_fn, y, true_mean, denoise, eps, snr,
                          corrector_steps, probability_flow, intermediate, schedule, seed=kwargs.get("seed"),
                          lengths=kwargs.get("lengths"), seeds=kwargs.get("seeds"), snapshots=kwargs.get("snapshots"),
-                         target=kwargs.get("target"))
+                         target=kwargs.get("target"), x_init=kwargs.get("x_init"), first_step=kwargs.get("first_step", 0),
+                         last_step=kwargs.get("last_step"))
 
 
 _ODE_KWARGS = ("first_step", "max_step", "max_nfe", "seed", "noise", "per_utterance", "lengths", "seeds")

@@ -34,6 +34,13 @@ with `all` the aligned draws next to the mean as <stem>_draw<k>.wav — their fl
 sample wherever nothing is converted on the way out (with --resample file the mean and every draw are converted back
 separately, and the identity holds only to that conversion's rounding).  The overflow net looks at the mean of the call's draws,
 whatever is written: one non-finite sample in any draw repeats the call.  --draws 1 is the ordinary run.  Not with --chunk or --sampler ode in this version.
+--init-dir DIR --t-start TAU [--init-scale {ls,none}] [--init-mean {mix,estimate}]: refine another separator's estimates
+(DiffSepModel.refine, ops.warm_start).  For input_dir/name.wav the estimates are DIR/s{k}/name.wav — the
+tree this tool writes.  They are scaled against the mixture (ls), normalised as the mixture is, diffused forward to the first
+step time at or below TAU with the SDE's own marginal, and only the reverse steps from there run: TAU = 0.5 at -N 30 is half the
+network evaluations.  The run prints the executed steps, the evaluations per file and the files whose gain fit fell back to 1.
+A missing estimate, one whose length or rate differs from its mixture's, --t-start without --init-dir (or the reverse) and a
+combination with --chunk, --draws, --sampler ode or --resample are refused by name before any engine is created.
 """
 import argparse
 from pathlib import Path
@@ -372,6 +379,115 @@ def separate_with_draws(args, files, rates, seeds, models, streams, kw):
     print(f"separated {len(files)} files into {args.output_dir} ({K} draws each, {args.draws_out})")
 
 
+def add_init_arguments(ap):
+    ap.add_argument("--init-dir", type=Path, default=None, metavar="DIR",
+                    help="refine another separator's estimates: for input_dir/name.wav read DIR/s{k}/name.wav, k = 0 .. S - 1 (the "
+                         "tree this tool writes, so one run's output can feed the next), diffuse them forward to --t-start and run "
+                         "only the reverse steps from there (DiffSepModel.refine).  Works with --batch, --streams, --seed, -N, "
+                         "--schedule and the precision flags; NOT with --chunk, --draws, --sampler ode or --resample in this version")
+    ap.add_argument("--t-start", type=float, default=None, metavar="TAU",
+                    help="with --init-dir: the diffusion time in (eps, 1] to start from; the run begins at the first step time at "
+                         "or below it (0.5 with -N 30: half the network evaluations)")
+    ap.add_argument("--init-scale", default=None, choices=["ls", "none"],
+                    help="with --init-dir: ls (default) fits one gain per estimate against the mixture first (estimates of "
+                         "arbitrary scale and sign); none takes them as they are")
+    ap.add_argument("--init-mean", default=None, choices=["mix", "estimate"],
+                    help="with --init-dir: the source average of the perturbed state comes from the mixture (default: the network "
+                         "was trained on sources that sum to it) or from the estimates (the reference's marginal_prob exactly)")
+
+
+def check_init_arguments(args, files):
+    """SystemExit, naming the flag or the file, for an --init-dir request this version does not run — before any engine exists;
+    -> the number of s{k} folders found (None without --init-dir).  args.init_scale / init_mean get their defaults."""
+    if args.init_dir is None:
+        for flag, v in (("--t-start", args.t_start), ("--init-scale", args.init_scale), ("--init-mean", args.init_mean)):
+            if v is not None:
+                raise SystemExit(f"{flag} goes with --init-dir")
+        return None
+    if args.t_start is None:
+        raise SystemExit("--init-dir needs --t-start: the diffusion time the refinement starts from")
+    if args.chunk is not None:
+        raise SystemExit("--init-dir with --chunk is not supported in this version: the estimates would have to be cut with the windows")
+    if args.draws is not None:
+        raise SystemExit("--init-dir with --draws is not supported in this version")
+    if args.sampler == "ode":
+        raise SystemExit("--init-dir with --sampler ode is not supported in this version: the ODE sampler has no start time")
+    if args.resample is not None:
+        raise SystemExit("--init-dir with --resample is not supported in this version: the estimates would have to be converted too")
+    if not 0.0 < args.t_start:
+        raise SystemExit(f"--t-start {args.t_start}: a diffusion time in (eps, 1] is needed")
+    S = 0
+    while (args.init_dir / f"s{S}").is_dir():
+        S += 1
+    for f in files:
+        sr, n = wavio.info(f)
+        for k in range(max(S, 1)):
+            p = args.init_dir / f"s{k}" / f.name
+            if not p.is_file():
+                raise SystemExit(f"--init-dir: missing estimate file {p} (for {f})")
+            sr_e, n_e = wavio.info(p)
+            if sr_e != sr:
+                raise SystemExit(f"--init-dir: {p} is at {sr_e} Hz, its mixture {f} at {sr} Hz")
+            if n_e != n:
+                raise SystemExit(f"--init-dir: {p} has {n_e} samples, its mixture {f} has {n}")
+    args.init_scale, args.init_mean = args.init_scale or "ls", args.init_mean or "mix"
+    return S
+
+
+def separate_refined(args, files, rates, seeds, models, streams, kw, S):
+    """--init-dir: the ring of the ordinary run with DiffSepModel.refine as the engine call; one line at the end with the executed
+    steps, the network evaluations and the files whose gain fit fell back"""
+    from . import sdes
+    lengths = rates.lengths
+    eng = models[0].score_model.engine()
+    if S != eng.S:
+        raise SystemExit(f"--init-dir: {S} source folders s0 .. s{S - 1} in {args.init_dir}, the model separates {eng.S} sources")
+    N = kw["N"] if kw.get("N") is not None else models[0].sde.N
+    try:
+        first = sdes.first_step_for(args.t_start, sdes.sampler_timesteps(N, models[0].t_eps, kw.get("schedule"), T=models[0].sde.T))
+    except ValueError as e:
+        raise SystemExit(f"--t-start {args.t_start}: {e}")
+    if seeds is None:  # one draw of torch's generator per file, as a file without --seed gets one per engine call
+        seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in files]
+    batches = inflight.plan_batches(range(len(files)), lengths, eng.padded_frames, max(1, args.batch))
+    inflight.reserve_largest(models, batches, lengths)
+    seen = {"nfe": None, "fell_back": []}
+
+    def run(model, mix_d, est_d, lens, sds):
+        sep, info = model.refine(mix_d, est_d, t_start=args.t_start, lengths=lens, seeds=sds, scale=args.init_scale,
+                                 mean_from=args.init_mean, check_finite=False, **kw)
+        return sep, info
+
+    def launch(w, j, group):
+        parts = rates.rows(group, [rates.load(i) for i in group], args.device)
+        to = eng.bucket_length(eng.padded_frames(max(lengths[i] for i in group)))
+        mix_d, lens = padded_on_device(parts, to, args.device)
+        est = torch.zeros((len(group), S, int(to)), dtype=torch.float32)
+        for b, i in enumerate(group):
+            for k in range(S):
+                est[b, k, :lens[b]] = wavio.load(args.init_dir / f"s{k}" / files[i].name)[0][0]
+        est_d = inflight.upload(est, args.device)
+        sds = [seeds[i] for i in group]
+        return group, lens, run(models[w], mix_d, est_d, lens, sds), mix_d, est_d, sds
+
+    def collect(w, item):
+        group, lens, result, mix_d, est_d, sds = item
+        sep, info = inflight.finite_or_rerun(models[w], streams[w], result, lambda fb: run(fb, mix_d, est_d, lens, sds),
+                                             what=str([files[i].name for i in group]))
+        with torch.cuda.stream(streams[w]):
+            outs = [(out.cpu(), sr) for out, sr in rates.restore(group, [sep[b, :, :lens[b]] for b in range(len(group))])]
+            fell = info["fallback"].cpu().tolist()
+        seen["nfe"] = info["nfe"]
+        seen["fell_back"] += [files[i].name for b, i in enumerate(group) if fell[b]]
+        for i, (out, sr) in zip(group, outs):
+            write_sources(args.output_dir, files[i].stem, out, sr)
+
+    inflight.Ring(streams, launch, collect).run(batches)
+    fb = f"; gain fit fell back to 1 for {sorted(seen['fell_back'])}" if seen["fell_back"] else ""
+    print(f"refined {len(files)} files from {args.init_dir} into {args.output_dir}: steps [{first}, {N}) of {N} from t = {args.t_start:g}, "
+          f"NFE {seen['nfe']} per file{fb}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Separate all the wav files in a specified folder")
     ap.add_argument("input_dir", type=Path)
@@ -407,8 +523,10 @@ def main(argv=None):
                          "write the sources back at the file's rate, cropped to its length (file), or at the model's rate (model); "
                          "default: such a file only draws a warning and its samples go to the model as they are")
     add_draws_arguments(ap)
+    add_init_arguments(ap)
     args = ap.parse_args(argv)
     check_draws_arguments(args, chunk=args.chunk is not None)
+    init_sources = check_init_arguments(args, sorted(args.input_dir.glob("*.wav")))
     if args.chunk is None and args.overlap is not None:
         raise SystemExit("--overlap goes with --chunk")
     if args.chunk is not None and args.sampler == "ode":
@@ -460,6 +578,8 @@ def main(argv=None):
         return
     if args.chunk is not None:
         return separate_chunked(args, files, rates, seeds, models, streams, kw)
+    if args.init_dir is not None:
+        return separate_refined(args, files, rates, seeds, models, streams, kw, init_sources)
     if args.draws is not None and (args.draws > 1 or args.draws_out != "mean"):  # (--draws 1 = one draw: the ordinary run)
         return separate_with_draws(args, files, rates, seeds, models, streams, kw)
     eng = model.score_model.engine()

@@ -215,6 +215,32 @@ int32_t diffsep_pc_sample_trace(diffsep_engine* e, const diffsep_sde_config* sde
                                 int32_t n_snap, const int32_t* snap_steps_host, float* snap_x, float* snap_xm,
                                 const float* target, double* gram, void* stream);
 
+/* diffsep_pc_sample_trace with both ends of the sampler open: a state to start from instead of the prior sample, and a range
+ * of the N reverse steps.  The reference starts only at t = T from prior_sampling (sdes/__init__.py:166-188); what it offers
+ * for an intermediate start is SDE.marginal_prob (sdes/sdes.py:322-324, PriorMixSDE :515-532), as its training uses it in
+ * sample_prior (pl_model.py:179-247): diffsep_warm_start below builds x_init from it.  This is the most general sampler entry;
+ * the three above forward to it with x_init = NULL, first_step = 0, last_step = 0 and enqueue exactly what they always did.
+ * All steps are ABSOLUTE indices of the N-point grid:
+ *   last_step == 0 means N; the steps i in [first_step, last_step) run, step i at time ts[i] of the same grid (linspace(1, eps, N)
+ *   or timesteps_host) with dt = 1/N (quirk Q1) and with the draws 1 + i (c + p) ... 1 + (i + 1)(c + p) - 1 of `noise` / of the
+ *   device RNG (c = corrector steps, 0 for corrector none; p = 1 unless predictor none; draw 0 is the prior's), so that a run
+ *   over [0, k) followed by a run over [k, N) from its result is bit for bit the run over [0, N);
+ *   ext->head_steps / tail_steps keep meaning absolute steps: a range that holds none of them never touches ext->tail_engine;
+ *   x_init [B,S,T] device f32, or NULL: copied into the state in place of the prior sample (draw 0 is then not generated; with
+ *   ext->lengths_host its tail is zeroed like the mixture's).  first_step > 0 needs it;
+ *   out: with last_step < N the state x itself, whatever smp->denoise says (it can be resumed from); with last_step == N as above;
+ *   nfe_out = (last_step - first_step) (corrector steps + 1);
+ *   snap_steps_host must lie in [first_step, last_step); of gram [N+1][B][3][S][S] the rows first_step .. last_step - 1 are
+ *   written, and row N only when last_step == N; every other row is left as it was.
+ * Refused with an error text before anything is enqueued, `out` untouched: a range outside 0 <= first_step < last_step <= N,
+ * first_step > 0 with x_init == NULL, a snapshot step outside the range, and everything diffsep_pc_sample_trace refuses. */
+int32_t diffsep_pc_sample_from(diffsep_engine* e, const diffsep_sde_config* sde, const diffsep_sampler_config* smp,
+                               const diffsep_sampler_ext* ext, const float* mix_norm, float* out, int32_t B, int64_t T,
+                               const float* noise, uint64_t seed, const float* timesteps_host, int32_t* nfe_out,
+                               int32_t n_snap, const int32_t* snap_steps_host, float* snap_x, float* snap_xm,
+                               const float* target, double* gram, const float* x_init, int32_t first_step,
+                               int32_t last_step, void* stream);
+
 /* The probability-flow ODE sampler: sdes.get_ode_sampler(...)() (sdes/__init__.py:193-278), i.e.
  * scipy.integrate.solve_ivp(method = RK45 | RK23) on dx/dt = f(x,t) - 0.5 G(t)^2 score(x,t,mix) (RSDE.sde with
  * probability_flow, sdes/sdes.py:130-160) from t = 1 down to eps, the whole batch [B,S,T] as ONE system (one error
@@ -810,6 +836,41 @@ int64_t diffsep_ensemble_workspace_bytes(int32_t B, int32_t K, int32_t S);
 int32_t diffsep_ensemble(const float* draws, const float* anchor, const int32_t* lengths, int32_t B, int32_t K, int32_t S,
                          int64_t T, float* mean_out, float* std_out, float* pick_out, int32_t* perm_out, double* dist_out,
                          int32_t* medoid_out, double* gram_out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- warm start: from another separator's estimates to the x_init of diffsep_pc_sample_from at a chosen diffusion time.  The
+ * reference holds the pieces and no such call: normalize_batch((mix, tgt)) (pl_model.py:81-88) and the forward marginal
+ * SDE.marginal_prob (sdes/sdes.py:322-324: MixSDE._mean :286-294 and _std :315-320; PriorMixSDE._std :515-532), which its training
+ * draws from in DiffSepModel.sample_prior (pl_model.py:179-247).  Two launches, asynchronous on `stream`, nothing read back:
+ *   fit (scale = DIFFSEP_WARM_SCALE_LS): per utterance over its own n = lengths[b] samples, in float64 from the fp32 samples, the
+ *     Gram matrix of the estimates and their inner products with the RAW mixture; gains = argmin_g || mix - sum_s g_s est_s ||^2 by
+ *     Cholesky.  A pivot <= 2^-40 trace / S (a silent estimate, two proportional estimates) sets every gain of that utterance to 1
+ *     and fallback_out[b] = 1 (otherwise 0).  DIFFSEP_WARM_SCALE_NONE: no pass, gains exactly 1.
+ *   apply and perturb, one pass over [B,S,T]:
+ *     x0_i = (gain_i est_i - mean_b) / std_b;   m = mix_norm / S (DIFFSEP_WARM_MEAN_MIX) or mean_s x0 (DIFFSEP_WARM_MEAN_ESTIMATE:
+ *     marginal_prob exactly);   x_init_i = m + exp(-lambda t_b)(x0_i - m) + (a mean_s z + p (z_i - mean_s z)) [sigma_mix],
+ *     a = sqrt(ev1(t_b)), p = sqrt(ev2(t_b)).
+ *   est [B,S,T], mix [B,1,T] (raw; needed by the fit only), mix_norm [B,1,T] (needed by DIFFSEP_WARM_MEAN_MIX only), mean, std, t [B]
+ *   (device f32; mean / std as diffsep_normalize_batch returns them, one time per utterance), sigma_mix [B,T] for PriorMixSDE and
+ *   NULL for MixSDE.  z [B,S,T], or NULL: generated in the kernel, bit for bit draw 0 (stream id 0) of
+ *   diffsep_randn_batch(seeds, lengths) when seeds (device [B]) is given, of diffsep_randn(B S T values, seed) otherwise — the draw
+ *   the sampler's prior would have used, so that a warm-started sampler call consumes a subset of the full call's draws.
+ *   lengths (device int32 [B], nullable): samples at or beyond lengths[b] are never summed and x_init is exactly zero there.
+ *   x_init [B,S,T] f32, gains_out [B][S] float64, fallback_out [B] int32: all required.
+ * Sums in the fixed order of the library's float64 block reductions, no atomics: every output row of utterance b is bit for bit
+ * that of the call on it alone (B = 1, T = n), in any batch, at any padded width, on any stream.  S in 1..3, B in 1..65535,
+ * 1 <= T < 2^31.  Refusals (shape, a null required pointer, z together with seeds, sigma_mix against the SDE kind, a workspace
+ * below diffsep_warm_start_workspace_bytes(B, S) or not 8-byte aligned with scale = ls) come before the first device call and
+ * write nothing.  diffsep_warm_start_workspace_bytes: host arithmetic only; -1 and a message for a refused shape. */
+#define DIFFSEP_WARM_SCALE_NONE 0
+#define DIFFSEP_WARM_SCALE_LS 1
+#define DIFFSEP_WARM_MEAN_MIX 0
+#define DIFFSEP_WARM_MEAN_ESTIMATE 1
+int64_t diffsep_warm_start_workspace_bytes(int32_t B, int32_t S);
+int32_t diffsep_warm_start(const diffsep_sde_config* sde, const float* est, const float* mix, const float* mix_norm,
+                           const float* mean, const float* std, const float* t, const float* z, const float* sigma_mix,
+                           const int32_t* lengths, const uint64_t* seeds, uint64_t seed, int32_t scale, int32_t mean_from,
+                           float* x_init, double* gains_out, int32_t* fallback_out, int32_t B, int32_t S, int64_t T,
+                           void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- the denoising score-matching loss (forward values only): DiffSepModel.sample_prior (pl_model.py:179-247),
  * compute_score_loss (:411-424), compute_score_loss_init_hack_pit (:370-405), compute_score_loss_with_pit_allthetime
