@@ -312,6 +312,37 @@ extern "C" int32_t diffsep_attn_fused(const void* x, const int64_t* gn_acc, cons
 
 extern "C" int32_t diffsep_conv2d_chunk(int32_t ksize, int32_t dtype) { return ds_conv_chunk(ksize == 3 ? 9 : 1, dtype); }
 
+// The general one-tap launch of conv_mfma.hip as a unit: what attention_core and attn_block (engine.hip) assemble by hand for
+// Q K^T, P V and V^T.  Y[b, m, n] = ((sum_k A[b | shared, m, k] Bt[b | shared, n, k]) / div_b[b] + bias + res) * out_scale with
+// A [M][lda], Bt dense [N][K], res [B][M][ldr], Y [B][M][ldy]; bias along n (mode 0, [N]) or along m (mode 1, [M]).
+extern "C" int32_t diffsep_gemm_nt(const void* a, const void* bt, const float* bias, const float* div_b, const void* res, void* y,
+                                   int32_t B, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldr, int32_t ldy,
+                                   int32_t a_batched, int32_t bt_batched, int32_t bias_mode, float out_scale, int32_t dtype,
+                                   void* stream) {
+  DS_CHECK(a && bt && y, "gemm_nt: null pointer");
+  DS_CHECK(dtype == DS_F32 || dtype == DS_BF16 || dtype == DS_F32_SPLIT, "gemm_nt: bad dtype");
+  DS_CHECK(B >= 1 && M >= 1 && N >= 1 && K >= 8 && K % 8 == 0, "gemm_nt: bad shape (K a multiple of 8)");
+  DS_CHECK(bias_mode == 0 || bias_mode == 1, "gemm_nt: bias_mode is 0 (along n) or 1 (along m)");
+  const int n8 = rup8(N);
+  DS_CHECK(lda >= K && lda % 8 == 0, "gemm_nt: lda must be >= K and a multiple of 8");
+  DS_CHECK(ldy >= n8 && ldy % 8 == 0, "gemm_nt: ldy must be >= N rounded up to 8 and a multiple of 8");
+  DS_CHECK(!res || (ldr >= n8 && ldr % 8 == 0), "gemm_nt: ldr must be >= N rounded up to 8 and a multiple of 8");
+  ConvArgs c;
+  memset(&c, 0, sizeof(c));
+  c.opts = ds_default_opts();
+  conv_input(c, view(a, 1, M, K, lda));
+  if (!a_batched) c.x_bs = 0;
+  c.w = bt; c.w_bs = bt_batched ? (long)N * K : 0;
+  c.bias = bias; c.bias_mode = bias_mode; c.div_b = div_b;
+  if (res) conv_residual(c, view(res, 1, M, N, ldr));
+  c.out_scale = out_scale;
+  conv_output(c, view(y, 1, M, N, ldy));
+  c.B = B; c.Cout = N; c.taps = 1;
+  const DtypeSplit ds = split_dtype(dtype);
+  c.dtype = ds.dtype; c.split = ds.split;
+  return ds_launch_conv(c, (hipStream_t)stream);
+}
+
 extern "C" int32_t diffsep_attention(const void* q, const void* k, const void* vt, void* o, int32_t B, int32_t L,
                                      int32_t C, int32_t ld, int32_t dtype, void* workspace, int64_t workspace_bytes,
                                      void* stream) {

@@ -175,6 +175,7 @@ _SIGS = {
     "diffsep_conv2d_fused": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F,
                                   _I, _P, _I, _P, _P, _P, _P, _I, _P]),
     "diffsep_conv2d_chunk": (_I, [_I, _I]),
+    "diffsep_gemm_nt": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
     "diffsep_last_conv_kernel": (C.c_char_p, []),
     "diffsep_gn_finalize_acc": (_I, [_P, _I, _P, _I, _I, _L, _I, _F, _P, _P, _P, _P, _P]),
     "diffsep_gn_apply": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

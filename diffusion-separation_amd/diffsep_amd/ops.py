@@ -311,16 +311,54 @@ def last_conv_kernel(kind="bf16"):
     return lib(kind).diffsep_last_conv_kernel().decode()
 
 
-def attention(q, k, vt, split=False):
-    """split=True (fp32 tensors only): both GEMMs with bf16x3 products (DIFFSEP_F32_SPLIT)."""
+def gemm_nt(a, bt, N, B=None, bias=None, bias_mode=0, div_b=None, res=None, out_scale=1.0, out=None, split=False):
+    """The general one-tap launch of conv_mfma.hip (diffsep_gemm_nt): y[b, m, n] = ((sum_k a[b | shared, m, k] bt[b | shared, n, k])
+    / div_b[b] + bias + res[b, m, n]) * out_scale.  a [B,M,lda] or [M,lda] (shared by the batch), bt dense [B,N,K] or [N,K] (shared;
+    K <= lda), bias f32 [N] (bias_mode 0) or [M] (bias_mode 1), div_b f32 [B], res [B,M,ldr].  out=<tensor> [B,M,ldy]: the output
+    buffer (ldy >= N rounded up to 8: the launch writes columns [0, that) and nothing else); default zeros of that width.
+    B: the batch size when both operands are shared."""
+    a_b, bt_b = a.dim() == 3, bt.dim() == 3
+    if B is None:
+        B = a.shape[0] if a_b else (bt.shape[0] if bt_b else 1)
+    M, lda = a.shape[-2:]
+    K = bt.shape[-1]
+    if bt.shape[-2] != N or not (a.is_contiguous() and bt.is_contiguous()) or (a_b and a.shape[0] != B) or (bt_b and bt.shape[0] != B):
+        raise ValueError("gemm_nt: a [B,M,lda] | [M,lda] and bt [B,N,K] | [N,K] dense, with one batch size")
+    y = torch.zeros((B, M, (N + 7) // 8 * 8), dtype=a.dtype, device=a.device) if out is None else out
+    if tuple(y.shape[:2]) != (B, M) or not y.is_contiguous() or (res is not None and (tuple(res.shape[:2]) != (B, M) or not res.is_contiguous())):
+        raise ValueError("gemm_nt: out and res must be dense [B,M,ld] tensors")
+    if (bias is not None and bias.numel() != (M if bias_mode else N)) or (div_b is not None and div_b.numel() != B):
+        raise ValueError("gemm_nt: bias is [N] (bias_mode 0) or [M] (bias_mode 1), div_b [B]")
+    call(_L(a), "diffsep_gemm_nt", _ptr(a), _ptr(bt), _ptr(bias), _ptr(div_b), _ptr(res), _ptr(y), B, M, N, K, lda,
+         res.shape[-1] if res is not None else 0, y.shape[-1], int(a_b), int(bt_b), bias_mode, out_scale, _dts(a, split), _stream_ptr())
+    return y
+
+
+def attention_workspace_bytes(B, L, element_size):
+    """(bytes of one of the two regions of diffsep_attention's workspace — scores, then probabilities —, bytes of both)"""
+    one = (B * L * ((L + 7) // 8 * 8) * element_size + 255) // 256 * 256
+    return one, 2 * one
+
+
+def attention(q, k, vt, split=False, return_workspace=False, workspace=None):
+    """split=True (fp32 tensors only): both GEMMs with bf16x3 products (DIFFSEP_F32_SPLIT).  return_workspace=True additionally
+    returns the scores and the probabilities [B,L,Lp] (q's type) as views of the workspace; workspace=<uint8 tensor>: the caller's
+    buffer of at least attention_workspace_bytes(...)[1] bytes."""
     B, L, Cc = q.shape
     Lp = (L + 7) // 8 * 8
     assert vt.shape == (B, Cc, Lp)
     o = torch.empty_like(q)
-    ws = torch.empty(2 * (B * L * Lp * q.element_size() + 256), dtype=torch.uint8, device=q.device)
+    one, both = attention_workspace_bytes(B, L, q.element_size())
+    ws = torch.empty(both, dtype=torch.uint8, device=q.device) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < both or ws.data_ptr() % 16:
+        raise ValueError("attention: workspace must be a dense 16-byte aligned uint8 tensor of attention_workspace_bytes(...)[1] bytes")
     call(_L(q), "diffsep_attention", _ptr(q), _ptr(k), _ptr(vt), _ptr(o), B, L, Cc, Cc, _dts(q, split), _ptr(ws), ws.numel(),
          _stream_ptr())
-    return o
+    if not return_workspace:
+        return o
+    n = B * L * Lp * q.element_size()
+    scores, probs = (ws[i * one:i * one + n].view(q.dtype).view(B, L, Lp) for i in (0, 1))
+    return o, scores, probs
 
 
 def resblock_forward(params, x, temb, out_ch, up=False, down=False):

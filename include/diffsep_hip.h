@@ -461,6 +461,15 @@ int32_t diffsep_conv2d_fused(const void* x, const void* x2, int32_t C1, const fl
  * [Cin_pad / kc][k*k][Cout][kc] (the layout the engine keeps its weights in: one K stage of the kernel is then
  * contiguous in memory and is fetched in full 128-byte lines). */
 int32_t diffsep_conv2d_chunk(int32_t ksize, int32_t dtype);
+/* The general one-tap launch of csrc/conv_mfma.hip (batched NT GEMM), as the unfused attention path assembles it for Q K^T, P V
+ * and V^T:  Y[b, m, n] = ((sum_k A[b | shared, m, k] * Bt[b | shared, n, k]) / div_b[b] + bias + res[b, m, n]) * out_scale.
+ * a [B | 1][M][lda], bt dense [B | 1][N][K] (a_batched / bt_batched = 0: one matrix shared by the batch), res [B][M][ldr] or NULL,
+ * y [B][M][ldy]; bias fp32 [N] (bias_mode 0, along n) or [M] (bias_mode 1, along m) or NULL; div_b fp32 [B] or NULL.  K, lda, ldr,
+ * ldy multiples of 8, ldr / ldy >= N rounded up to 8.  Columns [N, N rounded up to 8) of y are written as zeros (res must hold
+ * zeros there), columns beyond are not touched.  dtype: DIFFSEP_F32, DIFFSEP_F32_SPLIT or DIFFSEP_BF16. */
+int32_t diffsep_gemm_nt(const void* a, const void* bt, const float* bias, const float* div_b, const void* res, void* y, int32_t B,
+                        int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldr, int32_t ldy, int32_t a_batched,
+                        int32_t bt_batched, int32_t bias_mode, float out_scale, int32_t dtype, void* stream);
 /* Name, with its template arguments, of the kernel instantiation that the calling thread's last convolution launch ran
  * (thread-local; "" before the first launch).  The fused attention kernel counts as one, from the unit entry point and from
  * the engine's block code alike: "attn_fused_kernel<LT>" with LT = 1, 2, 4, 8 tiles of 32 pixels.  So does every GroupNorm-apply /

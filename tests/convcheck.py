@@ -1,4 +1,5 @@
 """Two instruments for the 3x3 convolution kernels, both against a CPU reference of the same operation, and what each can see.
+(tests/gemmcheck.py carries both to the 1x1 / GEMM instantiations of conv_mfma.hip and the unfused attention chain, on these pieces.)
 
 1. EXACT INTEGERS (exact_case / check_exact): bit for bit, no tolerance.  x holds integers 0..3 (times 32 in a raw launch, through
    the affine 32 x + 32 otherwise), weights are -1 / 0 / +1 with exactly 32 non-zero (tap, cin) positions per output channel, every
@@ -146,13 +147,15 @@ class ExactCase:
     pass
 
 
-def exact_case(tag, B, H, W, C1, C2, CO, mode, res=False, skip=None, cin_real=None, big=False, out_scale=0.5, with_bb=True):
+def exact_case(tag, B, H, W, C1, C2, CO, mode, res=False, skip=None, cin_real=None, big=False, out_scale=0.5, with_bb=True, ksize=3):
     """mode "raw": x = 32 * ints, no table; "affine" / "silu": x = ints through scale 32, shift 32 (padding stays 0).
     Tensors are float32 on the CPU with integer values; ref [B,H,W,CO] is the value before storage.  out_scale = 1 and
-    with_bb=False (c.bb None): the first-layer and pyramid-head kernels, which take neither a scale nor a per-sample bias."""
-    assert mode in ("raw", "affine", "silu")
+    with_bb=False (c.bb None): the first-layer and pyramid-head kernels, which take neither a scale nor a per-sample bias.
+    ksize = 1 (tests/gemmcheck.py): min(32, real input channels) non-zero weights per output channel."""
+    assert mode in ("raw", "affine", "silu") and ksize in (1, 3)
     c = ExactCase()
     C = C1 + C2
+    kk = ksize * ksize
     big = big or B * H * W * CO * C * 9 > 1e9  # (float32 on the CPU is exact on these numbers too: tests/test_convcheck_cpu.py)
     cr = cin_real or C
     xi = _ints(tag + ".x", (B, H, W, C), 0, 3)
@@ -162,8 +165,8 @@ def exact_case(tag, B, H, W, C1, C2, CO, mode, res=False, skip=None, cin_real=No
     c.a, c.b = x[..., :C1].contiguous(), (x[..., C1:].contiguous() if C2 else None)
     c.sc, c.sh = torch.full((B, C), 32.0), torch.full((B, C), 32.0)
     h = x if mode == "raw" else xi * 32.0 + 32.0
-    w = torch.zeros(CO, C, 3, 3)
-    w[:, :cr] = sparse_signs(tag + ".w", CO, 9 * cr, 32).reshape(CO, 3, 3, cr).permute(0, 3, 1, 2)
+    w = torch.zeros(CO, C, ksize, ksize)
+    w[:, :cr] = sparse_signs(tag + ".w", CO, kk * cr, min(32, kk * cr)).reshape(CO, ksize, ksize, cr).permute(0, 3, 1, 2)
     c.w = w
     c.bias, c.bb = _ints(tag + ".bias", (CO,), -2, 2) * 32.0, _ints(tag + ".bb", (B, CO), -2, 2) * 32.0
     ref = _conv(h, w, big) + c.bias.double()
@@ -331,7 +334,7 @@ class ConvCheck:
         else:
             A_skip = 0.0
         self.ref = ref * out_scale
-        K = (9 * C + n_skip + 6) * (2 if big else 1)
+        K = (w.shape[-1] ** 2 * C + n_skip + 6) * (2 if big else 1)  # (9 Cin for the 3x3 kernels, Cin for the 1x1 / GEMM route)
         inner = K * 2.0 ** -23 * A_all
         if dh is not None:
             inner = inner + _conv(dh, aw, big)

@@ -8,7 +8,7 @@ affine and affine + SiLU launches of the weight-stationary, small-image, pyramid
 any wrong tap, halo, seam, slab, padding or statistic on one element, cannot see rounding or the SiLU at ordinary arguments.
 (2) The per-element bound (ConvCheck in the matches-torch tests, test_conv_activation_probe): every output element within its own
 derived rounding budget of a float64 reference; sees a local fault above about one storage ulp of the summed inputs, nothing
-smaller."""
+smaller.  The 1x1 / GEMM instantiations and the unfused attention chain carry both in tests/gemmcheck.py and tests/test_gemm_gpu.py."""
 import math
 
 import numpy as np
