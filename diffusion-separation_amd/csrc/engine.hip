@@ -118,6 +118,22 @@ static Tn e_tensor(diffsep_engine* e, int B, int H, int W, int C) {
   return t;
 }
 float* e_f32(diffsep_engine* e, size_t n) { return (float*)e_alloc(e, n * 4); }
+// ---- option "trace": one record per tensor / side array a step has just written (outputs only; engine_host.h)
+static void trace_raw(diffsep_engine* e, const char* kind, const char* role, const void* p, int B, int H, int W, int C, int ld,
+                      int f32, const long long* sa, const char* kernel = "") {
+  if (!e->tracing || e->dry) return;
+  const char* a = e->arena;
+  const char* q = (const char*)p;
+  const long long off = (a && q >= a && q < a + e->cap) ? (long long)(q - a) : -1;
+  e->trace.push_back({kind, role, kernel ? kernel : "", e->trace_mod, B, H, W, C, ld, f32, off,
+                      sa ? (long long)((const char*)sa - e->stats_ptr) : -1});
+}
+static void trace_tn(diffsep_engine* e, const char* kind, const char* role, const Tn& t, int B, const char* kernel = "") {
+  trace_raw(e, kind, role, t.p, B, t.H, t.W, t.C, t.ld, 0, t.sa, kernel);
+}
+static void trace_f32(diffsep_engine* e, const char* kind, const char* role, const float* p, int B, int n) {
+  trace_raw(e, kind, role, p, B, 1, 1, n, n, 1, nullptr);
+}
 static const float* P(diffsep_engine* e, const PRef& r) { return e->d_blob + r.off; }
 static const void* PK(diffsep_engine* e, long off) { return e->d_pack + off * e->esz; }
 static const void* PKF(diffsep_engine* e, long off) { return off >= 0 ? e->d_pack + off * e->esz : nullptr; }
@@ -157,6 +173,7 @@ struct Conv {
   const GnAff* gn = nullptr;         // the input is SiLU(GroupNorm(x))
   const SkipConv* skip = nullptr;
   bool want_stats = false;           // the output gets GroupNorm accumulators (y.sa)
+  const char* role = "out";          // what the output is to its block (option "trace")
 };
 // The launcher's view of a Conv writing into y (no launch, no allocation: stats_acc is conv()'s to set)
 static ConvArgs conv_args(const diffsep_engine* e, const Conv& c, const Tn& y, int B) {
@@ -201,7 +218,11 @@ static int conv(diffsep_engine* e, const Conv& c, Tn& y, int B, hipStream_t st) 
             (long)((char*)y.sa - e->stats_ptr), a.Cin, c.Cout, c.taps, a.H, a.W, c.res != nullptr, c.skip != nullptr,
             c.bias_b != nullptr, p.cls);
   if (e->dry || ablated(e, a.H)) return 0;
-  if (!e->prof) return ds_launch_conv(a, p, st);
+  if (!e->prof) {
+    const int rc = ds_launch_conv(a, p, st);
+    trace_tn(e, "conv", c.role, y, B, ds_last_conv_kernel());
+    return rc;
+  }
   diffsep_engine::ProfRec r;
   r.flops = 2.0 * ((double)a.taps * a.Cin + (a.sx ? a.sCin : 0)) * a.Cout * (double)a.H * a.W * a.B;
   {  // algorithmic HBM bytes: input (+ fused skip input) + output (+ residual) once each, weights once
@@ -214,6 +235,7 @@ static int conv(diffsep_engine* e, const Conv& c, Tn& y, int B, hipStream_t st) 
   r.B = a.B; r.H = a.H; r.W = a.W; r.Cin = a.Cin; r.Cout = a.Cout; r.taps = a.taps; r.sCin = a.sx ? a.sCin : 0; r.res = a.res != nullptr;
   const int rc = prof_launch(e, st, r, [&]() { return ds_launch_conv(a, p, st); });
   e->prof_recs.back().kernel = ds_last_conv_kernel();  // (the instantiation the dispatch chose)
+  trace_tn(e, "conv", c.role, y, B, ds_last_conv_kernel());
   return rc;
 }
 
@@ -232,11 +254,15 @@ static int gn_stats(diffsep_engine* e, const Tn& x, const float* gamma, const fl
   aff.shift = e_f32(e, (size_t)B * x.C);
   if (have_acc) {
     if (e->dry || (e->ablate & 16u)) return 0;
+    trace_f32(e, "gn_finalize", "scale", aff.scale, B, x.C);
+    trace_f32(e, "gn_finalize", "shift", aff.shift, B, x.C);
     return ds_launch_gn_finalize_acc(x.sa, x.p2 ? x.C1 : x.C, x.sa2, x.p2 ? x.C - x.C1 : 0, B, (long)x.H * x.W, groups,
                                      1e-6f, gamma, beta, aff.scale, aff.shift, st);
   }
   void* ws = e_alloc(e, (size_t)ds_gn_workspace_bytes(B, x.H, x.W, x.C));
   if (e->dry) return 0;
+  trace_f32(e, "gn_stats", "scale", aff.scale, B, x.C);
+  trace_f32(e, "gn_stats", "shift", aff.shift, B, x.C);
   return ds_launch_gn_stats(x.p, x.ld, x.p2, x.ld2, x.C1, B, x.H, x.W, x.C, groups, 1e-6f, gamma, beta, ws, aff.scale,
                             aff.shift, e->cfg.dtype, st);
 }
@@ -311,9 +337,10 @@ int res_block(diffsep_engine* e, const Module& m, const Tn& x, const float* temb
       h1p = e_tensor(e, B, Ho, Wo, m.out_ch);
       Tn h1 = e_tensor(e, B, Ho, Wo, m.out_ch);
       const long half0 = 4L * 9 * m.out_ch * 32;  // chunk-major [Cin / 32][9][Cout][32]: the first source = the first 4 chunks
+      c0a.role = "h1p";
       if (conv(e, c0a, h1p, B, st)) return 1;
       Conv c0b(xb, PK(e, m.pk0 + half0), m.out_ch, 9);
-      c0b.w_frag = PKF(e, m.pf0b); c0b.gn = &gb; c0b.res = &h1p; c0b.want_stats = true;
+      c0b.w_frag = PKF(e, m.pf0b); c0b.gn = &gb; c0b.res = &h1p; c0b.want_stats = true; c0b.role = "h1";
       if (conv(e, c0b, h1, B, st)) return 1;
       if (gn_stats(e, h1, P(e, m.gn1_w), P(e, m.gn1_b), B, a1, st, true)) return 1;
       out = e_tensor(e, B, Ho, Wo, m.out_ch);
@@ -322,6 +349,7 @@ int res_block(diffsep_engine* e, const Module& m, const Tn& x, const float* temb
       const SkipConv sk = {&xa, PK(e, m.pk2), weight_chunk(9, 128, 0, e->cfg.dtype), PKF(e, m.pf2a)};
       Conv c1(h1, PK(e, m.pk1), m.out_ch, 9);
       c1.w_frag = PKF(e, m.pf1); c1.gn = &a1; c1.skip = &sk; c1.bias = P(e, m.conv1_b); c1.bias_b = P(e, m.conv2_b);
+      c1.role = "outp";
       if (conv(e, c1, outp, B, st)) return 1;
       Conv c2b(xb, PK(e, m.pk2b), m.out_ch, 1);
       c2b.res = &outp; c2b.scale = kInvSqrt2; c2b.want_stats = true;
@@ -336,10 +364,12 @@ int res_block(diffsep_engine* e, const Module& m, const Tn& x, const float* temb
     h0m = e_tensor(e, B, Ho, Wo, m.in_ch);
     xr = e_tensor(e, B, Ho, Wo, m.in_ch);
     if (gn_apply(e, x, &a0, &h0m, &xr, B, 1, mode, st)) return 1;
+    trace_tn(e, "gn_apply", "h0m", h0m, B, ds_last_conv_kernel());
+    trace_tn(e, "gn_apply", "xr", xr, B, ds_last_conv_kernel());
   }
   if (!m.has_conv2) DS_CHECK(xr.p2 == nullptr, "internal: identity skip on a concat view");
   Conv c0(mode ? h0m : x, PK(e, m.pk0), m.out_ch, 9);  // (a resampling block's input is already act(GN(.)), resampled)
-  c0.w_frag = PKF(e, m.pf0); c0.gn = mode ? nullptr : &a0; c0.want_stats = true;
+  c0.w_frag = PKF(e, m.pf0); c0.gn = mode ? nullptr : &a0; c0.want_stats = true; c0.role = "h1";
   c0.bias = P(e, m.conv0_b); c0.bias_b = temb; c0.bias_b_ld = e->arch.dense_total;
   if (conv(e, c0, h1, B, st)) return 1;
   if (gn_stats(e, h1, P(e, m.gn1_w), P(e, m.gn1_b), B, a1, st, true)) return 1;
@@ -349,7 +379,7 @@ int res_block(diffsep_engine* e, const Module& m, const Tn& x, const float* temb
   if (m.has_conv2) {  // narrow blocks (<= 32 couts use the 32-cout tile, which has no skip path): separate 1x1 launch
     skip = e_tensor(e, B, Ho, Wo, m.out_ch);
     Conv c2(xr, PK(e, m.pk2), m.out_ch, 1);
-    c2.bias = P(e, m.conv2_b);
+    c2.bias = P(e, m.conv2_b); c2.role = "skip";
     if (conv(e, c2, skip, B, st)) return 1;
   }
   Conv c1(h1, PK(e, m.pk1), m.out_ch, 9);
@@ -414,15 +444,18 @@ int attn_block(diffsep_engine* e, const Module& m, const Tn& x, int B, Tn& out, 
     r.bytes = (double)e->esz * (2.0 * B * L * C + 3.0 * C * C);
     r.cls = DS_CLS_ATTN; r.B = B; r.H = x.H; r.W = x.W; r.Cin = C; r.Cout = C; r.taps = 1; r.res = 1;
     r.kernel = "attn_fused_kernel";
-    return prof_launch(e, st, r, [&]() { return ds_launch_attn_fused(a, st); });
+    const int rc = prof_launch(e, st, r, [&]() { return ds_launch_attn_fused(a, st); });
+    trace_tn(e, "attn_fused", "out", out, B, ds_last_conv_kernel());
+    return rc;
   }
   GnAff a0;
   if (gn_stats(e, x, P(e, m.gn0_w), P(e, m.gn0_b), B, a0, st)) return 1;
   Tn h = e_tensor(e, B, x.H, x.W, C);
   if (gn_apply(e, x, &a0, &h, nullptr, B, 0, 0, st)) return 1;
+  trace_tn(e, "gn_apply", "h", h, B, ds_last_conv_kernel());
   Tn q = e_tensor(e, B, x.H, x.W, C), k = e_tensor(e, B, x.H, x.W, C);
   Conv cq(h, PK(e, m.pk_nin[0]), C, 1), ck(h, PK(e, m.pk_nin[1]), C, 1);
-  cq.bias = P(e, m.nin_b[0]); ck.bias = P(e, m.nin_b[1]);
+  cq.bias = P(e, m.nin_b[0]); ck.bias = P(e, m.nin_b[1]); cq.role = "q"; ck.role = "k";
   if (conv(e, cq, q, B, st) || conv(e, ck, k, B, st)) return 1;
   // V^T[b, c, l] = sum_c' Wv[c', c] h[b, l, c'] + b[c]: A = packed Wv^T ([C][C]), Bt = h, bias along rows
   void* vt = e_alloc(e, (size_t)B * C * Lp * e->esz);
@@ -447,6 +480,10 @@ int attn_block(diffsep_engine* e, const Module& m, const Tn& x, int B, Tn& out, 
     Tn qv = q, ov = o;  // [B][L][C] GEMM views
     qv.H = ov.H = 1; qv.W = ov.W = L;
     if (attention_core(qv, k.p, vt, ov, B, scores, probs, e->cfg.dtype, st, e->split)) return 1;
+    trace_raw(e, "gemm", "vt", vt, B, 1, C, L, Lp, 0, nullptr);          // V^T [B][C][Lp]
+    trace_raw(e, "gemm", "scores", scores, B, 1, L, L, Lp, 0, nullptr);  // [B][L][Lp]
+    trace_raw(e, "softmax", "probs", probs, B, 1, L, Lp, Lp, 0, nullptr);  // (the padding columns [L, Lp) are written too: zeros)
+    trace_tn(e, "gemm", "o", o, B);
   }
   // (the dry run must see this call too: it sizes the accumulator region)
   Conv co(o, PK(e, m.pk_nin[3]), C, 1);
@@ -463,6 +500,9 @@ static int net_forward(diffsep_engine* e, const Tn& x0, const float* t, const Tn
   const diffsep_model_config& c = e->cfg;
   const int nf = c.nf;
   size_t mi = 0;
+  e->trace_mod = -1;
+  // (the module the forward enters, for option "trace")
+  auto next = [&]() -> const Module& { e->trace_mod = (int)mi; return A.mods[mi++]; };
   // ---- time embedding (ncsnpp.py:324-343) and every block's Dense_0(act(temb)) (layerspp.py:311-312)
   float* emb = e_f32(e, (size_t)B * 2 * nf);
   float* t1 = e_f32(e, (size_t)B * 4 * nf);
@@ -476,6 +516,10 @@ static int net_forward(diffsep_engine* e, const Tn& x0, const float* t, const Tn
     if (ds_launch_linear(emb, P(e, l1.w0), P(e, l1.b0), t1, B, 2 * nf, 4 * nf, 0, st)) return 1;
     if (ds_launch_linear(t1, P(e, l2.w0), P(e, l2.b0), temb, B, 4 * nf, 4 * nf, 1, st)) return 1;
     if (ds_launch_linear_t(temb, e->d_dense_w, e->d_dense_b, proj, B, 4 * nf, A.dense_total, 1, st)) return 1;
+    trace_f32(e, "fourier", "emb", emb, B, 2 * nf);
+    trace_f32(e, "linear", "t1", t1, B, 4 * nf);
+    trace_f32(e, "linear", "temb", temb, B, 4 * nf);
+    trace_f32(e, "linear", "proj", proj, B, A.dense_total);
   }
   // ---- input conv
   const Module& cin = A.mods[mi++];
@@ -483,7 +527,8 @@ static int net_forward(diffsep_engine* e, const Tn& x0, const float* t, const Tn
   {
     Tn h = e_tensor(e, B, x0.H, x0.W, nf);
     Conv ci(x0, PK(e, cin.pk0), nf, 9);
-    ci.bias = P(e, cin.b0); ci.want_stats = true;
+    ci.bias = P(e, cin.b0); ci.want_stats = true; ci.role = "conv_in";
+    e->trace_mod = (int)mi - 1;
     if (conv(e, ci, h, B, st)) return 1;
     hs.push_back(h);
   }
@@ -492,35 +537,36 @@ static int net_forward(diffsep_engine* e, const Tn& x0, const float* t, const Tn
   Tn h;
   for (int i = 0; i < L; ++i) {
     for (int k = 0; k < c.num_res_blocks; ++k) {
-      if (res_block(e, A.mods[mi++], hs.back(), proj, B, h, st)) return 1;
+      if (res_block(e, next(), hs.back(), proj, B, h, st)) return 1;
       if (h.H == c.attn_resolution) {
         DS_CHECK(mi < A.mods.size() && A.mods[mi].kind == MK_ATTN, "attention placement mismatch (image height)");
         Tn ha;
-        if (attn_block(e, A.mods[mi++], h, B, ha, st)) return 1;
+        if (attn_block(e, next(), h, B, ha, st)) return 1;
         h = ha;
       }
       hs.push_back(h);
     }
     if (i != L - 1) {
-      if (res_block(e, A.mods[mi++], hs.back(), proj, B, h, st)) return 1;
+      if (res_block(e, next(), hs.back(), proj, B, h, st)) return 1;
       // input pyramid: FIR down, Combine = conv1x1(pyr) + h   (ncsnpp.py:383-386, layerspp.py:52-57)
       Tn pd = e_tensor(e, B, pyr_in.H / 2, pyr_in.W / 2, pyr_in.C);
+      const Module& cm = next();
       if (gn_apply(e, pyr_in, nullptr, nullptr, &pd, B, 0, 2, st)) return 1;
+      trace_tn(e, "gn_apply", "pd", pd, B, ds_last_conv_kernel());
       pyr_in = pd;
-      const Module& cm = A.mods[mi++];
       DS_CHECK(cm.kind == MK_COMBINE, "internal: expected Combine");
       Tn hc = e_tensor(e, B, h.H, h.W, h.C);
       Conv cc(pyr_in, PK(e, cm.pk0), h.C, 1);
-      cc.bias = P(e, cm.b0); cc.res = &h; cc.want_stats = true;
+      cc.bias = P(e, cm.b0); cc.res = &h; cc.want_stats = true; cc.role = "combine";
       if (conv(e, cc, hc, B, st)) return 1;
       hs.push_back(hc);
     }
   }
   h = hs.back();
   Tn t2;
-  if (res_block(e, A.mods[mi++], h, proj, B, t2, st)) return 1;
-  if (attn_block(e, A.mods[mi++], t2, B, h, st)) return 1;
-  if (res_block(e, A.mods[mi++], h, proj, B, t2, st)) return 1;
+  if (res_block(e, next(), h, proj, B, t2, st)) return 1;
+  if (attn_block(e, next(), t2, B, h, st)) return 1;
+  if (res_block(e, next(), h, proj, B, t2, st)) return 1;
   h = t2;
 
   Tn pyramid;
@@ -531,29 +577,30 @@ static int net_forward(diffsep_engine* e, const Tn& x0, const float* t, const Tn
       hs.pop_back();
       const Tn cat = cat_view(h, s);  // torch.cat([h, hs.pop()], dim=1) read in place (ncsnpp.py:411)
       Tn hn2;
-      if (res_block(e, A.mods[mi++], cat, proj, B, hn2, st)) return 1;
+      if (res_block(e, next(), cat, proj, B, hn2, st)) return 1;
       h = hn2;
     }
     if (h.H == c.attn_resolution) {
       DS_CHECK(mi < A.mods.size() && A.mods[mi].kind == MK_ATTN, "attention placement mismatch (image height)");
       Tn ha;
-      if (attn_block(e, A.mods[mi++], h, B, ha, st)) return 1;
+      if (attn_block(e, next(), h, B, ha, st)) return 1;
       h = ha;
     }
     // output pyramid (ncsnpp.py:419-440): conv3x3(act(GN(h))) [+ FIR up of the previous pyramid]
-    const Module& g = A.mods[mi++];
-    const Module& cv = A.mods[mi++];
+    const Module& g = A.mods[mi++];  // (GroupNorm of the pyramid head: no launch of its own)
+    const Module& cv = next();
     DS_CHECK(g.kind == MK_GN && cv.kind == MK_CONV3, "internal: expected pyramid GN + conv");
     hipStream_t sp = st;  // (the pyramid chain on a side stream was measured 6 % slower: profiles/experiments)
     GnAff ga;
     if (gn_stats(e, h, P(e, g.w0), P(e, g.b0), B, ga, sp, true)) return 1;
     Tn pnew = e_tensor(e, B, h.H, h.W, A.cpad_in);
     Conv cp(h, PK(e, cv.pk0), A.chan_in, 9);
-    cp.bias = P(e, cv.b0); cp.gn = &ga;
+    cp.bias = P(e, cv.b0); cp.gn = &ga; cp.role = "pnew";
     Tn pu;
     if (have_pyr) {
       pu = e_tensor(e, B, h.H, h.W, A.cpad_in);
       if (gn_apply(e, pyramid, nullptr, nullptr, &pu, B, 0, 1, sp)) return 1;
+      trace_tn(e, "gn_apply", "pu", pu, B, ds_last_conv_kernel());
       cp.res = &pu;
     }
     if (conv(e, cp, pnew, B, sp)) return 1;
@@ -561,16 +608,17 @@ static int net_forward(diffsep_engine* e, const Tn& x0, const float* t, const Tn
     have_pyr = true;
     if (i != 0) {
       Tn hu;
-      if (res_block(e, A.mods[mi++], h, proj, B, hu, st)) return 1;
+      if (res_block(e, next(), h, proj, B, hu, st)) return 1;
       h = hu;
     }
   }
   DS_CHECK(hs.empty() && mi == A.mods.size(), "internal: module walk did not consume all modules");
   // h = pyramid / t ; out = output_layer(h)   (ncsnpp.py:472-477)
+  e->trace_mod = -1;
   if (pyr_out) { *pyr_out = pyramid; return 0; }
   Tn yy = y;
   Conv co(pyramid, PK(e, A.pk_out), A.chan_out, 1);
-  co.bias = P(e, A.out_b); co.div_b = t;
+  co.bias = P(e, A.out_b); co.div_b = t; co.role = "y";
   return conv(e, co, yy, B, st);
 }
 
@@ -597,6 +645,7 @@ static int score_forward_impl(diffsep_engine* e, const float* xt, const float* t
                                      e->arch.cpad_in, 1, c.dtype, e->d_tab, ws_f, st, dft_split);
         }))
       return 1;
+  trace_tn(e, "stft", "x0", x0, B);
   Tn pyr;
   if (net_forward(e, x0, t, y, B, st, &pyr)) return 1;
   if (!e->dry && !(e->ablate & 128u))
@@ -819,6 +868,26 @@ extern "C" int32_t diffsep_engine_debug_arena(const diffsep_engine* e, void** ba
   *base = e->arena; *bytes = (int64_t)e->cap; *fwd_base = (int64_t)e->fwd_base;
   return 0;
 }
+extern "C" int32_t diffsep_engine_debug_trace(const diffsep_engine* e, int64_t* fields, char* names, int32_t cap, int32_t* n) {
+  DS_CHECK(e && n, "debug_trace: null argument");
+  *n = (int32_t)e->trace.size();
+  const long long sb = e->stats_ptr && e->arena ? (long long)(e->stats_ptr - e->arena) : 0;
+  for (int i = 0; i < *n && i < cap; ++i) {
+    const auto& r = e->trace[i];
+    if (fields) {
+      const int64_t v[DIFFSEP_TRACE_FIELDS] = {r.mod, r.B, r.H, r.W, r.C, r.ld, r.f32, r.off, r.stats_off >= 0 ? sb + r.stats_off : -1};
+      memcpy(fields + (size_t)DIFFSEP_TRACE_FIELDS * i, v, sizeof(v));
+    }
+    if (names) {
+      char* o = names + (size_t)DIFFSEP_TRACE_NAME_BYTES * i;
+      memset(o, 0, DIFFSEP_TRACE_NAME_BYTES);
+      snprintf(o, 16, "%s", r.kind);
+      snprintf(o + 16, 16, "%s", r.role);
+      snprintf(o + 32, DIFFSEP_TRACE_NAME_BYTES - 32, "%s", r.kernel.c_str());
+    }
+  }
+  return 0;
+}
 extern "C" int64_t diffsep_engine_device_bytes(const diffsep_engine* e) {
   return e ? e->weight_bytes + (int64_t)e->cap + (int64_t)e->ode_cap : 0;
 }
@@ -844,6 +913,10 @@ extern "C" int32_t diffsep_engine_set_option(diffsep_engine* e, const char* name
     // stft.hip reads the PROCESS default (ds_default_opts): an engine-level value would be accepted and do nothing
     ds_set_error("engine_set_option: 'no_stft_fused' is a process-level option (diffsep_set_option / DIFFSEP_NO_STFT_FUSED)");
     return 1;
+  } else if (!strcmp(name, "trace")) {  // (host bookkeeping: no launch decision depends on it, plans and graphs stay)
+    e->trace_on = value != 0;
+    e->trace.clear();
+    return 0;
   } else if (!strcmp(name, "track_tensors")) {
     e->track_tensors = value != 0;
     e->tracked.clear();
@@ -868,6 +941,7 @@ extern "C" int64_t diffsep_engine_get_option(const diffsep_engine* e, const char
   if (!strcmp(name, "graph_cache")) return e->graph_cap;
   if (!strcmp(name, "graphs_cached")) return (int64_t)e->graphs.size();
   if (!strcmp(name, "ablate")) return e->ablate;
+  if (!strcmp(name, "trace")) return e->trace_on ? 1 : 0;
   if (!opt_bit(name, &bit)) return (e->opts & bit) ? 1 : 0;
   return -1;
 }
@@ -931,12 +1005,19 @@ extern "C" int32_t diffsep_engine_profile_records(diffsep_engine* e, diffsep_pro
   return 0;
 }
 
+// option "trace": the records of the forward that begins here replace the last one's; nothing else records (run_nfe, capture)
+struct TraceScope {
+  diffsep_engine* e;
+  explicit TraceScope(diffsep_engine* e_) : e(e_) { e->trace.clear(); e->trace_mod = -1; e->tracing = e->trace_on; }
+  ~TraceScope() { e->tracing = false; }
+};
 extern "C" int32_t diffsep_score_forward(diffsep_engine* e, const float* xt, const float* t, const float* mix,
                                          float* out, int32_t B, int64_t T, void* stream) {
   DS_CHECK(e && xt && t && mix && out, "score_forward: null argument");
   StreamScope sc_(e, stream);
   hipStream_t st = sc_.st;
   if (ensure_plan(e, B, T, st)) return 1;
+  const TraceScope ts_(e);
   return score_forward_impl(e, xt, t, mix, out, B, T, st);
 }
 
@@ -951,6 +1032,7 @@ extern "C" int32_t diffsep_backbone_forward(diffsep_engine* e, const void* x, co
   DS_CHECK(diffsep_padded_frames(&e->cfg, T) == W, "internal: width/length mapping");
   if (ensure_plan(e, B, T, st)) return 1;
   const int H = e->cfg.n_fft / 2 + 1;
+  const TraceScope ts_(e);
   e->top = e->fwd_base;
   if (stats_begin(e, st)) return 1;
   Tn xin; xin.p = (void*)x; xin.C = xin.ld = e->arch.cpad_in; xin.H = H; xin.W = W;
@@ -961,6 +1043,7 @@ extern "C" int32_t diffsep_backbone_forward(diffsep_engine* e, const void* x, co
   if (ds_launch_fill(sh, -1.f, (long)B * e->arch.cpad_in, st)) return 1;
   GnAff aff{sc, sh};
   if (gn_apply(e, xin, &aff, &x0, nullptr, B, 0, 0, st)) return 1;  // x = 2x - 1 (ncsnpp.py:347-349)
+  trace_tn(e, "gn_apply", "x0", x0, B, ds_last_conv_kernel());
   Tn yo; yo.p = y; yo.C = yo.ld = e->arch.cpad_out; yo.H = H; yo.W = W;
   return net_forward(e, x0, t, yo, B, st);
 }

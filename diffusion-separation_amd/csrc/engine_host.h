@@ -310,6 +310,17 @@ struct diffsep_engine {
   bool track_tensors = false;
   struct Tracked { void* p; long n; int H, W, C; };
   std::vector<Tracked> tracked;
+  // option "trace": every tensor and side array an eager forward WRITES gets a record (diffsep_engine_debug_trace; the
+  // checker is tests/netcheck.py).  trace_on = the option, tracing = inside diffsep_score_forward / diffsep_backbone_forward with
+  // the option on (graph capture and the samplers never record), trace_mod = the module the forward is in (-1 outside the list).
+  // Host bookkeeping only: no launch decision reads any of it.
+  bool trace_on = false, tracing = false;
+  int trace_mod = -1;
+  struct TraceRec {
+    const char* kind; const char* role; std::string kernel;
+    int mod, B, H, W, C, ld, f32; long long off, stats_off;
+  };
+  std::vector<TraceRec> trace;
   // DIFFSEP_F32_SPLIT: fp32 tensors, every MFMA product as 3 bf16 MFMAs on hi / lo halves (cfg.dtype stays DS_F32)
   int split = 0;
   // optional per-launch timing of the MFMA kernels (HIP events on the launch stream)

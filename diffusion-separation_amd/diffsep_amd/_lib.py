@@ -83,6 +83,9 @@ class ProfRecord(C.Structure):  # diffsep_prof_record
                 ("cls", C.c_int32), ("_pad", C.c_int32), ("flops", C.c_double), ("bytes", C.c_double), ("ms", C.c_double)]
 
 
+TRACE_FIELDS, TRACE_NAME_BYTES = 9, 160  # diffsep_engine_debug_trace: int64 fields and name bytes per record
+
+
 class DiffsepError(RuntimeError):
     pass
 
@@ -130,6 +133,7 @@ _SIGS = {
     "diffsep_engine_reserve": (_I, [_P, _I, _L, _P]),
     "diffsep_engine_debug_absmax": (_I, [_P, C.POINTER(C.c_double), _I, C.POINTER(_I)]),
     "diffsep_engine_debug_arena": (_I, [_P, C.POINTER(_P), C.POINTER(_L), C.POINTER(_L)]),
+    "diffsep_engine_debug_trace": (_I, [_P, C.POINTER(_L), C.c_char_p, _I, C.POINTER(_I)]),
     "diffsep_num_frames": (_I, [C.POINTER(ModelConfig), _L]),
     "diffsep_padded_frames": (_I, [C.POINTER(ModelConfig), _L]),
     "diffsep_score_forward": (_I, [_P, _P, _P, _P, _P, _I, _L, _P]),

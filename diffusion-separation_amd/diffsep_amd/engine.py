@@ -127,7 +127,8 @@ class Engine:
         "no_rw_helper" (the 64 -> 64 GroupNorm launches of the register-weight kernel without helper waves: same bits); launch
         geometry of the register-weight kernel: "rw_half", "rw_quarter", "rw_big_half" ("no_stft_fused" is a process
         default only: diffsep_set_option).  Others: "graph_cache" (captured graphs kept, LRU), "ablate" (measurement aid),
-        "track_tensors", "dbg_alloc".  Synchronises the device, drops the captured graphs."""
+        "track_tensors", "trace" (debug_trace), "dbg_alloc".  Synchronises the device, drops the captured graphs (the three
+        debug switches do neither)."""
         call(self._L, "diffsep_engine_set_option", self._h, str(name).encode(), int(value))
 
     def get_option(self, name):
@@ -207,6 +208,50 @@ class Engine:
         class _Raw:
             __cuda_array_interface__ = {"shape": (nb.value,), "typestr": "|u1", "data": (base.value, False), "version": 2}
         return torch.as_tensor(_Raw(), device=f"cuda:{self.device.index or 0}" if hasattr(self.device, "index") else "cuda"), fb.value
+
+    def debug_trace(self):
+        """[dict] of diffsep_engine_debug_trace: one record per tensor or side array the last eager forward wrote
+        (set_option("trace", 1) first), in launch order: kind, role, kernel, mod, B, H, W, C, ld, f32, offset (bytes into the
+        arena, -1: the caller's buffer) and stats (ABSOLUTE arena offset in bytes of the [B,C,2] int64 accumulators, or -1).
+        Debug / test aid; trace_view / trace_stats turn a record into tensors."""
+        n = C.c_int32(0)
+        call(self._L, "diffsep_engine_debug_trace", self._h, None, None, 0, C.byref(n))
+        nf, nb = _lib.TRACE_FIELDS, _lib.TRACE_NAME_BYTES
+        fields = (C.c_int64 * (nf * max(1, n.value)))()
+        names = C.create_string_buffer(nb * max(1, n.value))
+        call(self._L, "diffsep_engine_debug_trace", self._h, fields, names, n.value, C.byref(n))
+        raw = names.raw
+        text = lambda i, lo, hi: raw[nb * i + lo:nb * i + hi].split(b"\0", 1)[0].decode()
+        keys = ("mod", "B", "H", "W", "C", "ld", "f32", "offset", "stats")
+        out = []
+        for i in range(n.value):
+            r = dict(zip(keys, (int(v) for v in fields[nf * i:nf * (i + 1)])), kind=text(i, 0, 16), role=text(i, 16, 32), kernel=text(i, 32, nb))
+            r["f32"] = bool(r["f32"])
+            out.append(r)
+        return out
+
+    def storage_dtype(self):
+        """torch type of the engine's activation tensors"""
+        if self.cfg.dtype != BF16:
+            return torch.float32
+        return torch.float16 if self.kind == "f16" else torch.bfloat16
+
+    def trace_view(self, rec, arena=None):
+        """a record of debug_trace() as a tensor [B,H,W,C] on the arena (no copy; the leading dimension becomes a stride)"""
+        arena = self.debug_arena()[0] if arena is None else arena
+        dt = torch.float32 if rec["f32"] else self.storage_dtype()
+        esz = torch.empty((), dtype=dt).element_size()
+        assert rec["offset"] >= 0 and rec["offset"] % esz == 0, "the record's tensor is not in the arena"
+        n = rec["B"] * rec["H"] * rec["W"] * rec["ld"]
+        flat = arena[rec["offset"]:rec["offset"] + n * esz].view(dt)
+        return flat.view(rec["B"], rec["H"], rec["W"], rec["ld"])[..., :rec["C"]]
+
+    def trace_stats(self, rec, arena=None):
+        """the int64 GroupNorm accumulators [B,C,2] of a record (sum * 2^24, sum of squares * 2^16), a view of the arena"""
+        arena = self.debug_arena()[0] if arena is None else arena
+        assert rec["stats"] >= 0 and rec["stats"] % 8 == 0, "the record has no accumulators"
+        n = rec["B"] * rec["C"] * 2
+        return arena[rec["stats"]:rec["stats"] + n * 8].view(torch.int64).view(rec["B"], rec["C"], 2)
 
     def backbone(self, x_nhwc, t):
         """NCSNpp.forward on a packed NHWC input [B,256,W,Cpad] (engine dtype storage)."""

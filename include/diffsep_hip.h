@@ -133,6 +133,24 @@ int32_t diffsep_engine_debug_arena(const diffsep_engine* e, void** base, int64_t
  * last forward, in allocation order, out[4 i ..] = {largest finite |value|, number of non-finite values, rows H, channels C};
  * *n = number of tensors (out may be NULL to query).  How far the half-precision engines are from 65504. */
 int32_t diffsep_engine_debug_absmax(diffsep_engine* e, double* out, int32_t cap, int32_t* n);
+/* Debug / test aid (engine option "trace" = 1, eager forwards: diffsep_score_forward, diffsep_backbone_forward): one record per
+ * tensor or side array the last forward WROTE, in launch order, of the query-then-fill form of diffsep_engine_debug_absmax
+ * (fields / names may be NULL to query *n; at most cap records are written).
+ * fields[DIFFSEP_TRACE_FIELDS i ..] = {mod, B, H, W, C, ld, f32, offset, stats}: mod = index of the module in the all_modules
+ * order, -1 outside it; the tensor is [B][H][W][C] with leading dimension ld, fp32 when f32 != 0 and of the engine's storage type
+ * otherwise; offset = its byte offset in the arena of diffsep_engine_debug_arena (-1: the caller's own buffer); stats = byte offset
+ * in the arena of its [B][C][2] int64 GroupNorm accumulators (they live in the statistics region at the start of the forward's
+ * allocations), or -1.
+ * names[DIFFSEP_TRACE_NAME_BYTES i ..] = three NUL-terminated strings at +0, +16 and +32: kind = the step that wrote it ("stft",
+ * "fourier", "linear", "conv", "gn_apply", "gn_finalize", "gn_stats", "gemm", "softmax", "attn_fused"); role = what the tensor is
+ * to its block ("x0", "emb", "t1", "temb", "proj", "conv_in", "h0m", "xr", "h1p", "h1", "skip", "outp", "out", "scale", "shift",
+ * "h", "q", "k", "vt", "scores", "probs", "o", "pd", "combine", "pu", "pnew", "y"); kernel = what diffsep_last_conv_kernel()
+ * reported after a convolution or fused-attention launch ("" otherwise).
+ * Inputs are not recorded: which tensors a step should have read is the checker's business (tests/netcheck.py).  Off by default;
+ * with the option off a forward launches exactly what it launches without this entry. */
+#define DIFFSEP_TRACE_FIELDS 9
+#define DIFFSEP_TRACE_NAME_BYTES 160
+int32_t diffsep_engine_debug_trace(const diffsep_engine* e, int64_t* fields, char* names, int32_t cap, int32_t* n);
 /* frames F = 1 + (T + n_fft - hop)/hop and padded width W = 64*ceil(F/64) for T samples
  * (score_models.py:83-91,107-112). Pure host arithmetic. */
 int32_t diffsep_num_frames(const diffsep_model_config* cfg, int64_t T);
