@@ -2,13 +2,15 @@
 // derives from its diffsep_ode_config (OdePlan) and the adaptive step controller (OdeCtl), ported from scipy 1.15
 // (integrate/_ivp/rk.py RungeKutta._step_impl, common.py select_initial_step / validate_tol, base.py OdeSolver.step, ivp.py
 // solve_ivp's loop).  diffsep_ode_sample drives one OdeCtl, diffsep_ode_sample_each one per utterance (sampler.hip);
-// tests/ode_ctl_main.cpp drives one on a small float64 system against scipy itself.  Plain C++17, no HIP.
+// tests/ode_ctl_main.cpp drives one on a small float64 system against scipy itself.  Below them: the plan of a fixed-step
+// solve (OdeFixedPlan, diffsep_ode_sample_fixed; tests/ode_fixed_main.cpp walks it).  Plain C++17, no HIP.
 #pragma once
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
 #include <string>
+#include <vector>
 
 #include "../../include/diffsep_hip.h"
 
@@ -154,3 +156,139 @@ struct OdeCtl {
     return false;
   }
 };
+
+// ------------------------------------------------------------------ fixed-step solves (diffsep_ode_sample_fixed)
+// The same ODE on a grid the caller chooses: no error norm decides anything, so the whole solve is known before its first
+// evaluation.  OdeFixedPlan is that knowledge — the grid, and the solve as a flat list of passes, one per network evaluation
+// — and the driver in sampler.hip only walks it; tests/ode_fixed_main.cpp walks it on a small float64 system.
+#define DS_ODEF_MAX_EVALS 16384  // steps x stages of one solve (the rows of the evaluation-time table)
+
+struct OdeFixedConfig {  // the arguments of diffsep_ode_sample_fixed that shape the solve
+  int method, steps;     // DIFFSEP_ODEF_*, M
+  double t_start, eps;   // t_start <= 0: 1.0 (sde.T)
+  int denoise, N;        // as diffsep_ode_config
+};
+
+// Explicit tableau of the one-step methods in OdePlan's layout (row s of A at A + s * DS_ODE_MAX_K) and, where the method
+// has an embedded Euler step, D with  step - Euler step = h sum_j D[j] K_j  (has_d; Euler and RK4 have none).
+// AB2 is no Runge-Kutta method: its first step is Heun's (this tableau), the others are built in ode_fixed_plan_fill.
+inline int ds_odef_tableau(int method, double* A, double* B, double* C, double* D, int* ns, bool* has_d) {
+  memset(A, 0, sizeof(double) * DS_ODE_MAX_K * DS_ODE_MAX_K);
+  memset(B, 0, sizeof(double) * DS_ODE_MAX_K);
+  memset(C, 0, sizeof(double) * DS_ODE_MAX_K);
+  memset(D, 0, sizeof(double) * DS_ODE_MAX_K);
+  *has_d = false;
+  switch (method) {
+    case DIFFSEP_ODEF_EULER:
+      *ns = 1; B[0] = 1.0;
+      return 0;
+    case DIFFSEP_ODEF_HEUN:
+    case DIFFSEP_ODEF_AB2:
+      *ns = 2; C[1] = 1.0; A[1 * DS_ODE_MAX_K + 0] = 1.0; B[0] = 0.5; B[1] = 0.5;
+      D[0] = -0.5; D[1] = 0.5; *has_d = true;
+      return 0;
+    case DIFFSEP_ODEF_MIDPOINT:
+      *ns = 2; C[1] = 0.5; A[1 * DS_ODE_MAX_K + 0] = 0.5; B[1] = 1.0;
+      D[0] = -1.0; D[1] = 1.0; *has_d = true;
+      return 0;
+    case DIFFSEP_ODEF_RK4:
+      *ns = 4; C[1] = 0.5; C[2] = 0.5; C[3] = 1.0;
+      A[1 * DS_ODE_MAX_K + 0] = 0.5; A[2 * DS_ODE_MAX_K + 1] = 0.5; A[3 * DS_ODE_MAX_K + 2] = 1.0;
+      B[0] = 1.0 / 6; B[1] = 1.0 / 3; B[2] = 1.0 / 3; B[3] = 1.0 / 6;
+      return 0;
+  }
+  return -1;
+}
+
+// One pass = what follows one network evaluation.  x is the evaluation's input (y itself at the first stage of a step):
+//   K[kout] = f((float) t_eval, x)
+//   mode 1:  x = fp32(y + (sum_{j < nk} c[j] K[j]) h)            the next evaluation's input
+//   mode 2:  y_new = y + h sum_{j < nk} c[j] K[j]                the step; with err_nk > 0 the local-error pass
+//            ||h sum_{j < err_nk} d[j] K[j]||_rms, ||y||_rms goes to slot `step`; then y <-> y_new, x = fp32(y),
+//            and with swap_k01 K[0] <-> K[1] (AB2 keeps the previous step's drift in K[0])
+// Sums run over j = 0, 1, ... in that order, as the device pass does.
+struct OdeFixedPass {
+  int step;       // the solver step the evaluation belongs to (which engine evaluates it: head_steps / tail_steps)
+  double t_eval;
+  int kout, mode, nk;
+  double c[DS_ODE_MAX_K];
+  double h;
+  int err_nk;
+  double d[DS_ODE_MAX_K];
+  int swap_k01;
+};
+
+struct OdeFixedPlan {
+  int method = 0, M = 0, n_evals = 0;
+  bool has_err = false;    // the method has an embedded Euler step
+  double eps = 0.0;
+  int denoise = 0, N = 0;
+  std::vector<double> t;   // the grid: M + 1 times, strictly descending, inside (0, 1]
+  std::vector<OdeFixedPass> pass;  // n_evals passes
+};
+
+// Fill and validate (`who`: the entry point's name in the message; timesteps: M + 1 host times or null for the uniform
+// grid t_start -> eps; want_err: the caller asks for the local-error trace); returns the message, empty when all is well.
+inline std::string ode_fixed_plan_fill(OdeFixedPlan& p, const OdeFixedConfig& oc, const double* timesteps, bool want_err,
+                                       const char* who) {
+  const std::string w(who);
+  p = OdeFixedPlan();
+  double A[DS_ODE_MAX_K * DS_ODE_MAX_K], B[DS_ODE_MAX_K], C[DS_ODE_MAX_K], D[DS_ODE_MAX_K];
+  int ns = 0;
+  if (ds_odef_tableau(oc.method, A, B, C, D, &ns, &p.has_err) != 0)
+    return w + ": method must be DIFFSEP_ODEF_EULER, HEUN, MIDPOINT, RK4 or AB2";
+  const bool ab2 = oc.method == DIFFSEP_ODEF_AB2;
+  const int M = oc.steps;
+  if (!(M >= 1)) return w + ": steps must be >= 1";
+  if (!((long)M * ns <= DS_ODEF_MAX_EVALS)) return w + ": steps x stages must be <= 16384";
+  if (!(oc.eps > 0.0 && oc.eps < 1.0)) return w + ": eps must be in (0, 1)";
+  if (!(oc.N >= 1 || !oc.denoise)) return w + ": the denoise step needs N >= 1";
+  if (want_err && !p.has_err)
+    return w + ": err_out needs a method with an embedded Euler step (HEUN, MIDPOINT, AB2), not EULER or RK4";
+  p.method = oc.method; p.M = M; p.eps = oc.eps; p.denoise = oc.denoise; p.N = oc.N;
+  p.t.resize((size_t)M + 1);
+  if (timesteps) {
+    for (int i = 0; i <= M; ++i) p.t[i] = timesteps[i];
+  } else {
+    const double t0 = oc.t_start <= 0.0 ? 1.0 : oc.t_start;
+    if (!(t0 > oc.eps)) return w + ": t_start must be above eps";
+    for (int i = 0; i < M; ++i) p.t[i] = t0 + (oc.eps - t0) * i / M;
+    p.t[M] = oc.eps;  // (t0 + (eps - t0) M / M rounds next to eps; the solve ends where the denoise step stands)
+  }
+  for (int i = 0; i <= M; ++i)
+    if (!(p.t[i] > 0.0 && p.t[i] <= 1.0 && (i == 0 || p.t[i] < p.t[i - 1])))
+      return w + ": the time grid must be strictly descending inside (0, 1]";
+
+  auto stage_pass = [&](int i, int s, double h) {  // the pass after stage s of Runge-Kutta step i
+    OdeFixedPass q;
+    memset(&q, 0, sizeof(q));
+    q.step = i; q.t_eval = p.t[i] + C[s] * h; q.kout = s; q.h = h;
+    if (s < ns - 1) {
+      q.mode = 1; q.nk = s + 1;
+      for (int j = 0; j <= s; ++j) q.c[j] = A[(s + 1) * DS_ODE_MAX_K + j];
+    } else {
+      q.mode = 2; q.nk = ns;
+      for (int j = 0; j < ns; ++j) q.c[j] = B[j];
+      if (p.has_err) { q.err_nk = ns; for (int j = 0; j < ns; ++j) q.d[j] = D[j]; }
+    }
+    p.pass.push_back(q);
+  };
+  for (int i = 0; i < M; ++i) {
+    const double h = p.t[i + 1] - p.t[i];
+    if (!ab2 || i == 0) {
+      for (int s = 0; s < ns; ++s) stage_pass(i, s, h);
+      continue;
+    }
+    // y_{n+1} = y_n + h_n ((1 + w/2) K_n - (w/2) K_{n-1}), w = h_n / h_{n-1}; K[0] = K_{n-1}, K[1] = K_n
+    const double wr = h / (p.t[i] - p.t[i - 1]);
+    OdeFixedPass q;
+    memset(&q, 0, sizeof(q));
+    q.step = i; q.t_eval = p.t[i]; q.kout = 1; q.mode = 2; q.nk = 2; q.h = h;
+    q.c[0] = -(wr / 2); q.c[1] = 1.0 + wr / 2;
+    q.err_nk = 2; q.d[0] = -(wr / 2); q.d[1] = wr / 2;
+    q.swap_k01 = 1;
+    p.pass.push_back(q);
+  }
+  p.n_evals = (int)p.pass.size();
+  return std::string();
+}

@@ -45,6 +45,15 @@ class SamplerExt(C.Structure):
 ODE_RK45, ODE_RK23 = 0, 1
 ODE_METHODS = {"RK45": ODE_RK45, "RK23": ODE_RK23}
 ODE_WORKSPACE_BYTES = 16384
+# diffsep_ode_sample_fixed: the fixed-step methods and the network evaluations of an M-step solve
+ODEF_EULER, ODEF_HEUN, ODEF_MIDPOINT, ODEF_RK4, ODEF_AB2 = 0, 1, 2, 3, 4
+ODEF_METHODS = {"euler": ODEF_EULER, "heun": ODEF_HEUN, "midpoint": ODEF_MIDPOINT, "rk4": ODEF_RK4, "ab2": ODEF_AB2}
+ODEF_ERR_METHODS = ("heun", "midpoint", "ab2")  # those with an embedded Euler step (err_out)
+
+
+def odef_nfe(method, steps):
+    """network evaluations of a fixed-step solve (the denoise evaluation is not counted)"""
+    return {"euler": steps, "heun": 2 * steps, "midpoint": 2 * steps, "rk4": 4 * steps, "ab2": steps + 1}[method]
 
 
 class OdeConfig(C.Structure):  # diffsep_ode_config
@@ -150,6 +159,8 @@ _SIGS = {
                                 C.POINTER(OdeInfo), _P]),
     "diffsep_ode_sample_each": (_I, [_P, C.POINTER(SdeConfig), C.POINTER(OdeConfig), C.POINTER(OdeExt), _P, _P, _P, _U64, _P,
                                      _I, _L, C.POINTER(OdeInfo), C.POINTER(_I), _P]),
+    "diffsep_ode_sample_fixed": (_I, [_P, C.POINTER(SdeConfig), _I, _I, C.c_double, C.c_double, _I, _I, C.POINTER(SamplerExt), _P,
+                                      _P, _P, _U64, C.POINTER(C.c_double), _P, _P, _I, _L, C.POINTER(_I), _P]),
     "diffsep_ode_tableau": (_I, [_I, _P, _P, _P, _P, C.POINTER(_I), C.POINTER(_I)]),
     "diffsep_ode_stage_update": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_double, _P, _P, _I,
                                       _I, _L, _P]),

@@ -417,3 +417,59 @@ class Engine:
                  _ptr(x_init), _ptr(noise), int(seed) % (1 << 64), _ptr(out), B, T, infos, C.byref(evals),
                  _stream_ptr(self.device))
         return out, [_lib.ode_info_dict(i) for i in infos], int(evals.value)
+
+    def ode_sample_fixed(self, mix_norm, sde, method="heun", steps=30, t_start=None, eps=3e-2, timesteps=None, denoise=True,
+                         N=30, x_init=None, noise=None, seed=0, lengths=None, seeds=None, tail=None, head_steps=0,
+                         tail_steps=0, want_err=False):
+        """The probability-flow ODE on a fixed grid (diffsep_ode_sample_fixed): `steps` steps of "euler", "heun", "midpoint",
+        "rk4" or "ab2" from t_start (None: 1.0) down to eps, or along timesteps (steps + 1 strictly descending times inside
+        (0, 1]).  The whole solve is ENQUEUED on the current stream, like pc_sample: nothing is read back, the call does not
+        block, and its cost is known beforehand (_lib.odef_nfe).  x_init / noise / seed / lengths / seeds as in pc_sample
+        (a start below 1 needs x_init, e.g. from ops.warm_start); tail / head_steps / tail_steps: the evaluations of the
+        first head_steps and last tail_steps SOLVER steps run on another Engine.  want_err (heun, midpoint, ab2): also the
+        local-error trace, a device float64 tensor [steps,B,2] of (RMS of step minus embedded Euler step, RMS of y_i) per
+        step and utterance, not read back here.  Returns (out [B,S,T], info: nfe, method, steps[, err])."""
+        if method not in _lib.ODEF_METHODS:
+            raise NotImplementedError(f"ode_sample_fixed: method '{method}' (one of {sorted(_lib.ODEF_METHODS)})")
+        mix_norm = self._f32(mix_norm)
+        B, one, T = mix_norm.shape
+        assert one == 1
+        M = int(steps)
+        sc = _lib.sde_config(sde)
+        for name, v in (("x_init", x_init), ("noise", noise)):
+            if v is not None:
+                assert tuple(v.shape) == (B, self.S, T), f"{name} must be [B,S,T]"
+        x_init = self._f32(x_init) if x_init is not None else None
+        noise = self._f32(noise) if noise is not None else None
+        ts = None
+        if timesteps is not None:
+            ts = np.ascontiguousarray(timesteps.detach().cpu().numpy() if hasattr(timesteps, "detach") else timesteps,
+                                      dtype=np.float64).reshape(-1)
+            if ts.size != M + 1:
+                raise _lib.DiffsepError(f"ode_sample_fixed: timesteps must hold steps + 1 = {M + 1} times, got {ts.size}")
+        ext = None  # (la / sa below: the host arrays its pointers refer to, alive until this method returns)
+        hybrid = tail is not None and (tail_steps > 0 or head_steps > 0)
+        if lengths is not None or seeds is not None or hybrid:
+            ext = _lib.SamplerExt()
+            if lengths is not None:
+                la, ext.lengths_host = _lib.host_array(lengths, np.int64, B, "lengths")
+            if seeds is not None:
+                sa, ext.seeds_host = _lib.host_array(seeds, np.uint64, B, "seeds")
+            if hybrid:
+                if tail.kind != self.kind:  # an engine handle means something to the library that created it only
+                    raise _lib.DiffsepError(f"the other engine was created by the '{tail.kind}' build of the library, this one "
+                                            f"by the '{self.kind}' build: create it with Engine(..., lib_kind='{self.kind}')")
+                ext.tail_engine, ext.tail_steps, ext.head_steps = tail._h, int(tail_steps), int(head_steps)
+        out = torch.empty((B, self.S, T), dtype=torch.float32, device=mix_norm.device)
+        err = torch.empty((max(M, 0), B, 2), dtype=torch.float64, device=mix_norm.device) if want_err else None
+        nfe = C.c_int32()
+        with torch.cuda.device(self.device):
+            call(self._L, "diffsep_ode_sample_fixed", self._h, C.byref(sc), _lib.ODEF_METHODS[method], M,
+                 float(t_start) if t_start is not None else 0.0, float(eps), int(bool(denoise)), int(N),
+                 C.byref(ext) if ext is not None else None, _ptr(mix_norm), _ptr(x_init), _ptr(noise), int(seed) % (1 << 64),
+                 ts.ctypes.data_as(C.POINTER(C.c_double)) if ts is not None else None, _ptr(out), _ptr(err), B, T,
+                 C.byref(nfe), _stream_ptr(self.device))
+        info = dict(nfe=int(nfe.value), method=method, steps=M)
+        if want_err:
+            info["err"] = err
+        return out, info

@@ -48,6 +48,14 @@ its batch needed, each record carries its `ode_status` (0 reached eps, -1 step t
 summary counts them (`ode_status_counts`) and names the `sampler`.  An ODE call blocks the host on one readback per step
 attempt, so --streams adds nothing to it.
 
+--sampler ode-fixed [--ode-method {euler,heun,midpoint,rk4,ab2} --ode-steps M --ode-err] separates with the same ODE on a
+fixed grid (sdes.get_ode_fixed_sampler, diffsep_ode_sample_fixed): M steps (default N) from t = 1 down to
+eps, -s/--schedule choosing the grid.  The call is enqueued like the PC sampler's and reads nothing back, so --streams keeps
+batches in flight; `nfe` is the plan's count (heun: 2 M), the summary names `ode_method` and `ode_steps`, and --ode-err adds
+`ode_local_err` to every record: the largest over the steps of rms(step - embedded Euler step) / rms(y), read once per batch at
+collect time.  Whether such a solve separates as well as the PC sampler at equal cost is not known (no trained checkpoint was
+at hand): the flag is the instrument.  Not with --fig, --trajectory or --draws in this version.
+
 --fig and --trajectory look inside the fused sampler through its tap (diffsep_pc_sample_trace: one small launch between the
 corrector and the predictor of a reverse step; batches, streams, seeds, --dtype hybrid and the records are what they are
 without them).  --fig: the batches that hold an utterance --save-n selects ask for snapshots of the figure's steps
@@ -89,7 +97,7 @@ from typing import Callable
 import torch
 import torch.distributed as dist
 
-from . import datasets, figures, inflight, metrics, ops, synth, wavio
+from . import _lib, datasets, figures, inflight, metrics, ops, synth, wavio
 from .dist_utils import gather_objects, rank_indices
 from .inflight import plan_batches  # (its callers import it from here)
 from .pl_model import DiffSepModel, cfg_get, default_config, enhancement_config
@@ -245,9 +253,18 @@ def build_parser():
     ap.add_argument("--batch", type=int, default=16,
                     help="utterances per engine call: those with the same padded spectrogram width share a call "
                          "(zero-padded to the longest; --batch 1 = the reference's one-utterance loop)")
-    ap.add_argument("--sampler", default="pc", choices=["pc", "ode"],
+    ap.add_argument("--sampler", default="pc", choices=["pc", "ode", "ode-fixed"],
                     help="pc (default): the reference's predictor-corrector sampler; ode: the probability-flow ODE (adaptive "
-                         "RK45), one step controller per utterance of a batch")
+                         "RK45), one step controller per utterance of a batch; ode-fixed: the same ODE on a fixed grid "
+                         "(--ode-method, --ode-steps), enqueued like pc, so --streams keeps batches in flight")
+    ap.add_argument("--ode-method", default=None, choices=["euler", "heun", "midpoint", "rk4", "ab2"],
+                    help="--sampler ode-fixed: the integrator (default heun); network evaluations for M steps: euler M, heun and "
+                         "midpoint 2 M, rk4 4 M, ab2 M + 1")
+    ap.add_argument("--ode-steps", type=int, default=None, metavar="M",
+                    help="--sampler ode-fixed: solver steps from t = 1 down to eps (default: the sampler's N)")
+    ap.add_argument("--ode-err", action="store_true",
+                    help="--sampler ode-fixed with heun, midpoint or ab2: record ode_local_err, the utterance's largest relative "
+                         "local error (max over the steps of rms(step - embedded Euler step) / rms(y)), read once per batch")
     ap.add_argument("--rtol", type=float, default=1e-5, help="--sampler ode: relative tolerance (reference default)")
     ap.add_argument("--atol", type=float, default=1e-5, help="--sampler ode: absolute tolerance (reference default)")
     ap.add_argument("--max-nfe", type=int, default=0,
@@ -293,6 +310,20 @@ def main(argv=None):
             raise SystemExit(f"{flag}: the ODE sampler has no fixed reverse steps to look at (--sampler pc)")
         if on and no_proc:
             raise SystemExit(f"{flag}: __no_proc__ scores the mixture itself, there is no sampler to look into")
+    if args.sampler != "ode-fixed":
+        for flag, on in (("--ode-method", args.ode_method is not None), ("--ode-steps", args.ode_steps is not None),
+                         ("--ode-err", args.ode_err)):
+            if on:
+                raise SystemExit(f"{flag} goes with --sampler ode-fixed")
+    else:
+        for flag, on in (("--fig", args.fig), ("--trajectory", args.trajectory), ("--draws", args.draws is not None)):
+            if on:
+                raise SystemExit(f"{flag} with --sampler ode-fixed is not supported in this version")
+        if args.ode_steps is not None and args.ode_steps < 1:
+            raise SystemExit(f"--ode-steps {args.ode_steps}: at least one step")
+        args.ode_method = args.ode_method or "heun"
+        if args.ode_err and args.ode_method not in _lib.ODEF_ERR_METHODS:
+            raise SystemExit(f"--ode-err with --ode-method {args.ode_method}: the method has no embedded Euler step (heun, midpoint, ab2)")
     if args.draws is None and args.draws_out is not None:
         raise SystemExit("--draws-out goes with --draws")
     if args.draws is not None:
@@ -350,6 +381,8 @@ def main(argv=None):
         tag_inf = f"N-{N}_snr-{snr}_corrstep-{cs}_denoise-{args.denoise}_schedule-{args.schedule}"
         if args.sampler == "ode":
             tag_inf += f"_sampler-ode_rtol-{args.rtol}_atol-{args.atol}"
+        if args.sampler == "ode-fixed":
+            tag_inf += f"_sampler-ode-fixed_method-{args.ode_method}_steps-{args.ode_steps or N}"
         if args.tag is not None:
             output_dir = args.output_dir / f"{args.tag}_{tag_inf}"
         elif args.ckpt is not None and not args.synthetic_weights:
@@ -422,6 +455,7 @@ class SplitRun:
     ahead: dict = field(default_factory=dict)  # batch number -> future of its host_stage()
     ode_reruns: dict = field(default_factory=dict)  # first utterance of a repeated ODE batch -> the repeat's per-utterance infos
     trace_reruns: dict = field(default_factory=dict)  # first utterance of a repeated traced batch -> the repeat's trace
+    fixed_reruns: dict = field(default_factory=dict)  # first utterance of a repeated ode-fixed batch -> the repeat's info
 
     def __post_init__(self):
         a = self.args
@@ -473,6 +507,11 @@ class SplitRun:
             a = self.args
             return model.get_ode_sampler(mix_n, N=self.sampler_kw["N"], denoise=a.denoise, rtol=a.rtol, atol=a.atol,
                                          max_nfe=a.max_nfe, lengths=lens, seeds=[self.seeds[i] for i in group])
+        if self.args.sampler == "ode-fixed":  # a fixed grid: enqueued like the PC call; sampler.info: nfe, method, steps[, err]
+            a = self.args
+            return model.get_ode_fixed_sampler(mix_n, N=self.sampler_kw["N"], denoise=a.denoise, method=a.ode_method,
+                                               steps=a.ode_steps, schedule=a.schedule, lengths=lens,
+                                               seeds=[self.seeds[i] for i in group], want_err=a.ode_err, check_finite=False)
         tap = {}
         if trace and any(self.wants_fig(i) for i in group):
             tap["snapshots"] = self.fig_steps
@@ -560,6 +599,8 @@ class SplitRun:
         out = sampler()
         if self.args.sampler == "ode":
             self.ode_reruns[b.group[0]] = sampler.info
+        elif self.args.sampler == "ode-fixed":
+            self.fixed_reruns[b.group[0]] = sampler.info
         elif traced:
             self.trace_reruns[b.group[0]] = sampler.trace
         return out
@@ -578,6 +619,11 @@ class SplitRun:
         ode = None  # --sampler ode: the utterances' own solver counts
         if not self.no_proc and a.sampler == "ode":
             ode = self.ode_reruns.pop(group[0], None) or b.sampler.info
+        fixed_err = None  # --sampler ode-fixed --ode-err: per utterance max over the steps of err / rms(y), one read per batch
+        if not self.no_proc and a.sampler == "ode-fixed" and a.ode_err:
+            info = self.fixed_reruns.pop(group[0], None) or b.sampler.info
+            with torch.cuda.stream(stream):
+                fixed_err = (info["err"][:, :, 0] / info["err"][:, :, 1]).amax(dim=0).cpu().tolist()
         with torch.cuda.stream(stream):
             mets = compute_metrics(est, tgt_n, self.n_src)
         trace = None  # what the sampler's tap left (--fig, --trajectory; none for a warm-up call)
@@ -617,6 +663,8 @@ class SplitRun:
                    "runtime": runtime, "len_s": lens[k] / self.fs}
             if ode is not None:
                 rec["ode_status"] = int(ode[k]["status"])
+            if fixed_err is not None:
+                rec["ode_local_err"] = float(fixed_err[k])
             if sloss is not None:
                 rec["score_loss"] = float(sloss[k])
             if dfields is not None:
@@ -674,6 +722,8 @@ class SplitRun:
                         # (DESIGN.md section 7); STOI / ESTOI is diffsep_amd.metrics.stoi (published algorithm, restated)
                         "not_computed": ["pesq"] + (["stoi"] if a.no_stoi else []) + (["csig", "cbak", "covl"] if a.composite else []),
                         "stoi_on": a.stoi_on, "stoi_extended": not a.stoi_no_extended, "pesq_mode": a.pesq_mode})
+        if model is not None and a.sampler == "ode-fixed":
+            summary.update({"ode_method": a.ode_method, "ode_steps": int(a.ode_steps or self.sampler_kw["N"])})
         if model is not None and a.sampler == "ode":
             summary["ode_status_counts"] = {str(c): sum(1 for r in flat if r.get("ode_status") == c) for c in (0, -1, 1)}
         with open(self.output_dir / f"{self.split}_summary.json", "w") as f:

@@ -265,6 +265,32 @@ class DiffSepModel:
         kwargs = {"eps": self.t_eps, **kwargs}
         return sdes.get_ode_sampler(sde, self, y, **kwargs)
 
+    def get_ode_fixed_sampler(self, y, N=None, check_finite=True, **kwargs):
+        """sdes.get_ode_fixed_sampler on this model (extension): the probability-flow ODE on a fixed grid,
+        one enqueued engine call of known cost.  eps defaults to t_eps, steps to the sampler's N, which is also the denoise
+        step's N.  check_finite: as in get_pc_sampler — the overflow net of the 16-bit modes; a caller that keeps batches in
+        flight passes False and calls rerun_if_nonfinite when it collects one."""
+        sde = self.sde.copy()
+        sde.N = self.sde.N if N is None else N
+        kwargs = {"eps": self.t_eps, **kwargs}
+        inner = sdes.get_ode_fixed_sampler(sde, self, y, **kwargs)
+        if not check_finite or not self.has_fallback():
+            return inner
+
+        def checked(z=None, **_):
+            def rerun(fb):
+                again = sdes.get_ode_fixed_sampler(sde, fb, y, **kwargs)
+                result = again(z)
+                checked.info = again.info
+                return result
+
+            result = inner(z)
+            checked.info = inner.info
+            return self.rerun_if_nonfinite(result, rerun)
+
+        checked.info = None
+        return checked
+
     def get_pc_sampler(self, predictor_name, corrector_name, y, N=None, minibatch=None, schedule=None, check_finite=True,
                        **kwargs):
         """check_finite (extension): the returned sampler looks at its samples and repeats the request on fallback_model()
@@ -342,15 +368,22 @@ class DiffSepModel:
         batched_sampling_fn.trace = None
         return batched_sampling_fn
 
-    def separate(self, mix, **kwargs):
+    def separate(self, mix, sampler="pc", **kwargs):
+        """sampler="pc" (the reference's call) or "ode-fixed" (extension: the fixed-step probability-flow solve; method=,
+        steps=, schedule=, seed= ... of get_ode_fixed_sampler)"""
         (mix_n, _), mean, std = self.normalize_batch((mix, None))
+        if sampler == "ode-fixed":
+            est, _ = self.get_ode_fixed_sampler(mix_n, **kwargs)()
+            return self.denormalize_batch(est, mean, std)
+        if sampler != "pc":
+            raise ValueError(f"separate: sampler must be 'pc' or 'ode-fixed', got '{sampler}'")
         skw = dict(cfg_get(self.config, "model.sampler", {}))
         skw.update(kwargs)
         est, *others = self.get_pc_sampler("reverse_diffusion", "ald2", mix_n, **skw)()
         return self.denormalize_batch(est, mean, std)
 
     def refine(self, mix, est, t_start=0.5, lengths=None, seeds=None, scale="ls", mean_from="mix", check_finite=True,
-               **sampler_kwargs):
+               sampler="pc", method="heun", steps=None, **sampler_kwargs):
         """Refine another separator's estimates (extension): est [B,S,T] is diffused forward to the step
         time ts[first] nearest below t_start with the SDE's own marginal (ops.warm_start: least-squares gains per file with
         scale "ls", the source average taken from the mixture with mean_from "mix"), and only the reverse steps [first, N) of the
@@ -360,7 +393,10 @@ class DiffSepModel:
         RNG seeds (default: one draw of torch's generator each); file b's perturbation is draw 0 of its seed — the prior draw of
         a full run — and its steps take the draws the full run's would.  Returns (sep [B,S,T], info): first_step, t (the start
         time), nfe, gains [B,S] float64 and fallback [B] int32 (1: the fit of that file met silent or proportional estimates
-        and used gains of 1) — both left on the device, nothing is read back here.  check_finite: as in get_pc_sampler."""
+        and used gains of 1) — both left on the device, nothing is read back here.  check_finite: as in get_pc_sampler.
+        sampler="ode-fixed" (DESIGN.md section 5l): a deterministic refinement — est is diffused to t_start ITSELF (no snapping to
+        a step grid) and `steps` steps (default N) of `method` of the fixed-step probability-flow solve run from t_start down to
+        eps (schedule= as in get_ode_fixed_sampler); info then holds t, nfe, method, steps, gains and fallback."""
         from .separate import scale_output
         if mix.dim() == 2:
             mix = mix[None]
@@ -371,9 +407,18 @@ class DiffSepModel:
         lens = [T] * B if lengths is None else [int(L) for L in lengths]
         skw = dict(sampler_kwargs)
         N = self.sde.N if skw.get("N") is None else int(skw["N"])
-        ts = sdes.sampler_timesteps(N, skw.get("eps", self.t_eps), skw.get("schedule"), T=self.sde.T)
-        first = sdes.first_step_for(t_start, ts)
-        t0 = float(ts[first])
+        if sampler not in ("pc", "ode-fixed"):
+            raise ValueError(f"refine: sampler must be 'pc' or 'ode-fixed', got '{sampler}'")
+        fixed = sampler == "ode-fixed"
+        if fixed:
+            eps_ = skw.get("eps", self.t_eps)
+            if not eps_ < float(t_start) <= self.sde.T:
+                raise ValueError(f"refine: t_start = {t_start} must lie in (eps, T] = ({eps_}, {self.sde.T}]")
+            first, t0 = None, float(t_start)
+        else:
+            ts = sdes.sampler_timesteps(N, skw.get("eps", self.t_eps), skw.get("schedule"), T=self.sde.T)
+            first = sdes.first_step_for(t_start, ts)
+            t0 = float(ts[first])
         mix_n = torch.zeros_like(mix)
         mean, std = (torch.empty(B, dtype=torch.float32, device=mix.device) for _ in range(2))
         for b, L in enumerate(lens):  # every file over ITS samples (pl_model.py:81-88), the tail left at zero
@@ -385,6 +430,15 @@ class DiffSepModel:
         t = torch.full((B,), t0, dtype=torch.float32, device=mix.device)
         x_init, gains, fallback = ops.warm_start(self.sde, est, mix, mix_n, mean, std, t, scale=scale, mean_from=mean_from,
                                                  seeds=seeds, lengths=lens)
+        if fixed:
+            run = self.get_ode_fixed_sampler(mix_n, check_finite=check_finite, method=method, steps=steps, t_start=t0,
+                                             **{**skw, "lengths": lens, "x_init": x_init})
+            with torch.no_grad():
+                sep, nfe = run()
+            out = torch.zeros_like(sep)
+            for b, L in enumerate(lens):
+                out[b, :, :L] = scale_output(mix[b:b + 1, :, :L], sep[b:b + 1, :, :L])[0]
+            return out, {"t": t0, "nfe": nfe, "method": method, "steps": run.info["steps"], "gains": gains, "fallback": fallback}
         sampler = self.get_pc_sampler("reverse_diffusion", "ald2", mix_n, check_finite=check_finite,
                                       **{**skw, "lengths": lens, "seeds": seeds, "x_init": x_init, "first_step": first})
         with torch.no_grad():

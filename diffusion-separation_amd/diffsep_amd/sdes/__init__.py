@@ -1,7 +1,8 @@
 """Sampler factories with the reference signatures (sdes/__init__.py:46-190).
 
 get_pc_sampler(...) returns a closure `pc_sampler() -> (x, nfe[, intermediates])`; get_ode_sampler(...) returns
-`ode_sampler(z=None) -> (x, nfe)`, the probability-flow ODE integrated by the engine's device-resident RK45 / RK23.  When score_fn is an
+`ode_sampler(z=None) -> (x, nfe)`, the probability-flow ODE integrated by the engine's device-resident RK45 / RK23;
+get_ode_fixed_sampler(...) the same ODE on a fixed grid at a cost known beforehand, enqueued like the PC sampler.  When score_fn is an
 engine-backed model and the request is the default path (reverse_diffusion + ald2/none, no
 intermediates) the whole loop runs as ONE engine call (hipGraph-replayed network evaluations, fused
 update kernels, on-device Philox noise seeded from torch's generator); otherwise the generic
@@ -18,7 +19,7 @@ from .predictors import Predictor, PredictorRegistry, ReverseDiffusionPredictor
 from .sdes import MixSDE, PriorMixSDE, SDERegistry
 
 __all__ = ["PredictorRegistry", "CorrectorRegistry", "SDERegistry", "Predictor", "Corrector", "MixSDE", "PriorMixSDE",
-           "get_pc_sampler", "get_pc_scheduled_sampler", "get_ode_sampler", "sampler_timesteps", "first_step_for"]
+           "get_pc_sampler", "get_pc_scheduled_sampler", "get_ode_sampler", "get_ode_fixed_sampler", "ode_fixed_timesteps", "sampler_timesteps", "first_step_for"]
 
 
 def _timesteps(sde, eps, schedule, device):
@@ -259,6 +260,81 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
             if inverse_scaler is not None:
                 x = inverse_scaler(x)
             return x, info["nfev"]
+
+    ode_sampler.info = None
+    return ode_sampler
+
+
+def ode_fixed_timesteps(steps, eps=3e-2, schedule="linear", t_start=1.0):
+    """The steps + 1 float64 times of a fixed-step solve from t_start down to eps (host numpy), by the rules of the scheduled
+    samplers above with sde.T -> t_start and N -> steps: "linear", "log", "revlog"."""
+    class _G:
+        pass
+    g = _G()
+    g.T, g.N = float(t_start), int(steps)
+    if schedule not in ("linear", "log", "revlog"):
+        raise NotImplementedError(f"Schedule '{schedule}' does not exist")
+    with torch.no_grad():
+        prev = torch.get_default_dtype()
+        try:
+            torch.set_default_dtype(torch.float64)
+            ts = _timesteps(g, eps, schedule, "cpu").to(torch.float64).numpy().copy()
+        finally:
+            torch.set_default_dtype(prev)
+    ts[0], ts[-1] = float(t_start), float(eps)  # (10 ** log10(x) is x to rounding only: the ends are the caller's numbers)
+    return ts
+
+
+_ODE_FIXED_KWARGS = ("seed", "noise", "lengths", "seeds", "x_init", "want_err", "timesteps")
+
+
+def get_ode_fixed_sampler(sde, score_fn, y, method="heun", steps=None, schedule=None, t_start=None, denoise=True, eps=3e-2,
+                          **kwargs):
+    """The probability-flow ODE of get_ode_sampler on a FIXED grid (no counterpart in the reference): `steps` steps (default
+    sde.N) of method "euler" (steps network evaluations), "heun" / "midpoint" (2 steps), "rk4" (4 steps) or "ab2" (two-step
+    Adams-Bashforth after a Heun step: steps + 1) from t_start (None: sde.T) down to eps, then (denoise) the reverse_diffusion
+    step at eps without noise.  One engine call (Engine.ode_sample_fixed) that is ENQUEUED and does not block: no error norm is
+    read back, so batches can be kept in flight as with the PC sampler.  Whether such a solve separates as well as the PC
+    sampler at equal cost is not known (no trained checkpoint was available when this was written): this is the instrument.
+
+    schedule: None (the uniform grid) or "linear" / "log" / "revlog" (ode_fixed_timesteps); timesteps= gives the steps + 1
+    times directly.  Further **kwargs: seed, noise ([B,S,T] prior draws), x_init ([B,S,T], the state at t_start; needed when
+    t_start < sde.T — ops.warm_start builds one), lengths / seeds (a zero-padded batch, per-utterance seeds), want_err (heun,
+    midpoint, ab2: the local-error trace [steps,B,2] on the device, ode_sampler.info["err"]).  On a dtype="hybrid" model
+    the evaluations of the first head_steps solver steps run on its split-precision engine.
+    Returns ode_sampler(z=None) -> (x, nfe); z [B,S,T] is used as the start state when given."""
+    if method not in _lib.ODEF_METHODS:
+        raise NotImplementedError(f"get_ode_fixed_sampler: method '{method}' is not implemented (one of {sorted(_lib.ODEF_METHODS)})")
+    bad = sorted(set(kwargs) - set(_ODE_FIXED_KWARGS))
+    if bad:
+        raise TypeError(f"get_ode_fixed_sampler() got unexpected keyword argument(s) {bad} (accepted: {list(_ODE_FIXED_KWARGS)})")
+    if not isinstance(sde, MixSDE):
+        raise TypeError("get_ode_fixed_sampler: sde must be a MixSDE / PriorMixSDE")
+    eng = _engine_of(score_fn)
+    if eng is None:
+        raise ValueError("get_ode_fixed_sampler: score_fn has no engine (an engine-backed DiffSepModel / ScoreModelNCSNpp is "
+                         "needed; the fixed-step ODE sampler has no host fallback)")
+    M = int(sde.N if steps is None else steps)
+    ts = kwargs.get("timesteps")
+    if ts is not None and schedule is not None:
+        raise ValueError("get_ode_fixed_sampler: schedule= and timesteps= are alternatives")
+    if schedule is not None:
+        ts = ode_fixed_timesteps(M, eps, schedule, sde.T if t_start is None else t_start)
+    seed = kwargs.get("seed")
+
+    def ode_sampler(z=None, **_):
+        with torch.no_grad():
+            s_ = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+            x0 = z if z is not None else kwargs.get("x_init")
+            tail = getattr(score_fn, "tail_engine", lambda: None)()
+            x, info = eng.ode_sample_fixed(y, sde.engine_config(), method=method, steps=M, t_start=t_start, eps=eps,
+                                           timesteps=ts, denoise=denoise, N=sde.N, x_init=x0,
+                                           noise=kwargs.get("noise") if x0 is None else None, seed=s_,
+                                           lengths=kwargs.get("lengths"), seeds=kwargs.get("seeds"), tail=tail,
+                                           head_steps=getattr(score_fn, "head_steps", 0) if tail is not None else 0,
+                                           want_err=bool(kwargs.get("want_err", False)))
+            ode_sampler.info = info
+            return x, info["nfe"]
 
     ode_sampler.info = None
     return ode_sampler

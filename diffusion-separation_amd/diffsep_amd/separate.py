@@ -41,6 +41,14 @@ step time at or below TAU with the SDE's own marginal, and only the reverse step
 network evaluations.  The run prints the executed steps, the evaluations per file and the files whose gain fit fell back to 1.
 A missing estimate, one whose length or rate differs from its mixture's, --t-start without --init-dir (or the reverse) and a
 combination with --chunk, --draws, --sampler ode or --resample are refused by name before any engine is created.
+--sampler ode-fixed [--ode-method {euler,heun,midpoint,rk4,ab2}] [--ode-steps M]: the probability-flow ODE on a fixed grid
+(DiffSepModel.get_ode_fixed_sampler, diffsep_ode_sample_fixed) — M steps (default N) of Heun's method (default)
+from t = 1 down to eps, deterministic given the seed, at a cost known beforehand (heun: 2 M network evaluations + the denoise
+one).  The call is enqueued like the PC sampler's, so --batch, --streams, --seed, --schedule, --resample and the precision flags
+(--fp32-steps counting solver steps) apply as they do there, and the written files do not depend on --batch or --streams.  With
+--init-dir DIR --t-start TAU the solve starts at TAU itself (no snapping to a step grid) and runs M steps from there.  Not with
+--chunk or --draws in this version.  Whether such a solve separates as well as the PC sampler at equal cost is not known (no
+trained checkpoint was at hand): this is the instrument.
 """
 import argparse
 from pathlib import Path
@@ -166,7 +174,11 @@ def separate_on_device(mix, model, sampler_kwargs, device, lengths=None, seeds=N
     if seeds is not None:
         extra["seeds"] = list(seeds)
     # (check_finite=False: the callers below collect the result later and run the model's overflow net then)
-    sampler = model.get_pc_sampler("reverse_diffusion", "ald2", mix_norm, check_finite=check_finite, **sampler_kwargs, **extra)
+    if sampler_kwargs.get("sampler") == "ode-fixed":  # --sampler ode-fixed: enqueued like the PC call (fixed_sampler_kwargs)
+        fkw = {k: v for k, v in sampler_kwargs.items() if k != "sampler"}
+        sampler = model.get_ode_fixed_sampler(mix_norm, check_finite=check_finite, **fkw, **extra)
+    else:
+        sampler = model.get_pc_sampler("reverse_diffusion", "ald2", mix_norm, check_finite=check_finite, **sampler_kwargs, **extra)
     with torch.no_grad():
         sep, nfe, *_ = sampler()
     if lengths is None:
@@ -175,6 +187,36 @@ def separate_on_device(mix, model, sampler_kwargs, device, lengths=None, seeds=N
     for b, L in enumerate(lengths):  # the least-squares scale of separate.py:73-78 is per file, over ITS samples
         out[b, :, :L] = scale_output(mix[b:b + 1, :, :L], sep[b:b + 1, :, :L])[0]
     return out
+
+
+def add_ode_fixed_arguments(ap):
+    ap.add_argument("--ode-method", default=None, choices=["euler", "heun", "midpoint", "rk4", "ab2"],
+                    help="--sampler ode-fixed: the integrator (default heun); network evaluations for M steps: euler M, heun and "
+                         "midpoint 2 M, rk4 4 M, ab2 M + 1")
+    ap.add_argument("--ode-steps", type=int, default=None, metavar="M",
+                    help="--sampler ode-fixed: solver steps from t = 1 (or --t-start) down to eps (default: the sampler's N)")
+
+
+def check_ode_fixed_arguments(args, unsupported):
+    """SystemExit, naming the flag, for what --sampler ode-fixed does not run in this version (unsupported: (flag, given) pairs)
+    and for its own flags given without it; args.ode_method gets its default"""
+    if args.sampler != "ode-fixed":
+        for flag, v in (("--ode-method", args.ode_method), ("--ode-steps", args.ode_steps)):
+            if v is not None:
+                raise SystemExit(f"{flag} goes with --sampler ode-fixed")
+        return
+    for flag, on in unsupported:
+        if on:
+            raise SystemExit(f"{flag} with --sampler ode-fixed is not supported in this version")
+    if args.ode_steps is not None and args.ode_steps < 1:
+        raise SystemExit(f"--ode-steps {args.ode_steps}: at least one step")
+    args.ode_method = args.ode_method or "heun"
+
+
+def fixed_sampler_kwargs(args, N):
+    """what separate_on_device / DiffSepModel.refine pass on for --sampler ode-fixed (the key "sampler" marks them)"""
+    return {"sampler": "ode-fixed", "N": N, "denoise": args.denoise, "schedule": args.schedule, "method": args.ode_method,
+            "steps": args.ode_steps}
 
 
 def separate_ode(mix, model, ode_kwargs, device, seed=None):
@@ -387,7 +429,8 @@ def add_init_arguments(ap):
                          "--schedule and the precision flags; NOT with --chunk, --draws, --sampler ode or --resample in this version")
     ap.add_argument("--t-start", type=float, default=None, metavar="TAU",
                     help="with --init-dir: the diffusion time in (eps, 1] to start from; the run begins at the first step time at "
-                         "or below it (0.5 with -N 30: half the network evaluations)")
+                         "or below it (0.5 with -N 30: half the network evaluations); with --sampler ode-fixed the solve starts at TAU "
+                         "itself and runs --ode-steps steps from there")
     ap.add_argument("--init-scale", default=None, choices=["ls", "none"],
                     help="with --init-dir: ls (default) fits one gain per estimate against the mixture first (estimates of "
                          "arbitrary scale and sign); none takes them as they are")
@@ -443,10 +486,15 @@ def separate_refined(args, files, rates, seeds, models, streams, kw, S):
     if S != eng.S:
         raise SystemExit(f"--init-dir: {S} source folders s0 .. s{S - 1} in {args.init_dir}, the model separates {eng.S} sources")
     N = kw["N"] if kw.get("N") is not None else models[0].sde.N
-    try:
-        first = sdes.first_step_for(args.t_start, sdes.sampler_timesteps(N, models[0].t_eps, kw.get("schedule"), T=models[0].sde.T))
-    except ValueError as e:
-        raise SystemExit(f"--t-start {args.t_start}: {e}")
+    fixed = kw.get("sampler") == "ode-fixed"
+    if fixed:  # (the solve starts at --t-start itself: there is no step grid to snap to)
+        if not models[0].t_eps < args.t_start <= models[0].sde.T:
+            raise SystemExit(f"--t-start {args.t_start}: a diffusion time in (eps, 1] = ({models[0].t_eps:g}, {models[0].sde.T:g}] is needed")
+    else:
+        try:
+            first = sdes.first_step_for(args.t_start, sdes.sampler_timesteps(N, models[0].t_eps, kw.get("schedule"), T=models[0].sde.T))
+        except ValueError as e:
+            raise SystemExit(f"--t-start {args.t_start}: {e}")
     if seeds is None:  # one draw of torch's generator per file, as a file without --seed gets one per engine call
         seeds = [int(torch.randint(0, 2 ** 62, (1,)).item()) for _ in files]
     batches = inflight.plan_batches(range(len(files)), lengths, eng.padded_frames, max(1, args.batch))
@@ -484,6 +532,10 @@ def separate_refined(args, files, rates, seeds, models, streams, kw, S):
 
     inflight.Ring(streams, launch, collect).run(batches)
     fb = f"; gain fit fell back to 1 for {sorted(seen['fell_back'])}" if seen["fell_back"] else ""
+    if fixed:
+        print(f"refined {len(files)} files from {args.init_dir} into {args.output_dir}: {kw['steps'] or N} {kw['method']} steps of the "
+              f"probability-flow ODE from t = {args.t_start:g}, NFE {seen['nfe']} per file{fb}")
+        return
     print(f"refined {len(files)} files from {args.init_dir} into {args.output_dir}: steps [{first}, {N}) of {N} from t = {args.t_start:g}, "
           f"NFE {seen['nfe']} per file{fb}")
 
@@ -505,10 +557,13 @@ def main(argv=None):
     ap.add_argument("--streams", type=int, default=1, help="engine calls in flight: K engines on K HIP streams")
     ap.add_argument("--seed", type=int, default=None,
                     help="file i (sorted) gets the i-th draw of a generator with this seed as its device RNG seed")
-    ap.add_argument("--sampler", default="pc", choices=["pc", "ode"],
+    ap.add_argument("--sampler", default="pc", choices=["pc", "ode", "ode-fixed"],
                     help="pc (default): the reference's predictor-corrector sampler; ode: the probability-flow ODE "
                          "(adaptive RK45, sdes.get_ode_sampler); with --batch K the files of a batch share the network "
-                         "evaluations, each with its own step controller")
+                         "evaluations, each with its own step controller; ode-fixed: the same ODE on a fixed grid "
+                         "(--ode-method, --ode-steps), deterministic given the seed, at a cost known beforehand, enqueued like pc "
+                         "(--batch, --streams, --schedule, --init-dir / --t-start all apply)")
+    add_ode_fixed_arguments(ap)
     ap.add_argument("--rtol", type=float, default=1e-5, help="--sampler ode: relative tolerance (reference default)")
     ap.add_argument("--atol", type=float, default=1e-5, help="--sampler ode: absolute tolerance (reference default)")
     ap.add_argument("--max-nfe", type=int, default=0,
@@ -525,6 +580,7 @@ def main(argv=None):
     add_draws_arguments(ap)
     add_init_arguments(ap)
     args = ap.parse_args(argv)
+    check_ode_fixed_arguments(args, (("--chunk", args.chunk is not None), ("--draws", args.draws is not None)))
     check_draws_arguments(args, chunk=args.chunk is not None)
     init_sources = check_init_arguments(args, sorted(args.input_dir.glob("*.wav")))
     if args.chunk is None and args.overlap is not None:
@@ -545,6 +601,8 @@ def main(argv=None):
         raise SystemExit("No GPU visible: this build has no CPU path (the reference falls back to CPU here)")
     torch.cuda.set_device(torch.device(args.device))
     model, kw = get_model(args)
+    if args.sampler == "ode-fixed":
+        kw = fixed_sampler_kwargs(args, kw["N"])
     models, streams = inflight.setup_workers(model, K, own_stream=False)  # (K = 1 runs on the current stream)
     model_sr = cfg_get(model.config, "model.fs", 8000)
     if args.output_dir.is_file():

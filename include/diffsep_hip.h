@@ -322,6 +322,51 @@ int32_t diffsep_ode_sample_each(diffsep_engine* e, const diffsep_sde_config* sde
                                 const diffsep_ode_ext* ext, const float* mix_norm, const float* x_init,
                                 const float* noise, uint64_t seed, float* out, int32_t B, int64_t T,
                                 diffsep_ode_info* infos, int32_t* evals_run, void* stream);
+/* The same ODE on a FIXED GRID with a budget the caller chooses (no counterpart in the reference, whose only ODE solve is the
+ * adaptive one above; the right-hand side is the reference's: RSDE.sde with probability_flow, sdes/sdes.py:130-160, as
+ * sdes/__init__.py:193-278 hands it to solve_ivp).  No error norm decides anything, so the call enqueues the whole solve on
+ * `stream` and returns: no readback, no event wait, no stream synchronisation — like diffsep_pc_sample_from, and with its
+ * extensions.  One network evaluation + one fused pass (csrc/ode.hip, the per-utterance form) per stage.
+ *   method, steps (M) : DIFFSEP_ODEF_EULER (M evaluations), HEUN and MIDPOINT (2 M), RK4 (4 M: the classic tableau) or AB2
+ *                       (M + 1): y_{n+1} = y_n + h_n ((1 + w/2) K_n - (w/2) K_{n-1}), w = h_n / h_{n-1}, after a first Heun step
+ *                       whose K_0 is kept;
+ *   t_start, eps      : the grid t_i = t_start + (eps - t_start) i / M, i < M, and t_M = eps; t_start <= 0 means 1.0 (sde.T);
+ *   timesteps_host    : NULL, or M + 1 HOST float64 times that replace that grid: strictly descending, inside (0, 1].
+ *                       h_i = t_{i+1} - t_i exactly (a true integration: the dt = 1/N of quirk Q1 is the denoise step's only);
+ *                       stage s of step i is evaluated at (float)(t_i + C[s] h_i), state in fp64, K in fp32, as above;
+ *   denoise, N        : as diffsep_ode_config: one reverse_diffusion predictor step at eps without noise, its x_mean;
+ *   x_init / noise / seed : the prior as in diffsep_ode_sample — the caller's state, or the prior sample from noise [B,S,T],
+ *                       or from draw 0 of the PC sampler's device generator under seed / ext->seeds_host.  A grid that starts
+ *                       below 1 needs x_init (diffsep_warm_start builds one at any time);
+ *   ext (may be NULL) : lengths_host — B independent zero-padded rows: row b inside its length is bit for bit the call on that
+ *                       utterance alone (B = 1, T = lengths[b], same seed) wherever the fp32 network evaluation does not depend
+ *                       on the batch, and its tail is zero; seeds_host — per-utterance seeds of the prior draw (unused with
+ *                       x_init); tail_engine with head_steps / tail_steps counted in SOLVER STEPS of this grid: every stage
+ *                       evaluation of the first head_steps and the last tail_steps steps runs on it (state and time copied
+ *                       over, the state lives on e; the denoise evaluation is e's).  A range that holds no such step never
+ *                       touches it;
+ *   err_out           : NULL, or device float64 [M][B][2] (HEUN, MIDPOINT, AB2): per step i and utterance b the RMS over the
+ *                       utterance of (step - embedded Euler step) = h (K1 - K0) / 2, h (K1 - K0), h (w/2)(K_n - K_{n-1}), and the
+ *                       RMS of y_i; fixed-order fp64 sums (the error-norm pass with rtol = 0, atol = 1), nothing read back.
+ *                       With NULL not one launch, copy or allocation is added and `out` is the same bits;
+ *   nfe_out           : the evaluation count above, known before the call (the denoise evaluation is not counted).
+ * Refused with an error text before anything is enqueued: an unknown method, steps < 1, steps x stages > 16384, a grid that
+ * is not strictly descending inside (0, 1], eps outside (0, 1), t_start <= eps, denoise with N < 1, err_out with EULER or
+ * RK4, x_init together with noise, a start below 1 without x_init, seeds with noise, and the length checks of
+ * diffsep_pc_sample_from.  Buffers: those of diffsep_ode_sample plus the uploaded tables (evaluation times [M x stages + 1][B],
+ * h [M][B], active, lengths: one upload through a pinned stage before the first evaluation) and, with err_out, one partial-sum
+ * slab per utterance.
+ * (The solve's shape is passed as plain arguments, not as a struct: host code keeps them in OdeFixedConfig, csrc/ode_host.h.) */
+#define DIFFSEP_ODEF_EULER 0
+#define DIFFSEP_ODEF_HEUN 1
+#define DIFFSEP_ODEF_MIDPOINT 2
+#define DIFFSEP_ODEF_RK4 3
+#define DIFFSEP_ODEF_AB2 4
+int32_t diffsep_ode_sample_fixed(diffsep_engine* e, const diffsep_sde_config* sde, int32_t method, int32_t steps,
+                                 double t_start, double eps, int32_t denoise, int32_t N, const diffsep_sampler_ext* ext,
+                                 const float* mix_norm, const float* x_init, const float* noise, uint64_t seed,
+                                 const double* timesteps_host, float* out, double* err_out, int32_t B, int64_t T,
+                                 int32_t* nfe_out, void* stream);
 /* Butcher tableau of RK45 / RK23 exactly as scipy's rk.py holds it (sdes/__init__.py:193-278 -> solve_ivp): A [ns][ns]
  * row-major, B [ns], C [ns], E [ns+1]; every pointer may be NULL (host memory, no GPU needed). */
 int32_t diffsep_ode_tableau(int32_t method, double* A, double* B, double* C, double* E, int32_t* n_stages,

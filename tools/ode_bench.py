@@ -1,7 +1,7 @@
 """Cost of the probability-flow ODE sampler (Engine.ode_sample, sdes.get_ode_sampler) on one GPU.
 
     python tools/ode_bench.py [--nf 64] [--B 16] [--T 32000] [--rtol 1e-5] [--atol 1e-5] [--max-nfe 600]
-                              [--dtypes f32,split,f16] [--reps 2] [--each]
+                              [--dtypes f32,split,f16] [--reps 2] [--each | --fixed]
 
 Synthetic weights, synthetic mixtures, MixSDE.  Per engine dtype: nfev / accepted / rejected / status of the solve, the
 wall time of one batch (median of --reps timed calls after one warm-up call), and the share of that time spent outside
@@ -14,6 +14,13 @@ network evaluation).  Per dtype: the wall time of one ode_sample_each call on th
 the SUM of the wall times of B calls of ode_sample on the utterances one by one (B = 1, the same seeds, after one warm-up
 call of that plan), the evaluations the batch call ran (evals_run = the largest nfev), the utterances' nfev range and
 whether every row of the batch call equals its B = 1 result bit for bit (expected on f32 only).
+
+--fixed: the fixed-step sampler (Engine.ode_sample_fixed: Heun M = 30, 60 evaluations + denoise, and Euler M = 30, 30 + denoise)
+next to the PC sampler of the same plan (N = 30, one corrector step: 60 evaluations) in the same process.  Per dtype, first one
+batch at a time — --reps timed calls of each of the three, alternating, after two warm-up calls each: median wall, min - max,
+and the wall per network evaluation — then --streams K (default 4) engines on K streams through inflight.Ring, --batches
+batches each, the three again alternating: wall per batch and batches per second; and the local-error trace of Heun at M = 30 and
+M = 120 (want_err).  Prints one JSON line per dtype.
 """
 import argparse
 import json
@@ -65,6 +72,63 @@ def bench_each(eng, mix_norm, args, name):
                           rows_equal_solo=equal)), flush=True)
 
 
+def bench_fixed(cfg, sd, mix_norm, args, name):
+    from diffsep_amd import inflight
+    K = max(1, args.streams)
+    # engines before streams: HIP hands out hardware queues in stream-creation order (inflight.setup_workers)
+    engines = [Engine(cfg, pack_state_dict(cfg, sd)) for _ in range(K)]
+    for e in engines:
+        e.reserve(mix_norm.shape[0], mix_norm.shape[2])
+    streams = [torch.cuda.Stream() for _ in range(K)]
+    runs = {"pc": (lambda e: e.pc_sample(mix_norm, MIX, N=30, corrector_steps=1, seed=1)[0], 60),
+            "heun30": (lambda e: e.ode_sample_fixed(mix_norm, MIX, method="heun", steps=30, seed=1)[0], 61),
+            "euler30": (lambda e: e.ode_sample_fixed(mix_norm, MIX, method="euler", steps=30, seed=1)[0], 31)}
+    res = dict(mode="fixed", dtype=name, nf=args.nf, B=mix_norm.shape[0], T=args.T, streams=K, batches=args.batches,
+               hw_queues=os.environ.get("GPU_MAX_HW_QUEUES"))
+    walls = {k: [] for k in runs}
+    for k, (fn, _) in runs.items():  # warm-up: plan, graph capture, buffers — on every engine
+        for e in engines:
+            fn(e)
+            fn(e)
+    torch.cuda.synchronize()
+    for _ in range(max(1, args.reps)):
+        for k, (fn, _) in runs.items():
+            out, w = timed(lambda: fn(engines[0]))
+            walls[k].append(w)
+            res[k + "_finite"] = bool(torch.isfinite(out).all())
+    for k, (_, evals) in runs.items():
+        ws = sorted(walls[k])
+        med = ws[len(ws) // 2]
+        res[k] = dict(evals=evals, wall_ms=round(med * 1e3, 2), min_ms=round(ws[0] * 1e3, 2), max_ms=round(ws[-1] * 1e3, 2),
+                      ms_per_eval=round(med * 1e3 / evals, 4))
+    # the local-error trace of Heun: per step the largest over the utterances of rms(step - Euler step) / rms(y)
+    for M in (30, 120):
+        _, info = engines[0].ode_sample_fixed(mix_norm, MIX, method="heun", steps=M, seed=1, want_err=True)
+        rel = (info["err"][:, :, 0] / info["err"][:, :, 1]).amax(dim=1).cpu()
+        res[f"heun{M}_local_err"] = dict(max=round(float(rel.max()), 5), median=round(float(rel.median()), 5),
+                                         first=[round(float(v), 5) for v in rel[:3]], last=[round(float(v), 5) for v in rel[-3:]],
+                                         step_of_max=int(rel.argmax()))
+    if K > 1:
+        for e in engines:
+            e.set_option("rw_quarter", 1)  # the throughput mode of the CLIs (DiffSepModel.set_throughput_mode)
+        ring = {k: [] for k in runs}
+        for rep_ in range(1 + max(1, args.reps)):  # (the first round warms the new option's graphs up and is dropped)
+            for k, (fn, _) in runs.items():
+                r = inflight.Ring(streams, lambda w, j, g: fn(engines[w]), lambda w, item: None)
+                _, w = timed(lambda: r.run(list(range(args.batches))))
+                if rep_:
+                    ring[k].append(w)
+        for k, (_, evals) in runs.items():
+            ws = sorted(ring[k])
+            med = ws[len(ws) // 2]
+            res[k + "_inflight"] = dict(wall_per_batch_ms=round(med * 1e3 / args.batches, 2), batches_per_s=round(args.batches / med, 3),
+                                        min_ms=round(ws[0] * 1e3 / args.batches, 2), max_ms=round(ws[-1] * 1e3 / args.batches, 2),
+                                        ms_per_eval=round(med * 1e3 / args.batches / evals, 4))
+    print(json.dumps(res), flush=True)
+    for e in engines:
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nf", type=int, default=64)
@@ -77,6 +141,9 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--pc-steps", type=int, default=30)
     ap.add_argument("--each", action="store_true", help="one ode_sample_each call against the sum of B calls at B = 1")
+    ap.add_argument("--fixed", action="store_true", help="the fixed-step sampler next to the PC sampler, alone and in flight")
+    ap.add_argument("--streams", type=int, default=4, help="--fixed: engines / streams in flight")
+    ap.add_argument("--batches", type=int, default=12, help="--fixed: batches per in-flight run")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
     mix = torch.from_numpy(synth.synth_batch(args.B, T=args.T)[0]).cuda()
@@ -86,6 +153,10 @@ def main():
         cfg = _lib.model_config(nf=args.nf, num_sources=2, dtype=DTYPES[name])
         if sd is None:
             sd = synth.synth_state_dict([(n, s) for n, s, _ in param_table(cfg)], 7)
+        if args.fixed:
+            bench_fixed(cfg, sd, mix_norm, args, name)
+            torch.cuda.empty_cache()
+            continue
         eng = Engine(cfg, pack_state_dict(cfg, sd))
         if args.each:
             bench_each(eng, mix_norm, args, name)
