@@ -489,6 +489,25 @@ struct OdeEachArgs {
   const double* h; const float* tnext; const int* active; const int* lens;
 };
 int ds_launch_ode_stage_each(const OdeEachArgs& e, hipStream_t st);
+// One step of an exponential integrator (DDIM / DPM-Solver++ 2M; ode.hip, ode_expint_each_kernel, the per-utterance form):
+// from y, the score at t_i and the previous data prediction x0p (null: none) to x0o = X0, yo = y' and xo = fp32(y'), with the
+// row c of OdeExpintPlan's table (ode_host.h; the operation order is stated at the kernel).  part != null: the partial sums of
+// (step - its DDIM step)^2 with the factors ga, gp = cd_j (w0_j - 1), and of y^2, laid out as mode 3 of the pass above lays
+// them out; then ds_launch_ode_norm_final_each.  No output may alias an input (items read all sources before they write).
+struct ExpintArgs {
+  const double* y; const float* score; const float* smix; const double* x0p;
+  double* x0o; double* yo; float* xo;
+  double c[DS_EXPINT_COEFS]; double ga, gp;
+  double* part;
+  const float* tnext; float* t_next_out; const int* active; const int* lens;
+  int B, S; long T;
+};
+inline void ds_expint_set_coef(ExpintArgs& a, const double* row) {  // row: DS_EXPINT_COEFS host values
+  memcpy(a.c, row, sizeof(a.c));
+  a.ga = row[DS_EI_CD_A] * (row[DS_EI_W0_A] - 1.0);
+  a.gp = row[DS_EI_CD_P] * (row[DS_EI_W0_P] - 1.0);
+}
+int ds_launch_ode_expint_each(const ExpintArgs& e, hipStream_t st);
 // norms[b][q] = sqrt(sum_blk part[b][2 blk + q]) / sqrt(S lens[b]) for the active utterances (the others keep theirs)
 int ds_launch_ode_norm_final_each(const double* part, const int* lens, const int* active, int B, int S, double* norms,
                                   hipStream_t st);

@@ -9,6 +9,7 @@
 // Two kernels walk the items — the whole batch as one system (ode_stage_kernel) and one system per utterance of a
 // zero-padded batch (ode_stage_each_kernel) — and share the item body, the block-partials tail and the final tree (both
 // in the fixed order of reduce_device.h), so that what an utterance computes is the same code whichever entry it came through.
+// A third kernel (ode_expint_each_kernel) is the one pass of the exponential integrators DDIM / DPM-Solver++ 2M, per utterance.
 // Contraction is off in this file: every sum and product rounds on its own, like numpy's, so that the stage inputs
 // can be reproduced bit for bit in float64 on the host (tests/test_ode_gpu.py).
 #include <string.h>
@@ -356,7 +357,183 @@ int ds_launch_ode_commit_each(double* y, const double* ynew, float* k0, const fl
   return 0;
 }
 
+// ------------------------------------------------------------------ exponential integrators: one step of DDIM / DPM-Solver++ 2M
+// The pass after the network evaluation at t_i (diffsep_ode_sample_expint): data prediction and step in one sweep, 40 bytes per
+// element (y, X0_prev and the score in; X0, y' and fp32(y') out).  Per time sample, in float64, every sum and product rounded on
+// its own (contraction is off), in exactly this order — sums over the sources run s = 0, 1, ... and are then divided by S:
+//   mx = (sum_s y_s) / S,  ms = (sum_s (double) score_s) / S,  mp = (sum_s X0p_s) / S
+//   q = (double) sigma_mix * (double) sigma_mix  (1 without sigma_mix),  eA = ev_A * q,  eP = ev_P * q
+//   xa = (mx + eA * ms) / alpha_A
+//   X0_s = xa + ((y_s - mx) + eP * ((double) score_s - ms)) / alpha_P
+//   mn = (sum_s X0_s) / S
+//   dA = w0_A * mn [+ w1_A * mp],  ya = cx_A * mx + cd_A * dA
+//   dP_s = w0_P * (X0_s - mn) [+ w1_P * (X0p_s - mp)]
+//   y'_s = ya + (cx_P * (y_s - mx) + cd_P * dP_s)
+// ([...]: with a previous X0 only), and for the trace  d_s = ga * (mn - mp) + gp * ((X0_s - mn) - (X0p_s - mp))  (0 without a
+// previous X0), q0 += d_s^2, q1 += y_s^2 over the item's samples v = 0 .. V, sources innermost.
+template <int V, bool VEC>
+__device__ inline void expint_item(const ExpintArgs& a, int b, long t0, double& q0, double& q1) {
+  const int S = a.S;
+  const long T = a.T;
+  const bool prev = a.x0p != nullptr;
+  double yv[DS_MAX_SRC][V], pv[DS_MAX_SRC][V];
+  float sv[DS_MAX_SRC][V], smv[V];
+#pragma unroll
+  for (int s = 0; s < DS_MAX_SRC; ++s) {
+    if (s >= S) continue;
+    const long o = ((long)b * S + s) * T + t0;
+    ldd<V, VEC>(a.y + o, yv[s]);
+    ldf<V, VEC>(a.score + o, sv[s]);
+    if (prev) ldd<V, VEC>(a.x0p + o, pv[s]);
+  }
+  if (a.smix) ldf<V, VEC>(a.smix + (long)b * T + t0, smv);
+  const double dS = (double)S;
+  const double* c = a.c;
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    double mx = 0.0, ms = 0.0, mp = 0.0;
+#pragma unroll
+    for (int s = 0; s < DS_MAX_SRC; ++s) {
+      if (s >= S) continue;
+      mx = mx + yv[s][v];
+      ms = ms + (double)sv[s][v];
+      if (prev) mp = mp + pv[s][v];
+    }
+    mx = mx / dS;
+    ms = ms / dS;
+    mp = mp / dS;
+    double q = 1.0;
+    if (a.smix) q = (double)smv[v] * (double)smv[v];
+    const double eA = c[DS_EI_EV_A] * q, eP = c[DS_EI_EV_P] * q;
+    const double xa = (mx + eA * ms) / c[DS_EI_AL_A];
+    double x0[DS_MAX_SRC], mn = 0.0;
+#pragma unroll
+    for (int s = 0; s < DS_MAX_SRC; ++s) {
+      if (s >= S) continue;
+      x0[s] = xa + ((yv[s][v] - mx) + eP * ((double)sv[s][v] - ms)) / c[DS_EI_AL_P];
+      mn = mn + x0[s];
+    }
+    mn = mn / dS;
+    double dA = c[DS_EI_W0_A] * mn;
+    if (prev) dA = dA + c[DS_EI_W1_A] * mp;
+    const double ya = c[DS_EI_CX_A] * mx + c[DS_EI_CD_A] * dA;
+#pragma unroll
+    for (int s = 0; s < DS_MAX_SRC; ++s) {
+      if (s >= S) continue;
+      double dP = c[DS_EI_W0_P] * (x0[s] - mn);
+      if (prev) dP = dP + c[DS_EI_W1_P] * (pv[s][v] - mp);
+      const double yn = ya + (c[DS_EI_CX_P] * (yv[s][v] - mx) + c[DS_EI_CD_P] * dP);
+      if (a.part) {
+        const double d = prev ? a.ga * (mn - mp) + a.gp * ((x0[s] - mn) - (pv[s][v] - mp)) : 0.0;
+        q0 = q0 + d * d;
+        q1 = q1 + yv[s][v] * yv[s][v];
+      }
+      pv[s][v] = x0[s];
+      yv[s][v] = yn;
+      sv[s][v] = (float)yn;
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < DS_MAX_SRC; ++s) {
+    if (s >= S) continue;
+    const long o = ((long)b * S + s) * T + t0;
+    std_<V, VEC>(a.x0o + o, pv[s]);
+    std_<V, VEC>(a.yo + o, yv[s]);
+    stf<V, VEC>(a.xo + o, sv[s]);
+  }
+}
+
+template <int V, bool VEC>
+__device__ inline void expint_each_items(const ExpintArgs& a, int b, long len, long nb, double& q0, double& q1) {
+  for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < len / V; it += nb * 256) expint_item<V, VEC>(a, b, it * V, q0, q1);
+}
+
+// grid (min(cdiv(T, 256), DS_ODE_MAX_BLOCKS), B): row b of the grid is utterance b, walked as ode_stage_each_kernel walks it
+// (the same items, blocks and partial-sum tree per utterance, whatever B, b and the padded T are); vec: expint_vec
+__global__ __launch_bounds__(256) void ode_expint_each_kernel(ExpintArgs a, int vec) {
+  const int b = blockIdx.y;
+  if (!a.active[b]) return;
+  const int S = a.S;
+  const long T = a.T, len = a.lens[b];
+  if (len < 1 || len > T) return;  // (the driver checks the lengths on the host; a bad table entry touches nothing)
+  if (a.tnext && blockIdx.x == 0 && threadIdx.x == 0) a.t_next_out[b] = a.tnext[b];
+  const long nb = ode_each_blocks(len);
+  double q0 = 0.0, q1 = 0.0;
+  if (blockIdx.x < nb) {
+    if (len % 4 != 0) expint_each_items<1, false>(a, b, len, nb, q0, q1);
+    else if (vec) expint_each_items<4, true>(a, b, len, nb, q0, q1);
+    else expint_each_items<4, false>(a, b, len, nb, q0, q1);
+  }
+  // the zero tail of the three outputs (every block of the row)
+  const long tail = T - len;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < tail * S; i += (long)gridDim.x * 256) {
+    const int s = (int)(i / tail);
+    const long o = ((long)b * S + s) * T + len + (i - (long)s * tail);
+    a.x0o[o] = 0.0;
+    a.yo[o] = 0.0;
+    a.xo[o] = 0.f;
+  }
+  if (a.part && blockIdx.x < nb) ode_block_partials(q0, q1, a.part + (long)b * 2 * DS_ODE_MAX_BLOCKS);
+}
+
+// float4 / double2 accesses: rows of a multiple of 4 samples and every tensor 16-byte aligned
+static bool expint_vec(const ExpintArgs& a) {
+  bool vec = a.T % 4 == 0;
+  const void* ps[] = {a.y, a.score, a.smix, a.x0p, a.x0o, a.yo, a.xo};
+  for (const void* p : ps) vec = vec && al16(p);
+  return vec;
+}
+
+int ds_launch_ode_expint_each(const ExpintArgs& a, hipStream_t st) {
+  DS_CHECK(a.S >= 1 && a.S <= DS_MAX_SRC && a.B >= 1 && a.B <= 65535 && a.T >= 1 && a.T <= 0x7fffffffL, "expint each: bad shape");
+  DS_CHECK(a.y && a.score && a.x0o && a.yo && a.xo, "expint each: y, the score and the three outputs are needed");
+  DS_CHECK(a.active && a.lens, "expint each: the tables active and lengths are needed");
+  DS_CHECK(!a.tnext || a.t_next_out, "expint each: t_next needs its output");
+  DS_CHECK((const double*)a.x0o != a.x0p && (const double*)a.x0o != a.y && (const double*)a.yo != a.y &&
+               (const double*)a.yo != a.x0p && a.x0o != a.yo,
+           "expint each: an output aliases an input or another output");
+  DS_CHECK(a.c[DS_EI_AL_A] > 0.0 && a.c[DS_EI_AL_P] > 0.0, "expint each: bad coefficient row (alpha <= 0)");
+  const int nb = (int)std::min<long>(cdiv(a.T, 256), DS_ODE_MAX_BLOCKS);
+  hipLaunchKernelGGL(ode_expint_each_kernel, dim3(nb, a.B), dim3(256), 0, st, a, expint_vec(a) ? 1 : 0);
+  DS_LAUNCH_CHECK();
+  return 0;
+}
+
 // ------------------------------------------------------------------ C-ABI: tableau + unit entry points
+extern "C" int32_t diffsep_expint_coefficients(const diffsep_sde_config* sde, int32_t method, int32_t steps, double t_start,
+                                               double eps, const double* timesteps_host, double* coef_out) {
+  DS_CHECK(sde && coef_out, "expint_coefficients: null argument");
+  const OdeExpintConfig oc{method, steps, t_start, eps, 0, 0};
+  OdeExpintPlan plan;
+  const std::string bad = ode_expint_plan_fill(plan, oc, *sde, timesteps_host, false, "expint_coefficients");
+  DS_CHECK(bad.empty(), bad);
+  memcpy(coef_out, plan.coef.data(), plan.coef.size() * sizeof(double));
+  return 0;
+}
+
+extern "C" int32_t diffsep_expint_update_each(const diffsep_sde_config* sde, const double* y, const float* score,
+                                              const float* sigma_mix, const double* x0_prev, const double* coef,
+                                              const int32_t* active, const int32_t* lengths, double* x0_out,
+                                              double* y_new_out, float* x_out, double* norms_out, int32_t B, int32_t S,
+                                              int64_t T, void* workspace, int64_t workspace_bytes, void* stream) {
+  DS_CHECK(sde && coef, "expint_update_each: null argument");
+  DS_CHECK((sde->kind == DIFFSEP_SDE_PRIORMIX) == (sigma_mix != nullptr),
+           "expint_update_each: PriorMixSDE with sigma_mix, MixSDE without");
+  DS_CHECK(!norms_out || (workspace && B >= 1 && workspace_bytes >= (int64_t)B * DIFFSEP_ODE_WORKSPACE_BYTES),
+           "expint_update_each: norms_out needs a workspace >= B * DIFFSEP_ODE_WORKSPACE_BYTES");
+  ExpintArgs a;
+  memset(&a, 0, sizeof(a));
+  a.y = y; a.score = score; a.smix = sigma_mix; a.x0p = x0_prev;
+  a.x0o = x0_out; a.yo = y_new_out; a.xo = x_out;
+  ds_expint_set_coef(a, coef);
+  a.part = norms_out ? (double*)workspace : nullptr;
+  a.active = active; a.lens = lengths;
+  a.B = B; a.S = S; a.T = T;
+  if (ds_launch_ode_expint_each(a, (hipStream_t)stream)) return 1;
+  if (norms_out) return ds_launch_ode_norm_final_each(a.part, lengths, active, B, S, norms_out, (hipStream_t)stream);
+  return 0;
+}
+
 extern "C" int32_t diffsep_ode_tableau(int32_t method, double* A, double* B, double* C, double* E, int32_t* n_stages,
                                        int32_t* error_order) {
   int ns = 0, eo = 0;

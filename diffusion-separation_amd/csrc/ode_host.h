@@ -3,7 +3,8 @@
 // (integrate/_ivp/rk.py RungeKutta._step_impl, common.py select_initial_step / validate_tol, base.py OdeSolver.step, ivp.py
 // solve_ivp's loop).  diffsep_ode_sample drives one OdeCtl, diffsep_ode_sample_each one per utterance (sampler.hip);
 // tests/ode_ctl_main.cpp drives one on a small float64 system against scipy itself.  Below them: the plan of a fixed-step
-// solve (OdeFixedPlan, diffsep_ode_sample_fixed; tests/ode_fixed_main.cpp walks it).  Plain C++17, no HIP.
+// solve (OdeFixedPlan, diffsep_ode_sample_fixed; tests/ode_fixed_main.cpp walks it) and of an exponential-integrator solve
+// (OdeExpintPlan, diffsep_ode_sample_expint; tests/expint_main.cpp walks it).  Plain C++17, no HIP.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -290,5 +291,108 @@ inline std::string ode_fixed_plan_fill(OdeFixedPlan& p, const OdeFixedConfig& oc
     p.pass.push_back(q);
   }
   p.n_evals = (int)p.pass.size();
+  return std::string();
+}
+
+// ------------------------------------------------------------------ exponential integrators (diffsep_ode_sample_expint)
+// DDIM and DPM-Solver++ 2M on the same grids.  A = 11^T / S and P = I - A commute with the mean matrix A + e^{-lambda t} P and
+// with the perturbation's L(t) = sqrt(ev1) A + sqrt(ev2) P, so the probability-flow ODE splits into two scalar diffusions, one
+// per eigenspace j in {A, P}:  alpha_A = 1, sigma_A^2 = ev1;  alpha_P = e^{-lambda t}, sigma_P^2 = ev2  (PriorMixSDE multiplies
+// both sigma_j by sigma_mix[b,t]; it cancels out of every coefficient below and enters the data prediction only).  With the half
+// log-SNR lam_j = ln alpha_j - 0.5 ln ev_j the linear drift and the noise schedule are integrated in closed form and only the
+// network's data prediction X0 is discretised.  Everything here is float64; the SDE's float parameters are widened as they are.
+#define DS_EXPINT_COEFS DIFFSEP_EXPINT_COEFS
+enum {  // one row of the table: step i, from t_i to t_{i+1}
+  DS_EI_CX_A = 0, DS_EI_CD_A, DS_EI_W0_A, DS_EI_W1_A,  // cx = sqrt(ev(t_{i+1}) / ev(t_i)), cd = -alpha(t_{i+1}) expm1(-h), w0, w1
+  DS_EI_CX_P, DS_EI_CD_P, DS_EI_W0_P, DS_EI_W1_P,
+  DS_EI_AL_A, DS_EI_EV_A, DS_EI_AL_P, DS_EI_EV_P  // alpha_j(t_i), ev_j(t_i): the data prediction at t_i
+};
+
+struct OdeExpintConfig {  // the arguments of diffsep_ode_sample_expint that shape the solve
+  int method, steps;      // DIFFSEP_EXPINT_*, M
+  double t_start, eps;    // t_start <= 0: 1.0 (sde.T)
+  int denoise, N;         // as diffsep_ode_config
+};
+
+struct OdeExpintPlan {
+  int method = 0, M = 0;
+  double eps = 0.0;
+  int denoise = 0, N = 0;
+  std::vector<double> t;     // the grid: M + 1 times, strictly descending, inside (0, 1]
+  std::vector<double> coef;  // [M][DS_EXPINT_COEFS]
+};
+
+// ev1, ev2 of MixSDE._cov_eigval (sdes/sdes.py:296-309) in float64, in its operation order
+inline void ds_expint_eig(const diffsep_sde_config& s, double t, double& ev1, double& ev2) {
+  const double r = (double)s.sigma_max / (double)s.sigma_min;
+  const double mult = (double)s.sigma_min * (double)s.sigma_min;
+  const double srp = pow(r, 2 * t);
+  ev1 = mult * (srp - 1);
+  ev2 = mult * (srp - exp(-2.0 * (double)s.d_lambda * t)) / (1.0 + (double)s.d_lambda / log(r));
+}
+
+// Fill and validate (`who`, timesteps as ode_fixed_plan_fill: the same grid, the same refusals in the same words; want_err:
+// the caller asks for the local-error trace); returns the message, empty when all is well.
+inline std::string ode_expint_plan_fill(OdeExpintPlan& p, const OdeExpintConfig& oc, const diffsep_sde_config& sde,
+                                        const double* timesteps, bool want_err, const char* who) {
+  const std::string w(who);
+  p = OdeExpintPlan();
+  if (!(oc.method == DIFFSEP_EXPINT_DDIM || oc.method == DIFFSEP_EXPINT_DPMPP2M))
+    return w + ": method must be DIFFSEP_EXPINT_DDIM or DIFFSEP_EXPINT_DPMPP2M";
+  if (!(sde.kind == DIFFSEP_SDE_MIX || sde.kind == DIFFSEP_SDE_PRIORMIX))
+    return w + ": the exponential integrators need a MixSDE or a PriorMixSDE (two eigenspaces with closed-form schedules)";
+  const int M = oc.steps;
+  if (!(M >= 1)) return w + ": steps must be >= 1";
+  if (!(M <= DS_ODEF_MAX_EVALS)) return w + ": steps must be <= 16384";
+  if (!(oc.eps > 0.0 && oc.eps < 1.0)) return w + ": eps must be in (0, 1)";
+  if (!(oc.N >= 1 || !oc.denoise)) return w + ": the denoise step needs N >= 1";
+  if (want_err && oc.method != DIFFSEP_EXPINT_DPMPP2M)
+    return w + ": err_out needs the second-order method (DPMPP2M: step minus its DDIM step), not DDIM";
+  p.method = oc.method; p.M = M; p.eps = oc.eps; p.denoise = oc.denoise; p.N = oc.N;
+  p.t.resize((size_t)M + 1);
+  if (timesteps) {
+    for (int i = 0; i <= M; ++i) p.t[i] = timesteps[i];
+  } else {
+    const double t0 = oc.t_start <= 0.0 ? 1.0 : oc.t_start;
+    if (!(t0 > oc.eps)) return w + ": t_start must be above eps";
+    for (int i = 0; i < M; ++i) p.t[i] = t0 + (oc.eps - t0) * i / M;
+    p.t[M] = oc.eps;
+  }
+  for (int i = 0; i <= M; ++i)
+    if (!(p.t[i] > 0.0 && p.t[i] <= 1.0 && (i == 0 || p.t[i] < p.t[i - 1])))
+      return w + ": the time grid must be strictly descending inside (0, 1]";
+  // per grid point and eigenspace: alpha, ev and the half log-SNR
+  const double a[2] = {0.0, (double)sde.d_lambda};
+  std::vector<double> al(2 * ((size_t)M + 1)), ev(al.size()), lam(al.size());
+  for (int i = 0; i <= M; ++i) {
+    double e[2];
+    ds_expint_eig(sde, p.t[i], e[0], e[1]);
+    if (!(e[0] > 0.0 && e[1] > 0.0))
+      return w + ": ev_1 <= 0 (or ev_2 <= 0) at a grid point: the covariance eigenvalues must be positive (sigma_max > sigma_min)";
+    for (int j = 0; j < 2; ++j) {
+      al[2 * i + j] = exp(-a[j] * p.t[i]);
+      ev[2 * i + j] = e[j];
+      lam[2 * i + j] = log(al[2 * i + j]) - 0.5 * log(e[j]);
+    }
+  }
+  p.coef.assign((size_t)M * DS_EXPINT_COEFS, 0.0);
+  for (int i = 0; i < M; ++i) {
+    double* c = p.coef.data() + (size_t)i * DS_EXPINT_COEFS;
+    for (int j = 0; j < 2; ++j) {
+      const double h = lam[2 * (i + 1) + j] - lam[2 * i + j];
+      double* cj = c + 4 * j;
+      cj[0] = sqrt(ev[2 * (i + 1) + j] / ev[2 * i + j]);
+      cj[1] = -al[2 * (i + 1) + j] * expm1(-h);
+      cj[2] = 1.0;
+      cj[3] = 0.0;
+      if (oc.method == DIFFSEP_EXPINT_DPMPP2M && i >= 1) {
+        const double r = (lam[2 * i + j] - lam[2 * (i - 1) + j]) / h;
+        cj[2] = 1.0 + 1.0 / (2.0 * r);
+        cj[3] = -1.0 / (2.0 * r);
+      }
+      c[DS_EI_AL_A + 2 * j] = al[2 * i + j];
+      c[DS_EI_EV_A + 2 * j] = ev[2 * i + j];
+    }
+  }
   return std::string();
 }

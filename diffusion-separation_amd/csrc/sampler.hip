@@ -824,3 +824,154 @@ extern "C" int32_t diffsep_ode_sample_fixed(diffsep_engine* e, const diffsep_sde
   if (nfe_out) *nfe_out = n_evals;
   return 0;
 }
+
+// ------------------------------------------------------------------ ... by exponential integrators (DDIM, DPM-Solver++ 2M)
+// The plan (ode_host.h: OdeExpintPlan) holds the grid and the per-step coefficient rows; the driver follows the fixed-step one
+// above: one upload of the time table, then per solver step one network evaluation (on e, or on the tail engine) and ONE pass
+// (ode.hip, ode_expint_each_kernel) that forms the data prediction and takes the step.  The two X0 histories are fp64 views of
+// the stage-derivative buffers K[0..1] and K[2..3], swapped by pointer like y and y_new.  Nothing is read back.
+extern "C" int32_t diffsep_ode_sample_expint(diffsep_engine* e, const diffsep_sde_config* sde, int32_t method, int32_t steps,
+                                             double t_start, double eps, int32_t denoise, int32_t N,
+                                             const diffsep_sampler_ext* ext, const float* mix_norm, const float* x_init,
+                                             const float* noise, uint64_t seed, const double* timesteps_host, float* out,
+                                             double* err_out, int32_t B, int64_t T, int32_t* nfe_out, void* stream) {
+  DS_CHECK(e && sde && mix_norm && out, "ode_sample_expint: null argument");
+  if (check_sde(e, sde, "ode_sample_expint")) return 1;
+  DS_CHECK(B >= 1 && B <= 65535 && T >= 1 && T <= 0x7fffffffLL, "ode_sample_expint: bad batch shape");
+  DS_CHECK(!(x_init && noise), "ode_sample_expint: x_init and noise are alternatives");
+  const OdeExpintConfig xc{method, steps, t_start, eps, denoise, N};
+  OdeExpintPlan plan;
+  const std::string bad = ode_expint_plan_fill(plan, xc, *sde, timesteps_host, err_out != nullptr, "ode_sample_expint");
+  DS_CHECK(bad.empty(), bad);
+  DS_CHECK(plan.t[0] >= 1.0 || x_init, "ode_sample_expint: a grid that starts below 1 needs the state to start from (x_init == NULL)");
+  const int M = plan.M;
+  const int64_t* lengths = ext ? ext->lengths_host : nullptr;
+  const uint64_t* seeds = ext ? ext->seeds_host : nullptr;
+  diffsep_engine* tail = (ext && (ext->tail_steps > 0 || ext->head_steps > 0)) ? ext->tail_engine : nullptr;
+  const int tail_steps = tail ? ext->tail_steps : 0;
+  const int head_steps = tail ? ext->head_steps : 0;
+  if (tail) {
+    DS_CHECK(tail != e, "ode_sample_expint: the tail engine must be a different engine");
+    diffsep_model_config a = e->cfg, b2 = tail->cfg;
+    a.dtype = b2.dtype = 0;
+    DS_CHECK(memcmp(&a, &b2, sizeof(a)) == 0, "ode_sample_expint: the tail engine must have the same architecture");
+  }
+  DS_CHECK(!seeds || !noise, "ode_sample_expint: per-utterance seeds are for device noise (noise == NULL)");
+  if (lengths) {
+    const int Wp = diffsep_padded_frames(&e->cfg, T);
+    for (int b = 0; b < B; ++b) {
+      DS_CHECK(lengths[b] >= 1 && lengths[b] <= T, "ode_sample_expint: utterance length outside [1, T]");
+      DS_CHECK(diffsep_padded_frames(&e->cfg, lengths[b]) == Wp,
+               "ode_sample_expint: every utterance of a mixed-length batch must have the padded frame count of T");
+    }
+  }
+
+  StreamScope sc_(e, stream);
+  hipStream_t st = sc_.st;
+  const int S = e->cfg.num_sources;
+  if (ensure_plan(e, B, T, st)) return 1;
+  if (tail && ensure_plan(tail, B, T, st)) return 1;
+  const size_t nst = (size_t)B * S * T;
+  // device tables of the whole solve: evaluation times [M + 1][B] (fp32) | active [B] (int)
+  const size_t off_act = (size_t)(M + 1) * B * 4;
+  const size_t tab_bytes = off_act + (size_t)B * 4;
+  OdeWork w;
+  if (ode_workspace(e, nst, err_out ? B : 0, tab_bytes, w)) return 1;
+  static_assert(DS_ODE_MAX_K >= 4, "the X0 histories take K[0..1] and K[2..3]");
+  double* x0_new = reinterpret_cast<double*>(w.K[0]);   // (K[j + 1] - K[j] >= 4 nst bytes, 256-byte aligned: ode_workspace)
+  double* x0_prev = reinterpret_cast<double*>(w.K[2]);
+  const float* d_tt = (const float*)w.tab;
+  const int* d_act = (const int*)(w.tab + off_act);
+  const SdeP sp = to_sdep(sde);
+  {
+    char* tp;
+    if (e->ode_tab_pin.acquire(tab_bytes, &tp)) return 1;
+    float* pt = reinterpret_cast<float*>(tp);
+    int* pa = reinterpret_cast<int*>(tp + off_act);
+    for (int i = 0; i <= M; ++i)
+      for (int b = 0; b < B; ++b) pt[(size_t)i * B + b] = (float)plan.t[i];
+    for (int b = 0; b < B; ++b) pa[b] = 1;
+    DS_HIP(hipMemcpyAsync(w.tab, tp, tab_bytes, hipMemcpyHostToDevice, st));
+    if (e->ode_tab_pin.record(st)) return 1;
+  }
+
+  // mixture, lengths and seeds -> device; the start state -> st_x with a zero tail (and y in fp64)
+  DS_HIP(hipMemcpyAsync(e->st_mix, mix_norm, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
+  {
+    char* xp;
+    if (e->ext_pin.acquire((size_t)B * 16, &xp)) return 1;
+    unsigned long long* ps = reinterpret_cast<unsigned long long*>(xp);
+    int* pl = reinterpret_cast<int*>(xp + (size_t)B * 8);
+    for (int b = 0; b < B; ++b) {
+      ps[b] = seeds ? seeds[b] : seed + 0x9E3779B97F4A7C15ull * (unsigned long long)b;  // (b = 0: the B = 1 stream of `seed`)
+      pl[b] = lengths ? (int)lengths[b] : (int)T;
+    }
+    DS_HIP(hipMemcpyAsync(e->st_seeds, ps, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    DS_HIP(hipMemcpyAsync(e->st_lens, pl, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    if (e->ext_pin.record(st)) return 1;
+  }
+  const int* lens = e->st_lens;                      // what the passes read: T without lengths
+  const int* tail_lens = lengths ? lens : nullptr;   // what masks a tail
+  if (lengths && ds_launch_mask_tail(e->st_mix, B, 1, T, lens, st)) return 1;
+  const float* smix = nullptr;
+  if (mixture_scale(e, sde, B, T, st, &smix)) return 1;
+  if (x_init) {
+    DS_HIP(hipMemcpyAsync(e->st_x, x_init, nst * 4, hipMemcpyDeviceToDevice, st));
+    if (lengths && ds_launch_mask_tail(e->st_x, B, S, T, lens, st)) return 1;
+  } else {
+    const float* z = noise;
+    if (!z) {  // draw 0 of the PC sampler's generator, keyed as that sampler keys it
+      if ((seeds || lengths) ? ds_launch_randn_batch(e->st_noise, B, S, T, (const uint64_t*)e->st_seeds, lens, 0, st)
+                             : ds_launch_randn(e->st_noise, (long)nst, seed, 0, st))
+        return 1;
+      z = e->st_noise;
+    }
+    if (ds_launch_sde_prior(sp, e->st_mix, z, e->st_x, B, S, T, smix, st, tail_lens)) return 1;
+  }
+  if (ds_launch_ode_cast(e->st_x, w.y, (long)nst, st)) return 1;
+
+  // the evaluation of solver step i: on this engine, or on the tail engine (state and time copied over)
+  bool tail_ready = false;
+  const float* score = e->st_score;
+  auto eval_score = [&](int i) -> int {
+    if (tail && (i >= M - tail_steps || i < head_steps)) {
+      if (!tail_ready) {
+        DS_HIP(hipMemcpyAsync(tail->st_mix, e->st_mix, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
+        tail_ready = true;
+      }
+      DS_HIP(hipMemcpyAsync(tail->st_x, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
+      DS_HIP(hipMemcpyAsync(tail->st_t, e->st_t, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+      score = tail->st_score;
+      return run_nfe(tail, B, T, st);
+    }
+    score = e->st_score;
+    return run_nfe(e, B, T, st);
+  };
+
+  DS_HIP(hipMemcpyAsync(e->st_t, d_tt, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+  for (int i = 0; i < M; ++i) {
+    if (eval_score(i)) return 1;
+    ExpintArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = w.y; a.score = score; a.smix = smix;
+    a.x0p = (method == DIFFSEP_EXPINT_DPMPP2M && i >= 1) ? x0_prev : nullptr;
+    a.x0o = x0_new; a.yo = w.ynew; a.xo = e->st_x;
+    ds_expint_set_coef(a, plan.coef.data() + (size_t)i * DS_EXPINT_COEFS);
+    a.part = err_out ? w.part : nullptr;
+    a.tnext = d_tt + (size_t)(i + 1) * B; a.t_next_out = e->st_t; a.active = d_act; a.lens = lens;
+    a.B = B; a.S = S; a.T = T;
+    if (prof_launch(e, st, hbm_rec("ode_expint_each (data prediction + exponential-integrator step)", 40.0 * nst, B, 1, (int)T, S),
+                    [&]() { return ds_launch_ode_expint_each(a, st); }))
+      return 1;
+    if (err_out && ds_launch_ode_norm_final_each(w.part, lens, d_act, B, S, err_out + (size_t)i * B * 2, st)) return 1;
+    std::swap(w.y, w.ynew);        // y <- y'
+    std::swap(x0_new, x0_prev);    // the X0 just written is the next step's previous one
+  }
+
+  diffsep_ode_config fin;
+  memset(&fin, 0, sizeof(fin));
+  fin.eps = eps; fin.denoise = denoise; fin.N = N;
+  if (ode_finish(e, sp, &fin, smix, w.y, out, B, S, T, tail_lens, st)) return 1;
+  if (nfe_out) *nfe_out = M;
+  return 0;
+}

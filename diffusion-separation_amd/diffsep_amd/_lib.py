@@ -56,6 +56,14 @@ def odef_nfe(method, steps):
     return {"euler": steps, "heun": 2 * steps, "midpoint": 2 * steps, "rk4": 4 * steps, "ab2": steps + 1}[method]
 
 
+# diffsep_ode_sample_expint: the exponential integrators of the same solve (steps network evaluations each) and the width of a
+# row of their coefficient table
+EXPINT_DDIM, EXPINT_DPMPP2M = 0, 1
+EXPINT_METHODS = {"ddim": EXPINT_DDIM, "dpmpp2m": EXPINT_DPMPP2M}
+EXPINT_ERR_METHODS = ("dpmpp2m",)  # err_out: the step minus its DDIM step
+EXPINT_COEFS = 12
+
+
 class OdeConfig(C.Structure):  # diffsep_ode_config
     _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("eps", C.c_double), ("first_step", C.c_double),
                 ("max_step", C.c_double), ("method", C.c_int32), ("max_nfe", C.c_int32), ("denoise", C.c_int32),
@@ -161,6 +169,11 @@ _SIGS = {
                                      _I, _L, C.POINTER(OdeInfo), C.POINTER(_I), _P]),
     "diffsep_ode_sample_fixed": (_I, [_P, C.POINTER(SdeConfig), _I, _I, C.c_double, C.c_double, _I, _I, C.POINTER(SamplerExt), _P,
                                       _P, _P, _U64, C.POINTER(C.c_double), _P, _P, _I, _L, C.POINTER(_I), _P]),
+    "diffsep_ode_sample_expint": (_I, [_P, C.POINTER(SdeConfig), _I, _I, C.c_double, C.c_double, _I, _I, C.POINTER(SamplerExt), _P,
+                                       _P, _P, _U64, C.POINTER(C.c_double), _P, _P, _I, _L, C.POINTER(_I), _P]),
+    "diffsep_expint_coefficients": (_I, [C.POINTER(SdeConfig), _I, _I, C.c_double, C.c_double, C.POINTER(C.c_double), _P]),
+    "diffsep_expint_update_each": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _P, _L,
+                                        _P]),
     "diffsep_ode_tableau": (_I, [_I, _P, _P, _P, _P, C.POINTER(_I), C.POINTER(_I)]),
     "diffsep_ode_stage_update": (_I, [C.POINTER(SdeConfig), _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_double, _P, _P, _I,
                                       _I, _L, _P]),
@@ -325,3 +338,21 @@ def ode_tableau(method="RK45"):
     A, B, Cc, E = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros(n + 1)
     call(l, "diffsep_ode_tableau", code, *(a.ctypes.data_as(C.c_void_p) for a in (A, B, Cc, E)), None, None)
     return A, B, Cc, E, n, eo.value
+
+
+def expint_coefficients(sde, method, steps, t_start=None, eps=3e-2, timesteps=None):
+    """diffsep_expint_coefficients: the float64 table [steps, EXPINT_COEFS] of "ddim" / "dpmpp2m" on the grid the fixed-step
+    solve builds from (steps, t_start, eps) or takes from timesteps (steps + 1 times); row i = cx_A cd_A w0_A w1_A | cx_P
+    cd_P w0_P w1_P | alpha_A ev_A alpha_P ev_P at t_i.  sde: the dict of sde_config.  Host code only (no GPU needed)."""
+    import numpy as np
+    M = int(steps)
+    ts = None
+    if timesteps is not None:
+        ts = np.ascontiguousarray(timesteps, dtype=np.float64).reshape(-1)
+        if ts.size != M + 1:
+            raise DiffsepError(f"expint_coefficients: timesteps must hold steps + 1 = {M + 1} times, got {ts.size}")
+    out = np.zeros((max(M, 0), EXPINT_COEFS))
+    call(lib(), "diffsep_expint_coefficients", C.byref(sde_config(sde)), EXPINT_METHODS.get(method, method), M,
+         float(t_start) if t_start is not None else 0.0, float(eps),
+         ts.ctypes.data_as(C.POINTER(C.c_double)) if ts is not None else None, out.ctypes.data_as(C.c_void_p))
+    return out

@@ -428,9 +428,14 @@ class Engine:
         (a start below 1 needs x_init, e.g. from ops.warm_start); tail / head_steps / tail_steps: the evaluations of the
         first head_steps and last tail_steps SOLVER steps run on another Engine.  want_err (heun, midpoint, ab2): also the
         local-error trace, a device float64 tensor [steps,B,2] of (RMS of step minus embedded Euler step, RMS of y_i) per
-        step and utterance, not read back here.  Returns (out [B,S,T], info: nfe, method, steps[, err])."""
-        if method not in _lib.ODEF_METHODS:
-            raise NotImplementedError(f"ode_sample_fixed: method '{method}' (one of {sorted(_lib.ODEF_METHODS)})")
+        step and utterance, not read back here.  method "ddim" / "dpmpp2m" (diffsep_ode_sample_expint):
+        the exponential integrators DDIM and DPM-Solver++ 2M on the same grid with the same arguments, `steps` network
+        evaluations each; want_err (dpmpp2m): RMS of the step minus its DDIM step (an exact 0 at step 0), RMS of y_i.
+        Returns (out [B,S,T], info: nfe, method, steps[, err])."""
+        expint = method in _lib.EXPINT_METHODS  # "ddim" / "dpmpp2m": diffsep_ode_sample_expint, the same argument list
+        if method not in _lib.ODEF_METHODS and not expint:
+            raise NotImplementedError(f"ode_sample_fixed: method '{method}' (one of {sorted(_lib.ODEF_METHODS)} or "
+                                      f"{sorted(_lib.EXPINT_METHODS)})")
         mix_norm = self._f32(mix_norm)
         B, one, T = mix_norm.shape
         assert one == 1
@@ -464,7 +469,8 @@ class Engine:
         err = torch.empty((max(M, 0), B, 2), dtype=torch.float64, device=mix_norm.device) if want_err else None
         nfe = C.c_int32()
         with torch.cuda.device(self.device):
-            call(self._L, "diffsep_ode_sample_fixed", self._h, C.byref(sc), _lib.ODEF_METHODS[method], M,
+            call(self._L, "diffsep_ode_sample_expint" if expint else "diffsep_ode_sample_fixed", self._h, C.byref(sc),
+                 _lib.EXPINT_METHODS[method] if expint else _lib.ODEF_METHODS[method], M,
                  float(t_start) if t_start is not None else 0.0, float(eps), int(bool(denoise)), int(N),
                  C.byref(ext) if ext is not None else None, _ptr(mix_norm), _ptr(x_init), _ptr(noise), int(seed) % (1 << 64),
                  ts.ctypes.data_as(C.POINTER(C.c_double)) if ts is not None else None, _ptr(out), _ptr(err), B, T,

@@ -48,13 +48,15 @@ its batch needed, each record carries its `ode_status` (0 reached eps, -1 step t
 summary counts them (`ode_status_counts`) and names the `sampler`.  An ODE call blocks the host on one readback per step
 attempt, so --streams adds nothing to it.
 
---sampler ode-fixed [--ode-method {euler,heun,midpoint,rk4,ab2} --ode-steps M --ode-err] separates with the same ODE on a
+--sampler ode-fixed [--ode-method {euler,heun,midpoint,rk4,ab2,ddim,dpmpp2m} --ode-steps M --ode-err] separates with the same ODE on a
 fixed grid (sdes.get_ode_fixed_sampler, diffsep_ode_sample_fixed): M steps (default N) from t = 1 down to
 eps, -s/--schedule choosing the grid.  The call is enqueued like the PC sampler's and reads nothing back, so --streams keeps
 batches in flight; `nfe` is the plan's count (heun: 2 M), the summary names `ode_method` and `ode_steps`, and --ode-err adds
 `ode_local_err` to every record: the largest over the steps of rms(step - embedded Euler step) / rms(y), read once per batch at
 collect time.  Whether such a solve separates as well as the PC sampler at equal cost is not known (no trained checkpoint was
-at hand): the flag is the instrument.  Not with --fig, --trajectory or --draws in this version.
+at hand): the flag is the instrument.  Not with --fig, --trajectory or --draws in this version.  --ode-method ddim / dpmpp2m
+ are the exponential integrators DDIM and DPM-Solver++ 2M: M evaluations each (`nfe` = M); --ode-err goes with
+dpmpp2m, where the step is compared with its DDIM step.
 
 --fig and --trajectory look inside the fused sampler through its tap (diffsep_pc_sample_trace: one small launch between the
 corrector and the predictor of a reverse step; batches, streams, seeds, --dtype hybrid and the records are what they are
@@ -257,14 +259,15 @@ def build_parser():
                     help="pc (default): the reference's predictor-corrector sampler; ode: the probability-flow ODE (adaptive "
                          "RK45), one step controller per utterance of a batch; ode-fixed: the same ODE on a fixed grid "
                          "(--ode-method, --ode-steps), enqueued like pc, so --streams keeps batches in flight")
-    ap.add_argument("--ode-method", default=None, choices=["euler", "heun", "midpoint", "rk4", "ab2"],
+    ap.add_argument("--ode-method", default=None, choices=["euler", "heun", "midpoint", "rk4", "ab2", "ddim", "dpmpp2m"],
                     help="--sampler ode-fixed: the integrator (default heun); network evaluations for M steps: euler M, heun and "
-                         "midpoint 2 M, rk4 4 M, ab2 M + 1")
+                         "midpoint 2 M, rk4 4 M, ab2 M + 1; ddim and dpmpp2m (DPM-Solver++ 2M), the exponential integrators: M")
     ap.add_argument("--ode-steps", type=int, default=None, metavar="M",
                     help="--sampler ode-fixed: solver steps from t = 1 down to eps (default: the sampler's N)")
     ap.add_argument("--ode-err", action="store_true",
                     help="--sampler ode-fixed with heun, midpoint or ab2: record ode_local_err, the utterance's largest relative "
-                         "local error (max over the steps of rms(step - embedded Euler step) / rms(y)), read once per batch")
+                         "local error (max over the steps of rms(step - embedded Euler step) / rms(y)), read once per batch; with "
+                         "dpmpp2m: of rms(step - its DDIM step) / rms(y)")
     ap.add_argument("--rtol", type=float, default=1e-5, help="--sampler ode: relative tolerance (reference default)")
     ap.add_argument("--atol", type=float, default=1e-5, help="--sampler ode: absolute tolerance (reference default)")
     ap.add_argument("--max-nfe", type=int, default=0,
@@ -322,7 +325,10 @@ def main(argv=None):
         if args.ode_steps is not None and args.ode_steps < 1:
             raise SystemExit(f"--ode-steps {args.ode_steps}: at least one step")
         args.ode_method = args.ode_method or "heun"
-        if args.ode_err and args.ode_method not in _lib.ODEF_ERR_METHODS:
+        if args.ode_err and args.ode_method in _lib.EXPINT_METHODS and args.ode_method not in _lib.EXPINT_ERR_METHODS:
+            raise SystemExit(f"--ode-err with --ode-method {args.ode_method}: the first-order method has no lower-order step to "
+                             "compare with (dpmpp2m)")
+        if args.ode_err and args.ode_method not in _lib.ODEF_ERR_METHODS + _lib.EXPINT_ERR_METHODS:
             raise SystemExit(f"--ode-err with --ode-method {args.ode_method}: the method has no embedded Euler step (heun, midpoint, ab2)")
     if args.draws is None and args.draws_out is not None:
         raise SystemExit("--draws-out goes with --draws")

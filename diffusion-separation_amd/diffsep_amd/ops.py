@@ -1098,3 +1098,29 @@ def ode_error_norm_each(sde, K, coef, h, active, lengths, y, rtol, atol, y_new=N
          _ptr(y), _ptr(y_new), _ode_ptrs(K), c.ctypes.data_as(C.c_void_p), len(c), int(k_out), _ptr(hd), _ptr(ad), _ptr(ld),
          float(rtol), float(atol), _ptr(out), B, S, T, _ptr(ws), ws.numel(), _stream_ptr())
     return out
+
+
+def expint_update_each(sde, y, score, coef, active, lengths, x0_prev=None, sigma_mix=None, want_norms=False, out=None):
+    """diffsep_expint_update_each: one step of DDIM / DPM-Solver++ 2M on caller buffers.  y float64 [B,S,T], score float32
+    [B,S,T], coef: one row of _lib.expint_coefficients (host), x0_prev: the previous step's X0 (float64; None: the w1 terms
+    are absent), sigma_mix [B,T] for PriorMixSDE; active / lengths [B] as in ode_stage_update_each.  out: optional
+    (x0, y_new, x) to write into (inactive rows keep what they hold), else zeros.  Returns (x0 float64, y_new float64,
+    x float32[, norms float64 [B,2]: RMS of the step minus its DDIM step, RMS of y])."""
+    B, S, T = y.shape
+    assert y.dtype == torch.float64 and score.dtype == torch.float32 and score.shape == y.shape
+    assert x0_prev is None or (x0_prev.dtype == torch.float64 and x0_prev.shape == y.shape)
+    c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+    assert c.size == _lib.EXPINT_COEFS, f"coef must hold {_lib.EXPINT_COEFS} values"
+    dev = y.device
+    ad = torch.as_tensor(active, dtype=torch.int32).to(dev).contiguous()
+    ld = torch.as_tensor(lengths, dtype=torch.int32).to(dev).contiguous()
+    assert ad.shape == (B,) and ld.shape == (B,), "active and lengths must be [B]"
+    if out is None:
+        out = (torch.zeros_like(y), torch.zeros_like(y), torch.zeros_like(score))
+    x0, y_new, x = out
+    norms = torch.zeros(B, 2, dtype=torch.float64, device=dev) if want_norms else None
+    ws = torch.empty(B * ODE_WORKSPACE_BYTES, dtype=torch.uint8, device=dev) if want_norms else None
+    call(lib(), "diffsep_expint_update_each", C.byref(sde_config(sde)), _ptr(y), _ptr(score), _ptr(sigma_mix), _ptr(x0_prev),
+         c.ctypes.data_as(C.c_void_p), _ptr(ad), _ptr(ld), _ptr(x0), _ptr(y_new), _ptr(x), _ptr(norms), B, S, T, _ptr(ws),
+         ws.numel() if want_norms else 0, _stream_ptr())
+    return (x0, y_new, x, norms) if want_norms else (x0, y_new, x)

@@ -302,9 +302,13 @@ def get_ode_fixed_sampler(sde, score_fn, y, method="heun", steps=None, schedule=
     t_start < sde.T — ops.warm_start builds one), lengths / seeds (a zero-padded batch, per-utterance seeds), want_err (heun,
     midpoint, ab2: the local-error trace [steps,B,2] on the device, ode_sampler.info["err"]).  On a dtype="hybrid" model
     the evaluations of the first head_steps solver steps run on its split-precision engine.
+    method "ddim" / "dpmpp2m" (DESIGN.md section 5m): the exponential integrators DDIM and DPM-Solver++ 2M, which integrate the
+    linear drift and the noise schedule of both eigenspaces of the SDE in closed form and discretise only the network's data
+    prediction — `steps` evaluations each, everything else as above; want_err with "dpmpp2m" (the step minus its DDIM step).
     Returns ode_sampler(z=None) -> (x, nfe); z [B,S,T] is used as the start state when given."""
-    if method not in _lib.ODEF_METHODS:
-        raise NotImplementedError(f"get_ode_fixed_sampler: method '{method}' is not implemented (one of {sorted(_lib.ODEF_METHODS)})")
+    if method not in _lib.ODEF_METHODS and method not in _lib.EXPINT_METHODS:
+        raise NotImplementedError(f"get_ode_fixed_sampler: method '{method}' is not implemented (one of "
+                                  f"{sorted(_lib.ODEF_METHODS) + sorted(_lib.EXPINT_METHODS)})")
     bad = sorted(set(kwargs) - set(_ODE_FIXED_KWARGS))
     if bad:
         raise TypeError(f"get_ode_fixed_sampler() got unexpected keyword argument(s) {bad} (accepted: {list(_ODE_FIXED_KWARGS)})")

@@ -41,14 +41,15 @@ step time at or below TAU with the SDE's own marginal, and only the reverse step
 network evaluations.  The run prints the executed steps, the evaluations per file and the files whose gain fit fell back to 1.
 A missing estimate, one whose length or rate differs from its mixture's, --t-start without --init-dir (or the reverse) and a
 combination with --chunk, --draws, --sampler ode or --resample are refused by name before any engine is created.
---sampler ode-fixed [--ode-method {euler,heun,midpoint,rk4,ab2}] [--ode-steps M]: the probability-flow ODE on a fixed grid
+--sampler ode-fixed [--ode-method {euler,heun,midpoint,rk4,ab2,ddim,dpmpp2m}] [--ode-steps M]: the probability-flow ODE on a fixed grid
 (DiffSepModel.get_ode_fixed_sampler, diffsep_ode_sample_fixed) — M steps (default N) of Heun's method (default)
 from t = 1 down to eps, deterministic given the seed, at a cost known beforehand (heun: 2 M network evaluations + the denoise
 one).  The call is enqueued like the PC sampler's, so --batch, --streams, --seed, --schedule, --resample and the precision flags
 (--fp32-steps counting solver steps) apply as they do there, and the written files do not depend on --batch or --streams.  With
 --init-dir DIR --t-start TAU the solve starts at TAU itself (no snapping to a step grid) and runs M steps from there.  Not with
 --chunk or --draws in this version.  Whether such a solve separates as well as the PC sampler at equal cost is not known (no
-trained checkpoint was at hand): this is the instrument.
+trained checkpoint was at hand): this is the instrument.  --ode-method ddim / dpmpp2m: DDIM and
+DPM-Solver++ 2M, exponential integrators that treat the SDE's linear drift and noise schedule in closed form, M evaluations each.
 """
 import argparse
 from pathlib import Path
@@ -190,9 +191,9 @@ def separate_on_device(mix, model, sampler_kwargs, device, lengths=None, seeds=N
 
 
 def add_ode_fixed_arguments(ap):
-    ap.add_argument("--ode-method", default=None, choices=["euler", "heun", "midpoint", "rk4", "ab2"],
+    ap.add_argument("--ode-method", default=None, choices=["euler", "heun", "midpoint", "rk4", "ab2", "ddim", "dpmpp2m"],
                     help="--sampler ode-fixed: the integrator (default heun); network evaluations for M steps: euler M, heun and "
-                         "midpoint 2 M, rk4 4 M, ab2 M + 1")
+                         "midpoint 2 M, rk4 4 M, ab2 M + 1; ddim and dpmpp2m (DPM-Solver++ 2M), the exponential integrators: M")
     ap.add_argument("--ode-steps", type=int, default=None, metavar="M",
                     help="--sampler ode-fixed: solver steps from t = 1 (or --t-start) down to eps (default: the sampler's N)")
 

@@ -367,6 +367,53 @@ int32_t diffsep_ode_sample_fixed(diffsep_engine* e, const diffsep_sde_config* sd
                                  const float* mix_norm, const float* x_init, const float* noise, uint64_t seed,
                                  const double* timesteps_host, float* out, double* err_out, int32_t B, int64_t T,
                                  int32_t* nfe_out, void* stream);
+/* The same ODE by EXPONENTIAL INTEGRATORS on the same grids: DDIM (first order) and DPM-Solver++ 2M (second-order multistep, step 0
+ * a DDIM step), M network evaluations each (no counterpart in the reference; the SDE is the reference's, sdes/sdes.py:180-349).
+ * A = 11^T / S and P = I - A commute with the mean matrix A + e^{-lambda t} P and with L(t) = sqrt(ev1) A + sqrt(ev2) P
+ * (MixSDE._cov_eigval, sdes/sdes.py:296-309), so the ODE is two scalar diffusions, one per eigenspace j in {A, P}:
+ * alpha_A = 1, sigma_A^2 = ev1; alpha_P = e^{-lambda t}, sigma_P^2 = ev2 (times sigma_mix[b,t]^2 for PriorMixSDE).  The linear drift
+ * and the noise schedule are integrated in closed form; only the network's data prediction is discretised.  Per step i from t_i
+ * to t_{i+1}, float64 on the host from the SDE's float parameters widened as they are, with a_A = 0, a_P = d_lambda:
+ *   alpha_j(t) = exp(-a_j t), ev_j(t) as _cov_eigval, lam_j = ln alpha_j - 0.5 ln ev_j, h_j = lam_j(t_{i+1}) - lam_j(t_i),
+ *   cx_j = sqrt(ev_j(t_{i+1}) / ev_j(t_i)), cd_j = -alpha_j(t_{i+1}) expm1(-h_j), w0_j = 1, w1_j = 0, and for DPMPP2M at i >= 1
+ *   r_j = h_j(i-1) / h_j(i), w0_j = 1 + 1 / (2 r_j), w1_j = -1 / (2 r_j).
+ * diffsep_expint_coefficients writes that table (host memory, no GPU needed): coef_out [steps][DIFFSEP_EXPINT_COEFS] =
+ *   cx_A cd_A w0_A w1_A | cx_P cd_P w0_P w1_P | alpha_A(t_i) ev_A(t_i) alpha_P(t_i) ev_P(t_i)
+ * for the grid diffsep_ode_sample_fixed builds from (steps, t_start, eps) or takes from timesteps_host, with its refusals in its
+ * words, and: an SDE kind that is neither MixSDE nor PriorMixSDE, a grid point where ev_1 <= 0, steps > 16384.
+ * The pass (csrc/ode.hip, one launch per step, per-utterance form), per time sample, every sum and product rounded on its own in
+ * float64 in the order written (sums over the sources run s = 0, 1, ..., then one division by S):
+ *   mx = mean_s y_s, ms = mean_s score_s, q = sigma_mix[b,t]^2 (widened, then squared; 1 for MixSDE),
+ *   X0_s = (mx + (ev_A q) ms) / alpha_A + ((y_s - mx) + (ev_P q) (score_s - ms)) / alpha_P          (Tweedie at t_i)
+ *   mX0n = mean_s X0_s, mX0p = mean_s X0p_s (the previous step's X0; without one both w1 terms are absent)
+ *   y'_s = (cx_A mx + cd_A (w0_A mX0n + w1_A mX0p)) + (cx_P (y_s - mx) + cd_P (w0_P (X0_s - mX0n) + w1_P (X0p_s - mX0p)))
+ * and the next network input is fp32(y'), evaluated at (float) t_{i+1}.
+ * diffsep_ode_sample_expint: the argument list, the grid, x_init / noise / seed, ext (lengths, seeds, tail engine counted in solver
+ * steps), denoise, the enqueued call without readback and the refusals of diffsep_ode_sample_fixed; nfe_out = steps.
+ *   err_out : NULL, or device float64 [M][B][2] (DPMPP2M only): per step and utterance the RMS of (step - its DDIM step) =
+ *             (cd_A (w0_A - 1)) (mX0n - mX0p) + (cd_P (w0_P - 1)) ((X0_s - mX0n) - (X0p_s - mX0p)), an exact 0 at step 0, and the RMS
+ *             of y_i; summed in the same launch into fixed-order fp64 partials, one small final launch per step.  With NULL not
+ *             one launch, copy or allocation is added and `out` is the same bits.
+ * Buffers: those of diffsep_ode_sample_fixed; the two X0 histories live in its stage-derivative buffers.
+ * diffsep_expint_update_each: the pass on caller buffers.  y, x0_prev (NULL: no previous X0), x0_out, y_new_out float64 [B,S,T];
+ * score, x_out float32 [B,S,T]; sigma_mix [B,T] for PriorMixSDE, else NULL; coef: HOST, one row of the table; active, lengths:
+ * DEVICE int32 [B] as in diffsep_ode_stage_update_each (inactive rows untouched, t >= lengths[b] never read and the three outputs
+ * written as exact zeros there); norms_out NULL, or device float64 [B][2] with workspace >= B * DIFFSEP_ODE_WORKSPACE_BYTES: the
+ * two values of err_out.  No output may alias an input. */
+#define DIFFSEP_EXPINT_DDIM 0
+#define DIFFSEP_EXPINT_DPMPP2M 1
+#define DIFFSEP_EXPINT_COEFS 12
+int32_t diffsep_ode_sample_expint(diffsep_engine* e, const diffsep_sde_config* sde, int32_t method, int32_t steps,
+                                  double t_start, double eps, int32_t denoise, int32_t N, const diffsep_sampler_ext* ext,
+                                  const float* mix_norm, const float* x_init, const float* noise, uint64_t seed,
+                                  const double* timesteps_host, float* out, double* err_out, int32_t B, int64_t T,
+                                  int32_t* nfe_out, void* stream);
+int32_t diffsep_expint_coefficients(const diffsep_sde_config* sde, int32_t method, int32_t steps, double t_start, double eps,
+                                    const double* timesteps_host, double* coef_out);
+int32_t diffsep_expint_update_each(const diffsep_sde_config* sde, const double* y, const float* score, const float* sigma_mix,
+                                   const double* x0_prev, const double* coef, const int32_t* active, const int32_t* lengths,
+                                   double* x0_out, double* y_new_out, float* x_out, double* norms_out, int32_t B, int32_t S,
+                                   int64_t T, void* workspace, int64_t workspace_bytes, void* stream);
 /* Butcher tableau of RK45 / RK23 exactly as scipy's rk.py holds it (sdes/__init__.py:193-278 -> solve_ivp): A [ns][ns]
  * row-major, B [ns], C [ns], E [ns+1]; every pointer may be NULL (host memory, no GPU needed). */
 int32_t diffsep_ode_tableau(int32_t method, double* A, double* B, double* C, double* E, int32_t* n_stages,

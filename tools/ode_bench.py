@@ -1,7 +1,7 @@
 """Cost of the probability-flow ODE sampler (Engine.ode_sample, sdes.get_ode_sampler) on one GPU.
 
     python tools/ode_bench.py [--nf 64] [--B 16] [--T 32000] [--rtol 1e-5] [--atol 1e-5] [--max-nfe 600]
-                              [--dtypes f32,split,f16] [--reps 2] [--each | --fixed]
+                              [--dtypes f32,split,f16] [--reps 2] [--each | --fixed [--distance]]
 
 Synthetic weights, synthetic mixtures, MixSDE.  Per engine dtype: nfev / accepted / rejected / status of the solve, the
 wall time of one batch (median of --reps timed calls after one warm-up call), and the share of that time spent outside
@@ -20,7 +20,10 @@ next to the PC sampler of the same plan (N = 30, one corrector step: 60 evaluati
 batch at a time — --reps timed calls of each of the three, alternating, after two warm-up calls each: median wall, min - max,
 and the wall per network evaluation — then --streams K (default 4) engines on K streams through inflight.Ring, --batches
 batches each, the three again alternating: wall per batch and batches per second; and the local-error trace of Heun at M = 30 and
-M = 120 (want_err).  Prints one JSON line per dtype.
+M = 120 (want_err).  The exponential integrators of the same entry ride along in every part: DDIM and DPM-Solver++ 2M at M = 30
+(30 evaluations + denoise), and the trace of 2M (step minus its DDIM step).  --distance adds the rel RMS distance of ddim / dpmpp2m /
+heun at M = 32, 64, 128 (no denoise) from the adaptive solve at --rtol / --atol (--max-nfe 0 lets it finish) from the same start
+state.  Prints one JSON line per dtype.
 """
 import argparse
 import json
@@ -82,7 +85,9 @@ def bench_fixed(cfg, sd, mix_norm, args, name):
     streams = [torch.cuda.Stream() for _ in range(K)]
     runs = {"pc": (lambda e: e.pc_sample(mix_norm, MIX, N=30, corrector_steps=1, seed=1)[0], 60),
             "heun30": (lambda e: e.ode_sample_fixed(mix_norm, MIX, method="heun", steps=30, seed=1)[0], 61),
-            "euler30": (lambda e: e.ode_sample_fixed(mix_norm, MIX, method="euler", steps=30, seed=1)[0], 31)}
+            "euler30": (lambda e: e.ode_sample_fixed(mix_norm, MIX, method="euler", steps=30, seed=1)[0], 31),
+            "ddim30": (lambda e: e.ode_sample_fixed(mix_norm, MIX, method="ddim", steps=30, seed=1)[0], 31),
+            "dpmpp2m30": (lambda e: e.ode_sample_fixed(mix_norm, MIX, method="dpmpp2m", steps=30, seed=1)[0], 31)}
     res = dict(mode="fixed", dtype=name, nf=args.nf, B=mix_norm.shape[0], T=args.T, streams=K, batches=args.batches,
                hw_queues=os.environ.get("GPU_MAX_HW_QUEUES"))
     walls = {k: [] for k in runs}
@@ -108,6 +113,23 @@ def bench_fixed(cfg, sd, mix_norm, args, name):
         res[f"heun{M}_local_err"] = dict(max=round(float(rel.max()), 5), median=round(float(rel.median()), 5),
                                          first=[round(float(v), 5) for v in rel[:3]], last=[round(float(v), 5) for v in rel[-3:]],
                                          step_of_max=int(rel.argmax()))
+    _, info = engines[0].ode_sample_fixed(mix_norm, MIX, method="dpmpp2m", steps=30, seed=1, want_err=True)
+    rel = (info["err"][:, :, 0] / info["err"][:, :, 1]).amax(dim=1).cpu()  # rms(step - its DDIM step) / rms(y)
+    res["dpmpp2m30_local_err"] = dict(max=round(float(rel.max()), 5), median=round(float(rel.median()), 5),
+                                      first=[round(float(v), 5) for v in rel[:3]], last=[round(float(v), 5) for v in rel[-3:]],
+                                      step_of_max=int(rel.argmax()))
+    if args.distance:  # how far the fixed-grid solves end from the adaptive one (RK45 at --rtol / --atol), same start state
+        z = torch.from_numpy(synth.synth_noise("ode_bench.distance", tuple(mix_norm.shape[:1]) + (2, args.T))).cuda()
+        x_T = ops.sde_prior(MIX, mix_norm, z)
+        ref, rinfo = engines[0].ode_sample(mix_norm, MIX, rtol=args.rtol, atol=args.atol, max_nfe=args.max_nfe, denoise=False,
+                                           x_init=x_T)
+        dist = dict(rk45_nfev=rinfo["nfev"], rk45_status=rinfo["status"])
+        for method in ("ddim", "dpmpp2m", "heun"):
+            for M in (32, 64, 128):
+                out, _ = engines[0].ode_sample_fixed(mix_norm, MIX, method=method, steps=M, denoise=False, x_init=x_T)
+                d = (out.double() - ref.double()).pow(2).mean().sqrt() / ref.double().pow(2).mean().sqrt()
+                dist[f"{method}{M}"] = round(float(d), 5)
+        res["distance_rel_rms"] = dist
     if K > 1:
         for e in engines:
             e.set_option("rw_quarter", 1)  # the throughput mode of the CLIs (DiffSepModel.set_throughput_mode)
@@ -144,6 +166,8 @@ def main():
     ap.add_argument("--fixed", action="store_true", help="the fixed-step sampler next to the PC sampler, alone and in flight")
     ap.add_argument("--streams", type=int, default=4, help="--fixed: engines / streams in flight")
     ap.add_argument("--batches", type=int, default=12, help="--fixed: batches per in-flight run")
+    ap.add_argument("--distance", action="store_true",
+                    help="--fixed: also the rel RMS distance of ddim / dpmpp2m / heun at M = 32, 64, 128 from the adaptive solve")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
     mix = torch.from_numpy(synth.synth_batch(args.B, T=args.T)[0]).cuda()
