@@ -400,5 +400,11 @@ int ensure_plan(diffsep_engine* e, int B, long T, hipStream_t st);
 int run_nfe(diffsep_engine* e, int B, long T, hipStream_t st);
 // sampler.hip: zero the tail t >= lens[b] of [B][rows][T] rows (the mixture of a mixed-length batch)
 int ds_launch_mask_tail(float* v, int B, int rows, long T, const int* lens, hipStream_t st);
+// sampler.hip: what every entry asks of the SDE description and of the batch extensions (`who`: the entry's name in the
+// message; a null extension field is not checked, and the lengths need no engine), and PriorMixSDE's noise scale of st_mix
+int check_sde(const diffsep_engine* e, const diffsep_sde_config* sde, const char* who);
+int check_batch_ext(const diffsep_model_config* cfg, const char* who, int B, long T, const int64_t* lengths,
+                    const uint64_t* seeds, const float* noise, const diffsep_engine* e, const diffsep_engine* tail);
+int mixture_scale(diffsep_engine* e, const diffsep_sde_config* sde, int B, long T, hipStream_t st, const float** smix);
 
 #pragma GCC visibility pop

@@ -164,11 +164,39 @@ struct OdeCtl {
 // — and the driver in sampler.hip only walks it; tests/ode_fixed_main.cpp walks it on a small float64 system.
 #define DS_ODEF_MAX_EVALS 16384  // steps x stages of one solve (the rows of the evaluation-time table)
 
-struct OdeFixedConfig {  // the arguments of diffsep_ode_sample_fixed that shape the solve
-  int method, steps;     // DIFFSEP_ODEF_*, M
+struct OdeFixedConfig {  // the arguments of diffsep_ode_sample_fixed / _expint that shape the solve
+  int method, steps;     // DIFFSEP_ODEF_* / DIFFSEP_EXPINT_*, M
   double t_start, eps;   // t_start <= 0: 1.0 (sde.T)
   int denoise, N;        // as diffsep_ode_config
 };
+using OdeExpintConfig = OdeFixedConfig;  // (the name the exponential-integrator side and its stand-alone program use)
+
+// The grid of both fixed-grid solves: M + 1 times, strictly descending, inside (0, 1] — `timesteps` (M + 1 host times) or, with
+// null, uniform from t_start to eps.  Returns the message (`who`: the entry point's name in it), empty when all is well.
+// `refusal`: what the caller's method refuses of the request (its err_out rule), if anything; it ranks after the argument checks
+// and before the grid's.  (The caller has bounded oc.steps from above.)
+inline std::string ode_grid_fill(const OdeFixedConfig& oc, const double* timesteps, const char* who, std::vector<double>& t,
+                                 const char* refusal = nullptr) {
+  const std::string w(who);
+  const int M = oc.steps;
+  if (!(M >= 1)) return w + ": steps must be >= 1";
+  if (!(oc.eps > 0.0 && oc.eps < 1.0)) return w + ": eps must be in (0, 1)";
+  if (!(oc.N >= 1 || !oc.denoise)) return w + ": the denoise step needs N >= 1";
+  if (refusal) return w + refusal;
+  t.resize((size_t)M + 1);
+  if (timesteps) {
+    for (int i = 0; i <= M; ++i) t[i] = timesteps[i];
+  } else {
+    const double t0 = oc.t_start <= 0.0 ? 1.0 : oc.t_start;
+    if (!(t0 > oc.eps)) return w + ": t_start must be above eps";
+    for (int i = 0; i < M; ++i) t[i] = t0 + (oc.eps - t0) * i / M;
+    t[M] = oc.eps;  // (t0 + (eps - t0) M / M rounds next to eps; the solve ends where the denoise step stands)
+  }
+  for (int i = 0; i <= M; ++i)
+    if (!(t[i] > 0.0 && t[i] <= 1.0 && (i == 0 || t[i] < t[i - 1])))
+      return w + ": the time grid must be strictly descending inside (0, 1]";
+  return std::string();
+}
 
 // Explicit tableau of the one-step methods in OdePlan's layout (row s of A at A + s * DS_ODE_MAX_K) and, where the method
 // has an embedded Euler step, D with  step - Euler step = h sum_j D[j] K_j  (has_d; Euler and RK4 have none).
@@ -240,25 +268,11 @@ inline std::string ode_fixed_plan_fill(OdeFixedPlan& p, const OdeFixedConfig& oc
     return w + ": method must be DIFFSEP_ODEF_EULER, HEUN, MIDPOINT, RK4 or AB2";
   const bool ab2 = oc.method == DIFFSEP_ODEF_AB2;
   const int M = oc.steps;
-  if (!(M >= 1)) return w + ": steps must be >= 1";
   if (!((long)M * ns <= DS_ODEF_MAX_EVALS)) return w + ": steps x stages must be <= 16384";
-  if (!(oc.eps > 0.0 && oc.eps < 1.0)) return w + ": eps must be in (0, 1)";
-  if (!(oc.N >= 1 || !oc.denoise)) return w + ": the denoise step needs N >= 1";
-  if (want_err && !p.has_err)
-    return w + ": err_out needs a method with an embedded Euler step (HEUN, MIDPOINT, AB2), not EULER or RK4";
+  const std::string bad = ode_grid_fill(oc, timesteps, who, p.t, (want_err && !p.has_err)
+      ? ": err_out needs a method with an embedded Euler step (HEUN, MIDPOINT, AB2), not EULER or RK4" : nullptr);
+  if (!bad.empty()) return bad;
   p.method = oc.method; p.M = M; p.eps = oc.eps; p.denoise = oc.denoise; p.N = oc.N;
-  p.t.resize((size_t)M + 1);
-  if (timesteps) {
-    for (int i = 0; i <= M; ++i) p.t[i] = timesteps[i];
-  } else {
-    const double t0 = oc.t_start <= 0.0 ? 1.0 : oc.t_start;
-    if (!(t0 > oc.eps)) return w + ": t_start must be above eps";
-    for (int i = 0; i < M; ++i) p.t[i] = t0 + (oc.eps - t0) * i / M;
-    p.t[M] = oc.eps;  // (t0 + (eps - t0) M / M rounds next to eps; the solve ends where the denoise step stands)
-  }
-  for (int i = 0; i <= M; ++i)
-    if (!(p.t[i] > 0.0 && p.t[i] <= 1.0 && (i == 0 || p.t[i] < p.t[i - 1])))
-      return w + ": the time grid must be strictly descending inside (0, 1]";
 
   auto stage_pass = [&](int i, int s, double h) {  // the pass after stage s of Runge-Kutta step i
     OdeFixedPass q;
@@ -308,12 +322,6 @@ enum {  // one row of the table: step i, from t_i to t_{i+1}
   DS_EI_AL_A, DS_EI_EV_A, DS_EI_AL_P, DS_EI_EV_P  // alpha_j(t_i), ev_j(t_i): the data prediction at t_i
 };
 
-struct OdeExpintConfig {  // the arguments of diffsep_ode_sample_expint that shape the solve
-  int method, steps;      // DIFFSEP_EXPINT_*, M
-  double t_start, eps;    // t_start <= 0: 1.0 (sde.T)
-  int denoise, N;         // as diffsep_ode_config
-};
-
 struct OdeExpintPlan {
   int method = 0, M = 0;
   double eps = 0.0;
@@ -331,9 +339,9 @@ inline void ds_expint_eig(const diffsep_sde_config& s, double t, double& ev1, do
   ev2 = mult * (srp - exp(-2.0 * (double)s.d_lambda * t)) / (1.0 + (double)s.d_lambda / log(r));
 }
 
-// Fill and validate (`who`, timesteps as ode_fixed_plan_fill: the same grid, the same refusals in the same words; want_err:
-// the caller asks for the local-error trace); returns the message, empty when all is well.
-inline std::string ode_expint_plan_fill(OdeExpintPlan& p, const OdeExpintConfig& oc, const diffsep_sde_config& sde,
+// Fill and validate (`who`, timesteps as ode_fixed_plan_fill: the grid is ode_grid_fill's; want_err: the caller asks for the
+// local-error trace); returns the message, empty when all is well.
+inline std::string ode_expint_plan_fill(OdeExpintPlan& p, const OdeFixedConfig& oc, const diffsep_sde_config& sde,
                                         const double* timesteps, bool want_err, const char* who) {
   const std::string w(who);
   p = OdeExpintPlan();
@@ -342,25 +350,11 @@ inline std::string ode_expint_plan_fill(OdeExpintPlan& p, const OdeExpintConfig&
   if (!(sde.kind == DIFFSEP_SDE_MIX || sde.kind == DIFFSEP_SDE_PRIORMIX))
     return w + ": the exponential integrators need a MixSDE or a PriorMixSDE (two eigenspaces with closed-form schedules)";
   const int M = oc.steps;
-  if (!(M >= 1)) return w + ": steps must be >= 1";
   if (!(M <= DS_ODEF_MAX_EVALS)) return w + ": steps must be <= 16384";
-  if (!(oc.eps > 0.0 && oc.eps < 1.0)) return w + ": eps must be in (0, 1)";
-  if (!(oc.N >= 1 || !oc.denoise)) return w + ": the denoise step needs N >= 1";
-  if (want_err && oc.method != DIFFSEP_EXPINT_DPMPP2M)
-    return w + ": err_out needs the second-order method (DPMPP2M: step minus its DDIM step), not DDIM";
+  const std::string bad = ode_grid_fill(oc, timesteps, who, p.t, (want_err && oc.method != DIFFSEP_EXPINT_DPMPP2M)
+      ? ": err_out needs the second-order method (DPMPP2M: step minus its DDIM step), not DDIM" : nullptr);
+  if (!bad.empty()) return bad;
   p.method = oc.method; p.M = M; p.eps = oc.eps; p.denoise = oc.denoise; p.N = oc.N;
-  p.t.resize((size_t)M + 1);
-  if (timesteps) {
-    for (int i = 0; i <= M; ++i) p.t[i] = timesteps[i];
-  } else {
-    const double t0 = oc.t_start <= 0.0 ? 1.0 : oc.t_start;
-    if (!(t0 > oc.eps)) return w + ": t_start must be above eps";
-    for (int i = 0; i < M; ++i) p.t[i] = t0 + (oc.eps - t0) * i / M;
-    p.t[M] = oc.eps;
-  }
-  for (int i = 0; i <= M; ++i)
-    if (!(p.t[i] > 0.0 && p.t[i] <= 1.0 && (i == 0 || p.t[i] < p.t[i - 1])))
-      return w + ": the time grid must be strictly descending inside (0, 1]";
   // per grid point and eigenspace: alpha, ev and the half log-SNR
   const double a[2] = {0.0, (double)sde.d_lambda};
   std::vector<double> al(2 * ((size_t)M + 1)), ev(al.size()), lam(al.size());

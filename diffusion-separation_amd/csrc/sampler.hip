@@ -26,8 +26,8 @@ int ds_launch_mask_tail(float* v, int B, int rows, long T, const int* lens, hipS
   return 0;
 }
 
-// What both samplers ask of the SDE description (`who`: the entry point's name in the message)
-static int check_sde(const diffsep_engine* e, const diffsep_sde_config* sde, const char* who) {
+// What every entry asks of the SDE description (`who`: the entry point's name in the message)
+int check_sde(const diffsep_engine* e, const diffsep_sde_config* sde, const char* who) {
   const std::string w(who);
   DS_CHECK(sde->kind == DIFFSEP_SDE_MIX || sde->kind == DIFFSEP_SDE_PRIORMIX, w + ": unknown SDE kind");
   DS_CHECK(sde->kind == DIFFSEP_SDE_MIX || sde->avg_len >= 1, w + ": PriorMixSDE needs avg_len >= 1");
@@ -35,12 +35,123 @@ static int check_sde(const diffsep_engine* e, const diffsep_sde_config* sde, con
   return 0;
 }
 // PriorMixSDE: the per-sample noise scale from the envelope of the mixture in st_mix (sdes.py:477-489); MixSDE: none (null)
-static int mixture_scale(diffsep_engine* e, const diffsep_sde_config* sde, int B, long T, hipStream_t st, const float** smix) {
+int mixture_scale(diffsep_engine* e, const diffsep_sde_config* sde, int B, long T, hipStream_t st, const float** smix) {
   *smix = nullptr;
   if (sde->kind != DIFFSEP_SDE_PRIORMIX) return 0;
   if (ds_launch_sigma_mix(e->st_mix, e->st_smix, B, T, sde->avg_len, st)) return 1;
   *smix = e->st_smix;
   return 0;
+}
+
+// What every entry asks of the batch extensions (diffsep_sampler_ext / diffsep_ode_ext, by field), before anything is
+// enqueued: the other engine, seeds against host noise, the lengths of a zero-padded batch.  A null field is not checked.
+int check_batch_ext(const diffsep_model_config* cfg, const char* who, int B, long T, const int64_t* lengths,
+                    const uint64_t* seeds, const float* noise, const diffsep_engine* e, const diffsep_engine* tail) {
+  const std::string w(who);
+  if (tail) {
+    const std::string must = w + ": the tail engine must ";
+    DS_CHECK(tail != e, must + "be a different engine");
+    diffsep_model_config a = e->cfg, b2 = tail->cfg;
+    a.dtype = b2.dtype = 0;
+    DS_CHECK(memcmp(&a, &b2, sizeof(a)) == 0, must + "have the same architecture");
+  }
+  DS_CHECK(!seeds || !noise, w + ": per-utterance seeds are for device noise (noise == NULL)");
+  if (lengths) {
+    const int Wp = diffsep_padded_frames(cfg, T);
+    for (int b = 0; b < B; ++b) {
+      DS_CHECK(lengths[b] >= 1 && lengths[b] <= T, w + ": utterance length outside [1, T]");
+      DS_CHECK(diffsep_padded_frames(cfg, lengths[b]) == Wp,
+               w + ": every utterance of a mixed-length batch must have the padded frame count of T");
+    }
+  }
+  return 0;
+}
+
+namespace {
+// The batch as the entries below see it on the device.  Which parts an entry uses decides the bits of its result, so each
+// choice is an argument of the two functions that fill this.
+struct SamplerBatch {
+  const int* lens = nullptr;       // st_lens once uploaded (T where no lengths are given): what per-utterance passes read
+  const int* tail_lens = nullptr;  // st_lens of a batch WITH lengths: what masks a tail
+  const float* smix = nullptr;     // PriorMixSDE's noise scale
+};
+
+// The evaluation of one step's score: on e, or — in the first head_steps and last tail_steps of n_steps steps — on the other
+// engine (mixture once, state and time every time copied over; the score read from there).
+struct ScoreEval {
+  diffsep_engine *e, *tail;
+  int head_steps, tail_steps, n_steps, B;
+  long T;
+  size_t nst;
+  hipStream_t st;
+  bool tail_ready = false;
+  const float* score;  // where the last evaluation left it
+  // the other engine an extension names: none unless it gives it a step
+  static diffsep_engine* other(const diffsep_sampler_ext* ext) {
+    return (ext && (ext->tail_steps > 0 || ext->head_steps > 0)) ? ext->tail_engine : nullptr;
+  }
+  ScoreEval(diffsep_engine* e_, diffsep_engine* tail_, const diffsep_sampler_ext* ext, int n_steps_, int B_, long T_,
+            size_t nst_, hipStream_t st_)
+      : e(e_), tail(tail_), head_steps(tail_ ? ext->head_steps : 0), tail_steps(tail_ ? ext->tail_steps : 0),
+        n_steps(n_steps_), B(B_), T(T_), nst(nst_), st(st_), score(e_->st_score) {}
+  int eval(int i) {
+    if (tail && (i >= n_steps - tail_steps || i < head_steps)) {
+      if (!tail_ready) {
+        DS_HIP(hipMemcpyAsync(tail->st_mix, e->st_mix, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
+        tail_ready = true;
+      }
+      DS_HIP(hipMemcpyAsync(tail->st_x, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
+      DS_HIP(hipMemcpyAsync(tail->st_t, e->st_t, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+      score = tail->st_score;
+      return run_nfe(tail, B, T, st);
+    }
+    score = e->st_score;
+    return run_nfe(e, B, T, st);
+  }
+};
+}  // namespace
+
+// mixture -> st_mix; with `upload` seeds (given, or seed + b * stride: b = 0 is the B = 1 stream of `seed`) and lengths (T
+// where none are given) -> st_seeds, st_lens through pinned staging, stream-ordered; the mixture's tails zeroed
+static int batch_mixture(diffsep_engine* e, SamplerBatch& sb, const float* mix_norm, int B, long T, const int64_t* lengths,
+                         const uint64_t* seeds, uint64_t seed, bool upload, hipStream_t st) {
+  DS_HIP(hipMemcpyAsync(e->st_mix, mix_norm, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
+  if (!upload) return 0;
+  char* pin;
+  if (e->ext_pin.acquire((size_t)B * 16, &pin)) return 1;
+  unsigned long long* ps = reinterpret_cast<unsigned long long*>(pin);
+  int* pl = reinterpret_cast<int*>(pin + (size_t)B * 8);
+  for (int b = 0; b < B; ++b) {
+    ps[b] = seeds ? seeds[b] : seed + 0x9E3779B97F4A7C15ull * (unsigned long long)b;
+    pl[b] = lengths ? (int)lengths[b] : (int)T;
+  }
+  DS_HIP(hipMemcpyAsync(e->st_seeds, ps, (size_t)B * 8, hipMemcpyHostToDevice, st));
+  DS_HIP(hipMemcpyAsync(e->st_lens, pl, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  if (e->ext_pin.record(st)) return 1;
+  sb.lens = e->st_lens;
+  sb.tail_lens = lengths ? e->st_lens : nullptr;
+  return lengths ? ds_launch_mask_tail(e->st_mix, B, 1, T, sb.lens, st) : 0;
+}
+
+// sigma_mix, then the start state -> st_x: the caller's x_init with its tails zeroed like the mixture's, or the prior sample
+// from z — null: from draw 0 of the device generator, the PC sampler's prior draw, keyed per utterance (st_seeds, st_lens)
+// with batch_rng and by `seed` for the whole batch without.  prior_lens: the lengths the prior sample is cut to, if any.
+static int batch_start(diffsep_engine* e, const diffsep_sde_config* sde, SamplerBatch& sb, int B, long T, const float* x_init,
+                       const float* z, bool batch_rng, uint64_t seed, const int* prior_lens, hipStream_t st) {
+  const int S = e->cfg.num_sources;
+  const size_t nst = (size_t)B * S * T;
+  if (mixture_scale(e, sde, B, T, st, &sb.smix)) return 1;
+  if (x_init) {
+    DS_HIP(hipMemcpyAsync(e->st_x, x_init, nst * 4, hipMemcpyDeviceToDevice, st));
+    return sb.tail_lens ? ds_launch_mask_tail(e->st_x, B, S, T, sb.tail_lens, st) : 0;
+  }
+  if (!z) {
+    if (batch_rng ? ds_launch_randn_batch(e->st_noise, B, S, T, (const uint64_t*)e->st_seeds, e->st_lens, 0, st)
+                  : ds_launch_randn(e->st_noise, (long)nst, seed, 0, st))
+      return 1;
+    z = e->st_noise;
+  }
+  return ds_launch_sde_prior(to_sdep(sde), e->st_mix, z, e->st_x, B, S, T, sb.smix, st, prior_lens);
 }
 
 // The sampler, with an optional tap on its intermediate states (reference sdes/__init__.py:168-186, `intermediate`; the
@@ -85,28 +196,12 @@ extern "C" int32_t diffsep_pc_sample_from(diffsep_engine* e, const diffsep_sde_c
            "pc_sample: the 'ald' corrector supports MixSDE only (sdes/correctors.py:64-67)");
   const int64_t* lengths = ext ? ext->lengths_host : nullptr;
   const uint64_t* seeds = ext ? ext->seeds_host : nullptr;
-  diffsep_engine* tail = (ext && (ext->tail_steps > 0 || ext->head_steps > 0)) ? ext->tail_engine : nullptr;
-  const int tail_steps = tail ? ext->tail_steps : 0;
-  const int head_steps = tail ? ext->head_steps : 0;
-  if (tail) {
-    DS_CHECK(tail != e, "pc_sample: the tail engine must be a different engine");
-    diffsep_model_config a = e->cfg, b2 = tail->cfg;
-    a.dtype = b2.dtype = 0;
-    DS_CHECK(memcmp(&a, &b2, sizeof(a)) == 0, "pc_sample: the tail engine must have the same architecture");
-  }
-  // (head_steps / tail_steps are absolute steps: a range that holds none of them never touches the other engine)
-  if (tail && !(first < head_steps || last > smp->N - tail_steps)) tail = nullptr;
+  diffsep_engine* tail = ScoreEval::other(ext);
   DS_CHECK(!lengths || smp->corrector != DIFFSEP_CORR_LANGEVIN,
            "pc_sample: the 'langevin' corrector couples the batch entries; it cannot run on a mixed-length batch");
-  DS_CHECK(!seeds || !noise, "pc_sample: per-utterance seeds are for device noise (noise == NULL)");
-  if (lengths) {
-    const int Wp = diffsep_padded_frames(&e->cfg, T);
-    for (int b = 0; b < B; ++b) {
-      DS_CHECK(lengths[b] >= 1 && lengths[b] <= T, "pc_sample: utterance length outside [1, T]");
-      DS_CHECK(diffsep_padded_frames(&e->cfg, lengths[b]) == Wp,
-               "pc_sample: every utterance of a mixed-length batch must have the padded frame count of T");
-    }
-  }
+  if (check_batch_ext(&e->cfg, "pc_sample", B, T, lengths, seeds, noise, e, tail)) return 1;
+  // (head_steps / tail_steps are absolute steps: a range that holds none of them never touches the other engine)
+  if (tail && !(first < ext->head_steps || last > smp->N - ext->tail_steps)) tail = nullptr;
   StreamScope sc_(e, stream);
   hipStream_t st = sc_.st;
   const int S = e->cfg.num_sources, N = smp->N;
@@ -132,26 +227,9 @@ extern "C" int32_t diffsep_pc_sample_from(diffsep_engine* e, const diffsep_sde_c
     e->ts_dev = ts;
     e->ts_B = B;
   }
-  DS_HIP(hipMemcpyAsync(e->st_mix, mix_norm, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
-  const int* lens = nullptr;
-  if (lengths || seeds) {  // per-utterance lengths / seeds -> device (pinned staging, stream-ordered)
-    char* pin;
-    if (e->ext_pin.acquire((size_t)B * 16, &pin)) return 1;
-    unsigned long long* ps = reinterpret_cast<unsigned long long*>(pin);
-    int* pl = reinterpret_cast<int*>(pin + (size_t)B * 8);
-    for (int b = 0; b < B; ++b) {
-      ps[b] = seeds ? seeds[b] : seed + 0x9E3779B97F4A7C15ull * (unsigned long long)b;  // (b = 0: the B = 1 stream of `seed`)
-      pl[b] = lengths ? (int)lengths[b] : (int)T;
-    }
-    DS_HIP(hipMemcpyAsync(e->st_seeds, ps, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    DS_HIP(hipMemcpyAsync(e->st_lens, pl, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    if (e->ext_pin.record(st)) return 1;
-    if (lengths) {
-      lens = e->st_lens;
-      hipLaunchKernelGGL(mask_tail_kernel, dim3(cdiv(T, 256), B), dim3(256), 0, st, e->st_mix, 1, (long)T, lens);
-      DS_LAUNCH_CHECK();
-    }
-  }
+  SamplerBatch sb;  // (seeds and lengths go up only when the extension gives one of them)
+  if (batch_mixture(e, sb, mix_norm, B, T, lengths, seeds, seed, lengths || seeds, st)) return 1;
+  const int* lens = sb.tail_lens;
   const bool batch_rng = !noise && (seeds || lengths);
 
   long draw = x_init ? 1 + (long)first * (csteps + npred) : 0;  // (a given state: draw 0, the prior's, is not generated)
@@ -170,43 +248,20 @@ extern "C" int32_t diffsep_pc_sample_from(diffsep_engine* e, const diffsep_sde_c
   };
   const float* z = nullptr;
   if (!x_init && next_noise(&z)) return 1;
-  const float* smix = nullptr;
-  if (mixture_scale(e, sde, B, T, st, &smix)) return 1;
-  if (x_init) {  // the caller's state instead of the prior; its tail zero like the mixture's
-    DS_HIP(hipMemcpyAsync(e->st_x, x_init, nst * 4, hipMemcpyDeviceToDevice, st));
-    if (lens && ds_launch_mask_tail(e->st_x, B, S, T, lens, st)) return 1;
-  } else if (ds_launch_sde_prior(sp, e->st_mix, z, e->st_x, B, S, T, smix, st, lens)) {
-    return 1;
-  }
+  if (batch_start(e, sde, sb, B, T, x_init, z, batch_rng, seed, lens, st)) return 1;  // (z: drawn above, counted and profiled)
+  const float* smix = sb.smix;
   DS_HIP(hipMemcpyAsync(e->st_xm, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
-  // one score evaluation of reverse step i: on this engine, or — in the last tail_steps steps — on the tail engine
-  // (state and time step copied over, the score read from there)
-  bool tail_ready = false;
-  const float* score = e->st_score;
-  auto eval_score = [&](int i) -> int {
-    if (tail && (i >= N - tail_steps || i < head_steps)) {
-      if (!tail_ready) {
-        DS_HIP(hipMemcpyAsync(tail->st_mix, e->st_mix, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
-        tail_ready = true;
-      }
-      DS_HIP(hipMemcpyAsync(tail->st_x, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
-      DS_HIP(hipMemcpyAsync(tail->st_t, e->st_t, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-      score = tail->st_score;
-      return run_nfe(tail, B, T, st);
-    }
-    score = e->st_score;
-    return run_nfe(e, B, T, st);
-  };
+  ScoreEval ev(e, tail, ext, N, B, T, nst, st);  // reverse step i is step i of N
   for (int i = first; i < last; ++i) {
     DS_HIP(hipMemcpyAsync(e->st_t, e->st_ts + (size_t)i * B, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
     for (int k = 0; k < csteps; ++k) {
-      if (eval_score(i)) return 1;
+      if (ev.eval(i)) return 1;
       if (next_noise(&z)) return 1;
       if (smp->corrector == DIFFSEP_CORR_LANGEVIN) {
-        if (ds_launch_langevin(smp->snr, e->st_x, score, z, e->st_x, e->st_xm, B, (long)S * T, e->st_lang, st))
+        if (ds_launch_langevin(smp->snr, e->st_x, ev.score, z, e->st_x, e->st_xm, B, (long)S * T, e->st_lang, st))
           return 1;
       } else if (prof_launch(e, st, hbm_rec("sde_corrector (ald2 update)", 4.0 * nst * 5.0, B, 1, (int)T, S), [&]() {  // x, score, z in; x, x_mean out
-                   return ds_launch_sde_corrector(sp, smp->snr, e->st_x, e->st_t, score, z, e->st_x, e->st_xm, B, S, T,
+                   return ds_launch_sde_corrector(sp, smp->snr, e->st_x, e->st_t, ev.score, z, e->st_x, e->st_xm, B, S, T,
                                                   smix, smp->corrector == DIFFSEP_CORR_ALD ? 1 : 0, st, lens);
                  })) {
         return 1;
@@ -229,10 +284,10 @@ extern "C" int32_t diffsep_pc_sample_from(diffsep_engine* e, const diffsep_sde_c
     if (smp->predictor != DIFFSEP_PRED_NONE) {
       // euler_maruyama (sdes/predictors.py:39-52) takes x + f*dt with the reverse drift f = drift - g^2 score and
       // noise g sqrt(dt): algebraically the reverse_diffusion step (dt = 1/N, G = g sqrt(dt)) — one kernel for both
-      if (eval_score(i)) return 1;
+      if (ev.eval(i)) return 1;
       if (next_noise(&z)) return 1;
       if (prof_launch(e, st, hbm_rec("sde_predictor (reverse-diffusion update)", 4.0 * nst * 5.0, B, 1, (int)T, S), [&]() {
-            return ds_launch_sde_predictor(sp, N, e->st_x, e->st_t, score, z, e->st_x, e->st_xm, B, S, T, smix, 0, st, lens);
+            return ds_launch_sde_predictor(sp, N, e->st_x, e->st_t, ev.score, z, e->st_x, e->st_xm, B, S, T, smix, 0, st, lens);
           }))
         return 1;
     } else {
@@ -342,14 +397,14 @@ static diffsep_engine::ProfRec ode_pass_rec(const char* name, size_t nst, int nk
 
 // solution.y[:, -1] (the last accepted state) -> float32; optional denoise: x_mean of one reverse_diffusion step at eps
 // without noise (reference denoise_update_fn; dt = 1/N, quirk Q1).  lens: the tails of a zero-padded batch stay zero.
-static int ode_finish(diffsep_engine* e, const SdeP& sp, const diffsep_ode_config* oc, const float* smix, const double* y,
+static int ode_finish(diffsep_engine* e, const SdeP& sp, double eps, int denoise, int N, const float* smix, const double* y,
                       float* out, int B, int S, long T, const int* lens, hipStream_t st) {
   const size_t nst = (size_t)B * S * T;
   if (ds_launch_ode_round(y, e->st_x, (long)nst, st)) return 1;
-  if (oc->denoise) {
-    if (ds_launch_fill(e->st_t, (float)oc->eps, B, st)) return 1;
+  if (denoise) {
+    if (ds_launch_fill(e->st_t, (float)eps, B, st)) return 1;
     if (run_nfe(e, B, T, st)) return 1;
-    if (ds_launch_sde_predictor(sp, oc->N, e->st_x, e->st_t, e->st_score, nullptr, e->st_xm, out, B, S, T, smix, 0, st, lens))
+    if (ds_launch_sde_predictor(sp, N, e->st_x, e->st_t, e->st_score, nullptr, e->st_xm, out, B, S, T, smix, 0, st, lens))
       return 1;
   } else {
     DS_HIP(hipMemcpyAsync(out, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
@@ -384,19 +439,10 @@ extern "C" int32_t diffsep_ode_sample(diffsep_engine* e, const diffsep_sde_confi
   const SdeP sp = to_sdep(sde);
 
   // x_T -> st_x (and y = x_T in fp64)
-  DS_HIP(hipMemcpyAsync(e->st_mix, mix_norm, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
-  const float* smix = nullptr;
-  if (mixture_scale(e, sde, B, T, st, &smix)) return 1;
-  if (x_init) {
-    DS_HIP(hipMemcpyAsync(e->st_x, x_init, nst * 4, hipMemcpyDeviceToDevice, st));
-  } else {
-    const float* z = noise;
-    if (!z) {  // the PC sampler's prior draw of the same seed (its draw 0)
-      if (ds_launch_randn(e->st_noise, (long)nst, seed, 0, st)) return 1;
-      z = e->st_noise;
-    }
-    if (ds_launch_sde_prior(sp, e->st_mix, z, e->st_x, B, S, T, smix, st)) return 1;
-  }
+  SamplerBatch sb;  // (no extension: nothing is uploaded, the prior draw is the whole batch's, nothing is cut or masked)
+  if (batch_mixture(e, sb, mix_norm, B, T, nullptr, nullptr, seed, false, st)) return 1;
+  if (batch_start(e, sde, sb, B, T, x_init, noise, false, seed, nullptr, st)) return 1;
+  const float* smix = sb.smix;
   if (ds_launch_ode_cast(e->st_x, w.y, (long)nst, st)) return 1;
 
   const OdeArgs base = ode_base_args(e, sp, smix, plan, w, B, S, T);
@@ -467,7 +513,7 @@ extern "C" int32_t diffsep_ode_sample(diffsep_engine* e, const diffsep_sde_confi
     }
   }
 
-  if (ode_finish(e, sp, oc, smix, w.y, out, B, S, T, nullptr, st)) return 1;
+  if (ode_finish(e, sp, oc->eps, oc->denoise, oc->N, smix, w.y, out, B, S, T, nullptr, st)) return 1;
   if (info) ode_info(c, info);
   return 0;
 }
@@ -490,14 +536,7 @@ extern "C" int32_t diffsep_ode_sample_each(diffsep_engine* e, const diffsep_sde_
   const int64_t* lengths = ext ? ext->lengths_host : nullptr;
   const uint64_t* seeds = ext ? ext->seeds_host : nullptr;
   DS_CHECK(!seeds || !(noise || x_init), "ode_sample_each: per-utterance seeds are for device noise (noise == NULL, x_init == NULL)");
-  if (lengths) {
-    const int Wp = diffsep_padded_frames(&e->cfg, T);
-    for (int b = 0; b < B; ++b) {
-      DS_CHECK(lengths[b] >= 1 && lengths[b] <= T, "ode_sample_each: utterance length outside [1, T]");
-      DS_CHECK(diffsep_padded_frames(&e->cfg, lengths[b]) == Wp,
-               "ode_sample_each: every utterance of a mixed-length batch must have the padded frame count of T");
-    }
-  }
+  if (check_batch_ext(&e->cfg, "ode_sample_each", B, T, lengths, nullptr, nullptr, nullptr, nullptr)) return 1;  // (seeds: above)
   OdePlan plan;
   const std::string bad = ode_plan_fill(plan, *oc, "ode_sample_each");
   DS_CHECK(bad.empty(), bad);
@@ -523,35 +562,13 @@ extern "C" int32_t diffsep_ode_sample_each(diffsep_engine* e, const diffsep_sde_
   const SdeP sp = to_sdep(sde);
 
   // mixture, lengths and seeds -> device; x_T -> st_x with a zero tail (and y = x_T in fp64)
-  DS_HIP(hipMemcpyAsync(e->st_mix, mix_norm, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
-  {
-    char* xp;
-    if (e->ext_pin.acquire((size_t)B * 16, &xp)) return 1;
-    unsigned long long* ps = reinterpret_cast<unsigned long long*>(xp);
-    int* pl = reinterpret_cast<int*>(xp + (size_t)B * 8);
-    for (int b = 0; b < B; ++b) {
-      ps[b] = seeds ? seeds[b] : seed + 0x9E3779B97F4A7C15ull * (unsigned long long)b;  // (b = 0: the B = 1 stream of `seed`)
-      pl[b] = lengths ? (int)lengths[b] : (int)T;
-    }
-    DS_HIP(hipMemcpyAsync(e->st_seeds, ps, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    DS_HIP(hipMemcpyAsync(e->st_lens, pl, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    if (e->ext_pin.record(st)) return 1;
-  }
-  const int* lens = e->st_lens;
-  if (lengths && ds_launch_mask_tail(e->st_mix, B, 1, T, lens, st)) return 1;
-  const float* smix = nullptr;
-  if (mixture_scale(e, sde, B, T, st, &smix)) return 1;
-  if (x_init) {
-    DS_HIP(hipMemcpyAsync(e->st_x, x_init, nst * 4, hipMemcpyDeviceToDevice, st));
-    if (lengths && ds_launch_mask_tail(e->st_x, B, S, T, lens, st)) return 1;
-  } else {
-    const float* z = noise;
-    if (!z) {  // utterance b: the PC sampler's prior draw of its seed (draw 0 of the B = 1 stream)
-      if (ds_launch_randn_batch(e->st_noise, B, S, T, (const uint64_t*)e->st_seeds, lens, 0, st)) return 1;
-      z = e->st_noise;
-    }
-    if (ds_launch_sde_prior(sp, e->st_mix, z, e->st_x, B, S, T, smix, st, lens)) return 1;
-  }
+  // (always uploaded; the prior draw always keyed per utterance — utterance b: draw 0 of the B = 1 stream of its seed — and
+  // the prior sample always cut to the lengths, T where none are given)
+  SamplerBatch sb;
+  if (batch_mixture(e, sb, mix_norm, B, T, lengths, seeds, seed, true, st)) return 1;
+  if (batch_start(e, sde, sb, B, T, x_init, noise, true, seed, sb.lens, st)) return 1;
+  const int* lens = sb.lens;
+  const float* smix = sb.smix;
   if (ds_launch_ode_cast(e->st_x, w.y, (long)nst, st)) return 1;
   std::vector<OdeCtl> u(B);
   std::vector<int> act(B, 1);
@@ -655,7 +672,7 @@ extern "C" int32_t diffsep_ode_sample_each(diffsep_engine* e, const diffsep_sde_
       if (act[b]) u[b].end_attempt(plan, pin[2 * b]);  // (y <- y_new, f <- f_new: taken on the device)
   }
 
-  if (ode_finish(e, sp, oc, smix, w.y, out, B, S, T, lengths ? lens : nullptr, st)) return 1;
+  if (ode_finish(e, sp, oc->eps, oc->denoise, oc->N, smix, w.y, out, B, S, T, sb.tail_lens, st)) return 1;
   if (infos)
     for (int b = 0; b < B; ++b) ode_info(u[b], &infos[b]);
   if (evals_run) *evals_run = evals;
@@ -683,24 +700,8 @@ extern "C" int32_t diffsep_ode_sample_fixed(diffsep_engine* e, const diffsep_sde
   const int M = plan.M, n_evals = plan.n_evals;
   const int64_t* lengths = ext ? ext->lengths_host : nullptr;
   const uint64_t* seeds = ext ? ext->seeds_host : nullptr;
-  diffsep_engine* tail = (ext && (ext->tail_steps > 0 || ext->head_steps > 0)) ? ext->tail_engine : nullptr;
-  const int tail_steps = tail ? ext->tail_steps : 0;
-  const int head_steps = tail ? ext->head_steps : 0;
-  if (tail) {
-    DS_CHECK(tail != e, "ode_sample_fixed: the tail engine must be a different engine");
-    diffsep_model_config a = e->cfg, b2 = tail->cfg;
-    a.dtype = b2.dtype = 0;
-    DS_CHECK(memcmp(&a, &b2, sizeof(a)) == 0, "ode_sample_fixed: the tail engine must have the same architecture");
-  }
-  DS_CHECK(!seeds || !noise, "ode_sample_fixed: per-utterance seeds are for device noise (noise == NULL)");
-  if (lengths) {
-    const int Wp = diffsep_padded_frames(&e->cfg, T);
-    for (int b = 0; b < B; ++b) {
-      DS_CHECK(lengths[b] >= 1 && lengths[b] <= T, "ode_sample_fixed: utterance length outside [1, T]");
-      DS_CHECK(diffsep_padded_frames(&e->cfg, lengths[b]) == Wp,
-               "ode_sample_fixed: every utterance of a mixed-length batch must have the padded frame count of T");
-    }
-  }
+  diffsep_engine* tail = ScoreEval::other(ext);
+  if (check_batch_ext(&e->cfg, "ode_sample_fixed", B, T, lengths, seeds, noise, e, tail)) return 1;
 
   StreamScope sc_(e, stream);
   hipStream_t st = sc_.st;
@@ -733,38 +734,12 @@ extern "C" int32_t diffsep_ode_sample_fixed(diffsep_engine* e, const diffsep_sde
   }
 
   // mixture, lengths and seeds -> device; the start state -> st_x with a zero tail (and y in fp64)
-  DS_HIP(hipMemcpyAsync(e->st_mix, mix_norm, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
-  {
-    char* xp;
-    if (e->ext_pin.acquire((size_t)B * 16, &xp)) return 1;
-    unsigned long long* ps = reinterpret_cast<unsigned long long*>(xp);
-    int* pl = reinterpret_cast<int*>(xp + (size_t)B * 8);
-    for (int b = 0; b < B; ++b) {
-      ps[b] = seeds ? seeds[b] : seed + 0x9E3779B97F4A7C15ull * (unsigned long long)b;  // (b = 0: the B = 1 stream of `seed`)
-      pl[b] = lengths ? (int)lengths[b] : (int)T;
-    }
-    DS_HIP(hipMemcpyAsync(e->st_seeds, ps, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    DS_HIP(hipMemcpyAsync(e->st_lens, pl, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    if (e->ext_pin.record(st)) return 1;
-  }
-  const int* lens = e->st_lens;                      // what the passes read: T without lengths
-  const int* tail_lens = lengths ? lens : nullptr;   // what masks a tail
-  if (lengths && ds_launch_mask_tail(e->st_mix, B, 1, T, lens, st)) return 1;
-  const float* smix = nullptr;
-  if (mixture_scale(e, sde, B, T, st, &smix)) return 1;
-  if (x_init) {
-    DS_HIP(hipMemcpyAsync(e->st_x, x_init, nst * 4, hipMemcpyDeviceToDevice, st));
-    if (lengths && ds_launch_mask_tail(e->st_x, B, S, T, lens, st)) return 1;
-  } else {
-    const float* z = noise;
-    if (!z) {  // draw 0 of the PC sampler's generator, keyed as that sampler keys it
-      if ((seeds || lengths) ? ds_launch_randn_batch(e->st_noise, B, S, T, (const uint64_t*)e->st_seeds, lens, 0, st)
-                             : ds_launch_randn(e->st_noise, (long)nst, seed, 0, st))
-        return 1;
-      z = e->st_noise;
-    }
-    if (ds_launch_sde_prior(sp, e->st_mix, z, e->st_x, B, S, T, smix, st, tail_lens)) return 1;
-  }
+  // (always uploaded; the prior draw keyed as the PC sampler keys it, the prior sample cut only to lengths that are given)
+  SamplerBatch sb;
+  if (batch_mixture(e, sb, mix_norm, B, T, lengths, seeds, seed, true, st)) return 1;
+  if (batch_start(e, sde, sb, B, T, x_init, noise, seeds || lengths, seed, sb.tail_lens, st)) return 1;
+  const int *lens = sb.lens, *tail_lens = sb.tail_lens;
+  const float* smix = sb.smix;
   if (ds_launch_ode_cast(e->st_x, w.y, (long)nst, st)) return 1;
 
   OdeArgs base;
@@ -772,31 +747,15 @@ extern "C" int32_t diffsep_ode_sample_fixed(diffsep_engine* e, const diffsep_sde
   base.s = sp; base.x = e->st_x; base.smix = smix;
   base.rtol = 0.0; base.atol = 1.0; base.part = w.part; base.B = B; base.S = S; base.T = T;
   base.kidx = -1;
-  // the evaluation of a stage of solver step i: on this engine, or on the tail engine (state and time copied over)
-  bool tail_ready = false;
-  const float* score = e->st_score;
-  auto eval_score = [&](int i) -> int {
-    if (tail && (i >= M - tail_steps || i < head_steps)) {
-      if (!tail_ready) {
-        DS_HIP(hipMemcpyAsync(tail->st_mix, e->st_mix, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
-        tail_ready = true;
-      }
-      DS_HIP(hipMemcpyAsync(tail->st_x, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
-      DS_HIP(hipMemcpyAsync(tail->st_t, e->st_t, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-      score = tail->st_score;
-      return run_nfe(tail, B, T, st);
-    }
-    score = e->st_score;
-    return run_nfe(e, B, T, st);
-  };
+  ScoreEval ev(e, tail, ext, M, B, T, nst, st);  // every stage of solver step i of M counts as step i
 
   DS_HIP(hipMemcpyAsync(e->st_t, d_tt, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
   for (int r = 0; r < n_evals; ++r) {
     const OdeFixedPass& p = plan.pass[r];
-    if (eval_score(p.step)) return 1;
+    if (ev.eval(p.step)) return 1;
     OdeEachArgs a;
     a.a = ode_pass_args(e, base, w, p.kout, p.mode, p.nk, p.c);
-    a.a.score = score;
+    a.a.score = ev.score;
     a.a.tt = d_tt + (size_t)r * B;
     a.h = d_h + (size_t)p.step * B; a.active = d_act; a.lens = lens;
     a.tnext = d_tt + (size_t)(r + 1) * B;
@@ -817,10 +776,7 @@ extern "C" int32_t diffsep_ode_sample_fixed(diffsep_engine* e, const diffsep_sde
     if (p.swap_k01) std::swap(w.K[0], w.K[1]);
   }
 
-  diffsep_ode_config fin;
-  memset(&fin, 0, sizeof(fin));
-  fin.eps = eps; fin.denoise = denoise; fin.N = N;
-  if (ode_finish(e, sp, &fin, smix, w.y, out, B, S, T, tail_lens, st)) return 1;
+  if (ode_finish(e, sp, eps, denoise, N, smix, w.y, out, B, S, T, tail_lens, st)) return 1;
   if (nfe_out) *nfe_out = n_evals;
   return 0;
 }
@@ -839,7 +795,7 @@ extern "C" int32_t diffsep_ode_sample_expint(diffsep_engine* e, const diffsep_sd
   if (check_sde(e, sde, "ode_sample_expint")) return 1;
   DS_CHECK(B >= 1 && B <= 65535 && T >= 1 && T <= 0x7fffffffLL, "ode_sample_expint: bad batch shape");
   DS_CHECK(!(x_init && noise), "ode_sample_expint: x_init and noise are alternatives");
-  const OdeExpintConfig xc{method, steps, t_start, eps, denoise, N};
+  const OdeFixedConfig xc{method, steps, t_start, eps, denoise, N};
   OdeExpintPlan plan;
   const std::string bad = ode_expint_plan_fill(plan, xc, *sde, timesteps_host, err_out != nullptr, "ode_sample_expint");
   DS_CHECK(bad.empty(), bad);
@@ -847,24 +803,8 @@ extern "C" int32_t diffsep_ode_sample_expint(diffsep_engine* e, const diffsep_sd
   const int M = plan.M;
   const int64_t* lengths = ext ? ext->lengths_host : nullptr;
   const uint64_t* seeds = ext ? ext->seeds_host : nullptr;
-  diffsep_engine* tail = (ext && (ext->tail_steps > 0 || ext->head_steps > 0)) ? ext->tail_engine : nullptr;
-  const int tail_steps = tail ? ext->tail_steps : 0;
-  const int head_steps = tail ? ext->head_steps : 0;
-  if (tail) {
-    DS_CHECK(tail != e, "ode_sample_expint: the tail engine must be a different engine");
-    diffsep_model_config a = e->cfg, b2 = tail->cfg;
-    a.dtype = b2.dtype = 0;
-    DS_CHECK(memcmp(&a, &b2, sizeof(a)) == 0, "ode_sample_expint: the tail engine must have the same architecture");
-  }
-  DS_CHECK(!seeds || !noise, "ode_sample_expint: per-utterance seeds are for device noise (noise == NULL)");
-  if (lengths) {
-    const int Wp = diffsep_padded_frames(&e->cfg, T);
-    for (int b = 0; b < B; ++b) {
-      DS_CHECK(lengths[b] >= 1 && lengths[b] <= T, "ode_sample_expint: utterance length outside [1, T]");
-      DS_CHECK(diffsep_padded_frames(&e->cfg, lengths[b]) == Wp,
-               "ode_sample_expint: every utterance of a mixed-length batch must have the padded frame count of T");
-    }
-  }
+  diffsep_engine* tail = ScoreEval::other(ext);
+  if (check_batch_ext(&e->cfg, "ode_sample_expint", B, T, lengths, seeds, noise, e, tail)) return 1;
 
   StreamScope sc_(e, stream);
   hipStream_t st = sc_.st;
@@ -896,64 +836,22 @@ extern "C" int32_t diffsep_ode_sample_expint(diffsep_engine* e, const diffsep_sd
   }
 
   // mixture, lengths and seeds -> device; the start state -> st_x with a zero tail (and y in fp64)
-  DS_HIP(hipMemcpyAsync(e->st_mix, mix_norm, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
-  {
-    char* xp;
-    if (e->ext_pin.acquire((size_t)B * 16, &xp)) return 1;
-    unsigned long long* ps = reinterpret_cast<unsigned long long*>(xp);
-    int* pl = reinterpret_cast<int*>(xp + (size_t)B * 8);
-    for (int b = 0; b < B; ++b) {
-      ps[b] = seeds ? seeds[b] : seed + 0x9E3779B97F4A7C15ull * (unsigned long long)b;  // (b = 0: the B = 1 stream of `seed`)
-      pl[b] = lengths ? (int)lengths[b] : (int)T;
-    }
-    DS_HIP(hipMemcpyAsync(e->st_seeds, ps, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    DS_HIP(hipMemcpyAsync(e->st_lens, pl, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    if (e->ext_pin.record(st)) return 1;
-  }
-  const int* lens = e->st_lens;                      // what the passes read: T without lengths
-  const int* tail_lens = lengths ? lens : nullptr;   // what masks a tail
-  if (lengths && ds_launch_mask_tail(e->st_mix, B, 1, T, lens, st)) return 1;
-  const float* smix = nullptr;
-  if (mixture_scale(e, sde, B, T, st, &smix)) return 1;
-  if (x_init) {
-    DS_HIP(hipMemcpyAsync(e->st_x, x_init, nst * 4, hipMemcpyDeviceToDevice, st));
-    if (lengths && ds_launch_mask_tail(e->st_x, B, S, T, lens, st)) return 1;
-  } else {
-    const float* z = noise;
-    if (!z) {  // draw 0 of the PC sampler's generator, keyed as that sampler keys it
-      if ((seeds || lengths) ? ds_launch_randn_batch(e->st_noise, B, S, T, (const uint64_t*)e->st_seeds, lens, 0, st)
-                             : ds_launch_randn(e->st_noise, (long)nst, seed, 0, st))
-        return 1;
-      z = e->st_noise;
-    }
-    if (ds_launch_sde_prior(sp, e->st_mix, z, e->st_x, B, S, T, smix, st, tail_lens)) return 1;
-  }
+  // (always uploaded; the prior draw keyed as the PC sampler keys it, the prior sample cut only to lengths that are given)
+  SamplerBatch sb;
+  if (batch_mixture(e, sb, mix_norm, B, T, lengths, seeds, seed, true, st)) return 1;
+  if (batch_start(e, sde, sb, B, T, x_init, noise, seeds || lengths, seed, sb.tail_lens, st)) return 1;
+  const int *lens = sb.lens, *tail_lens = sb.tail_lens;
+  const float* smix = sb.smix;
   if (ds_launch_ode_cast(e->st_x, w.y, (long)nst, st)) return 1;
 
-  // the evaluation of solver step i: on this engine, or on the tail engine (state and time copied over)
-  bool tail_ready = false;
-  const float* score = e->st_score;
-  auto eval_score = [&](int i) -> int {
-    if (tail && (i >= M - tail_steps || i < head_steps)) {
-      if (!tail_ready) {
-        DS_HIP(hipMemcpyAsync(tail->st_mix, e->st_mix, (size_t)B * T * 4, hipMemcpyDeviceToDevice, st));
-        tail_ready = true;
-      }
-      DS_HIP(hipMemcpyAsync(tail->st_x, e->st_x, nst * 4, hipMemcpyDeviceToDevice, st));
-      DS_HIP(hipMemcpyAsync(tail->st_t, e->st_t, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-      score = tail->st_score;
-      return run_nfe(tail, B, T, st);
-    }
-    score = e->st_score;
-    return run_nfe(e, B, T, st);
-  };
+  ScoreEval ev(e, tail, ext, M, B, T, nst, st);
 
   DS_HIP(hipMemcpyAsync(e->st_t, d_tt, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
   for (int i = 0; i < M; ++i) {
-    if (eval_score(i)) return 1;
+    if (ev.eval(i)) return 1;
     ExpintArgs a;
     memset(&a, 0, sizeof(a));
-    a.y = w.y; a.score = score; a.smix = smix;
+    a.y = w.y; a.score = ev.score; a.smix = smix;
     a.x0p = (method == DIFFSEP_EXPINT_DPMPP2M && i >= 1) ? x0_prev : nullptr;
     a.x0o = x0_new; a.yo = w.ynew; a.xo = e->st_x;
     ds_expint_set_coef(a, plan.coef.data() + (size_t)i * DS_EXPINT_COEFS);
@@ -968,10 +866,7 @@ extern "C" int32_t diffsep_ode_sample_expint(diffsep_engine* e, const diffsep_sd
     std::swap(x0_new, x0_prev);    // the X0 just written is the next step's previous one
   }
 
-  diffsep_ode_config fin;
-  memset(&fin, 0, sizeof(fin));
-  fin.eps = eps; fin.denoise = denoise; fin.N = N;
-  if (ode_finish(e, sp, &fin, smix, w.y, out, B, S, T, tail_lens, st)) return 1;
+  if (ode_finish(e, sp, eps, denoise, N, smix, w.y, out, B, S, T, tail_lens, st)) return 1;
   if (nfe_out) *nfe_out = M;
   return 0;
 }

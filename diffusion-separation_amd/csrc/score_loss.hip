@@ -445,14 +445,7 @@ extern "C" int32_t diffsep_score_loss_validate(const diffsep_model_config* cfg, 
   DS_CHECK(B >= 1 && T >= 1, "score_loss: empty batch or signal");
   DS_CHECK(loss->pit_mode >= 0 && loss->pit_mode <= 2,
            "score_loss: pit_mode must be 0 (none), 1 (true-mix anchor) or 2 (mean_0 anchor)");
-  if (lengths_host) {
-    const int Wp = diffsep_padded_frames(cfg, T);
-    for (int b = 0; b < B; ++b) {
-      DS_CHECK(lengths_host[b] >= 1 && lengths_host[b] <= T, "score_loss: utterance length outside [1, T]");
-      DS_CHECK(diffsep_padded_frames(cfg, lengths_host[b]) == Wp,
-               "score_loss: every utterance of a mixed-length batch must have the padded frame count of T");
-    }
-  }
+  if (check_batch_ext(cfg, "score_loss", B, T, lengths_host, nullptr, nullptr, nullptr, nullptr)) return 1;
   DS_CHECK(workspace_bytes >= (int64_t)sl_slab_bytes(B, T),
            "score_loss: workspace too small (diffsep_score_loss_workspace_bytes)");
   return 0;
@@ -465,9 +458,7 @@ extern "C" int32_t diffsep_score_loss(diffsep_engine* e, const diffsep_sde_confi
                                       int64_t T, void* workspace, int64_t workspace_bytes, void* stream) {
   DS_CHECK(e && sde && cfg && mix_norm && target && t && out && workspace, "score_loss: null argument");
   if (diffsep_score_loss_validate(&e->cfg, cfg, B, T, lengths_host, workspace_bytes)) return 1;
-  DS_CHECK(sde->kind == DIFFSEP_SDE_MIX || sde->kind == DIFFSEP_SDE_PRIORMIX, "score_loss: unknown SDE kind");
-  DS_CHECK(sde->kind == DIFFSEP_SDE_MIX || sde->avg_len >= 1, "score_loss: PriorMixSDE needs avg_len >= 1");
-  DS_CHECK(sde->ndim == e->cfg.num_sources, "score_loss: sde.ndim != num_sources");
+  if (check_sde(e, sde, "score_loss")) return 1;
   StreamScope sc_(e, stream);
   hipStream_t st = sc_.st;
   const int S = e->cfg.num_sources;
@@ -488,10 +479,7 @@ extern "C" int32_t diffsep_score_loss(diffsep_engine* e, const diffsep_sde_confi
     if (ds_launch_mask_tail(e->st_mix, B, 1, T, lens, st)) return 1;
   }
   const float* smix = nullptr;
-  if (sde->kind == DIFFSEP_SDE_PRIORMIX) {
-    if (ds_launch_sigma_mix(e->st_mix, e->st_smix, B, T, sde->avg_len, st)) return 1;
-    smix = e->st_smix;
-  }
+  if (mixture_scale(e, sde, B, T, st, &smix)) return 1;
   PerturbArgs pa;
   pa.s = to_sdep(sde);
   pa.x0 = target; pa.mix = e->st_mix; pa.t = e->st_t; pa.z = z; pa.smix = smix; pa.beta = beta; pa.lens = lens;

@@ -264,6 +264,38 @@ class Engine:
                  _stream_ptr(self.device))
         return y
 
+    def _ext_arrays(self, ext, B, lengths, seeds):
+        """lengths / seeds -> the host-pointer fields of a SamplerExt or OdeExt; returns the arrays they refer to, which the
+        caller keeps alive until its library call has returned"""
+        keep = []
+        for name, v, dt in (("lengths", lengths, np.int64), ("seeds", seeds, np.uint64)):
+            if v is not None:
+                arr, ptr = _lib.host_array(v, dt, B, name)
+                setattr(ext, name + "_host", ptr)
+                keep.append(arr)
+        return keep
+
+    def _sampler_ext(self, B, lengths, seeds, tail, tail_steps, head_steps):
+        """(SamplerExt or None when the call uses no extension, the host arrays to keep alive)"""
+        hybrid = tail is not None and (tail_steps > 0 or head_steps > 0)
+        if lengths is None and seeds is None and not hybrid:
+            return None, []
+        ext = _lib.SamplerExt()
+        keep = self._ext_arrays(ext, B, lengths, seeds)
+        if hybrid:
+            if tail.kind != self.kind:  # an engine handle means something to the library that created it only
+                raise _lib.DiffsepError(f"the other engine was created by the '{tail.kind}' build of the library, this one "
+                                        f"by the '{self.kind}' build: create it with Engine(..., lib_kind='{self.kind}')")
+            ext.tail_engine, ext.tail_steps, ext.head_steps = tail._h, int(tail_steps), int(head_steps)
+        return ext, keep
+
+    def _state_args(self, B, T, x_init, noise):
+        """x_init / noise [B,S,T] as the library takes them (None stays None)"""
+        for name, v in (("x_init", x_init), ("noise", noise)):
+            if v is not None:
+                assert tuple(v.shape) == (B, self.S, T), f"{name} must be [B,S,T]"
+        return (self._f32(x_init) if x_init is not None else None), (self._f32(noise) if noise is not None else None)
+
     def pc_sample(self, mix_norm, sde, N=30, corrector_steps=1, snr=0.5, eps=0.03, denoise=True,
                   predictor="reverse_diffusion", corrector="ald2", noise=None, seed=0, timesteps=None, lengths=None,
                   seeds=None, tail=None, tail_steps=0, head_steps=0, snapshots=None, snapshot_means=True, target=None,
@@ -303,19 +335,8 @@ class Engine:
             ts = np.ascontiguousarray(timesteps, dtype=np.float32)
             assert ts.size >= N
         nfe = C.c_int32()
-        ext = None  # (la / sa below: the host arrays its pointers refer to, alive until this method returns)
-        if lengths is not None or seeds is not None or (tail is not None and (tail_steps > 0 or head_steps > 0)):
-            ext = _lib.SamplerExt()
-            if lengths is not None:
-                la, ext.lengths_host = _lib.host_array(lengths, np.int64, B, "lengths")
-            if seeds is not None:
-                sa, ext.seeds_host = _lib.host_array(seeds, np.uint64, B, "seeds")
-            if tail is not None and (tail_steps > 0 or head_steps > 0):
-                if tail.kind != self.kind:  # an engine handle means something to the library that created it only
-                    raise _lib.DiffsepError(f"the other engine was created by the '{tail.kind}' build of the library, this one "
-                                            f"by the '{self.kind}' build: create it with Engine(..., lib_kind='{self.kind}')")
-                ext.tail_engine, ext.tail_steps, ext.head_steps = tail._h, int(tail_steps), int(head_steps)
-        ranged = x_init is not None or first_step != 0 or last_step is not None
+        ext, keep = self._sampler_ext(B, lengths, seeds, tail, tail_steps, head_steps)  # (keep: alive until this returns)
+        ranged =x_init is not None or first_step != 0 or last_step is not None
         first, last = int(first_step), int(N if last_step is None else last_step)
         if x_init is not None:
             x_init = self._f32(x_init)
@@ -366,11 +387,7 @@ class Engine:
         oc = _lib.OdeConfig(float(rtol), float(atol), float(eps), float(first_step or 0.0),
                             float(max_step) if max_step is not None else 0.0, _lib.ODE_METHODS[method], int(max_nfe or 0),
                             int(bool(denoise)), int(N))
-        for name, v in (("x_init", x_init), ("noise", noise)):
-            if v is not None:
-                assert tuple(v.shape) == (B, self.S, T), f"{name} must be [B,S,T]"
-        x_init = self._f32(x_init) if x_init is not None else None
-        noise = self._f32(noise) if noise is not None else None
+        x_init, noise = self._state_args(B, T, x_init, noise)
         out = torch.empty((B, self.S, T), dtype=torch.float32, device=mix_norm.device)
         return mix_norm, sc, oc, x_init, noise, out
 
@@ -405,11 +422,8 @@ class Engine:
         mix_norm, sc, oc, x_init, noise, out = self._ode_setup(mix_norm, sde, method, rtol, atol, eps, first_step, max_step,
                                                                max_nfe, denoise, N, x_init, noise)
         B, _, T = mix_norm.shape
-        ext = _lib.OdeExt()  # (la / sa below: the host arrays its pointers refer to, alive until this method returns)
-        if lengths is not None:
-            la, ext.lengths_host = _lib.host_array(lengths, np.int64, B, "lengths")
-        if seeds is not None:
-            sa, ext.seeds_host = _lib.host_array(seeds, np.uint64, B, "seeds")
+        ext = _lib.OdeExt()
+        keep = self._ext_arrays(ext, B, lengths, seeds)  # (alive until this method returns)
         infos = (_lib.OdeInfo * B)()
         evals = C.c_int32()
         with torch.cuda.device(self.device):
@@ -441,31 +455,15 @@ class Engine:
         assert one == 1
         M = int(steps)
         sc = _lib.sde_config(sde)
-        for name, v in (("x_init", x_init), ("noise", noise)):
-            if v is not None:
-                assert tuple(v.shape) == (B, self.S, T), f"{name} must be [B,S,T]"
-        x_init = self._f32(x_init) if x_init is not None else None
-        noise = self._f32(noise) if noise is not None else None
+        x_init, noise = self._state_args(B, T, x_init, noise)
         ts = None
         if timesteps is not None:
             ts = np.ascontiguousarray(timesteps.detach().cpu().numpy() if hasattr(timesteps, "detach") else timesteps,
                                       dtype=np.float64).reshape(-1)
             if ts.size != M + 1:
                 raise _lib.DiffsepError(f"ode_sample_fixed: timesteps must hold steps + 1 = {M + 1} times, got {ts.size}")
-        ext = None  # (la / sa below: the host arrays its pointers refer to, alive until this method returns)
-        hybrid = tail is not None and (tail_steps > 0 or head_steps > 0)
-        if lengths is not None or seeds is not None or hybrid:
-            ext = _lib.SamplerExt()
-            if lengths is not None:
-                la, ext.lengths_host = _lib.host_array(lengths, np.int64, B, "lengths")
-            if seeds is not None:
-                sa, ext.seeds_host = _lib.host_array(seeds, np.uint64, B, "seeds")
-            if hybrid:
-                if tail.kind != self.kind:  # an engine handle means something to the library that created it only
-                    raise _lib.DiffsepError(f"the other engine was created by the '{tail.kind}' build of the library, this one "
-                                            f"by the '{self.kind}' build: create it with Engine(..., lib_kind='{self.kind}')")
-                ext.tail_engine, ext.tail_steps, ext.head_steps = tail._h, int(tail_steps), int(head_steps)
-        out = torch.empty((B, self.S, T), dtype=torch.float32, device=mix_norm.device)
+        ext, keep = self._sampler_ext(B, lengths, seeds, tail, tail_steps, head_steps)  # (keep: alive until this returns)
+        out =torch.empty((B, self.S, T), dtype=torch.float32, device=mix_norm.device)
         err = torch.empty((max(M, 0), B, 2), dtype=torch.float64, device=mix_norm.device) if want_err else None
         nfe = C.c_int32()
         with torch.cuda.device(self.device):
